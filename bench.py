@@ -9,10 +9,15 @@ One "step" = one pass of the hot path over one batch already resident in HBM:
 The zlib/JSON container is host work and is not in the timed region.  With N > 1 every rank encodes its own batch (weak
 scaling, no data-path collective; `--scaling strong` shards ONE global batch of --batch images over the ranks instead);
 RCCL carries only the barrier, the max-reduction of the time and the final stats gather.
-Next to `value` (inputs and outputs in HBM) the line carries SURVEY 8(d)'s host->host figure (`host_to_host_mpix_s`,
-`pcie_frac`), the decoder (`decode_mpix_s`), the oracle timed on this box's host cores (`cpu_baseline`).
+A plain run times exactly --steps steps in one region and prints the headline line (`value`, `ms_per_step`, ...).  With
+`--full` the timed region is repeated `--regions` times (default 5), HIP events bracket the BCD launches inside it
+(`roofline`), an untimed pass with every launch bracketed gives `kernels`, and the line also carries SURVEY 8(d)'s
+host->host figure (`host_to_host_mpix_s`, `pcie_frac`), the decoder (`decode_mpix_s`), the other workloads (`sweep`) and
+the oracle timed on this box's host cores (`cpu_baseline`).  `--dump-outputs DIR` writes the factors of the last timed
+step as float32 .npy files (a fixed, seeded sample of images when they would exceed 64 MB).
 
   python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 --full
   python bench.py --gpus N ...          # no launcher: bench.py starts its own N ranks (fresh child processes, before
                                         # this process has imported torch or touched a GPU) and exits with their code
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -409,6 +414,31 @@ def timed_stats(samples_ms):
     return s[0], med, s[-1]
 
 
+DUMP_BYTES = 64 * 10**6  # what --dump-outputs may write in all
+
+
+def dump_outputs(ctx, directory, arrays, budget):
+    """--dump-outputs: `arrays` (name -> CUDA tensor, images along dim 0) as DIR/<name>.npy in float32.  When the whole would
+    exceed `budget` bytes, the same fixed, seeded sample of images is taken from every array and its indices are written
+    to DIR/sample_images.npy (float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    B = next(iter(arrays.values())).shape[0]
+    per_image = 4 * sum(t[0].numel() for t in arrays.values())
+    rows = None
+    if per_image * B > budget:
+        n = (budget - 8 * B - 4096) // per_image  # (the index file, the .npy headers)
+        assert n >= 1, f"one image's outputs ({per_image} B) exceed the --dump-outputs budget of {budget} B"
+        rows = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+        np.save(os.path.join(directory, "sample_images.npy"), rows.astype(np.float64))
+        idx = torch.from_numpy(rows).to(next(iter(arrays.values())).device)
+        arrays = {name: t.index_select(0, idx) for name, t in arrays.items()}
+    host = ctx.to_host(*arrays.values())  # (raises if a persistent launch of the timed steps gave up)
+    for name, t in zip(arrays, host):
+        np.save(os.path.join(directory, name + ".npy"), t.numpy().astype(np.float32))
+
+
 def synthetic_batch(torch, dev, lo, count, H, W, base_seed=1234):
     """Images lo .. lo+count-1 of the synthetic dataset, drawn straight into this rank's own batch buffer: image i is
     `randint(0, 256, (3, H, W))` from a generator seeded with base_seed + i, so a rank's block does not depend on the
@@ -430,10 +460,16 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="images per GPU per step (0 = the config's: 256 / 512); with "
                                                          "--scaling strong, the GLOBAL batch sharded over the ranks")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
-    ap.add_argument("--regions", type=int, default=5, help="how many times the timed region of --steps steps is repeated")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host->host, decode and CPU legs")
+    ap.add_argument("--full", action="store_true", help="also the figures beyond the headline: repeated timed regions, "
+                                                        "roofline and per-kernel times, host->host, decode, sweep and CPU legs")
+    ap.add_argument("--regions", type=int, default=None, help="how many times the timed region of --steps steps is repeated "
+                                                              "(default 1; 5 with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the host->host, decode, sweep and CPU legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the factors of the last timed step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
     assert args.gpus >= 1 and args.steps >= 1 and args.regions >= 1
     global _JOB_CORES
     _JOB_CORES = _usable_cores()
@@ -519,6 +555,7 @@ def main():
     dims = _lib.plane_dims(H, W)
     if args.config == "svd":
         R = cfg["svd_rank"]
+        out_names = ("U", "V", "qparams")
 
         def step():
             return ctx.svd_encode_rgb(images, R)
@@ -526,9 +563,10 @@ def main():
     else:
         U = torch.empty((B, sum(d[4] * r for d, r in zip(dims, RANKS))), dtype=torch.int8, device=dev)
         V = torch.empty((B, 64 * sum(RANKS)), dtype=torch.int8, device=dev)
+        out_names = ("U", "V")
 
         def step():
-            lrf_amd.qmf_factorize_batch(images, RANKS, NUM_ITERS, BOUNDS, out=(U, V))
+            return lrf_amd.qmf_factorize_batch(images, RANKS, NUM_ITERS, BOUNDS, out=(U, V))
 
     def barrier():
         torch.cuda.synchronize()
@@ -543,16 +581,18 @@ def main():
         step()
     for _ in range(args.warmup):
         step()
-    # Inside the timed regions only the dominant kernel (the BCD pass, K launches per step) carries HIP event pairs on
-    # the launching stream: an event pair costs stream time (0.15 ms per step when all 22 launches are bracketed).
-    ctx.profile_kernels([_lib.LRF_K_BCD, _lib.LRF_K_BCD_PERSIST])
-    ctx.profile_reset()
+    # --full: inside the timed regions only the dominant kernel (the BCD pass, K launches per step) carries HIP event pairs
+    # on the launching stream: an event pair costs stream time (0.15 ms per step when all 22 launches are bracketed).
+    if args.full:
+        ctx.profile_kernels([_lib.LRF_K_BCD, _lib.LRF_K_BCD_PERSIST])
+        ctx.profile_reset()
     region_s, own_s = [], []
     for _ in range(args.regions):  # each region: barrier + synchronize, EXACTLY --steps steps, synchronize + barrier
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             step()
+        result = step()  # the last step's outputs, kept for --dump-outputs
         torch.cuda.synchronize()
         own_s.append(time.perf_counter() - t0)  # this rank's own steps, before it waits for the others
         barrier()
@@ -562,16 +602,20 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt_r = float(t.item())
         region_s.append(dt_r)
-    ctx.profile(False)
-    bcd_total_ms, bcd_launches = ctx.kernel_time(_lib.LRF_K_BCD)
-    bcdp_total_ms, bcdp_launches = ctx.kernel_time(_lib.LRF_K_BCD_PERSIST)
-    # per-kernel breakdown: a separate, untimed pass with every launch bracketed
-    ctx.profile(True)
-    ctx.profile_reset()
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    ctx.profile(False)
+    if args.dump_outputs:
+        suffix = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(ctx, args.dump_outputs, {n + suffix: t for n, t in zip(out_names, result)}, DUMP_BYTES // world)
+    if args.full:
+        ctx.profile(False)
+        bcd_total_ms, bcd_launches = ctx.kernel_time(_lib.LRF_K_BCD)
+        bcdp_total_ms, bcdp_launches = ctx.kernel_time(_lib.LRF_K_BCD_PERSIST)
+        # per-kernel breakdown: a separate, untimed pass with every launch bracketed
+        ctx.profile(True)
+        ctx.profile_reset()
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        ctx.profile(False)
     dt_min, dt, dt_max = timed_stats(region_s)
     rank_stats = None
     own_ms = timed_stats(own_s)[1] / args.steps * 1e3
@@ -592,7 +636,7 @@ def main():
 
     extras = {}
     h2h_pair = None
-    if not args.no_extras and args.config != "svd":  # every rank takes part in the (collective-timed) host->host legs
+    if args.full and not args.no_extras and args.config != "svd":  # every rank takes part in the (collective-timed) host->host legs
         Ud, Vd = U.cpu(), V.cpu()
         host = images.cpu().pin_memory()
         h2h, h2h_pair = host_to_host(torch, dist, _lib, dev_index, images, host, H, W, RANKS, min(args.steps, 10), args.warmup,
@@ -604,72 +648,75 @@ def main():
 
     if rank == 0:
         value = total_px / dt / 1e6
-        kern = {}
-        for kid, name in _lib.KERNEL_NAMES.items():
-            ms, n = ctx.kernel_time(kid)
-            if n:
-                kern[name] = {"launches_per_step": n / 2, "avg_ms": ms / n, "ms_per_step": ms / 2}
         ms_step = dt / args.steps * 1e3
         if args.config == "svd":
             metric = "Mpixels/sec svd_encode (RGB, 8x8 patch, quality 2.5, uint8 factors)"
-            M = dims[0][4]
-            # whole step: u8 in (3 B/px) + X [M,192] written once and read twice (Gram, U = X w) as BYTES since round 3 (3 B/px
-            # each; fp32 until round 2: 12 B/px each) + factors
-            alg_bytes = B * (3 * H * W + 3 * M * 192 + (M + 192) * cfg["svd_rank"])
-            achieved = alg_bytes / (ms_step * 1e-3) / 1e9
-            roof = {"bound": "hbm",
-                    "note": "the step is paced by the per-matrix eigen-solver chain (256 matrices of 192 x 192, one workgroup "
-                            "each: k_any_tridiag_reg + k_any_eig are two thirds of it), not by bytes; the HBM figure is for completeness",
-                    "kernel": "svd_encode (all kernels of the step)", "achieved": round(achieved, 1),
-                    "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": None,
-                    "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(ms_step, 5)}
         else:
             metric = "Mpixels/sec qmf_encode (8x8 patch, r=7, 10 iters)"
-            # dominant kernel: one BCD pass (k_bcd_w).  Algorithmic bytes per launch (DESIGN.md "Roofline"):
-            # X read once (4 B per patch element) + int8 U written once.
-            alg_bytes = B * (sum(d[4] for d in dims) * 64 * 4 + sum(d[4] * r for d, r in zip(dims, RANKS)))
-            traffic = None
-            tfile = os.path.join(ROOT, "profiles", "traffic_latest.json")
-            if bcdp_launches:
-                # the iterations run in ONE launch (k_bcd_p: the U-update passes pulled from a queue, the V updates inside):
-                # all K of them since round 5 (no k_bcd launch is seen then), iterations 2..K before; algorithmic bytes of that
-                # launch = that many passes
-                first_inside = bcd_launches == 0
-                passes = NUM_ITERS if first_inside else NUM_ITERS - 1
-                bcd_ms = bcdp_total_ms / bcdp_launches  # live, from the timed regions (rank 0's GPU)
-                achieved = passes * alg_bytes / (bcd_ms * 1e-3) / 1e9
-                if args.config == "kodak" and B == 256 and os.path.exists(tfile):
-                    try:
-                        traffic = json.load(open(tfile)).get("k_bcd_p", {}).get("hbm_bytes_per_launch")
-                    except (ValueError, OSError):
-                        traffic = None
-                roof = {"bound": "hbm", "kernel": "k_bcd_p", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
-                        "frac": round(achieved / 8000.0, 4), "traffic": traffic,
-                        "algorithmic_bytes_per_launch": passes * alg_bytes, "avg_launch_ms": round(bcd_ms, 5),
-                        "launches_measured": bcdp_launches,
-                        "traffic_source": ("profiles/traffic_latest.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                           "command on the same sources (tools/run_profiles_r05.sh, tools/make_traffic.py) — a committed "
-                                           "measurement, not collected in this run") if traffic is not None else None,
-                        "note": ("k_bcd_p = iterations 1..%d in one launch (%d U-update passes of %d B each + the per-matrix V updates, "
-                                 "which the launch-per-iteration path ran as k_vupdate)" % (NUM_ITERS, passes, alg_bytes)) if first_inside else
-                                ("k_bcd_p = iterations 2..%d in one launch (%d U-update passes of %d B each + the per-matrix V updates, "
-                                 "which the launch-per-iteration path ran as k_vupdate); the first iteration is k_bcd_w<1>: "
-                                 "%.5f ms per launch" % (NUM_ITERS, passes, alg_bytes, bcd_total_ms / max(bcd_launches, 1)))}
+        if args.full:
+            kern = {}
+            for kid, name in _lib.KERNEL_NAMES.items():
+                ms, n = ctx.kernel_time(kid)
+                if n:
+                    kern[name] = {"launches_per_step": n / 2, "avg_ms": ms / n, "ms_per_step": ms / 2}
+            if args.config == "svd":
+                M = dims[0][4]
+                # whole step: u8 in (3 B/px) + X [M,192] written once and read twice (Gram, U = X w) as BYTES since round 3 (3 B/px
+                # each; fp32 until round 2: 12 B/px each) + factors
+                alg_bytes = B * (3 * H * W + 3 * M * 192 + (M + 192) * cfg["svd_rank"])
+                achieved = alg_bytes / (ms_step * 1e-3) / 1e9
+                roof = {"bound": "hbm",
+                        "note": "the step is paced by the per-matrix eigen-solver chain (256 matrices of 192 x 192, one workgroup "
+                                "each: k_any_tridiag_reg + k_any_eig are two thirds of it), not by bytes; the HBM figure is for completeness",
+                        "kernel": "svd_encode (all kernels of the step)", "achieved": round(achieved, 1),
+                        "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": None,
+                        "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(ms_step, 5)}
             else:
-                bcd_ms = bcd_total_ms / bcd_launches  # live, from the timed regions (rank 0's GPU)
-                achieved = alg_bytes / (bcd_ms * 1e-3) / 1e9
-                if args.config == "kodak" and B == 256 and os.path.exists(tfile):
-                    try:
-                        traffic = json.load(open(tfile)).get("k_bcd", {}).get("hbm_bytes_per_launch")
-                    except (ValueError, OSError):
-                        traffic = None
-                roof = {"bound": "hbm", "kernel": "k_bcd_w", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
-                        "frac": round(achieved / 8000.0, 4), "traffic": traffic,
-                        "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(bcd_ms, 5),
-                        "launches_measured": bcd_launches,
-                        "traffic_source": ("profiles/traffic_latest.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                           "command on the same sources (tools/run_profiles_r05.sh, tools/make_traffic.py) — a committed "
-                                           "measurement, not collected in this run") if traffic is not None else None}
+                # dominant kernel: one BCD pass (k_bcd_w).  Algorithmic bytes per launch (DESIGN.md "Roofline"):
+                # X read once (4 B per patch element) + int8 U written once.
+                alg_bytes = B * (sum(d[4] for d in dims) * 64 * 4 + sum(d[4] * r for d, r in zip(dims, RANKS)))
+                traffic = None
+                tfile = os.path.join(ROOT, "profiles", "traffic_latest.json")
+                if bcdp_launches:
+                    # the iterations run in ONE launch (k_bcd_p: the U-update passes pulled from a queue, the V updates inside):
+                    # all K of them since round 5 (no k_bcd launch is seen then), iterations 2..K before; algorithmic bytes of that
+                    # launch = that many passes
+                    first_inside = bcd_launches == 0
+                    passes = NUM_ITERS if first_inside else NUM_ITERS - 1
+                    bcd_ms = bcdp_total_ms / bcdp_launches  # live, from the timed regions (rank 0's GPU)
+                    achieved = passes * alg_bytes / (bcd_ms * 1e-3) / 1e9
+                    if args.config == "kodak" and B == 256 and os.path.exists(tfile):
+                        try:
+                            traffic = json.load(open(tfile)).get("k_bcd_p", {}).get("hbm_bytes_per_launch")
+                        except (ValueError, OSError):
+                            traffic = None
+                    roof = {"bound": "hbm", "kernel": "k_bcd_p", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
+                            "frac": round(achieved / 8000.0, 4), "traffic": traffic,
+                            "algorithmic_bytes_per_launch": passes * alg_bytes, "avg_launch_ms": round(bcd_ms, 5),
+                            "launches_measured": bcdp_launches,
+                            "traffic_source": ("profiles/traffic_latest.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                               "command on the same sources (tools/run_profiles_r05.sh, tools/make_traffic.py) — a committed "
+                                               "measurement, not collected in this run") if traffic is not None else None,
+                            "note": ("k_bcd_p = iterations 1..%d in one launch (%d U-update passes of %d B each + the per-matrix V updates, "
+                                     "which the launch-per-iteration path ran as k_vupdate)" % (NUM_ITERS, passes, alg_bytes)) if first_inside else
+                                    ("k_bcd_p = iterations 2..%d in one launch (%d U-update passes of %d B each + the per-matrix V updates, "
+                                     "which the launch-per-iteration path ran as k_vupdate); the first iteration is k_bcd_w<1>: "
+                                     "%.5f ms per launch" % (NUM_ITERS, passes, alg_bytes, bcd_total_ms / max(bcd_launches, 1)))}
+                else:
+                    bcd_ms = bcd_total_ms / bcd_launches  # live, from the timed regions (rank 0's GPU)
+                    achieved = alg_bytes / (bcd_ms * 1e-3) / 1e9
+                    if args.config == "kodak" and B == 256 and os.path.exists(tfile):
+                        try:
+                            traffic = json.load(open(tfile)).get("k_bcd", {}).get("hbm_bytes_per_launch")
+                        except (ValueError, OSError):
+                            traffic = None
+                    roof = {"bound": "hbm", "kernel": "k_bcd_w", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
+                            "frac": round(achieved / 8000.0, 4), "traffic": traffic,
+                            "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(bcd_ms, 5),
+                            "launches_measured": bcd_launches,
+                            "traffic_source": ("profiles/traffic_latest.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                               "command on the same sources (tools/run_profiles_r05.sh, tools/make_traffic.py) — a committed "
+                                               "measurement, not collected in this run") if traffic is not None else None}
         out = {
             "metric": metric,
             "value": round(value, 2),
@@ -697,20 +744,22 @@ def main():
             "timing_note": "each region = barrier + synchronize, exactly `steps` steps, synchronize + barrier, max over ranks; "
                            "value / ms_per_step are the median region's",
             "rccl_ranks": world, "collective_backend": backend, "self_launched": os.environ.get("LRF_BENCH_SELF_LAUNCHED") == "1",
-            "roofline": roof,
             # 75.1 algorithmic bytes per input pixel for the whole encode at K = 10
             "whole_encode_frac_of_hbm_peak": round(75.1 * total_px / world / dt / 8e12, 4) if args.config != "svd" else None,
-            "kernels": {k: {a: round(b, 5) for a, b in v.items()} for k, v in kern.items()},
-            "kernels_note": "per-kernel breakdown from a separate untimed pass with every launch bracketed by events (k_bcd_persist = "
-                            "the iterations in one launch where k_bcd_p runs — all K of them at ranks <= 16, the V updates inside; "
-                            "k_bcd / k_vupdate appear only where an iteration is a launch of its own; k_planes_gram = k_planes16_gram, the patch "
-                            "matrices and the luma planes' Gram partials in one kernel, k_gram then covers the chroma planes only); roofline.avg_launch_ms is "
-                            "measured inside the timed regions (events on the BCD launches only)",
         }
         out["ranks"] = rank_stats
         out["forced_dist"] = force_dist
+        out["full"] = args.full
+        if args.full:
+            out["roofline"] = roof
+            out["kernels"] = {k: {a: round(b, 5) for a, b in v.items()} for k, v in kern.items()}
+            out["kernels_note"] = ("per-kernel breakdown from a separate untimed pass with every launch bracketed by events (k_bcd_persist = "
+                                   "the iterations in one launch where k_bcd_p runs — all K of them at ranks <= 16, the V updates inside; "
+                                   "k_bcd / k_vupdate appear only where an iteration is a launch of its own; k_planes_gram = k_planes16_gram, the patch "
+                                   "matrices and the luma planes' Gram partials in one kernel, k_gram then covers the chroma planes only); roofline.avg_launch_ms is "
+                                   "measured inside the timed regions (events on the BCD launches only)")
         out.update(extras)
-        if world == 1 and not args.no_extras and args.config != "svd":
+        if args.full and world == 1 and not args.no_extras and args.config != "svd":
             out.update(decode_leg(torch, _lib, ctx, U, V, H, W, RANKS, args.steps))
             if args.config == "kodak" and B == 256:
                 out.update(sweep_leg(torch, lrf_amd, _lib, ctx, images, H, W))

@@ -76,7 +76,7 @@ def test_bench_rccl_path_executes_at_world_size_1():
     per-rank figures (own ms_per_step, NUMA binding, packer threads) and SURVEY 8(d)'s bytes-out leg."""
     if torch.cuda.is_initialized():
         pytest.skip("this process has already initialised the GPU: run the file first (it is the first of the suite)")
-    out = _bench_forced_dist(["--gpus", "1", "--steps", "2", "--warmup", "1", "--regions", "2", "--batch", "16", "--no-cpu-baseline"])
+    out = _bench_forced_dist(["--gpus", "1", "--steps", "2", "--warmup", "1", "--regions", "2", "--batch", "16", "--full", "--no-cpu-baseline"])
     assert out["n_gpus"] == 1 and out["collective_backend"] == "nccl" and out["forced_dist"] is True and out["rccl_ranks"] == 1
     r0 = out["ranks"][0]
     assert r0["device"] == 0 and r0["pixels_per_region"] == 2 * 16 * 512 * 768
@@ -108,7 +108,7 @@ def test_bench_bare_gpus_2_runs_two_ranks():
     n_gpus 1).  Weak scaling: both ranks encode --batch images; the line carries the host->host leg of both."""
     if torch.cuda.is_initialized():
         pytest.skip("this process has already initialised the GPU: run the file first (it is the first of the suite)")
-    out = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--regions", "2", "--batch", "8", "--no-cpu-baseline"])
+    out = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--regions", "2", "--batch", "8", "--full", "--no-cpu-baseline"])
     assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and out["self_launched"] is True
     assert out["steps"] == 2 and out["timed_regions"] == 2 and out["scaling"] == "weak"
     assert out["config"]["global_batch"] == 16 and len(out["ranks"]) == 2
@@ -133,6 +133,27 @@ def test_bench_strong_scaling_generates_only_the_ranks_block():
     assert out["config"]["images_this_rank"] == [0, 3] and out["config"]["rank_input_bytes"] == share
     assert out["config"]["input_generation_peak_bytes"] < 2 * share
     assert sum(r["pixels_per_region"] for r in out["ranks"]) == 6 * 1365 * 2048
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times ONE region of exactly --steps steps and prints the headline only; --dump-outputs writes
+    the factors of the last timed step as float32 .npy, the same for any --steps / --warmup (seeded inputs)."""
+    if torch.cuda.is_initialized():
+        pytest.skip("this process has already initialised the GPU: run the file first (it is the first of the suite)")
+    import numpy as np
+    dumps = []
+    for steps, warmup in ((3, 1), (1, 0)):
+        d = tmp_path / f"steps{steps}"
+        out = _bench(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--batch", "8", "--dump-outputs", str(d)])
+        assert out["steps"] == steps and out["warmup"] == warmup and out["timed_regions"] == 1 and out["full"] is False
+        assert not {"roofline", "kernels", "host_to_host_mpix_s", "decode_mpix_s", "sweep", "cpu_baseline"} & set(out)
+        assert abs(out["value"] - 8 * 512 * 768 / (out["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * out["value"]
+        assert sorted(os.listdir(d)) == ["U.npy", "V.npy"]
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("U", "V")})
+    U, V = dumps[0]["U"], dumps[0]["V"]
+    assert U.dtype == V.dtype == np.float32 and U.shape == (8, 6144 * 7 + 2 * 1536 * 3) and V.shape == (8, 64 * 13)
+    assert U.min() >= -16 and U.max() <= 15 and np.array_equal(U, np.round(U)) and np.abs(U).max() > 0
+    assert all(np.array_equal(dumps[0][n], dumps[1][n]) for n in ("U", "V"))
 
 
 def test_two_ranks_real_encoder_equal_single_process(tmp_path):

@@ -11,19 +11,19 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --config clic --steps 5 --warmup 1 > $OUT/bench_clic.json 2> $OUT/bench_clic.err
-python bench.py --config svd --steps 5 --warmup 1 > $OUT/bench_svd.json 2> $OUT/bench_svd.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --config clic --steps 5 --warmup 1 > $OUT/bench_clic.json 2> $OUT/bench_clic.err
+python bench.py --full --config svd --steps 5 --warmup 1 > $OUT/bench_svd.json 2> $OUT/bench_svd.err
 python tools/run_config3_fused.py $OUT/config3_fused.json > $OUT/config3_fused.txt 2> $OUT/config3_fused.err
 LRF_SWEEP_BATCH=256 python3 $REPO/tools/dev_rank_sweep.py > $OUT/rank_sweep256.txt 2> $OUT/rank_sweep256.err
 python3 $REPO/tools/dev_rank_sweep.py > $OUT/rank_sweep64.txt 2> $OUT/rank_sweep64.err
 cd /tmp
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o run -- python3 $REPO/bench.py --no-cpu-baseline > $OUT/stats_bench.json 2> $OUT/stats.err
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_plain -o run -- python3 $REPO/bench.py --no-extras > $OUT/stats_plain_bench.json 2> $OUT/stats_plain.err
-rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o run -- python3 $REPO/bench.py --no-extras --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_fetch.err
-rocprofv3 --output-format csv --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o run -- python3 $REPO/bench.py --no-extras --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_write.err
-rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU GRBM_GUI_ACTIVE -d $OUT/sq_a -o run -- python3 $REPO/bench.py --no-extras --steps 2 --warmup 1 > /dev/null 2> $OUT/sq_a.err
-rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $OUT/sq_b -o run -- python3 $REPO/bench.py --no-extras --steps 2 --warmup 1 > /dev/null 2> $OUT/sq_b.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats -o run -- python3 $REPO/bench.py --full --no-cpu-baseline > $OUT/stats_bench.json 2> $OUT/stats.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_plain -o run -- python3 $REPO/bench.py --full --no-extras > $OUT/stats_plain_bench.json 2> $OUT/stats_plain.err
+rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o run -- python3 $REPO/bench.py --full --no-extras --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_fetch.err
+rocprofv3 --output-format csv --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o run -- python3 $REPO/bench.py --full --no-extras --steps 2 --warmup 1 > /dev/null 2> $OUT/pmc_write.err
+rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU GRBM_GUI_ACTIVE -d $OUT/sq_a -o run -- python3 $REPO/bench.py --full --no-extras --steps 2 --warmup 1 > /dev/null 2> $OUT/sq_a.err
+rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $OUT/sq_b -o run -- python3 $REPO/bench.py --full --no-extras --steps 2 --warmup 1 > /dev/null 2> $OUT/sq_b.err
 export LRF_SWEEP_BATCH=256
 for t in 16,8,8 26,13,13; do
   n=$(echo $t | tr , _)
@@ -33,8 +33,8 @@ for t in 16,8,8 26,13,13; do
   rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU GRBM_GUI_ACTIVE -d $OUT/sq_a_r$n -o run -- python3 $REPO/tools/dev_rank_sweep.py $t > /dev/null 2> $OUT/sq_a_r$n.err
 done
 unset LRF_SWEEP_BATCH
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_svd -o run -- python3 $REPO/bench.py --config svd --steps 3 --warmup 1 > /dev/null 2> $OUT/stats_svd.err
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_clic -o run -- python3 $REPO/bench.py --config clic --steps 3 --warmup 1 --no-extras > /dev/null 2> $OUT/stats_clic.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_svd -o run -- python3 $REPO/bench.py --full --config svd --steps 3 --warmup 1 > /dev/null 2> $OUT/stats_svd.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_clic -o run -- python3 $REPO/bench.py --full --config clic --steps 3 --warmup 1 --no-extras > /dev/null 2> $OUT/stats_clic.err
 cd $REPO
 python tools/bench_anyshape.py 256 20 > $OUT/anyshape.txt 2> $OUT/anyshape.err
 python tools/make_traffic.py $OUT/pmc_fetch $OUT/pmc_write > $OUT/traffic.json
