@@ -93,7 +93,7 @@ int bcdp_launch(lrf_ctx* c, const PersistPlan& pp, const float* X, const PlaneDe
     long wgs = (total_waves + LRF_BCDW_WAVES - 1) / LRF_BCDW_WAVES;
     if (wgs > 512) wgs = 512; // two workgroups per CU resident; later ones would only find the queue empty
     // LDS per wave: the largest share a family of the call needs
-    int wave_lds = (64 * 64 + 64 * 8) * 4; // ranks <= 8 (LRF_BCDW_LDS / LRF_BCDW_WAVES)
+    int wave_lds = (64 * 64 + 64 * 8) * 4 + LRF_BCDP_USTAGE; // ranks <= 8: X tile, u tile, U-span staging (18.5 KB: 8 waves per CU)
     if (pp.f16 && LRF_BCDW16_WAVE_LDS > wave_lds) wave_lds = LRF_BCDW16_WAVE_LDS;
     const BcdpTabs t16{f16.vf, f16.bf, f16.pp, f16.qp, f16.wf}, t64{f64.vf, f64.bf, f64.pp, f64.qp, f64.wf};
     gp.exact_int = 1;

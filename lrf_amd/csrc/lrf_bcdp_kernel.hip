@@ -50,29 +50,39 @@ struct BcdpTabs {
     const float* wf; // the initialisation's W0 = V0 / sigma (k_bcd_p<.., .., true>: the first iteration's old U is X @ W0)
 };
 
-__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// (address-space-1 pointers: `global_` instructions, never `flat_`)
+__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load((const LRF_GLOBAL float*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_sc1(float* p, float v)
 {
 #ifdef LRF_BCDP_PLAIN_PSTORE // timing experiment only
     *p = v;
 #else
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store((LRF_GLOBAL float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
 }
-__device__ __forceinline__ void st_sc1_u32_unaligned(void* p, unsigned v)
+// 16-B sc1 load at byte offset `off` from a WAVE-UNIFORM base: buffer_load_dwordx4 ... sc1 (aux bit 4 = sc1 on gfx950; a
+// compiler-tracked load, so its result is waited for where it is used).  The raw buffer is unbounded (DATA_FORMAT 32).
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x4 ld_sc1_x4u(const void* base, unsigned off)
 {
-#ifdef LRF_BCDP_PLAIN_USTORE // timing experiment only
-    *reinterpret_cast<u32_unaligned*>(p) = v;
-#else
-    asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#endif
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, 0x7fffffff, 0x00020000);
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16));
 }
-__device__ __forceinline__ unsigned ld_sc1_u32_unaligned(const void* p) // the caller waits (s_waitcnt vmcnt(0)) before the use
-{
-    unsigned v;
-    asm volatile("global_load_dword %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-    return v;
-}
+__device__ __forceinline__ f32x4 ld_sc1_x4(const float* base, unsigned off) { return __builtin_bit_cast(f32x4, ld_sc1_x4u(base, off)); }
+// sc1 stores of 16, 8, 4, 2, 1 bytes at a naturally aligned address (no result register: a hand-issued store is safe; the
+// wave's `s_waitcnt vmcnt(0)` before its ticket covers them)
+__device__ __forceinline__ void st_sc1_x4(void* p, u32x4 v) { asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
+__device__ __forceinline__ void st_sc1_x2(void* p, u32x2 v) { asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
+__device__ __forceinline__ void st_sc1_b32(void* p, unsigned v) { asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
+__device__ __forceinline__ void st_sc1_b16(void* p, unsigned v) { asm volatile("global_store_short %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
+__device__ __forceinline__ void st_sc1_b8(void* p, unsigned v) { asm volatile("global_store_byte %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
+
+// ranks <= 8: a block's partial slot (bcdp_w_block -> bcdp_vupdate) is DENSE at the plane's rank: P^T as [R][64] (entry (r, n) =
+// sum over the block's rows of u_r x_n), then b' = U^T U as [R][R]; 64 R + R R floats, stored as whole 16-B chunks (the slot
+// stride stays 64 LRF_RP floats: the padding of the last chunk lies inside the slot)
+__device__ __forceinline__ int bcdp_dense_chunks(int R) { return (64 * R + R * R + 3) >> 2; }
+#define LRF_BCDP_USTAGE 544 // bytes per wave: a 64-row U span (<= 512 B) at its address's phase mod 16, plus a 16-B read past it
 
 // ---- V updates on ONE wave (lane = row of V).  lds: the wave's own share (>= 17 KB) --------------------------------------------
 // a' = ((P0 + P1) + P2) + ... per element, b' likewise, at rank pitch 16: element e of the [64][16] table = lane + 64 j
@@ -114,32 +124,71 @@ __device__ __forceinline__ void bcdp_wave_sync() // LDS written by some lanes is
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// ranks <= 8: k_vupdate<8> (a_s [64][16], v_s [64][16], gt_s)
-__device__ __forceinline__ void bcdp_vupdate(const PlaneDesc& pd, int pli, const float* __restrict__ Ppart, const float* __restrict__ Qpart,
-                                             float* __restrict__ Vf, float* __restrict__ Bf, int8_t* __restrict__ V8, const GsParams gp,
-                                             int write_i8, float* lds, int lane)
+// ranks <= 8: the dense slots of the plane's blocks summed per element in block order (((P0 + P1) + P2) + ..., as bcdp_sum16)
+// into sum_s (LDS, 16-B aligned): chunk c = lane + 64 j (j < 3: 64 R + R R <= 576 floats) of every slot, four blocks' loads
+// in flight at a time (48 registers)
+__device__ __forceinline__ void bcdp_sum_dense(const PlaneDesc& pd, const float* __restrict__ Ppart, int lane, float* sum_s)
+{
+    const int nch = bcdp_dense_chunks(pd.R), nj = (nch + 63) >> 6;
+    const float* base = Ppart + (long)pd.blk0 * 64 * LRF_RP;
+    f32x4 acc[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    constexpr int NB = 4;
+    for (int b0 = 0; b0 < pd.nblk; b0 += NB) {
+        f32x4 pv[NB][3];
+#pragma unroll
+        for (int k = 0; k < NB; k++) {
+            const unsigned blk = b0 + k < pd.nblk ? b0 + k : b0;
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const int c = lane + 64 * j < nch ? lane + 64 * j : nch - 1; // (inside the slot)
+                if (j < nj) pv[k][j] = ld_sc1_x4(base, (blk * 64 * LRF_RP + 4 * c) * 4);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NB; k++)
+            if (b0 + k < pd.nblk) {
+#pragma unroll
+                for (int j = 0; j < 3; j++)
+                    if (j < nj) acc[j] = (b0 + k == 0) ? pv[k][j] : acc[j] + pv[k][j];
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+        if (lane + 64 * j < nch) *reinterpret_cast<f32x4*>(&sum_s[4 * (lane + 64 * j)]) = acc[j];
+}
+
+// ranks <= 8: k_vupdate<8> (a_s [64][16], v_s [64][16], gt_s; sum_s: the summed dense slot)
+__device__ __forceinline__ void bcdp_vupdate(const PlaneDesc& pd, int pli, const float* __restrict__ Ppart, float* __restrict__ Vf,
+                                             float* __restrict__ Bf, int8_t* __restrict__ V8, const GsParams gp, int write_i8, float* lds, int lane)
 {
     float* a_s = lds;
     float* v_s = lds + 64 * LRF_RP;
     float* gt_s = lds + 2 * 64 * LRF_RP;
+    float* sum_s = gt_s + LRF_GT_STRIDE; // [R][64] then [R][R] (16-B aligned)
     const int R = pd.R;
-    float acc[16], q[4];
-    bcdp_sum16(pd, Ppart, Qpart, lane, acc, q);
+    bcdp_sum_dense(pd, Ppart, lane, sum_s);
+    const float* Vg = Vf + (long)pli * 64 * LRF_RP;
+#pragma unroll
+    for (int j = 0; j < 4; j++) *reinterpret_cast<f32x4*>(&v_s[4 * (lane + 64 * j)]) = ld_sc1_x4(Vg, 16 * (lane + 64 * j));
+    bcdp_wave_sync();
 #pragma unroll
     for (int j = 0; j < 16; j++) {
-        a_s[lane + 64 * j] = acc[j];
-        v_s[lane + 64 * j] = ld_sc1(Vf + (long)pli * 64 * LRF_RP + lane + 64 * j);
+        const int idx = lane + 64 * j, n = idx >> 4, r = idx & 15; // a' entry (n, r)
+        a_s[idx] = r < R ? sum_s[r * 64 + n] : 0.f;
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int idx = lane + 64 * j, jj = idx >> 4, r = idx & 15; // b' entry (jj, r)
         if (jj < R && r < R) {
+            const float q = sum_s[64 * R + jj * R + r];
             if (jj == r) {
-                const float den = (q[j] + 0.f) + LRF_EPS;
+                const float den = (q + 0.f) + LRF_EPS;
                 gt_s[r * LRF_GT_LD + LRF_GT_DEN] = den;
                 gt_s[r * LRF_GT_LD + LRF_GT_RDEN] = 1.0f / den;
             } else {
-                gt_s[r * LRF_GT_LD + (jj < r ? jj : jj - 1)] = q[j];
+                gt_s[r * LRF_GT_LD + (jj < r ? jj : jj - 1)] = q;
             }
         }
     }
@@ -168,7 +217,8 @@ __device__ __forceinline__ void bcdp_vupdate(const PlaneDesc& pd, int pli, const
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         float* gt_g = Bf + (long)pli * LRF_GT_STRIDE;
-        for (int i = lane; i < R * LRF_GT_LD; i += 64) st_sc1(gt_g + i, gt_n[i]);
+        static_assert(LRF_GT_LD % 4 == 0, "the b table goes out in 16-B chunks");
+        for (int i = 4 * lane; i < R * LRF_GT_LD; i += 256) st_sc1_x4(gt_g + i, *reinterpret_cast<const u32x4*>(&gt_n[i]));
     }
 }
 
@@ -341,13 +391,13 @@ __device__ __forceinline__ void bcdp_vupdate32(const PlaneDesc& pd, int pli, con
 
 // ---- ranks <= 8: one (matrix, 384-row block) on one wave — k_bcd_w<0> (lrf_bcdw_kernel.hip) operation for operation, with the
 // V table, the b table, the old int8 rows and the partial tables reached through sc1 accesses.  Xs: the wave's LDS share
-// (X tile 16 KB, then the fp32 u tile 2 KB).
+// (X tile 16 KB, then the fp32 u tile 2 KB, then the U-span staging area, LRF_BCDP_USTAGE bytes).
 // MODE 1 (round 5, k_bcd_p<.., .., true>): the call's FIRST iteration, k_bcd_w<1> — the old U is X @ W0 (the initialisation's
 // table Wf, written before the launch), no int8 rows are read.
 template <int MODE>
 __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const PlaneDesc& pd, const BlockDesc& bd, const float* __restrict__ Vf,
                                              const float* __restrict__ Wf, const float* __restrict__ Bf, int8_t* __restrict__ U, float* __restrict__ Ppart,
-                                             float* __restrict__ Qpart, const GsParams& gp, float* Xs, const int lane)
+                                             const GsParams& gp, float* Xs, const int lane)
 {
     constexpr int RMAX = 8;
     const int li = lane & 15, lq = lane >> 4;
@@ -369,21 +419,35 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
     const int nsub = (nrows + 63) >> 6;
     const bool native = pd.native_t2_u != 0;
 
+    // the V table: row 16 kb + li, columns 0..7 = two 16-B chunks; the b table: entry tn < 7 of row tr, or its reciprocal
+    // denominator (tn = 7), picked out of the 16-B chunk that holds it; the denominator from the chunk at LRF_GT_RDEN
     float vreg[8][4], wreg[MODE == 1 ? 8 : 1][4];
 #pragma unroll
-    for (int r = 0; r < 8; r++)
+    for (int kb = 0; kb < 4; kb++)
 #pragma unroll
-        for (int kb = 0; kb < 4; kb++) {
-            vreg[r][kb] = ld_sc1(Vp + (16 * kb + li) * LRF_RP + r);
-            if constexpr (MODE == 1) wreg[r][kb] = Wf[((long)bd.plane * 64 + 16 * kb + li) * LRF_RP + r];
+        for (int h = 0; h < 2; h++) {
+            const f32x4 v4 = ld_sc1_x4(Vp, ((16 * kb + li) * LRF_RP + 4 * h) * 4);
+#pragma unroll
+            for (int c = 0; c < 4; c++) vreg[4 * h + c][kb] = v4[c];
         }
-    float tab[5];
+    if constexpr (MODE == 1) {
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int ci = 16 * j + li, tr = ci >> 3, tn = ci & 7;
-        tab[j] = ld_sc1(gt + tr * LRF_GT_LD + (tn < 7 ? tn : LRF_GT_RDEN));
+        for (int r = 0; r < 8; r++)
+#pragma unroll
+            for (int kb = 0; kb < 4; kb++) wreg[r][kb] = Wf[((long)bd.plane * 64 + 16 * kb + li) * LRF_RP + r];
     }
-    tab[4] = ld_sc1(gt + (li & 7) * LRF_GT_LD + LRF_GT_DEN);
+    static_assert(LRF_GT_LD % 4 == 0 && LRF_GT_RDEN % 4 == 0 && LRF_GT_DEN == LRF_GT_RDEN + 1, "b-table chunks");
+    float tab[5];
+    {
+        const int tn = li & 7, e = tn < 7 ? (tn & 3) : 0;
+        f32x4 t4[5];
+#pragma unroll
+        for (int j = 0; j < 4; j++) t4[j] = ld_sc1_x4(gt, ((2 * j + (li >> 3)) * LRF_GT_LD + (tn < 7 ? (tn & 4) : LRF_GT_RDEN)) * 4);
+        t4[4] = ld_sc1_x4(gt, ((li & 7) * LRF_GT_LD + LRF_GT_RDEN) * 4);
+#pragma unroll
+        for (int j = 0; j < 4; j++) tab[j] = e == 0 ? t4[j][0] : e == 1 ? t4[j][1] : e == 2 ? t4[j][2] : t4[j][3];
+        tab[4] = t4[4][1];
+    }
 
     f32x4 xq[4][4];
     auto issue_x = [&](int t, int T0, int T1, bool live) {
@@ -399,31 +463,39 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
             }
         }
     };
-    // The old int8 row with compiler-tracked sc1 loads: three ALIGNED dwords that cover the row's R <= 8 bytes (a hand-issued
-    // asm load would leave its result register open to compiler copies before the data has landed); row_bytes() shifts
-    // them into place.  The last dword is clamped to the one that holds the row's last byte (never past the allocation).
-    unsigned uraw[3];
-    int ush = 0;
-    auto issue_u = [&](int t) {
-        int row = t * 64 + lane;
-        row = row < nrows ? row : nrows - 1;
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(Ub + (long)row * R);
-        const uintptr_t base = a0 & ~(uintptr_t)3, last = (a0 + R - 1) & ~(uintptr_t)3;
-        ush = (int)(a0 & 3);
-        const unsigned* p0 = reinterpret_cast<const unsigned*>(base);
-        const unsigned* p1 = reinterpret_cast<const unsigned*>(base + 4 <= last ? base + 4 : last);
-        const unsigned* p2 = reinterpret_cast<const unsigned*>(base + 8 <= last ? base + 8 : last);
-#ifdef LRF_BCDP_PLAIN_U
-        uraw[0] = *p0; uraw[1] = *p1; uraw[2] = *p2;
-#else
-        uraw[0] = __hip_atomic_load(p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uraw[1] = __hip_atomic_load(p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uraw[2] = __hip_atomic_load(p2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
+    // int8 U rows as whole spans: the 64 rows of sub-tile t are ONE contiguous span of the wave's own, bytes [a, a + len) with
+    // a = Ub + 64 R t.  It passes through the wave's LDS staging area `ust` at the address's phase (span byte i at a % 16 + i),
+    // so that 16-B slot k of the staging area is the naturally aligned 16 bytes at (a & ~15) + 16 k; lane k < nslots moves slot k.
+    //   old rows: lane k loads slot k with a compiler-tracked 16-B sc1 load one sub-tile ahead (a slot holds a byte of the span:
+    //   never past the allocation's last aligned 16 bytes), lands it in staging, and every lane reads its row from there;
+    //   new rows: every lane writes its R bytes to staging, and lane k stores the span's bytes of slot k — 16-B sc1 stores, and
+    //   at an unaligned head or tail naturally aligned 8/4/2/1-byte sc1 stores that stay INSIDE the span (the bytes beside it
+    //   belong to other waves' spans, written at the same time).
+    uint8_t* ust = reinterpret_cast<uint8_t*>(Xs + 64 * 64 + 64 * RMAX);
+    const uintptr_t uaddr = reinterpret_cast<uintptr_t>(Ub);
+    const uint8_t* ub16 = reinterpret_cast<const uint8_t*>(uaddr & ~(uintptr_t)15); // wave-uniform base of the old-row loads
+    auto span_of = [&](int t, uintptr_t& a, int& len, int& nsl) {
+        a = uaddr + (uintptr_t)(64 * R * t);
+        const int nr = nrows - 64 * t;
+        len = (nr < 64 ? nr : 64) * R;
+        nsl = ((int)(a & 15) + len + 15) >> 4;
     };
-    auto row_bytes = [&](unsigned& lo, unsigned& hi) { // bytes 0..3 and 4..7 of the row (bytes at or past R: unspecified)
-        lo = __builtin_amdgcn_alignbyte(uraw[1], uraw[0], (unsigned)ush);
-        hi = __builtin_amdgcn_alignbyte(uraw[2], uraw[1], (unsigned)ush);
+    u32x4 uvec;
+    int unsl = 0, uph = 0; // the loaded span's slot count and phase
+    auto issue_u = [&](int t) {
+        uintptr_t a;
+        int len;
+        span_of(t, a, len, unsl);
+        uph = (int)(a & 15);
+        const int k = lane < unsl ? lane : unsl - 1;
+        uvec = ld_sc1_x4u(ub16, (unsigned)((a & ~(uintptr_t)15) - reinterpret_cast<uintptr_t>(ub16)) + 16 * k);
+    };
+    auto row_bytes = [&](int ph, unsigned& lo, unsigned& hi) { // the lane's row in staging: bytes 0..3, 4..7 (at or past R: unspecified)
+        const int o = ph + lane * R; // <= 15 + 63 * 8: the three aligned dwords end inside the staging area
+        const unsigned* w = reinterpret_cast<const unsigned*>(ust + (o & ~3));
+        const unsigned w0 = w[0], w1 = w[1], w2 = w[2];
+        lo = __builtin_amdgcn_alignbyte(w1, w0, (unsigned)(o & 3));
+        hi = __builtin_amdgcn_alignbyte(w2, w1, (unsigned)(o & 3));
     };
 
     f32x4 accP[4], accQ = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -444,14 +516,10 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
             }
         float u[RMAX];
         const int row = r0 + lane;
+        int cph = 0;
         if constexpr (MODE == 0) {
-            unsigned lo, hi;
-            row_bytes(lo, hi);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                u[r] = (float)(int)(int8_t)(lo >> (8 * r));
-                u[4 + r] = (float)(int)(int8_t)(hi >> (8 * r));
-            }
+            if (lane < unsl) *reinterpret_cast<u32x4*>(ust + 16 * lane) = uvec;
+            cph = uph;
         }
         const int tn = t + 1;
         const bool more = tn < nsub;
@@ -462,6 +530,15 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if constexpr (MODE == 0) {
+            unsigned lo, hi;
+            row_bytes(cph, lo, hi);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                u[r] = (float)(int)(int8_t)(lo >> (8 * r));
+                u[4 + r] = (float)(int)(int8_t)(hi >> (8 * r));
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         float a[RMAX];
 #pragma unroll
@@ -483,27 +560,46 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int r = 0; r < RMAX; r += 4) *reinterpret_cast<f32x4*>(&us[lane * RMAX + r]) = (f32x4){u[r], u[r + 1], u[r + 2], u[r + 3]};
+        // the new row into staging (the old span there has been read: every lane's row_bytes is behind it)
+        uintptr_t sa;
+        int slen, snsl;
+        span_of(t, sa, slen, snsl);
+        const int sph = (int)(sa & 15);
         if (row < nrows) {
-            int8_t* uo = Ub + (long)row * R;
-            unsigned lo = 0, hi = 0;
+            uint8_t* d = ust + sph + lane * R;
 #pragma unroll
-            for (int r = 0; r < 4; r++) {
-                lo |= ((unsigned)(int)u[r] & 0xffu) << (8 * r);
-                hi |= ((unsigned)(int)u[4 + r] & 0xffu) << (8 * r);
-            }
-            if (R >= 4) {
-                st_sc1_u32_unaligned(uo, lo);
-                const unsigned long long w = ((unsigned long long)hi << 32) | lo;
-                st_sc1_u32_unaligned(uo + R - 4, (unsigned)(w >> (8 * (R - 4))));
-            } else {
-                __hip_atomic_store(uo, (int8_t)lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (R > 1) __hip_atomic_store(uo + 1, (int8_t)(lo >> 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (R > 2) __hip_atomic_store(uo + 2, (int8_t)(lo >> 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            for (int r = 0; r < RMAX; r++)
+                if (r < R) d[r] = (uint8_t)(int)u[r];
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (lane < snsl) { // slot `lane` of the span: bytes [lo, hi) of the aligned 16 at s
+            const uintptr_t s0 = (sa & ~(uintptr_t)15) + 16 * lane;
+            const uint8_t* src = ust + 16 * lane;
+            int lo = lane == 0 ? sph : 0;
+            const int hi = lane == snsl - 1 ? sph + slen - 16 * lane : 16;
+            if (lo == 0 && hi == 16) {
+                st_sc1_x4(reinterpret_cast<void*>(s0), *reinterpret_cast<const u32x4*>(src));
+            } else {
+                while (lo < hi) { // naturally aligned pieces inside [lo, hi)
+                    void* dst = reinterpret_cast<void*>(s0 + lo);
+                    if ((lo & 7) == 0 && lo + 8 <= hi) {
+                        st_sc1_x2(dst, *reinterpret_cast<const u32x2*>(src + lo));
+                        lo += 8;
+                    } else if ((lo & 3) == 0 && lo + 4 <= hi) {
+                        st_sc1_b32(dst, *reinterpret_cast<const unsigned*>(src + lo));
+                        lo += 4;
+                    } else if ((lo & 1) == 0 && lo + 2 <= hi) {
+                        st_sc1_b16(dst, *reinterpret_cast<const uint16_t*>(src + lo));
+                        lo += 2;
+                    } else {
+                        st_sc1_b8(dst, src[lo]);
+                        lo += 1;
+                    }
+                }
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         float pu[16], qu[8];
 #pragma unroll
@@ -527,20 +623,28 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
-    const long slot = (long)pd.blk0 + bd.blk;
-    float* Pp = Ppart + slot * 64 * LRF_RP;
+    // the dense slot (bcdp_dense_chunks) through the X tile's LDS, which the loop's closing barrier has freed: lane (li, lq)
+    // holds P[16 lq + 4 reg + c][li] in accP[c][reg], i.e. the 16 B of P^T row li at column 16 lq + 4 reg; b' entry
+    // (4 lq + reg, li) = mine + other.  Then whole 16-B chunks out, consecutive lanes on consecutive chunks.
+    float* ps = Xs;
+    if (li < R) {
 #pragma unroll
-    for (int c = 0; c < 4; c++)
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++) st_sc1(Pp + (4 * (4 * lq + reg) + c) * LRF_RP + li, accP[c][reg]);
-    float* Qp = Qpart + slot * LRF_RP * LRF_RP;
+        for (int reg = 0; reg < 4; reg++)
+            *reinterpret_cast<f32x4*>(&ps[li * 64 + 16 * lq + 4 * reg]) = (f32x4){accP[0][reg], accP[1][reg], accP[2][reg], accP[3][reg]};
+    }
 #pragma unroll
     for (int reg = 0; reg < 4; reg++) {
         const int i = 4 * lq + reg;
         const float mine = accQ[reg];
         const float other = __shfl(mine, ((lq + 2) & 3) * 16 + ((li + 8) & 15), 64);
-        st_sc1(Qp + i * LRF_RP + li, (i < 8 && li < 8) ? mine + other : 0.f);
+        if (i < R && li < R) ps[64 * R + i * R + li] = mine + other;
     }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float* Pp = Ppart + ((long)pd.blk0 + bd.blk) * 64 * LRF_RP;
+    const int nch = bcdp_dense_chunks(R);
+    for (int c = lane; c < nch; c += 64) st_sc1_x4(Pp + 4 * c, *reinterpret_cast<const u32x4*>(&ps[4 * c]));
 }
 
 // F16: planes of ranks 9..16 may occur (w16_block); NP32 > 0: planes of ranks 2 NP32 - 1 / 2 NP32 (17..32) may occur
@@ -631,9 +735,9 @@ __global__ __launch_bounds__(64 * LRF_BCDW_WAVES) __attribute__((amdgpu_waves_pe
         const bool first = FIRST && it == 0; // wave-uniform
         if (fam == 0) {
             if (first) {
-                if constexpr (FIRST) bcdp_w_block<1>(X, pd, bd, t16.vf, t16.wf, t16.bf, U, t16.pp, t16.qp, gp, Xs, ln);
+                if constexpr (FIRST) bcdp_w_block<1>(X, pd, bd, t16.vf, t16.wf, t16.bf, U, t16.pp, gp, Xs, ln);
             } else
-                bcdp_w_block<0>(X, pd, bd, t16.vf, nullptr, t16.bf, U, t16.pp, t16.qp, gp, Xs, ln);
+                bcdp_w_block<0>(X, pd, bd, t16.vf, nullptr, t16.bf, U, t16.pp, gp, Xs, ln);
         }
         if constexpr (F16) {
             if (fam == 1) {
@@ -665,7 +769,7 @@ __global__ __launch_bounds__(64 * LRF_BCDW_WAVES) __attribute__((amdgpu_waves_pe
             const int last = it == niter - 1 ? 1 : 0;
             int lv = lane;
             asm volatile("" : "+v"(lv)); // (as `ln` above)
-            if (fam == 0) bcdp_vupdate(pd, bd.plane, t16.pp, t16.qp, t16.vf, t16.bf, V8, gp, last, Xs, lv);
+            if (fam == 0) bcdp_vupdate(pd, bd.plane, t16.pp, t16.vf, t16.bf, V8, gp, last, Xs, lv);
             if constexpr (F16) {
                 if (fam == 1) bcdp_vupdate16(pd, bd.plane, t16.pp, t16.qp, t16.vf, t16.bf, V8, gp, last, Xs, lv);
             }

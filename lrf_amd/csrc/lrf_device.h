@@ -153,15 +153,21 @@ struct MemLaunch {
     static __device__ __forceinline__ void st_u32(void* p, unsigned v) { *reinterpret_cast<u32_unaligned*>(p) = v; } // any alignment
     static __device__ __forceinline__ void st_u8(int8_t* p, int8_t v) { *p = v; }
 };
+//              The accesses go through address-space-1 pointers: `global_` instructions, never `flat_` (only `global_` / `buffer_`
+//              sc1 loads may stand in for the acquire).
+#define LRF_GLOBAL __attribute__((address_space(1)))
 struct MemSc1 {
     static constexpr bool kSc1 = true;
-    static __device__ __forceinline__ float ld(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    static __device__ __forceinline__ unsigned ld_u32(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    static __device__ __forceinline__ void st(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    static __device__ __forceinline__ float ld(const float* p) { return __hip_atomic_load((const LRF_GLOBAL float*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    static __device__ __forceinline__ unsigned ld_u32(const unsigned* p)
+    {
+        return __hip_atomic_load((const LRF_GLOBAL unsigned*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    static __device__ __forceinline__ void st(float* p, float v) { __hip_atomic_store((LRF_GLOBAL float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     static __device__ __forceinline__ void st_u32(void* p, unsigned v) // any alignment (an atomic store wants four)
     {
         asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
     }
-    static __device__ __forceinline__ void st_u8(int8_t* p, int8_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    static __device__ __forceinline__ void st_u8(int8_t* p, int8_t v) { __hip_atomic_store((LRF_GLOBAL int8_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 };
 #endif
