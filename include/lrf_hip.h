@@ -84,7 +84,8 @@ int lrf_ctx_trim(lrf_ctx* ctx);
 #define LRF_K_GRAM 5         /* exact Gram matrices (input of the SVD initialisation) */
 #define LRF_K_BCD_PERSIST 6  /* the iterations of a large call in ONE launch (k_bcd_p: U updates + V updates) */
 #define LRF_K_PLANES_GRAM 7  /* rgb -> patch matrices + the luma planes' exact Gram partials in one kernel (k_planes16_gram: large calls) */
-#define LRF_K_COUNT 8
+#define LRF_K_METRICS 8      /* squared error + SSIM of image pairs (lrf_image_metrics_u8: its whole launch sequence counts as one) */
+#define LRF_K_COUNT 9
 int lrf_ctx_profile(lrf_ctx* ctx, int enable);
 /* The same for a subset of the kernels: bit (1 << LRF_K_x) per kernel id, 0 = off.  An event pair costs a few
  * microseconds of stream time per launch (0.15 ms per 22-launch encode when every kernel is timed); bench.py times
@@ -220,6 +221,26 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* ctx, const uint8_t* rgb, int64_t B, int
  */
 int lrf_qmf_decode_rgb_u8(lrf_ctx* ctx, const int8_t* U, const int8_t* V, int64_t B, int64_t H, int64_t W,
                           const int R[3], uint8_t* rgb);
+
+/* ---- scoring (the third stage of the reference's experiment loop) ----------------------------- */
+
+/*
+ * Squared error and SSIM of B pairs of uint8 images, a [B,C,H,W] against b [B,C,H,W] (contiguous, device memory): what
+ * lrf/utils/misc.py:107-108 computes per image on the host with lrf/utils/metrics.py:57-71 (psnr) and :74-91 (ssim, through
+ * scikit-image's structural_similarity(channel_axis=0, data_range=img1.max() - img1.min())).
+ *   sse  [B]  sum over the C*H*W samples of (a - b)^2, an exact integer (PSNR = 20 log10(max_value / sqrt(sse / (C H W))) is the
+ *             caller's one line)
+ *   ssim [B]  float64, or NULL to skip the SSIM work: 7x7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance (49/48),
+ *             data_range = max - min of a's image (per image), S averaged over the window positions that lie wholly inside the
+ *             image (rows 3 .. H-4, columns 3 .. W-4 of every channel), then the mean of the C channel means.  The window sums
+ *             are exact integers; float64 enters with the four brackets of S, and one division per window.  A constant first
+ *             image (data_range 0) gives what the host formula gives: NaN wherever b's window is constant too.
+ * Deterministic, and an image's results do not depend on B or on its place in the batch (no floating-point atomics: one
+ * partial sum per tile of 24 x 64 window positions, added in a fixed order).  Asynchronous on the context's stream.
+ * LRF_EINVAL: NULL a / b / sse, B or C < 1, B > 65535, H or W < 7 when ssim is asked for (the reference raises ValueError).
+ */
+int lrf_image_metrics_u8(lrf_ctx* ctx, const uint8_t* a, const uint8_t* b, int B, int C, int H, int W, uint64_t* sse /* [B] */,
+                         double* ssim /* [B] or NULL */);
 
 /* ---- the SVD baseline ------------------------------------------------- */
 

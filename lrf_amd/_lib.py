@@ -10,10 +10,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblrf_hip.so")
 
 LRF_MAX_RANK = 64
-LRF_K_PLANES, LRF_K_INIT, LRF_K_BCD, LRF_K_VUPDATE, LRF_K_DECODE, LRF_K_GRAM, LRF_K_BCD_PERSIST, LRF_K_PLANES_GRAM = range(8)
+LRF_K_PLANES, LRF_K_INIT, LRF_K_BCD, LRF_K_VUPDATE, LRF_K_DECODE, LRF_K_GRAM, LRF_K_BCD_PERSIST, LRF_K_PLANES_GRAM, LRF_K_METRICS = range(9)
 KERNEL_NAMES = {LRF_K_PLANES: "k_planes", LRF_K_GRAM: "k_gram", LRF_K_INIT: "k_init", LRF_K_BCD: "k_bcd",
                 LRF_K_VUPDATE: "k_vupdate", LRF_K_DECODE: "k_decode", LRF_K_BCD_PERSIST: "k_bcd_persist",
-                LRF_K_PLANES_GRAM: "k_planes_gram"}
+                LRF_K_PLANES_GRAM: "k_planes_gram", LRF_K_METRICS: "k_metrics"}
 
 _lib = None
 _lock = threading.Lock()
@@ -76,6 +76,7 @@ def load():
                                                     c_int, c_void_p, c_void_p, c_void_p]
         lib.lrf_qmf_decode_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, ctypes.POINTER(c_int),
                                               c_void_p]
+        lib.lrf_image_metrics_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
         lib.lrf_svd_encode_rgb_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.lrf_svd_decode_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p]
         lib.lrf_qmf_rgbspace_encode_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p,
@@ -119,7 +120,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_image_metrics_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -180,6 +181,22 @@ def rgbspace_dims_any(H, W, patch_size):
     v = [c_i64() for _ in range(4)]
     check(load().lrf_rgbspace_dims_any(H, W, p, q, *[ctypes.byref(x) for x in v]))
     return tuple(int(x.value) for x in v)
+
+
+def check_metrics_args(a, b, want_ssim=True):
+    """The argument checks of lrf_image_metrics_u8 on two tensors, before any device is touched: TypeError for anything but
+    uint8 tensors, ValueError for shapes that are not one [B,C,H,W] (B, C >= 1) or too small for the 7x7 window."""
+    import torch
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError(f"image metrics take uint8 tensors, got {t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"Input images must have the same (B, C, H, W) shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, C, H, W = a.shape
+    if B < 1 or C < 1 or H < 1 or W < 1 or B > 65535:
+        raise ValueError(f"shape {tuple(a.shape)} out of range")
+    if want_ssim and min(H, W) < 7:
+        raise ValueError("win_size exceeds image extent.")
 
 
 def _dptr(t):
@@ -399,6 +416,21 @@ class Context:
         check(self._lib.lrf_qmf_decode_rgb_u8(self._h, _dptr(U), _dptr(V), B, H, W, R, _dptr(rgb)))
         return rgb
 
+    def image_metrics(self, a, b, want_ssim=True):
+        """uint8 CUDA tensors a, b [B,C,H,W] -> (sse int64 [B], ssim float64 [B] or None) on the device (lrf_image_metrics_u8):
+        the exact sum of squared differences and the SSIM `lrf_amd.metrics.ssim(a[i], b[i])` defines, per image"""
+        import torch
+        check_metrics_args(a, b, want_ssim)
+        if not (a.is_cuda and b.is_cuda and a.device == b.device and a.device.index == self.device):
+            raise ValueError(f"image_metrics needs both tensors on cuda:{self.device}, got {a.device} and {b.device}")
+        if not (a.is_contiguous() and b.is_contiguous()):
+            raise ValueError("image_metrics needs contiguous tensors")
+        B, C, H, W = a.shape
+        sse = torch.empty((B,), dtype=torch.int64, device=a.device)
+        ssim = torch.empty((B,), dtype=torch.float64, device=a.device) if want_ssim else None
+        self.use_torch_stream()
+        check(self._lib.lrf_image_metrics_u8(self._h, _dptr(a), _dptr(b), B, C, H, W, _dptr(sse), _dptr(ssim)))
+        return sse, ssim
 
     def planes_any(self, rgb, patch_size, ch, chroma=None):
         """rgb uint8 [B,3,H,W] (CUDA) -> X fp32 [B, M, N] of plane ch for patches (p, q) (None: the plane itself)"""

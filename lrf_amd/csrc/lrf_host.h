@@ -80,6 +80,7 @@ struct lrf_ctx {
     DevBuf gpart, gexp; // exact Gram partials (128-bit integers per chunk) and per-matrix grid exponents (lrf_gram_kernels.hip)
     DevBuf sx, sg, svn, swn, suf, smm; // SVD baseline workspace
     DevBuf any_uf, any_vf, any_a, any_b, any_p, any_e2, any_g, any_td; // any-shape path (lrf_anyshape_host.inc)
+    DevBuf metrics; // lrf_image_metrics_u8: a float64 slot per (image, channel, tile), then (max, 255 - min) per image
     DevBuf vf16, wf16, bf16, pp16, qp16; // the pitch-16 tables of a call that mixes kernel families (plan_runs)
     // host staging for descriptor tables (pinned)
     void* h_stage = nullptr;

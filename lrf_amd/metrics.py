@@ -73,3 +73,41 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
         s = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
         per_channel.append(s[pad:-pad, pad:-pad].mean(dtype=np.float64))
     return torch.tensor(np.mean(per_channel))
+
+
+def image_metrics_batch(img1: torch.Tensor, img2: torch.Tensor, max_value: int = 255, want_ssim: bool = True, device=None) -> dict:
+    """`mse`, `psnr` and `ssim` above for a whole batch of uint8 images on the GPU (lrf_image_metrics_u8, include/lrf_hip.h).
+
+    img1, img2: uint8 [B,C,H,W] or one [C,H,W] pair; host tensors are uploaded.  Returns device tensors of shape [B]:
+    "sse" int64 (the exact sum of squared differences), "mse" = sse / (C H W) and "psnr" = 20 log10(max_value / sqrt(mse))
+    in float64 (inf where the images are equal, as `psnr` gives), "ssim" float64: the quantity `ssim(img1[i], img2[i])` defines
+    (data_range from img1[i]; NaN where it gives NaN), absent with want_ssim=False.  The window sums are exact integers, so the
+    results differ from the host functions by float64 rounding only (and by psnr's float32)."""
+    from . import _lib
+    if isinstance(img1, torch.Tensor) and isinstance(img2, torch.Tensor) and img1.dim() == 3 and img2.dim() == 3:
+        img1, img2 = img1.unsqueeze(0), img2.unsqueeze(0)
+    _lib.check_metrics_args(img1, img2, want_ssim)  # (before a context exists: these refusals need no GPU)
+    if device is None and img1.is_cuda:
+        device = img1.device.index
+    if device is None and img2.is_cuda:
+        device = img2.device.index
+    ctx = _lib.context(device)
+    dev = torch.device("cuda", ctx.device)
+    a, b = img1.to(dev).contiguous(), img2.to(dev).contiguous()
+    sse, s = ctx.image_metrics(a, b, want_ssim=want_ssim)
+    n = a.shape[1] * a.shape[2] * a.shape[3]
+    m = sse.double() / n
+    out = {"sse": sse, "mse": m, "psnr": 20 * torch.log10(max_value / torch.sqrt(m))}
+    if want_ssim:
+        out["ssim"] = s
+    return out
+
+
+def psnr_batch(img1: torch.Tensor, img2: torch.Tensor, max_value: int = 255) -> torch.Tensor:
+    """float64 device tensor [B]: `image_metrics_batch(...)["psnr"]` without the SSIM work"""
+    return image_metrics_batch(img1, img2, max_value=max_value, want_ssim=False)["psnr"]
+
+
+def ssim_batch(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
+    """float64 device tensor [B]: `image_metrics_batch(...)["ssim"]`"""
+    return image_metrics_batch(img1, img2)["ssim"]
