@@ -84,7 +84,8 @@ int lrf_ctx_trim(lrf_ctx* ctx);
 #define LRF_K_GRAM 5         /* exact Gram matrices (input of the SVD initialisation) */
 #define LRF_K_BCD_PERSIST 6  /* the iterations of a large call in ONE launch (k_bcd_p: U updates + V updates) */
 #define LRF_K_PLANES_GRAM 7  /* rgb -> patch matrices + the luma planes' exact Gram partials in one kernel (k_planes16_gram: large calls) */
-#define LRF_K_METRICS 8      /* squared error + SSIM of image pairs (lrf_image_metrics_u8: its whole launch sequence counts as one) */
+#define LRF_K_METRICS 8      /* scoring: squared error + SSIM of image pairs (lrf_image_metrics_u8) and the squared error of a sweep from its
+                                factors (lrf_qmf_sweep_sse_rgb_u8); the whole launch sequence of a call counts as one */
 #define LRF_K_COUNT 9
 int lrf_ctx_profile(lrf_ctx* ctx, int enable);
 /* The same for a subset of the kernels: bit (1 << LRF_K_x) per kernel id, 0 = off.  An event pair costs a few
@@ -241,6 +242,27 @@ int lrf_qmf_decode_rgb_u8(lrf_ctx* ctx, const int8_t* U, const int8_t* V, int64_
  */
 int lrf_image_metrics_u8(lrf_ctx* ctx, const uint8_t* a, const uint8_t* b, int B, int C, int H, int W, uint64_t* sse /* [B] */,
                          double* ssim /* [B] or NULL */);
+
+/*
+ * Squared error of a quality sweep straight from its factors: for q = 0 .. Q-1 and every image b,
+ *   sse[q][b] = sum over the 3*H*W samples of (rgb_b - decode(U_q,b, V_q,b))^2, an exact integer,
+ * where decode is byte for byte what lrf_qmf_decode_rgb_u8 writes — the kernels run the same device functions and compare each run
+ * of decoded bytes with the source where the decode kernel stores it; no decoded image exists.  Equal to lrf_qmf_decode_rgb_u8
+ * followed by lrf_image_metrics_u8(ssim = NULL) per triple, for every geometry and rank (1..64 per plane) those accept.
+ *   rgb   [B,3,H,W] uint8, the source images
+ *   U, V  laid out as lrf_qmf_encode_sweep_rgb_u8 writes them for (B, H, W, Q, R); Q = 1 is lrf_qmf_encode_rgb_u8's layout
+ *   R     [Q][3] ranks per triple (host memory)
+ *   sse   [Q][B] uint64 (device memory)
+ * Integer sums (uint32 per lane and wave, uint64 per workgroup, one 64-bit integer atomic per workgroup): deterministic, and an
+ * image's result depends on neither B, Q nor its place.  Asynchronous on the context's stream, except that the first call of a
+ * new (B, H, W, R) uploads a small table and waits for the stream.  One launch covers all (triple, image, tile) items when both
+ * sides are multiples of 16 and every triple is within ranks (32,16,16); other geometries take one launch per rank-bound class
+ * of the strip kernel (at most five), plus one each for the triples only the general kernels serve.
+ * LRF_EINVAL: a NULL pointer, Q outside [1,4096], B outside [1,65535], a rank outside [1,64].  After lrf_ctx_trim the table is
+ * uploaded again.
+ */
+int lrf_qmf_sweep_sse_rgb_u8(lrf_ctx* ctx, const uint8_t* rgb /* [B,3,H,W] */, const int8_t* U, const int8_t* V, int64_t B, int64_t H,
+                             int64_t W, int Q, const int* R /* [Q][3] */, uint64_t* sse /* [Q][B] */);
 
 /* ---- the SVD baseline ------------------------------------------------- */
 

@@ -77,6 +77,7 @@ def load():
         lib.lrf_qmf_decode_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, ctypes.POINTER(c_int),
                                               c_void_p]
         lib.lrf_image_metrics_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+        lib.lrf_qmf_sweep_sse_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int), c_void_p]
         lib.lrf_svd_encode_rgb_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.lrf_svd_decode_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p]
         lib.lrf_qmf_rgbspace_encode_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p,
@@ -120,7 +121,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_image_metrics_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -197,6 +198,36 @@ def check_metrics_args(a, b, want_ssim=True):
         raise ValueError(f"shape {tuple(a.shape)} out of range")
     if want_ssim and min(H, W) < 7:
         raise ValueError("win_size exceeds image extent.")
+
+
+def check_sweep_sse_args(rgb, factors, triples):
+    """The argument checks of lrf_qmf_sweep_sse_rgb_u8 on its tensors, before any device is touched.  rgb: uint8 [B,3,H,W];
+    triples: Q >= 1 rank triples, every rank in 1..64; factors: one (U, V) int8 pair per triple, shaped [B, sum_c M_c R_c] and
+    [B, 64 sum_c R_c] for that triple (the kernel indexes the factors from (H, W) and the ranks alone: sizes that disagree would
+    be out-of-bounds reads).  TypeError for anything but tensors of these types, ValueError for everything else."""
+    import torch
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8:
+        raise TypeError(f"sweep_sse takes a uint8 image tensor, got {rgb.dtype if isinstance(rgb, torch.Tensor) else type(rgb).__name__}")
+    if rgb.dim() != 4 or rgb.shape[1] != 3 or min(rgb.shape) < 1 or rgb.shape[0] > 65535:
+        raise ValueError(f"images must be [B,3,H,W] with 1 <= B <= 65535, got {tuple(rgb.shape)}")
+    B, _, H, W = rgb.shape
+    if factors is None or triples is None or len(triples) < 1 or len(triples) > 4096 or len(factors) != len(triples):
+        raise ValueError("sweep_sse needs one (U, V) pair per rank triple, 1 to 4096 of them")
+    dims = plane_dims(H, W)
+    dev = None
+    for t, pair in zip(triples, factors):
+        if len(t) != 3 or any(int(r) != r or r < 1 or r > 64 for r in t):
+            raise ValueError(f"rank triple {tuple(t)}: three ranks in 1..64 expected")
+        if pair is None or len(pair) != 2 or pair[0] is None or pair[1] is None:
+            raise ValueError(f"rank triple {tuple(t)}: a (U, V) pair expected")
+        U, V = pair
+        if not isinstance(U, torch.Tensor) or not isinstance(V, torch.Tensor) or U.dtype != torch.int8 or V.dtype != torch.int8:
+            raise TypeError("factors must be int8 tensors")
+        nu, nv = sum(d[4] * int(r) for d, r in zip(dims, t)), 64 * sum(int(r) for r in t)
+        dev = U.device if dev is None else dev
+        if tuple(U.shape) != (B, nu) or tuple(V.shape) != (B, nv) or U.device != dev or V.device != dev:
+            raise ValueError(f"factor buffers do not match the geometry at ranks {tuple(t)}: expected int8 U {(B, nu)} and V {(B, nv)} on "
+                             f"{dev}, got {tuple(U.shape)} on {U.device} and {tuple(V.shape)} on {V.device}")
 
 
 def _dptr(t):
@@ -431,6 +462,33 @@ class Context:
         self.use_torch_stream()
         check(self._lib.lrf_image_metrics_u8(self._h, _dptr(a), _dptr(b), B, C, H, W, _dptr(sse), _dptr(ssim)))
         return sse, ssim
+
+    def sweep_sse(self, rgb, factors, triples):
+        """The squared error of a sweep straight from its factors (lrf_qmf_sweep_sse_rgb_u8): rgb uint8 CUDA [B,3,H,W], `factors`
+        one (U, V) pair per rank triple of `triples`, as encode_sweep_rgb returns them (one pair: encode_rgb's) -> int64 CUDA
+        tensor [Q, B], sse[q][b] = what image_metrics(rgb, decode_rgb(U_q, V_q, H, W, triples[q]), want_ssim=False)[0][b] gives,
+        without the decoded images.  Pairs that are not already consecutive views of two flat buffers are copied into such."""
+        import torch
+        check_sweep_sse_args(rgb, factors, triples)
+        if not (rgb.is_cuda and rgb.device.index == self.device and factors[0][0].device == rgb.device):
+            raise ValueError(f"sweep_sse needs its tensors on cuda:{self.device}, got {rgb.device} and {factors[0][0].device}")
+        if not rgb.is_contiguous():
+            raise ValueError("sweep_sse needs a contiguous image tensor")
+        B, _, H, W = rgb.shape
+
+        def flat(ts):  # the C layout: triple after triple, back to back
+            p = ts[0].data_ptr()
+            for t in ts:
+                if not t.is_contiguous() or t.data_ptr() != p or t.untyped_storage().data_ptr() != ts[0].untyped_storage().data_ptr():
+                    return torch.cat([x.reshape(-1) for x in ts])
+                p += t.numel()
+            return ts[0]
+        U, V = flat([f[0] for f in factors]), flat([f[1] for f in factors])
+        sse = torch.empty((len(triples), B), dtype=torch.int64, device=rgb.device)
+        R = (c_int * (3 * len(triples)))(*[int(r) for t in triples for r in t])
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_sweep_sse_rgb_u8(self._h, _dptr(rgb), _dptr(U), _dptr(V), B, H, W, len(triples), R, _dptr(sse)))
+        return sse
 
     def planes_any(self, rgb, patch_size, ch, chroma=None):
         """rgb uint8 [B,3,H,W] (CUDA) -> X fp32 [B, M, N] of plane ch for patches (p, q) (None: the plane itself)"""

@@ -118,6 +118,101 @@ def qmf_encode_sweep(images: torch.Tensor, qualities=None, ranks=None, bounds=(-
     return [out[t] for t in triples]
 
 
+def target_candidates(image_hw, qualities):
+    """The rank triples a quality grid gives on an H x W image, each once, in ascending quality, with the LOWEST quality that
+    gives it: ([triple], [quality]).  (Neighbouring qualities often round to the same ranks: 32 qualities, ~24 triples.)"""
+    triples, lowest = [], []
+    for q in sorted(qualities):
+        t = tuple(qmf_ranks(image_hw, None, q))
+        if t not in triples:
+            triples.append(t)
+            lowest.append(q)
+    return triples, lowest
+
+
+def select_target(sse: torch.Tensor, n: int, target: torch.Tensor):
+    """The choice qmf_encode_target makes, from exact squared errors: sse int64 [Q,B] (candidate q in ascending quality, image b),
+    n samples per image, target float64 [B] in dB -> (table float64 [Q,B] of PSNR, index int64 [B], reached bool [B]).
+    index[b] is the FIRST candidate whose PSNR >= target[b] — every candidate is looked at, nothing assumes that PSNR grows with
+    quality — and, where none reaches it, the first candidate of the highest PSNR (reached False).  sse = 0 is PSNR inf, which
+    reaches every target.  Evaluated on the device `sse` lives on, by the expression image_metrics_batch uses."""
+    from .metrics import psnr_from_sse
+    table = psnr_from_sse(sse, n)[1]
+    ok = table >= target.to(table.device).reshape(1, -1)
+    reached = ok.any(dim=0)
+    first_ok = torch.argmax(ok.to(torch.uint8), dim=0)  # (argmax: the first of equal maxima)
+    best = torch.argmax(table, dim=0)
+    return table, torch.where(reached, first_ok, best), reached
+
+
+def _check_target_args(images, psnr, qualities, num_iters):
+    """qmf_encode_target's refusals, raised before a GPU is asked for -> (qualities as a list, target as float64 [B])"""
+    if not isinstance(images, torch.Tensor):
+        raise TypeError(f"qmf_encode_target takes a tensor of images, got {type(images).__name__}")
+    if images.dtype != torch.uint8:
+        raise NotImplementedError("qmf_encode_target: the HIP path takes uint8 images")
+    if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
+        raise ValueError(f"qmf_encode_target takes a batch [B,3,H,W], got {tuple(images.shape)}")
+    if num_iters < 1:
+        raise NotImplementedError("qmf_encode_target: num_iters = 0 (the truncated initialisation) is outside the fused sweep")
+    qualities = list(qualities)
+    if not qualities or any(not (0 <= q <= 100) for q in qualities):
+        raise ValueError("qmf_encode_target: 'qualities' must be a non-empty sequence of numbers between 0 and 100")
+    target = torch.as_tensor(psnr, dtype=torch.float64).reshape(-1)
+    B = images.shape[0]
+    if target.numel() not in (1, B) or bool(torch.isnan(target).any()):
+        raise ValueError(f"qmf_encode_target: 'psnr' must be one number or one per image ({B}), got {target.numel()} values")
+    return qualities, target.expand(B).contiguous()
+
+
+def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
+                      pack_workers: Optional[int] = None) -> dict:
+    """Per image of a batch [B,3,H,W], the smallest-quality stream that reaches `psnr` dB (one number, or one per image).
+
+    Default branch only (YCbCr, 8x8 patches, uint8, num_iters >= 1).  Every distinct rank triple of `qualities` is factorised on
+    the GPU (triples within rank 32 in one lrf_qmf_encode_sweep_rgb_u8 call, larger ones one call each) and scored there
+    straight from its factors (lrf_qmf_sweep_sse_rgb_u8: no image is decoded to memory, nothing but a [Q,B] table leaves the
+    kernel).  Per image the lowest quality whose PSNR >= psnr wins; if none does, the candidate of the highest PSNR
+    (reached False).  Only the winners' factors come to the host and only they are packed (zlib-9): B streams, not Q x B.
+
+    Returns {"streams": B byte streams, stream i byte-identical to qmf_encode_batch(images[i:i+1], quality=quality[i])[0];
+    "quality": the chosen quality per image (the lowest of those that share its rank triple); "psnr": float64 [B], the chosen
+    stream's PSNR, what psnr_batch gives for its decode; "reached": bool [B]; "table": float64 [Q,B], the PSNR of every
+    (quality of `qualities`, image) pair}.  The tensors are host tensors."""
+    qualities, target = _check_target_args(images, psnr, qualities, num_iters)
+    H, W = images.shape[-2:]
+    B = images.shape[0]
+    triples, lowest = target_candidates((H, W), qualities)
+    ctx = _lib.context(images.device.index if images.is_cuda else None)
+    dev = (images if images.is_cuda else images.cuda(ctx.device)).contiguous()
+    lo, hi = math.ceil(bounds[0]), math.floor(bounds[1])
+    fused = [t for t in triples if max(t) <= 32]
+    factors = dict(zip(fused, ctx.encode_sweep_rgb(dev, fused, num_iters, lo, hi, None))) if fused else {}
+    sse = torch.empty((len(triples), B), dtype=torch.int64, device=dev.device)
+    if fused:
+        sse[[triples.index(t) for t in fused]] = ctx.sweep_sse(dev, [factors[t] for t in fused], fused)
+    for i, t in enumerate(triples):
+        if t not in factors:  # a rank above 32: the per-triple encoder, scored by a sweep of one
+            factors[t] = qmf_factorize_batch(dev, list(t), num_iters, bounds)
+            sse[i] = ctx.sweep_sse(dev, [factors[t]], [t])[0]
+    table, index, reached = select_target(sse, 3 * H * W, target)
+    chosen_psnr = table.gather(0, index.reshape(1, -1))[0]
+    table, index, reached, chosen_psnr = table.cpu(), index.cpu(), reached.cpu(), chosen_psnr.cpu()
+    streams = [None] * B
+    for i, t in enumerate(triples):  # images choose different triples: one gather, one copy and one packing call per group
+        rows = torch.nonzero(index == i).reshape(-1)
+        if rows.numel() == 0:
+            continue
+        sel = rows.to(dev.device)
+        Uh, Vh = (x.numpy() for x in ctx.to_host(factors[t][0].index_select(0, sel), factors[t][1].index_select(0, sel)))
+        packed = pack_streams_native(Uh, Vh, (H, W), list(t), bounds, (8, 8), "uint8", threads=pack_workers or default_pack_threads())
+        for b, s in zip(rows.tolist(), packed):
+            streams[b] = s
+    row_of = [triples.index(tuple(qmf_ranks((H, W), None, q))) for q in qualities]
+    return {"streams": streams, "quality": [lowest[i] for i in index.tolist()], "psnr": chosen_psnr, "reached": reached,
+            "table": table[row_of]}
+
+
 def qmf_factorize_host(images: torch.Tensor, ranks: Sequence[int], num_iters: int = 10, bounds=(-16, 15), init_sign=None,
                        out=None, slots: int = 2, sub_batch: int = 0, device=None):
     """Host -> host form of qmf_factorize_batch: `images` is a uint8 CPU tensor [B,3,H,W]

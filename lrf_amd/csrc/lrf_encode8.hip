@@ -6,6 +6,7 @@
 #include "lrf_kernels.hip"
 #include "lrf_bcdw_kernel.hip"
 #include "lrf_bcdw16_kernel.hip"
+#include "lrf_sweep_sse_kernel.hip"
 
 // gram_exp: the fixed-point grid exponent of the exact Gram matrix (max|x| < 2^gram_exp) when the caller knows it — 8 for the
 // planes of qmf_encode — or LRF_GRAM_EXP_FROM_DATA: one more pass over X finds it per matrix
@@ -557,6 +558,40 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64
     return run_bcd(c, X, t, K, lo, hi, 1, nullptr, U, V);
 }
 
+// which decode body serves a geometry and a rank triple (lrf_qmf_decode_rgb_u8 and lrf_qmf_sweep_sse_rgb_u8 share it)
+enum { DEC_TILE16 = 0, DEC_STRIP = 1, DEC_R8 = 2, DEC_ANY = 3 };
+struct DecodePlan {
+    int kind;
+    int cls; // tiled kinds: index of the rank bounds (chroma, luma) = (4,8) (8,8) (8,16) (16,16) (16,32)
+};
+static DecodePlan decode_plan(const ImageGeom& g, int64_t H, int64_t W, const int R[3], bool aligned8)
+{
+    static const bool no_tiled = dev_flag("LRF_DECODE_NO_TILED");
+    // the tiled kernels (k_decode16: sides multiples of 16; k_decode_strip: any height, four-aligned chroma columns) are
+    // instantiated for the rank bounds (chroma, luma) = (4,8) (8,8) (8,16) (16,16) (16,32): the reference's quality sweep up to 40
+    const int rcm = R[1] > R[2] ? R[1] : R[2];
+    const int RCb = rcm <= 4 ? 4 : (rcm <= 8 ? 8 : 16), RLb = R[0] <= 8 ? 8 : (R[0] <= 16 ? 16 : 32);
+    const bool tiled_ranks = R[0] <= 32 && rcm <= 16 && !no_tiled;
+    const bool sides16 = H % 16 == 0 && W % 16 == 0 && aligned8;
+    const bool strip_ok = W % 2 == 0 && g.p[0].left_crop % 2 == 0 && (g.p[1].left_crop - g.p[0].left_crop / 2) % 4 == 0 && g.p[1].w == W / 2;
+    if (tiled_ranks && (sides16 || strip_ok)) {
+        int cls;
+        if (RLb == 8 && RCb == 4) cls = 0;
+        else if (RLb == 8 && RCb == 8) cls = 1;
+        else if (RLb == 16 && RCb <= 8) cls = 2;
+        else if (RLb <= 16) cls = 3;
+        else cls = 4;
+        return DecodePlan{sides16 ? DEC_TILE16 : DEC_STRIP, cls};
+    }
+    return DecodePlan{(R[0] <= 8 && R[1] <= 8 && R[2] <= 8) ? DEC_R8 : DEC_ANY, 0};
+}
+// groups of four pixels per thread of k_decode8 / k_sse8: as many as leave the call ~2048 workgroups (small calls keep one group per thread)
+static long decode8_reps(long images, long n4)
+{
+    const long reps = images * ((n4 + 255) / 256) / 2048;
+    return reps < 1 ? 1 : (reps > 16 ? 16 : reps);
+}
+
 int lrf_qmf_decode_rgb_u8(lrf_ctx* c, const int8_t* U, const int8_t* V, int64_t B, int64_t H, int64_t W, const int R[3],
                           uint8_t* rgb)
 {
@@ -575,36 +610,28 @@ int lrf_qmf_decode_rgb_u8(lrf_ctx* c, const int8_t* U, const int8_t* V, int64_t 
     }
     long n4 = (long)H * ((W + 3) / 4);
     Prof p(c, LRF_K_DECODE);
-    static const bool no_tiled = dev_flag("LRF_DECODE_NO_TILED");
-    // the tiled kernels (k_decode16: sides multiples of 16; k_decode_strip: any height, four-aligned chroma columns) are
-    // instantiated for the rank bounds (chroma, luma) = (4,8) (8,8) (8,16) (16,16) (16,32): the reference's quality sweep up to 40
-    const int rcm = R[1] > R[2] ? R[1] : R[2];
-    const int RCb = rcm <= 4 ? 4 : (rcm <= 8 ? 8 : 16), RLb = R[0] <= 8 ? 8 : (R[0] <= 16 ? 16 : 32);
-    const bool tiled_ranks = R[0] <= 32 && rcm <= 16 && !no_tiled;
-    const bool sides16 = H % 16 == 0 && W % 16 == 0 && (reinterpret_cast<uintptr_t>(rgb) & 7) == 0;
-    const bool strip_ok = W % 2 == 0 && g.p[0].left_crop % 2 == 0 && (g.p[1].left_crop - g.p[0].left_crop / 2) % 4 == 0 && g.p[1].w == W / 2;
-    if (tiled_ranks && (sides16 || strip_ok)) {
+    const DecodePlan plan = decode_plan(g, H, W, R, (reinterpret_cast<uintptr_t>(rgb) & 7) == 0);
+    if (plan.kind == DEC_TILE16 || plan.kind == DEC_STRIP) {
         const int per_strip = (g.p[0].nw + 31) / 32;
         const dim3 grid16((unsigned)((H / 16) * per_strip), (unsigned)B), grids((unsigned)(((g.p[0].nh + 1) / 2) * per_strip), (unsigned)B);
 #define LRF_DECODE_TILED(RC, RL)                                                                                                  \
     do {                                                                                                                         \
-        if (sides16)                                                                                                             \
+        if (plan.kind == DEC_TILE16)                                                                                             \
             hipLaunchKernelGGL((k_decode16<RC, RL>), grid16, dim3(256), 0, c->stream, U, V, (int)H, (int)W, g, R[0], R[1], R[2], u_img, v_img, rgb); \
         else                                                                                                                     \
             hipLaunchKernelGGL((k_decode_strip<RC, RL>), grids, dim3(256), 0, c->stream, U, V, (int)H, (int)W, g, R[0], R[1], R[2], u_img, v_img, rgb, per_strip); \
     } while (0)
-        if (RLb == 8 && RCb == 4) LRF_DECODE_TILED(4, 8);
-        else if (RLb == 8 && RCb == 8) LRF_DECODE_TILED(8, 8);
-        else if (RLb == 16 && RCb <= 8) LRF_DECODE_TILED(8, 16);
-        else if (RLb <= 16) LRF_DECODE_TILED(16, 16);
-        else LRF_DECODE_TILED(16, 32);
+        switch (plan.cls) {
+        case 0: LRF_DECODE_TILED(4, 8); break;
+        case 1: LRF_DECODE_TILED(8, 8); break;
+        case 2: LRF_DECODE_TILED(8, 16); break;
+        case 3: LRF_DECODE_TILED(16, 16); break;
+        default: LRF_DECODE_TILED(16, 32); break;
+        }
 #undef LRF_DECODE_TILED
     }
-    else if (R[0] <= 8 && R[1] <= 8 && R[2] <= 8)
-{
-        // groups of four pixels per thread: as many as leave the call ~2048 workgroups (small calls keep one group per thread)
-        long reps = (long)B * ((n4 + 255) / 256) / 2048;
-        reps = reps < 1 ? 1 : (reps > 16 ? 16 : reps);
+    else if (plan.kind == DEC_R8) {
+        const long reps = decode8_reps(B, n4);
         hipLaunchKernelGGL(k_decode8, dim3((unsigned)((n4 + 256 * reps - 1) / (256 * reps)), (unsigned)B), dim3(256), 0, c->stream, U, V, (int)H, (int)W,
                            g, R[0], R[1], R[2], u_img, v_img, rgb, (int)reps);
     }
@@ -612,6 +639,101 @@ int lrf_qmf_decode_rgb_u8(lrf_ctx* c, const int8_t* U, const int8_t* V, int64_t 
         hipLaunchKernelGGL(k_decode, dim3((unsigned)((n4 + 255) / 256), (unsigned)B), dim3(256), 0, c->stream, U, V, (int)H, (int)W,
                            g, R[0], R[1], R[2], u_img, v_img, rgb);
     LAUNCH_CHECK();
+    return LRF_OK;
+}
+
+// The squared error of Q x B decodes against the B source images, without the decoded images (kernels and the choice of the
+// work item: lrf_sweep_sse_kernel.hip).  The triples are sorted by the decode body that serves them — for a geometry the tiled
+// 16-aligned body covers and ranks <= (32,16,16) that is ONE launch over all (triple, image, tile) items — and described by a table on
+// the device, which stays resident while calls repeat the same (B, H, W, triples).
+int lrf_qmf_sweep_sse_rgb_u8(lrf_ctx* c, const uint8_t* rgb, const int8_t* U, const int8_t* V, int64_t B, int64_t H, int64_t W, int Q, const int* R,
+                             uint64_t* sse)
+{
+    if (!c || !rgb || !U || !V || !R || !sse) return set_err(LRF_EINVAL, "NULL argument");
+    if (B < 1 || B > 65535) return set_err(LRF_EINVAL, "B=%ld out of range [1,65535]", (long)B);
+    if (Q < 1 || Q > 4096) return set_err(LRF_EINVAL, "Q=%d out of range [1,4096]", Q);
+    ImageGeom g;
+    int rc = make_geom(H, W, &g);
+    if (rc) return rc;
+    for (int i = 0; i < 3 * Q; i++)
+        if (R[i] < 1 || R[i] > 64) return set_err(LRF_EINVAL, "rank %d out of range", R[i]);
+    LRF_ON_DEVICE(c);
+    // the table: the items of the tiled body first, then k_sse8's, then k_sse_any's (source rows of 16-aligned images are read in
+    // 8-byte pieces whatever the pointer: loads need no alignment, so DEC_TILE16 does not ask for it here)
+    std::vector<SseItem> items[3];
+    int tiled_kind = DEC_STRIP;
+    long uo = 0, vo = 0;
+    for (int q = 0; q < Q; q++) {
+        const int* r = R + 3 * q;
+        SseItem it{};
+        it.u_base = uo;
+        it.v_base = vo;
+        for (int ch = 0; ch < 3; ch++) { it.u_img += (long)g.p[ch].M * r[ch]; it.v_img += 64L * r[ch]; }
+        it.R0 = r[0]; it.R1 = r[1]; it.R2 = r[2];
+        it.q = q;
+        const DecodePlan plan = decode_plan(g, H, W, r, true);
+        it.cls = plan.cls;
+        if (plan.kind == DEC_TILE16) tiled_kind = DEC_TILE16; // (a property of the geometry: the same for every tiled triple)
+        items[plan.kind <= DEC_STRIP ? 0 : plan.kind - 1].push_back(it);
+        uo += B * it.u_img;
+        vo += B * it.v_img;
+    }
+    const long n4 = (long)H * ((W + 3) / 4);
+    const int per_strip = (g.p[0].nw + 31) / 32;
+    const long tiles = tiled_kind == DEC_TILE16 ? (H / 16) * per_strip : (long)((g.p[0].nh + 1) / 2) * per_strip;
+    const long reps = decode8_reps(B * (long)items[1].size(), n4);
+    const long groups[3] = {tiles, (n4 + 256 * reps - 1) / (256 * reps), (n4 + 255) / 256};
+    if (tiled_kind == DEC_STRIP) // a launch per class: the classes stand together
+        std::stable_sort(items[0].begin(), items[0].end(), [](const SseItem& a, const SseItem& b) { return a.cls < b.cls; });
+    std::vector<SseItem> tab;
+    for (int k = 0; k < 3; k++) {
+        if (groups[k] * (long)items[k].size() >= (1L << 31)) return set_err(LRF_EINVAL, "%ld work items in one launch: split the sweep", groups[k] * (long)items[k].size());
+        tab.insert(tab.end(), items[k].begin(), items[k].end());
+    }
+    const size_t tb = tab.size() * sizeof(SseItem);
+    if (c->sse_key.size() != tb || memcmp(c->sse_key.data(), tab.data(), tb) != 0 || !c->sse_tab.p) {
+        c->sse_key.clear();
+        if ((rc = upload(c, c->sse_tab, tab.data(), tb))) return rc;
+        c->sse_key.assign((const char*)tab.data(), (const char*)tab.data() + tb);
+    }
+    const SseItem* d_tab = (const SseItem*)c->sse_tab.p;
+    unsigned long long* d_sse = reinterpret_cast<unsigned long long*>(sse);
+    Prof p(c, LRF_K_METRICS); // the scoring stage: timed with lrf_image_metrics_u8
+    HIP_TRY(hipMemsetAsync(sse, 0, (size_t)Q * B * sizeof(uint64_t), c->stream));
+    if (tiled_kind == DEC_TILE16 && !items[0].empty()) {
+        const int nq = (int)items[0].size();
+        hipLaunchKernelGGL((k_sse_tiled<false, -1>), dim3((unsigned)(tiles * nq), (unsigned)B), dim3(256), 0, c->stream, rgb, U, V, (int)H, (int)W, g, d_tab, nq,
+                           per_strip, (int)B, d_sse);
+        LAUNCH_CHECK();
+    } else {
+        for (size_t i0 = 0; i0 < items[0].size();) { // the strip body: one launch per class present
+            size_t i1 = i0;
+            while (i1 < items[0].size() && items[0][i1].cls == items[0][i0].cls) i1++;
+            const int nq = (int)(i1 - i0);
+            const dim3 grid((unsigned)(tiles * nq), (unsigned)B);
+#define LRF_SSE_STRIP(CLS) hipLaunchKernelGGL((k_sse_tiled<true, CLS>), grid, dim3(256), 0, c->stream, rgb, U, V, (int)H, (int)W, g, d_tab + i0, nq, per_strip, (int)B, d_sse)
+            switch (items[0][i0].cls) {
+            case 0: LRF_SSE_STRIP(0); break;
+            case 1: LRF_SSE_STRIP(1); break;
+            case 2: LRF_SSE_STRIP(2); break;
+            case 3: LRF_SSE_STRIP(3); break;
+            default: LRF_SSE_STRIP(4); break;
+            }
+#undef LRF_SSE_STRIP
+            LAUNCH_CHECK();
+            i0 = i1;
+        }
+    }
+    if (int nq = (int)items[1].size()) {
+        hipLaunchKernelGGL(k_sse8, dim3((unsigned)(groups[1] * nq), (unsigned)B), dim3(256), 0, c->stream, rgb, U, V, (int)H, (int)W, g,
+                           d_tab + items[0].size(), nq, (int)reps, (int)B, d_sse);
+        LAUNCH_CHECK();
+    }
+    if (int nq = (int)items[2].size()) {
+        hipLaunchKernelGGL(k_sse_any, dim3((unsigned)(groups[2] * nq), (unsigned)B), dim3(256), 0, c->stream, rgb, U, V, (int)H, (int)W, g,
+                           d_tab + items[0].size() + items[1].size(), nq, (int)B, d_sse);
+        LAUNCH_CHECK();
+    }
     return LRF_OK;
 }
 

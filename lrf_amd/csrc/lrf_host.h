@@ -81,6 +81,8 @@ struct lrf_ctx {
     DevBuf sx, sg, svn, swn, suf, smm; // SVD baseline workspace
     DevBuf any_uf, any_vf, any_a, any_b, any_p, any_e2, any_g, any_td; // any-shape path (lrf_anyshape_host.inc)
     DevBuf metrics; // lrf_image_metrics_u8: a float64 slot per (image, channel, tile), then (max, 255 - min) per image
+    DevBuf sse_tab; // lrf_qmf_sweep_sse_rgb_u8: its table of rank triples (SseItem) ...
+    std::vector<char> sse_key; // ... and the bytes now resident there (calls that repeat a sweep skip the synchronising upload)
     DevBuf vf16, wf16, bf16, pp16, qp16; // the pitch-16 tables of a call that mixes kernel families (plan_runs)
     // host staging for descriptor tables (pinned)
     void* h_stage = nullptr;

@@ -1438,7 +1438,38 @@ __global__ __launch_bounds__(256) void k_emit_init(const float* __restrict__ X, 
 
 // ------------------------------------------------------------------------------------------------
 // K4: int8 factors -> uint8 RGB.  One thread per 4 horizontally adjacent pixels.
+//
+// The four kernels below are thin: each names its image and hands the per-thread work to a __device__ body (decode8_body,
+// decode16_tile, decode_strip_tile, decode_body) that ends every run of decoded bytes in a SINK.  DecodeStore, the sink of
+// these kernels, stores the bytes; the sink of lrf_sweep_sse_kernel.hip compares them with the source image instead.  A sink has
+//   put8(y, x, pk)       eight pixels of row y from column x, channel k as the two dwords pk[k] (put8u: no alignment known)
+//   put4(ch, y, x, w)    four pixels of one channel as a dword
+//   put1(ch, y, x, v)    one byte
+// so the arithmetic up to the clamped, truncated byte exists once.
 // ------------------------------------------------------------------------------------------------
+struct DecodeStore {
+    uint8_t* out; // the image [3][H][W]
+    long hw;
+    int W;
+    __device__ __forceinline__ void put8(int y, int x, const uint2 (&pk)[3]) const
+    {
+        uint8_t* dst = out + (long)y * W + x;
+#pragma unroll
+        for (int k = 0; k < 3; k++) *reinterpret_cast<uint2*>(dst + k * hw) = pk[k];
+    }
+    __device__ __forceinline__ void put8u(int y, int x, const uint2 (&pk)[3]) const
+    {
+        uint8_t* dst = out + (long)y * W + x;
+#pragma unroll
+        for (int k = 0; k < 3; k++) *reinterpret_cast<uint2 __attribute__((aligned(1)))*>(dst + k * hw) = pk[k];
+    }
+    __device__ __forceinline__ void put4(int ch, int y, int x, unsigned w) const
+    {
+        *reinterpret_cast<uint32_t __attribute__((aligned(1)))*>(out + (long)ch * hw + (long)y * W + x) = w;
+    }
+    __device__ __forceinline__ void put1(int ch, int y, int x, unsigned v) const { out[(long)ch * hw + (long)y * W + x] = (uint8_t)v; }
+};
+
 __device__ __forceinline__ float recon_at(const int8_t* __restrict__ Uc, const int8_t* __restrict__ Vc, int R,
                                           const PlaneGeom& pg, int y, int x)
 {
@@ -1454,13 +1485,11 @@ __device__ __forceinline__ float recon_at(const int8_t* __restrict__ Uc, const i
 // to 8 columns), a thread keeps the u row of the patch it is in and reloads it only when the patch changes (four
 // horizontally adjacent pixels touch at most two luma and two chroma patches), and the four output bytes of a
 // channel leave as one dword.  Same arithmetic and order as k_decode.
-__global__ __launch_bounds__(256) void k_decode8(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W,
-                                                 ImageGeom g, int R0, int R1, int R2, long u_img, long v_img,
-                                                 uint8_t* __restrict__ rgb, int reps)
+// Ui / Vi: the image's factors; bx: the workgroup's index inside the image; Vs: 3 x 64 x 8 floats of LDS.
+template <class Sink>
+__device__ __forceinline__ void decode8_body(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0,
+                                             int R1, int R2, int bx, int reps, float (*Vs)[64 * 8], Sink& sink)
 {
-    __shared__ float Vs[3][64 * 8];
-    const int8_t* Ui = U + (long)blockIdx.y * u_img;
-    const int8_t* Vi = V + (long)blockIdx.y * v_img;
     const int8_t* Uc[3] = {Ui, Ui + (long)g.p[0].M * R0, Ui + (long)g.p[0].M * R0 + (long)g.p[1].M * R1};
     const int8_t* Vc[3] = {Vi, Vi + 64 * R0, Vi + 64 * R0 + 64 * R1};
     const int Rc[3] = {R0, R1, R2};
@@ -1474,10 +1503,9 @@ __global__ __launch_bounds__(256) void k_decode8(const int8_t* __restrict__ U, c
     // loads per thread and a barrier) is then staged once for up to 16384 pixels instead of 1024 — with one group per thread
     // that prologue, not the arithmetic, set the pace (512 x 1365x2048: 4.8 -> 3.4 ms)
     for (int rep = 0; rep < reps; rep++) {
-    long o = ((long)blockIdx.x * reps + rep) * 256 + threadIdx.x;
+    long o = ((long)bx * reps + rep) * 256 + threadIdx.x;
     if (o >= (long)H * w4) return;
     int y = (int)(o / w4), x0 = (int)(o - (long)y * w4) * 4;
-    uint8_t* out = rgb + (long)blockIdx.y * 3 * H * W;
     float sh = (float)g.p[1].h / (float)H, sw = (float)g.p[1].w / (float)W;
     int sy = (int)floorf((float)y * sh);
     if (sy > g.p[1].h - 1) sy = g.p[1].h - 1;
@@ -1519,14 +1547,22 @@ __global__ __launch_bounds__(256) void k_decode8(const int8_t* __restrict__ U, c
     }
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
-        uint8_t* dst = out + (long)ch * H * W + (long)y * W + x0;
         if (x0 + 3 < W) {
-            *reinterpret_cast<uint32_t __attribute__((aligned(1)))*>(dst) = packed[ch];
+            sink.put4(ch, y, x0, packed[ch]);
         } else {
-            for (int i = 0; x0 + i < W; i++) dst[i] = (uint8_t)(packed[ch] >> (8 * i));
+            for (int i = 0; x0 + i < W; i++) sink.put1(ch, y, x0 + i, (uint8_t)(packed[ch] >> (8 * i)));
         }
     }
     }
+}
+
+__global__ __launch_bounds__(256) void k_decode8(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W,
+                                                 ImageGeom g, int R0, int R1, int R2, long u_img, long v_img,
+                                                 uint8_t* __restrict__ rgb, int reps)
+{
+    __shared__ float Vs[3][64 * 8];
+    DecodeStore sink{rgb + (long)blockIdx.y * 3 * H * W, (long)H * W, W};
+    decode8_body(U + (long)blockIdx.y * u_img, V + (long)blockIdx.y * v_img, H, W, g, R0, R1, R2, (int)blockIdx.x, reps, Vs, sink);
 }
 
 // Fast path of K4 for images whose sides are multiples of 16 (no padding, no crop, exact 2x nearest
@@ -1578,50 +1614,66 @@ __device__ __forceinline__ unsigned decode16_pack4(float a, float b, float c, fl
     return (ua | (ub << 8)) | ((uc | (ud << 8)) << 16);
 }
 
-template <int RC, int RL> // rank bounds of the chroma planes (4, 8, 16) and of luma (8, 16, 32): table sizes and loop lengths
-__global__ __launch_bounds__(256) void k_decode16(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W,
-                                                  ImageGeom g, int R0, int R1, int R2, long u_img, long v_img,
-                                                  uint8_t* __restrict__ rgb)
+// the V tables of an image as floats in LDS, [r][n] per plane, rows past the plane's rank zero: VsL [RL][64], VsC [2][RC][64]
+template <int RC, int RL>
+__device__ __forceinline__ void decode_stage_v(const int8_t* (&Vc)[3], const int (&Rc)[3], float* __restrict__ VsL, float* __restrict__ VsC)
 {
-    __shared__ __attribute__((aligned(16))) float VsL[RL][64], VsC[2][RC][64];
-    const int8_t* Ui = U + (long)blockIdx.y * u_img;
-    const int8_t* Vi = V + (long)blockIdx.y * v_img;
-    const int8_t* Uc[3] = {Ui, Ui + (long)g.p[0].M * R0, Ui + (long)g.p[0].M * R0 + (long)g.p[1].M * R1};
-    const int8_t* Vc[3] = {Vi, Vi + 64 * R0, Vi + 64 * R0 + 64 * R1};
-    const int Rc[3] = {R0, R1, R2};
-    const int nwl = g.p[0].nw, nwc = g.p[1].nw;
-    const int per_strip = (nwl + 31) / 32;
-    const int strip = blockIdx.x / per_strip;
-    const int ww = (blockIdx.x - strip * per_strip) * 32 + (threadIdx.x & 31);
-    const int wwc = ww < nwl ? ww : nwl - 1; // threads past the last patch load what the last one loads and store nothing
-    const int rp = threadIdx.x >> 5; // row pair inside the strip: image rows 16 strip + 2 rp, + 1
-    // the u rows of the luma patch and of the two chroma patches: issued before the V table is staged, so that the two
-    // memory round trips of a workgroup overlap
-    unsigned wl[RL / 4], wb[RC / 4], wr[RC / 4];
-    const long mrow[3] = {(long)(2 * strip + (rp >> 2)) * nwl + wwc, (long)strip * nwc + (wwc >> 1), (long)strip * nwc + (wwc >> 1)};
-    decode_u_load<RL>(Uc[0] + mrow[0] * R0, R0, wl);
-    decode_u_load<RC>(Uc[1] + mrow[1] * R1, R1, wb);
-    decode_u_load<RC>(Uc[2] + mrow[2] * R2, R2, wr);
     for (int e = threadIdx.x; e < RL * 64; e += 256) {
         const int r = e >> 6, n = e & 63;
-        VsL[r][n] = (r < R0) ? (float)Vc[0][n * R0 + r] : 0.f;
+        VsL[r * 64 + n] = (r < Rc[0]) ? (float)Vc[0][n * Rc[0] + r] : 0.f;
     }
     for (int e = threadIdx.x; e < 2 * RC * 64; e += 256) {
         const int c = e / (RC * 64), r = (e >> 6) % RC, n = e & 63;
-        VsC[c][r][n] = (r < Rc[1 + c]) ? (float)Vc[1 + c][n * Rc[1 + c] + r] : 0.f;
+        VsC[(c * RC + r) * 64 + n] = (r < Rc[1 + c]) ? (float)Vc[1 + c][n * Rc[1 + c] + r] : 0.f;
     }
-    __syncthreads();
-    if (ww >= nwl) return;
-    float ul[RL], ub[RC], ur[RC]; // zero padded to the rank bounds
-    decode_u_unpack<RL>(wl, ul);
-    decode_u_unpack<RC>(wb, ub);
-    decode_u_unpack<RC>(wr, ur);
-    // chroma: samples (row 8 strip + rp of the plane = row rp of the patch, columns 4 (ww & 1) .. + 3)
-    float cb[4] = {0.f, 0.f, 0.f, 0.f}, cr[4] = {0.f, 0.f, 0.f, 0.f};
+}
+
+// eight luma values of patch row n0 / 8 from the u row and the staged table, the colour chain with the four chroma samples under
+// them, clamp + truncate: the eight pixels of a row as two dwords per channel
+template <int RL>
+__device__ __forceinline__ void decode_row8(const float (&ul)[RL], const float* __restrict__ VsL, int n0, const float (&cb)[4], const float (&cr)[4],
+                                            uint2 (&pk)[3])
+{
+    float y[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < RL; r++) {
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(&VsL[r * 64 + n0]);
+        const f32x4 v1 = *reinterpret_cast<const f32x4*>(&VsL[r * 64 + n0 + 4]);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            y[i] = fmaf(ul[r], v0[i], y[i]);
+            y[4 + i] = fmaf(ul[r], v1[i], y[4 + i]);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        float ch[3][4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { // the k-ordered chains without their no-op steps
+            const float c0 = y[4 * h + i], c1 = cb[2 * h + (i >> 1)], c2 = cr[2 * h + (i >> 1)];
+            ch[0][i] = fmaf(1.402f, c2, c0);
+            ch[1][i] = fmaf(-0.714136f, c2, fmaf(-0.344136f, c1, c0));
+            ch[2][i] = fmaf(1.772f, c1, c0);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const unsigned w = decode16_pack4(ch[k][0], ch[k][1], ch[k][2], ch[k][3]);
+            if (h == 0) pk[k].x = w; else pk[k].y = w;
+        }
+    }
+}
+
+// four chroma samples of both planes (columns nc .. nc + 3 of the patch element index) from the u rows, "+ -128.f"
+template <int RC>
+__device__ __forceinline__ void decode_chroma4(const float (&ub)[RC], const float (&ur)[RC], const float* __restrict__ VsC, int nc, float (&cb)[4],
+                                               float (&cr)[4])
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++) cb[i] = cr[i] = 0.f;
 #pragma unroll
     for (int r = 0; r < RC; r++) {
-        const f32x4 vb = *reinterpret_cast<const f32x4*>(&VsC[0][r][rp * 8 + 4 * (ww & 1)]);
-        const f32x4 vr = *reinterpret_cast<const f32x4*>(&VsC[1][r][rp * 8 + 4 * (ww & 1)]);
+        const f32x4 vb = *reinterpret_cast<const f32x4*>(&VsC[r * 64 + nc]);
+        const f32x4 vr = *reinterpret_cast<const f32x4*>(&VsC[(RC + r) * 64 + nc]);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             cb[i] = fmaf(ub[r], vb[i], cb[i]);
@@ -1633,42 +1685,56 @@ __global__ __launch_bounds__(256) void k_decode16(const int8_t* __restrict__ U, 
         cb[i] = cb[i] + -128.f;
         cr[i] = cr[i] + -128.f;
     }
-    const long hw = (long)H * W;
-    uint8_t* out = rgb + (long)blockIdx.y * 3 * hw + (long)(16 * strip + 2 * rp) * W + 8 * ww;
+}
+
+// bx: the workgroup's tile (16-row strip x 32 luma patches) inside the image; VsL / VsC: LDS, 16-byte aligned
+template <int RC, int RL, class Sink> // rank bounds of the chroma planes (4, 8, 16) and of luma (8, 16, 32): table sizes and loop lengths
+__device__ __forceinline__ void decode16_tile(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, const ImageGeom& g, int R0, int R1, int R2,
+                                              int bx, float* __restrict__ VsL, float* __restrict__ VsC, Sink& sink)
+{
+    const int8_t* Uc[3] = {Ui, Ui + (long)g.p[0].M * R0, Ui + (long)g.p[0].M * R0 + (long)g.p[1].M * R1};
+    const int8_t* Vc[3] = {Vi, Vi + 64 * R0, Vi + 64 * R0 + 64 * R1};
+    const int Rc[3] = {R0, R1, R2};
+    const int nwl = g.p[0].nw, nwc = g.p[1].nw;
+    const int per_strip = (nwl + 31) / 32;
+    const int strip = bx / per_strip;
+    const int ww = (bx - strip * per_strip) * 32 + (threadIdx.x & 31);
+    const int wwc = ww < nwl ? ww : nwl - 1; // threads past the last patch load what the last one loads and store nothing
+    const int rp = threadIdx.x >> 5; // row pair inside the strip: image rows 16 strip + 2 rp, + 1
+    // the u rows of the luma patch and of the two chroma patches: issued before the V table is staged, so that the two
+    // memory round trips of a workgroup overlap
+    unsigned wl[RL / 4], wb[RC / 4], wr[RC / 4];
+    const long mrow[3] = {(long)(2 * strip + (rp >> 2)) * nwl + wwc, (long)strip * nwc + (wwc >> 1), (long)strip * nwc + (wwc >> 1)};
+    decode_u_load<RL>(Uc[0] + mrow[0] * R0, R0, wl);
+    decode_u_load<RC>(Uc[1] + mrow[1] * R1, R1, wb);
+    decode_u_load<RC>(Uc[2] + mrow[2] * R2, R2, wr);
+    decode_stage_v<RC, RL>(Vc, Rc, VsL, VsC);
+    __syncthreads();
+    if (ww >= nwl) return;
+    float ul[RL], ub[RC], ur[RC]; // zero padded to the rank bounds
+    decode_u_unpack<RL>(wl, ul);
+    decode_u_unpack<RC>(wb, ub);
+    decode_u_unpack<RC>(wr, ur);
+    // chroma: samples (row 8 strip + rp of the plane = row rp of the patch, columns 4 (ww & 1) .. + 3)
+    float cb[4], cr[4];
+    decode_chroma4<RC>(ub, ur, VsC, rp * 8 + 4 * (ww & 1), cb, cr);
 #pragma unroll
     for (int rr = 0; rr < 2; rr++) {
-        float y[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int n0 = (2 * (rp & 3) + rr) * 8;
-#pragma unroll
-        for (int r = 0; r < RL; r++) {
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(&VsL[r][n0]);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(&VsL[r][n0 + 4]);
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                y[i] = fmaf(ul[r], v0[i], y[i]);
-                y[4 + i] = fmaf(ul[r], v1[i], y[4 + i]);
-            }
-        }
         uint2 pk[3];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            float ch[3][4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) { // the k-ordered chains without their no-op steps
-                const float c0 = y[4 * h + i], c1 = cb[2 * h + (i >> 1)], c2 = cr[2 * h + (i >> 1)];
-                ch[0][i] = fmaf(1.402f, c2, c0);
-                ch[1][i] = fmaf(-0.714136f, c2, fmaf(-0.344136f, c1, c0));
-                ch[2][i] = fmaf(1.772f, c1, c0);
-            }
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const unsigned w = decode16_pack4(ch[k][0], ch[k][1], ch[k][2], ch[k][3]);
-                if (h == 0) pk[k].x = w; else pk[k].y = w;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) *reinterpret_cast<uint2*>(out + k * hw + (long)rr * W) = pk[k];
+        decode_row8<RL>(ul, VsL, (2 * (rp & 3) + rr) * 8, cb, cr, pk);
+        sink.put8(16 * strip + 2 * rp + rr, 8 * ww, pk);
     }
+}
+
+template <int RC, int RL>
+__global__ __launch_bounds__(256) void k_decode16(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W,
+                                                  ImageGeom g, int R0, int R1, int R2, long u_img, long v_img,
+                                                  uint8_t* __restrict__ rgb)
+{
+    __shared__ __attribute__((aligned(16))) float VsL[RL * 64], VsC[2 * RC * 64];
+    const long hw = (long)H * W;
+    DecodeStore sink{rgb + (long)blockIdx.y * 3 * hw, hw, W};
+    decode16_tile<RC, RL>(U + (long)blockIdx.y * u_img, V + (long)blockIdx.y * v_img, g, R0, R1, R2, (int)blockIdx.x, VsL, VsC, sink);
 }
 
 // k_decode16's tiling for every height and for the widths where the four chroma samples under a thread's eight pixels are
@@ -1679,21 +1745,17 @@ __global__ __launch_bounds__(256) void k_decode16(const int8_t* __restrict__ U, 
 // lrf/compression/utils.py:98-105): the two rows of a thread usually share it (then the chroma sums are computed once, as
 // in k_decode16), otherwise the second row's are computed separately, from the u rows of its own chroma patch.
 // Same arithmetic as k_decode8 / k_decode16.
-template <int RC, int RL> // rank bounds of the chroma planes (4, 8, 16) and of luma (8, 16, 32)
-__global__ __launch_bounds__(256) void k_decode_strip(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W,
-                                                      ImageGeom g, int R0, int R1, int R2, long u_img, long v_img,
-                                                      uint8_t* __restrict__ rgb, int per_strip)
+template <int RC, int RL, class Sink> // rank bounds of the chroma planes (4, 8, 16) and of luma (8, 16, 32)
+__device__ __forceinline__ void decode_strip_tile(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0,
+                                                  int R1, int R2, int bx, int per_strip, float* __restrict__ VsL, float* __restrict__ VsC, Sink& sink)
 {
-    __shared__ __attribute__((aligned(16))) float VsL[RL][64], VsC[2][RC][64];
-    const int8_t* Ui = U + (long)blockIdx.y * u_img;
-    const int8_t* Vi = V + (long)blockIdx.y * v_img;
     const int8_t* Uc[3] = {Ui, Ui + (long)g.p[0].M * R0, Ui + (long)g.p[0].M * R0 + (long)g.p[1].M * R1};
     const int8_t* Vc[3] = {Vi, Vi + 64 * R0, Vi + 64 * R0 + 64 * R1};
     const int Rc[3] = {R0, R1, R2};
     const PlaneGeom pl = g.p[0], pc = g.p[1];
     const int nwl = pl.nw, nwc = pc.nw;
-    const int strip = blockIdx.x / per_strip;
-    const int ww = (blockIdx.x - strip * per_strip) * 32 + (threadIdx.x & 31);
+    const int strip = bx / per_strip;
+    const int ww = (bx - strip * per_strip) * 32 + (threadIdx.x & 31);
     const int rp = threadIdx.x >> 5; // row pair inside the strip: padded luma rows 16 strip + 2 rp, + 1
     const int prow = 2 * strip + (rp >> 2);
     const bool live = ww < nwl && prow < pl.nh;
@@ -1718,14 +1780,7 @@ __global__ __launch_bounds__(256) void k_decode_strip(const int8_t* __restrict__
     decode_u_load<RL>(Uc[0] + ((long)prc * nwl + wwc) * R0, R0, wl);
     decode_u_load<RC>(Uc[1] + mc0 * R1, R1, wb);
     decode_u_load<RC>(Uc[2] + mc0 * R2, R2, wr);
-    for (int e = threadIdx.x; e < RL * 64; e += 256) {
-        const int r = e >> 6, n = e & 63;
-        VsL[r][n] = (r < R0) ? (float)Vc[0][n * R0 + r] : 0.f;
-    }
-    for (int e = threadIdx.x; e < 2 * RC * 64; e += 256) {
-        const int c = e / (RC * 64), r = (e >> 6) % RC, n = e & 63;
-        VsC[c][r][n] = (r < Rc[1 + c]) ? (float)Vc[1 + c][n * Rc[1 + c] + r] : 0.f;
-    }
+    decode_stage_v<RC, RL>(Vc, Rc, VsL, VsC);
     __syncthreads();
     if (!live) return;
     float ul[RL], ub[RC], ur[RC]; // zero padded to the rank bounds
@@ -1733,29 +1788,8 @@ __global__ __launch_bounds__(256) void k_decode_strip(const int8_t* __restrict__
     decode_u_unpack<RC>(wb, ub);
     decode_u_unpack<RC>(wr, ur);
     float cb[4], cr[4];
-    auto chroma = [&](int qq) { // samples (padded row qq, padded columns cx .. cx + 3) of both planes, "+ -128.f"
-#pragma unroll
-        for (int i = 0; i < 4; i++) cb[i] = cr[i] = 0.f;
-        const int nc = (qq & 7) * 8 + (cx & 7);
-#pragma unroll
-        for (int r = 0; r < RC; r++) {
-            const f32x4 vb = *reinterpret_cast<const f32x4*>(&VsC[0][r][nc]);
-            const f32x4 vr = *reinterpret_cast<const f32x4*>(&VsC[1][r][nc]);
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                cb[i] = fmaf(ub[r], vb[i], cb[i]);
-                cr[i] = fmaf(ur[r], vr[i], cr[i]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            cb[i] = cb[i] + -128.f;
-            cr[i] = cr[i] + -128.f;
-        }
-    };
-    chroma(q[0]);
-    const long hw = (long)H * W;
-    uint8_t* out = rgb + (long)blockIdx.y * 3 * hw;
+    // samples (padded row qq, padded columns cx .. cx + 3) of both planes
+    decode_chroma4<RC>(ub, ur, VsC, (q[0] & 7) * 8 + (cx & 7), cb, cr);
     const bool xfull = x0 >= 0 && x0 + 8 <= W;
 #pragma unroll
     for (int rr = 0; rr < 2; rr++) {
@@ -1767,67 +1801,47 @@ __global__ __launch_bounds__(256) void k_decode_strip(const int8_t* __restrict__
                 decode_u_unpack<RC>(wb, ub);
                 decode_u_unpack<RC>(wr, ur);
             }
-            chroma(q[1]);
+            decode_chroma4<RC>(ub, ur, VsC, (q[1] & 7) * 8 + (cx & 7), cb, cr);
         }
         if (y < 0 || y >= H) continue;
-        float yv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int n0 = (2 * (rp & 3) + rr) * 8;
-#pragma unroll
-        for (int r = 0; r < RL; r++) {
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(&VsL[r][n0]);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(&VsL[r][n0 + 4]);
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                yv[i] = fmaf(ul[r], v0[i], yv[i]);
-                yv[4 + i] = fmaf(ul[r], v1[i], yv[4 + i]);
-            }
-        }
         uint2 pk[3];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            float ch[3][4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) { // the k-ordered chains without their no-op steps
-                const float c0 = yv[4 * h + i], c1 = cb[2 * h + (i >> 1)], c2 = cr[2 * h + (i >> 1)];
-                ch[0][i] = fmaf(1.402f, c2, c0);
-                ch[1][i] = fmaf(-0.714136f, c2, fmaf(-0.344136f, c1, c0));
-                ch[2][i] = fmaf(1.772f, c1, c0);
-            }
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const unsigned w = decode16_pack4(ch[k][0], ch[k][1], ch[k][2], ch[k][3]);
-                if (h == 0) pk[k].x = w; else pk[k].y = w;
-            }
-        }
-        uint8_t* dst = out + (long)y * W + x0;
+        decode_row8<RL>(ul, VsL, (2 * (rp & 3) + rr) * 8, cb, cr, pk);
         if (xfull) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) *reinterpret_cast<uint2 __attribute__((aligned(1)))*>(dst + k * hw) = pk[k];
+            sink.put8u(y, x0, pk);
         } else { // the crop cuts this thread's run: byte by byte
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 const unsigned long long w = ((unsigned long long)pk[k].y << 32) | pk[k].x;
                 for (int j = 0; j < 8; j++)
-                    if (x0 + j >= 0 && x0 + j < W) dst[k * hw + j] = (uint8_t)(w >> (8 * j));
+                    if (x0 + j >= 0 && x0 + j < W) sink.put1(k, y, x0 + j, (uint8_t)(w >> (8 * j)));
             }
         }
     }
 }
 
-__global__ __launch_bounds__(256) void k_decode(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W,
-                                                ImageGeom g, int R0, int R1, int R2, long u_img, long v_img,
-                                                uint8_t* __restrict__ rgb)
+template <int RC, int RL>
+__global__ __launch_bounds__(256) void k_decode_strip(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W,
+                                                      ImageGeom g, int R0, int R1, int R2, long u_img, long v_img,
+                                                      uint8_t* __restrict__ rgb, int per_strip)
+{
+    __shared__ __attribute__((aligned(16))) float VsL[RL * 64], VsC[2 * RC * 64];
+    const long hw = (long)H * W;
+    DecodeStore sink{rgb + (long)blockIdx.y * 3 * hw, hw, W};
+    decode_strip_tile<RC, RL>(U + (long)blockIdx.y * u_img, V + (long)blockIdx.y * v_img, H, W, g, R0, R1, R2, (int)blockIdx.x, per_strip, VsL, VsC, sink);
+}
+
+// every geometry and rank: bx = the workgroup's index inside the image (256 groups of four pixels each)
+template <class Sink>
+__device__ __forceinline__ void decode_body(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0, int R1,
+                                            int R2, long bx, Sink& sink)
 {
     int w4 = (W + 3) >> 2;
-    long o = (long)blockIdx.x * 256 + threadIdx.x;
+    long o = bx * 256 + threadIdx.x;
     if (o >= (long)H * w4) return;
     int y = (int)(o / w4), x0 = (int)(o - (long)y * w4) * 4;
-    const int8_t* Ui = U + (long)blockIdx.y * u_img;
-    const int8_t* Vi = V + (long)blockIdx.y * v_img;
     const int8_t* Uc[3] = {Ui, Ui + (long)g.p[0].M * R0, Ui + (long)g.p[0].M * R0 + (long)g.p[1].M * R1};
     const int8_t* Vc[3] = {Vi, Vi + 64 * R0, Vi + 64 * R0 + 64 * R1};
     const int Rc[3] = {R0, R1, R2};
-    uint8_t* out = rgb + (long)blockIdx.y * 3 * H * W;
     const float T[3][3] = {{1.0f, 0.0f, 1.402f}, {1.0f, -0.344136f, -0.714136f}, {1.0f, 1.772f, 0.0f}};
     // nearest up-sampling source rows/cols (ATen: floor(dst * (in/out)) in fp32, clamped)
     float sh = (float)g.p[1].h / (float)H, sw = (float)g.p[1].w / (float)W;
@@ -1849,7 +1863,15 @@ __global__ __launch_bounds__(256) void k_decode(const int8_t* __restrict__ U, co
             acc = fmaf(T[ch][1], c[1], acc);
             acc = fmaf(T[ch][2], c[2], acc);
             acc = fminf(fmaxf(acc, 0.f), 255.f);
-            out[(long)ch * H * W + (long)y * W + x] = (uint8_t)acc; // truncation (to_dtype)
+            sink.put1(ch, y, x, (uint8_t)acc); // truncation (to_dtype)
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_decode(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W,
+                                                ImageGeom g, int R0, int R1, int R2, long u_img, long v_img,
+                                                uint8_t* __restrict__ rgb)
+{
+    DecodeStore sink{rgb + (long)blockIdx.y * 3 * H * W, (long)H * W, W};
+    decode_body(U + (long)blockIdx.y * u_img, V + (long)blockIdx.y * v_img, H, W, g, R0, R1, R2, (long)blockIdx.x, sink);
 }

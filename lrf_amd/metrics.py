@@ -75,6 +75,28 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
     return torch.tensor(np.mean(per_channel))
 
 
+def psnr_from_sse(sse: torch.Tensor, n: int, max_value: int = 255):
+    """(mse, psnr) in float64 from exact integer squared errors over n samples each: mse = sse / n, psnr = 20 log10(max_value /
+    sqrt(mse)), inf where sse is 0.  The ONE expression behind image_metrics_batch and qmf_encode_target, evaluated where `sse` lives."""
+    m = sse.double() / n
+    return m, 20 * torch.log10(max_value / torch.sqrt(m))
+
+
+def sweep_sse_batch(images: torch.Tensor, factors, triples, device=None) -> torch.Tensor:
+    """The exact squared error of every (rank triple, image) pair of a sweep, straight from its int8 factors on the GPU
+    (lrf_qmf_sweep_sse_rgb_u8, include/lrf_hip.h): no image is decoded to memory.
+
+    images: uint8 [B,3,H,W] (a host tensor is uploaded); triples: Q rank triples; factors: one (U, V) pair of int8 CUDA tensors per
+    triple, as `Context.encode_sweep_rgb` (or, for one triple, `qmf_factorize_batch`) returns them.  Returns an int64 device tensor
+    [Q, B], equal to image_metrics_batch(images, decode of the factors)["sse"] per triple; psnr_from_sse turns it into PSNR."""
+    from . import _lib
+    _lib.check_sweep_sse_args(images, factors, triples)  # (before a context exists: these refusals need no GPU)
+    if device is None:
+        device = factors[0][0].device.index
+    ctx = _lib.context(device)
+    return ctx.sweep_sse(images.to(torch.device("cuda", ctx.device)).contiguous(), factors, [tuple(int(r) for r in t) for t in triples])
+
+
 def image_metrics_batch(img1: torch.Tensor, img2: torch.Tensor, max_value: int = 255, want_ssim: bool = True, device=None) -> dict:
     """`mse`, `psnr` and `ssim` above for a whole batch of uint8 images on the GPU (lrf_image_metrics_u8, include/lrf_hip.h).
 
@@ -95,9 +117,8 @@ def image_metrics_batch(img1: torch.Tensor, img2: torch.Tensor, max_value: int =
     dev = torch.device("cuda", ctx.device)
     a, b = img1.to(dev).contiguous(), img2.to(dev).contiguous()
     sse, s = ctx.image_metrics(a, b, want_ssim=want_ssim)
-    n = a.shape[1] * a.shape[2] * a.shape[3]
-    m = sse.double() / n
-    out = {"sse": sse, "mse": m, "psnr": 20 * torch.log10(max_value / torch.sqrt(m))}
+    m, p = psnr_from_sse(sse, a.shape[1] * a.shape[2] * a.shape[3], max_value)
+    out = {"sse": sse, "mse": m, "psnr": p}
     if want_ssim:
         out["ssim"] = s
     return out
