@@ -6,8 +6,8 @@ import pytest
 
 from conftest import QMF_CASES, Case
 
-# cases whose every product lies in the pinned region (R <= 7, see lrf_oracle.c header) and whose planes have
-# full column rank, so that even the *initialisation* is determined up to sign
+# cases whose planes have full column rank, so that even the *initialisation* is determined up to sign (the order of the
+# oracle's products is pinned to the reference's up to rank 205: tools/pin_oracle_anyshape.py, lrf_oracle.c header)
 EXACT_CASES = ["tiny_q7", "tiny_r7", "tiny_it1", "tiny_it2", "odd_q7", "odd_r7", "smooth_q7", "smooth_r7", "s1_q7",
                "s1_r7", "nat_q7", "nat_r7", "s2odd_q7", "tiny_rank2"]
 
