@@ -33,31 +33,18 @@ int bcd32_bprep(hipStream_t rs, const PlaneDesc* pl, const float* vf, float* bf,
     return LRF_OK;
 }
 
-// The wave kernels take a run whose planes all have ranks 17..32, from LRF_BCDW32_MIN_BLOCKS blocks on:
-//   mode 0 (iterations >= 2): exact-integer bounds ((R - 1) 64 mx^3 < 2^24) with |b| within int16 (64 mx^2 <= 32767): the
-//           lane = row Gauss-Seidel on int16 pairs (k_bcd_w32);
-//   mode 1 (the first iteration, old U = X W0): one rank for the whole run and no plane small enough for ATen's native
-//           order of `uu @ bb` (k_bcd_w32f).
-bool bcd32_wave_kernels_apply(const FamRun& r, bool exact_int, long mx_b, int mode)
-{
-    static const bool w32_off = dev_flag("LRF_NO_BCDW32"); // dev build: k_bcd_mid instead
-    static const long w32_min = env_long("LRF_BCDW32_MIN_BLOCKS", LRF_BCDW32_MIN_BLOCKS); // test hook (lrf_env.h)
-    if (r.fam != 2 || !bcd_wave_variant() || w32_off || r.rmin < 17 || r.nblocks < w32_min) return false;
-    if (mode == 0) return exact_int && 64 * mx_b * mx_b <= 32767;
-    if (mode == 1) return !r.any_native && r.rmin == r.rmax;
-    return false;
-}
-
-int bcd32_update_u(lrf_ctx* c, hipStream_t rs, const BcdLaunch& a, const FamRun& r, long mx_b)
+// the U update of a rank 17..32 run by the kernel the plan names (bcd_kernel, lrf_plan.cpp)
+int bcd32_update_u(lrf_ctx* c, hipStream_t rs, const BcdLaunch& a, BcdChoice ch)
 {
     int rc = bcd32_attrs(c);
     if (rc) return rc;
     const int nbr = a.nblocks;
-    if (a.mode == 0 && bcd32_wave_kernels_apply(r, a.gp.exact_int != 0, mx_b, 0)) {
+    switch (ch.k) {
+    case BCD_K_W32:
 #define LRF_LAUNCH_W32(NP)                                                                                           \
     hipLaunchKernelGGL((k_bcd_w32<NP>), dim3((nbr + LRF_BCDW32_WAVES - 1) / LRF_BCDW32_WAVES), dim3(64 * LRF_BCDW32_WAVES), LRF_BCDW32_LDS(NP), \
                        rs, a.X, a.pl, a.bl, a.vf, a.bf, a.U, a.pp, a.qp, a.gp, nbr)
-        switch ((r.rmax + 1) >> 1) {
+        switch (ch.arg) {
         case 9: LRF_LAUNCH_W32(9); break;
         case 10: LRF_LAUNCH_W32(10); break;
         case 11: LRF_LAUNCH_W32(11); break;
@@ -68,18 +55,20 @@ int bcd32_update_u(lrf_ctx* c, hipStream_t rs, const BcdLaunch& a, const FamRun&
         default: LRF_LAUNCH_W32(16); break;
         }
 #undef LRF_LAUNCH_W32
-    } else if (a.mode == 1 && bcd32_wave_kernels_apply(r, a.gp.exact_int != 0, mx_b, 1)) {
+        break;
+    case BCD_K_W32F:
 #define LRF_LAUNCH_W32F(RR)                                                                                          \
     case RR:                                                                                                         \
         hipLaunchKernelGGL((k_bcd_w32f<RR>), dim3(nbr), dim3(64), LRF_BCDW32F_LDS, rs, a.X, a.pl, a.bl, a.vf, a.wf, a.bf, a.U, a.pp, a.qp, a.gp, nbr); \
         break;
-        switch (r.rmax) {
+        switch (ch.arg) {
             LRF_LAUNCH_W32F(17) LRF_LAUNCH_W32F(18) LRF_LAUNCH_W32F(19) LRF_LAUNCH_W32F(20) LRF_LAUNCH_W32F(21) LRF_LAUNCH_W32F(22)
             LRF_LAUNCH_W32F(23) LRF_LAUNCH_W32F(24) LRF_LAUNCH_W32F(25) LRF_LAUNCH_W32F(26) LRF_LAUNCH_W32F(27) LRF_LAUNCH_W32F(28)
             LRF_LAUNCH_W32F(29) LRF_LAUNCH_W32F(30) LRF_LAUNCH_W32F(31) LRF_LAUNCH_W32F(32)
         }
 #undef LRF_LAUNCH_W32F
-    } else {
+        break;
+    case BCD_K_MID:
 #define LRF_LAUNCH_MID(MODE)                                                                                         \
     hipLaunchKernelGGL((k_bcd_mid<MODE>), dim3(nbr), dim3(256), sizeof(MidLds<MODE>), rs, a.X, a.pl, a.bl, a.vf, a.wf, a.bf, a.U0, a.U, a.pp, \
                        a.qp, a.gp)
@@ -87,6 +76,8 @@ int bcd32_update_u(lrf_ctx* c, hipStream_t rs, const BcdLaunch& a, const FamRun&
         else if (a.mode == 2) LRF_LAUNCH_MID(2);
         else LRF_LAUNCH_MID(0);
 #undef LRF_LAUNCH_MID
+        break;
+    default: return set_err(LRF_EINVAL, "internal: kernel %d is not one of ranks 17..32", (int)ch.k);
     }
     LAUNCH_CHECK();
     return LRF_OK;

@@ -1,5 +1,5 @@
 // lrf_ctx.hip — host side of liblrf_hip.so that owns no kernel: error convention, the context and its workspace, image
-// geometry, descriptor tables and the launch plan of a call (kernel families, their streams), the memory helpers of the C ABI
+// geometry, descriptor tables, the streams of a call's kernel families (its launch plan: lrf_plan.cpp), the memory helpers of the C ABI
 // (include/lrf_hip.h).  The kernels and their launch sequences: lrf_encode8.hip (the 64-column path), lrf_any.hip (any-shape,
 // RGB colour space, svd); the host -> host pipeline: lrf_pipe.hip.
 #include "lrf_host.h"
@@ -107,25 +107,7 @@ int make_geom(int64_t H, int64_t W, ImageGeom* g)
     return LRF_OK;
 }
 
-// ---- descriptor tables ------------------------------------------------------------------------
-void add_plane(Tables& t, long x_off, long u_off, long v_off, long u0_off, long v0_off, int M, int R, int sign_off)
-{
-    PlaneDesc pd;
-    memset(&pd, 0, sizeof(pd));
-    pd.x_off = x_off; pd.u_off = u_off; pd.v_off = v_off; pd.u0_off = u0_off; pd.v0_off = v0_off;
-    pd.M = M; pd.R = R;
-    pd.blk0 = (int)t.blocks.size();
-    pd.nblk = (M + LRF_KC - 1) / LRF_KC;
-    pd.native_t2_u = ((long)(R - 1) * M < 400) ? 1 : 0;
-    pd.sign_off = sign_off;
-    int pi = (int)t.planes.size();
-    pd.init_src = pi; // (a sweep call's table builder points the lower-rank planes of a matrix at its largest-rank plane)
-    for (int b = 0; b < pd.nblk; b++) t.blocks.push_back(BlockDesc{pi, b * LRF_KC, b, 0});
-    pd.gch0 = 0; // the Gram chunks are cut when the table is complete (finish_gram_chunks)
-    pd.ngch = 0;
-    t.planes.push_back(pd);
-}
-
+// ---- descriptor tables (add_plane: lrf_plan.cpp) ------------------------------------------------
 int check_params(int64_t M, int64_t N, int R, int K, int lo, int hi)
 {
     if (N != LRF_PATCH_ELEMS) return set_err(LRF_ENOTSUP, "N=%ld: only N=%d (8x8 patches) is implemented", (long)N, LRF_PATCH_ELEMS);
@@ -141,55 +123,12 @@ int check_params(int64_t M, int64_t N, int R, int K, int lo, int hi)
     return LRF_OK;
 }
 
-// padded rank of the V / W / partial tables: 16 (one MFMA tile, the tuned kernels) or 64 (lrf_bigrank_kernels.hip)
-int table_rmax(const Tables& t)
+// ---- the launch plan's settings and what the context holds per run (struct FamRun, lrf_plan.h) --
+PlanSettings plan_settings(const lrf_ctx* c)
 {
-    int rmax = 1;
-    for (const PlaneDesc& pd : t.planes) rmax = pd.R > rmax ? pd.R : rmax;
-    return rmax;
-}
-int table_rp(const Tables& t) { return table_rmax(t) <= 16 ? 16 : LRF_RPB; }
-
-// ---- kernel families of a call (struct FamRun, lrf_host.h) -----------------------------------
-bool bcd_wave_variant()
-{
-    static const bool v = !dev_flag("LRF_BCD_WG"); // LRF_BCD_WG=1 (dev build): the workgroup kernel k_bcd instead of k_bcd_w
-    return v;
-}
-// Since the families of a call run side by side on streams of their own (round 3) — or in one persistent launch (round 5) — the
-// split pays from 1024 blocks on (64 x 512x768: (16,8,8) 0.93 -> 0.89 ms, (20,10,10) 2.04 -> 1.36 with k_bcd_w32 on the luma run);
-// calls with a rank above 16 split from 256 blocks (24 images: (20,10,10) 1.27 -> 1.04 ms, 12 images 1.06 -> 0.99).
-bool plan_splits(long nblocks, int rmax_t)
-{
-    static const bool no_split = dev_flag("LRF_NO_FAMILY_SPLIT");
-    static const long env_blocks = env_long("LRF_FAMILY_SPLIT_BLOCKS", -1); // test hook (lrf_env.h)
-    const long min_blocks = env_blocks >= 0 ? env_blocks : (rmax_t > 16 ? 256 : 1024);
-    return !no_split && bcd_wave_variant() && rmax_t <= LRF_BIG_TO_ANY_RANK && nblocks >= min_blocks;
-}
-std::vector<FamRun> plan_runs(const Tables& t)
-{
-    const int rmax_t = table_rmax(t);
-    const bool split = plan_splits((long)t.blocks.size(), rmax_t);
-    std::vector<FamRun> runs;
-    for (int p = 0; p < (int)t.planes.size(); p++) {
-        const PlaneDesc& pd = t.planes[p];
-        const int fam = split ? fam_of_rank(pd.R) : (rmax_t > 16 ? 2 : fam_of_rank(rmax_t));
-        if (runs.empty() || runs.back().fam != fam) runs.push_back(FamRun{p, 0, pd.blk0, 0, 1, fam, fam == 2 ? LRF_RPB : 16, pd.R, false, 0});
-        FamRun& r = runs.back();
-        r.any_native = r.any_native || pd.native_t2_u != 0;
-        if (pd.init_src == p && r.nbase == r.nplanes) r.nbase++; // (the table builders put a run's self-initialising planes first)
-        r.nplanes++;
-        r.nblocks += pd.nblk;
-        r.rmax = pd.R > r.rmax ? pd.R : r.rmax;
-        r.rmin = pd.R < r.rmin ? pd.R : r.rmin;
-    }
-    return runs;
-}
-bool plan_is_mixed(const std::vector<FamRun>& runs)
-{
-    bool p16 = false, p64 = false;
-    for (const FamRun& r : runs) (r.pitch == 16 ? p16 : p64) = true;
-    return p16 && p64;
+    PlanSettings s = plan_settings_env();
+    s.persist_arch = c->persist_arch;
+    return s;
 }
 FamBufs run_bufs(lrf_ctx* c, const FamRun& r, bool mixed)
 {
@@ -198,14 +137,13 @@ FamBufs run_bufs(lrf_ctx* c, const FamRun& r, bool mixed)
 }
 
 hipStream_t run_stream(lrf_ctx* c, size_t run_idx) { return (c->fam_forked && run_idx > 0) ? c->fam_stream[run_idx - 1] : c->stream; }
-// stage_only: the fork is joined again inside the caller's stage (run_init's initialisation kernels) — kernel profiling may stay
-// on (the stage's event pair on the caller's stream encloses fork and join); a fork that lasts into run_bcd is refused while
-// profiling is on (the per-launch event pairs are recorded on the caller's stream only).
-int fam_fork_streams(lrf_ctx* c, size_t nruns, bool stage_only)
+// FAM_STREAMS_INIT: the fork is joined again inside the caller's stage (run_init's initialisation kernels) — kernel profiling may
+// stay on (the stage's event pair on the caller's stream encloses fork and join); a fork that lasts into run_bcd is refused
+// while profiling is on (the per-launch event pairs are recorded on the caller's stream only).
+int fam_fork_streams(lrf_ctx* c, FamStreams layout, size_t nruns)
 {
-    static const bool off = dev_flag("LRF_NO_FAMILY_STREAMS");
     c->fam_forked = false;
-    if (off || !c->fam_parallel || (c->profile && !stage_only) || nruns < 2 || nruns > 3) return LRF_OK;
+    if (layout == FAM_STREAMS_NONE || (c->profile && layout != FAM_STREAMS_INIT) || nruns < 2 || nruns > 3) return LRF_OK;
     if (!c->fam_fork) HIP_TRY(hipEventCreateWithFlags(&c->fam_fork, hipEventDisableTiming));
     for (size_t i = 0; i + 1 < nruns; i++) {
         if (!c->fam_stream[i]) HIP_TRY(hipStreamCreateWithFlags(&c->fam_stream[i], hipStreamNonBlocking));
@@ -262,7 +200,7 @@ static void finish_gram_chunks(Tables& t)
     }
 }
 
-int upload_tables(lrf_ctx* c, Tables& t)
+int upload_tables(lrf_ctx* c, Tables& t, const BcdPlan& plan)
 {
     finish_gram_chunks(t);
     // the tables only depend on the call's geometry: skip the (synchronising) upload when nothing changed
@@ -298,13 +236,13 @@ int upload_tables(lrf_ctx* c, Tables& t)
     if ((rc = ensure(c, c->gpart, t.gchunks.size() * (size_t)LRF_GRAM_SLOT * sizeof(ulonglong2)))) return rc;
     if ((rc = ensure(c, c->gexp, t.planes.size() * sizeof(int)))) return rc;
     size_t np = t.planes.size(), nb = t.blocks.size();
-    size_t rp = (size_t)table_rp(t), gts = rp == 16 ? (size_t)LRF_GT_STRIDE : (size_t)LRF_GTB_STRIDE;
+    size_t rp = (size_t)plan.rp, gts = rp == 16 ? (size_t)LRF_GT_STRIDE : (size_t)LRF_GTB_STRIDE;
     if ((rc = ensure(c, c->vf, np * 64 * rp * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->wf, np * 64 * rp * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->bf, np * gts * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->ppart, nb * 64 * rp * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->qpart, nb * rp * rp * sizeof(float)))) return rc;
-    if (plan_is_mixed(plan_runs(t))) {
+    if (plan.mixed) {
         if ((rc = ensure(c, c->vf16, np * 64 * 16 * sizeof(float)))) return rc;
         if ((rc = ensure(c, c->wf16, np * 64 * 16 * sizeof(float)))) return rc;
         if ((rc = ensure(c, c->bf16, np * (size_t)LRF_GT_STRIDE * sizeof(float)))) return rc;

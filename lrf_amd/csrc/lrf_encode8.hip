@@ -10,7 +10,7 @@
 
 // gram_exp: the fixed-point grid exponent of the exact Gram matrix (max|x| < 2^gram_exp) when the caller knows it — 8 for the
 // planes of qmf_encode — or LRF_GRAM_EXP_FROM_DATA: one more pass over X finds it per matrix
-static int run_init(lrf_ctx* c, const float* X, const Tables& t, const int8_t* sign_dev, int gram_exp)
+static int run_init(lrf_ctx* c, const float* X, const Tables& t, const BcdPlan& plan, const int8_t* sign_dev, int gram_exp)
 {
     if (!(c->attr_done & (1u << 0))) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_init<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InitLds<8>)));
@@ -22,7 +22,7 @@ static int run_init(lrf_ctx* c, const float* X, const Tables& t, const int8_t* s
         HIP_TRY(hipFuncSetAttribute((const void*)k_init<64, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InitLds<64>)));
         c->attr_done |= 1u << 0;
     }
-    int rmax = table_rmax(t), rp = table_rp(t), nplanes = (int)t.planes.size();
+    const int nplanes = (int)t.planes.size();
     {
         Prof p(c, LRF_K_GRAM);
         if (gram_exp == LRF_GRAM_EXP_FROM_DATA) {
@@ -43,23 +43,18 @@ static int run_init(lrf_ctx* c, const float* X, const Tables& t, const int8_t* s
         }
     }
     Prof p(c, LRF_K_INIT);
-    const std::vector<FamRun> runs = plan_runs(t);
-    const bool mixed = plan_is_mixed(runs);
-    // A call whose iterations run in the persistent kernel keeps one stream — except here: the initialisation kernels of its
-    // families are per-matrix latency chains that leave most of a CU idle (k_init<16> 190 us for 256 luma planes, k_init<8> 180
-    // us for 512 chroma planes, one round of workgroups each), and LDS admits one workgroup of the first beside two of the
-    // second: forked for this stage only, the later runs (chroma: more, smaller workgroups) enqueued first, joined at once.
+    const std::vector<FamRun>& runs = plan.runs;
+    const bool mixed = plan.mixed;
+    // A call whose iterations run in the persistent kernel keeps one stream — except here (FAM_STREAMS_INIT): the initialisation
+    // kernels of its families are per-matrix latency chains that leave most of a CU idle (k_init<16> 190 us for 256 luma planes,
+    // k_init<8> 180 us for 512 chroma planes, one round of workgroups each), and LDS admits one workgroup of the first beside two
+    // of the second: forked for this stage only, the later runs (chroma: more, smaller workgroups) enqueued first, joined at once.
     // (The order of the enqueues does not show in the step time — measured both ways at five rank triples — because the
     // streams' queues place their workgroups side by side either way.)  Since round 5's LDS layout (InitLds) a ZR = 32 workgroup
     // has two ZR = 16 ones beside it as well ((26,13,13): the stage 484 -> ~340 us).
-    static const bool init_fork_off = dev_flag("LRF_NO_INIT_FORK");
-    const bool init_only_fork = !c->fam_parallel && c->init_parallel && !init_fork_off;
-    if (init_only_fork) c->fam_parallel = true;
-    {
-        int rcf = fam_fork_streams(c, runs.size(), init_only_fork);
-        if (init_only_fork) c->fam_parallel = false;
-        if (rcf) return rcf;
-    }
+    const bool init_only_fork = plan.streams == FAM_STREAMS_INIT;
+    int rcf = fam_fork_streams(c, plan.streams, runs.size());
+    if (rcf) return rcf;
     long ninit = 0;
     for (const FamRun& r : runs) ninit += r.nbase;
     const bool dense = ninit > 256; // more initialisation workgroups than CUs (k_init's DENSE)
@@ -85,17 +80,16 @@ static int run_init(lrf_ctx* c, const float* X, const Tables& t, const int8_t* s
 #undef LRF_LAUNCH_INIT
         LAUNCH_CHECK();
     }
-    (void)rmax;
     if (init_only_fork) {
         int rcj = fam_join_streams(c, runs.size());
         if (rcj) return rcj;
     }
     bool shares = false;
     for (const FamRun& r : runs) shares = shares || r.nbase != r.nplanes;
-    if (shares) { // a sweep call (its entry point keeps one stream): the other ranks' planes take their columns from the base planes
+    if (shares) { // a sweep call (its plan keeps one stream): the other ranks' planes take their columns from the base planes
         if (c->fam_forked) return set_err(LRF_EINVAL, "internal: a call that shares initialisations between planes must not fork its families");
         hipLaunchKernelGGL(k_init_share, dim3(nplanes), dim3(256), 0, c->stream, (const PlaneDesc*)c->planes.p, (float*)c->vf.p, (float*)c->wf.p,
-                           (float*)c->vf16.p, (float*)c->wf16.p, plan_splits((long)t.blocks.size(), table_rmax(t)) ? 1 : 0, mixed ? 1 : 0, rp);
+                           (float*)c->vf16.p, (float*)c->wf16.p, plan.split ? 1 : 0, mixed ? 1 : 0, plan.rp);
         LAUNCH_CHECK();
     }
     return LRF_OK;
@@ -106,27 +100,23 @@ static GsParams make_gs(int lo, int hi)
     GsParams gp;
     gp.lo = (float)lo;
     gp.hi = (float)hi;
-    int mx = abs(lo) > abs(hi) ? abs(lo) : abs(hi);
+    const long mx = bounds_mx(lo, hi);
     gp.flimit = (float)(mx + 2);
     gp.fthr = 0.5f - 8e-7f * (float)(mx + 2); // see gs_row: q~ is within 3 ulp (< 2e-7 |q|) of fl(num/den)
-    gp.exact_int = 0; // set per call by run_bcd (depends on the largest rank)
+    gp.exact_int = 0; // set per run by run_bcd (FamRun::exact_int)
     return gp;
 }
 
-// mode: 1 = old U from X @ W0 (after run_init), 2 = old U from caller's fp32 U0
-static int run_bcd(lrf_ctx* c, const float* X, const Tables& t, int K, int lo, int hi, int first_mode, const float* U0,
-                   int8_t* U, int8_t* V)
+// the iterations of the plan (plan.first_mode: 1 = old U from X @ W0 after run_init, 2 = old U from the caller's fp32 U0)
+static int run_bcd(lrf_ctx* c, const float* X, const BcdPlan& plan, const float* U0, int8_t* U, int8_t* V)
 {
     const PlaneDesc* pl = (const PlaneDesc*)c->planes.p;
     const BlockDesc* bl = (const BlockDesc*)c->blocks.p;
-    GsParams gp = make_gs(lo, hi);
-    if (table_rmax(t) > LRF_BIG_TO_ANY_RANK) return set_err(LRF_ENOTSUP, "internal: ranks above %d iterate on the any-shape kernels", LRF_BIG_TO_ANY_RANK);
-    const std::vector<FamRun> runs = plan_runs(t);
-    const bool mixed = plan_is_mixed(runs);
-    // k_bcd_w (one wave per block, no barriers) for rank <= 8 runs — of LRF_BCDW_MIN_BLOCKS blocks or more: with fewer than a
-    // wave per SIMD what counts is the latency of ONE block, and there the four waves of the workgroup kernel k_bcd share a
-    // block's sub-tile (one 512x768 image: 27.9 -> 17.0 us per launch, 8 images 28.5 -> 18.2, 32 images 31.7 -> 27.6; equal at 48)
-    const bool wave_variant = bcd_wave_variant();
+    const int K = plan.K;
+    const GsParams gp = make_gs(plan.lo, plan.hi);
+    if (plan.rmax > LRF_BIG_TO_ANY_RANK) return set_err(LRF_ENOTSUP, "internal: ranks above %d iterate on the any-shape kernels", LRF_BIG_TO_ANY_RANK);
+    const std::vector<FamRun>& runs = plan.runs;
+    const bool mixed = plan.mixed;
     if (!(c->attr_done & (1u << 1))) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_bcd_w<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LRF_BCDW_LDS));
         HIP_TRY(hipFuncSetAttribute((const void*)k_bcd_w<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LRF_BCDW_LDS));
@@ -148,35 +138,21 @@ static int run_bcd(lrf_ctx* c, const float* X, const Tables& t, int K, int lo, i
             if (rcb) return rcb;
         }
     }
-    // Iterations >= 2 with bounds where every term and partial sum of `uu @ bb` is an exact integer in fp32 for the largest
-    // rank of a run ((R - 1) 64 mx^3 < 2^24): the order of that sum is immaterial, which lets ranks 9..16 (gs_row_lds) and
-    // 17..32 (k_bcd_w32, k_bcd_mid) replace the reference's dependent chain by independent fmas, bit for bit
-    const long mx_b = abs(lo) > abs(hi) ? abs(lo) : abs(hi);
-    static const bool exact_off = dev_flag("LRF_GENERIC_GS");
-    static const long w16_min = env_long("LRF_BCDW16_MIN_BLOCKS", LRF_BCDW16_MIN_BLOCKS); // test hook (lrf_env.h)
-    // Iterations 2..K of a large call in ONE launch (k_bcd_p<F16, NP32>, lrf_bcd_persist.hip): the U updates of all iterations
-    // and planes pulled from a queue, each matrix's V update done by the last of its blocks to finish (bcdp_plan says which
-    // calls).  Such a call never forks its families onto streams (plan_fam_parallel).
-    const PersistPlan persist = bcdp_plan(c, runs, K, lo, hi);
-    // ... and the first iteration as well when its old U is X @ W0 of the initialisation just run (first_mode 1) and no plane of
-    // ranks 9..16 is small enough for ATen's native order (bcdp_plan has checked that already): then the b tables above are
-    // the last launch before k_bcd_p.
-    const bool persist_first = persist.use && persist.first && first_mode == 1;
     for (int it = 0; it < K; it++) {
-        if (persist.use && it == (persist_first ? 0 : 1)) {
+        if (plan.persist && it == (plan.persist_first ? 0 : 1)) { // the remaining iterations in one launch (lrf_bcd_persist.hip)
             const FamRun& r0 = runs.front();
             long nb = 0, np = 0;
             for (const FamRun& r : runs) { nb += r.nblocks; np += r.nplanes; }
             // the table sets of the two rank pitches (run_bufs): a call without ranks above 16 has only the pitch-16 one
             FamBufs f16{nullptr, nullptr, nullptr, nullptr, nullptr}, f64 = f16;
             for (const FamRun& r : runs) (r.pitch == 16 ? f16 : f64) = run_bufs(c, r, mixed);
-            int rcp = bcdp_launch(c, persist, X, pl, bl + r0.block0, (int)nb, (int)np, r0.plane0, f16, f64, U, V, gp, persist_first ? K : K - 1, persist_first);
+            int rcp = bcdp_launch(c, plan, X, pl, bl + r0.block0, (int)nb, (int)np, r0.plane0, f16, f64, U, V, gp);
             if (rcp) return rcp;
             break;
         }
         {
             Prof p(c, LRF_K_BCD);
-            const int mode = (it == 0) ? first_mode : 0;
+            const int mode = (it == 0) ? plan.first_mode : 0;
             for (size_t ri = 0; ri < runs.size(); ri++) {
                 const FamRun& r = runs[ri];
                 hipStream_t rs = run_stream(c, ri);
@@ -184,43 +160,34 @@ static int run_bcd(lrf_ctx* c, const float* X, const Tables& t, int K, int lo, i
                 const BlockDesc* blr = bl + r.block0;
                 const int nbr = r.nblocks;
                 GsParams gpr = gp;
-                gpr.exact_int = (!exact_off && (long)(r.rmax - 1) * 64 * mx_b * mx_b * mx_b < (1L << 24)) ? 1 : 0;
+                gpr.exact_int = r.exact_int ? 1 : 0;
+                const BcdChoice ch = (it == 0) ? r.first : r.later;
 #define LRF_LAUNCH_W(MODE)                                                                                           \
     hipLaunchKernelGGL((k_bcd_w<MODE>), dim3((nbr + LRF_BCDW_WAVES - 1) / LRF_BCDW_WAVES), dim3(64 * LRF_BCDW_WAVES), LRF_BCDW_LDS, rs, X, pl, blr, \
                        (const float*)fb.vf, (const float*)fb.wf, (const float*)fb.bf, U0, U, fb.pp, fb.qp, gpr, nbr)
 #define LRF_LAUNCH_WG(MODE, RMAX)                                                                                    \
     hipLaunchKernelGGL((k_bcd<MODE, RMAX>), dim3(nbr), dim3(256), 0, rs, X, pl, blr, (const float*)fb.vf, (const float*)fb.wf, \
                        (const float*)fb.bf, U0, U, fb.pp, fb.qp, gpr)
-                if (r.fam == 2) {
-                    // ranks 17..32: k_bcd_w32 / k_bcd_w32f (one wave per block) or the workgroup kernel k_bcd_mid (lrf_bcd32.hip)
-                    const BcdLaunch a{X, pl, blr, nbr, fb.vf, fb.wf, fb.bf, U0, U, fb.pp, fb.qp, gpr, mode};
-                    int rcu = bcd32_update_u(c, rs, a, r, mx_b);
-                    if (rcu) return rcu;
-                    continue;
-                } else if (r.fam == 0 && wave_variant && nbr >= LRF_BCDW_MIN_BLOCKS) {
-                    if (mode == 1) LRF_LAUNCH_W(1);
-                    else if (mode == 2) LRF_LAUNCH_W(2);
-                    else LRF_LAUNCH_W(0);
-                } else if (r.fam == 0) {
-                    if (mode == 1) LRF_LAUNCH_WG(1, 8);
-                    else if (mode == 2) LRF_LAUNCH_WG(2, 8);
-                    else LRF_LAUNCH_WG(0, 8);
-                } else if (wave_variant && nbr >= w16_min && ((mode == 0 && gpr.exact_int) || (mode == 1 && !r.any_native))) {
-                    // ranks 9..16 (and the lower-rank planes of such a run): iterations >= 2 with exact-integer bounds, and
-                    // the first iteration from the initialisation's W0 unless a plane is small enough for ATen's native order
 #define LRF_LAUNCH_W16(MODE)                                                                                         \
     hipLaunchKernelGGL((k_bcd_w16<MODE>), dim3((nbr + LRF_BCDW16_WAVES - 1) / LRF_BCDW16_WAVES), dim3(64 * LRF_BCDW16_WAVES), LRF_BCDW16_LDS, \
                        rs, X, pl, blr, (const float*)fb.vf, (const float*)fb.wf, (const float*)fb.bf, U, fb.pp, fb.qp, gpr, nbr)
-                    if (mode == 1) LRF_LAUNCH_W16(1);
-                    else LRF_LAUNCH_W16(0);
-#undef LRF_LAUNCH_W16
-                } else {
-                    if (mode == 1) LRF_LAUNCH_WG(1, 16);
-                    else if (mode == 2) LRF_LAUNCH_WG(2, 16);
-                    else LRF_LAUNCH_WG(0, 16);
+#define LRF_BY_MODE(LAUNCH, ...) if (mode == 1) LAUNCH(1, ##__VA_ARGS__); else if (mode == 2) LAUNCH(2, ##__VA_ARGS__); else LAUNCH(0, ##__VA_ARGS__)
+                switch (ch.k) {
+                case BCD_K_W: LRF_BY_MODE(LRF_LAUNCH_W); break;
+                case BCD_K_WG8: LRF_BY_MODE(LRF_LAUNCH_WG, 8); break;
+                case BCD_K_WG16: LRF_BY_MODE(LRF_LAUNCH_WG, 16); break;
+                case BCD_K_W16: if (mode == 1) LRF_LAUNCH_W16(1); else LRF_LAUNCH_W16(0); break;
+                default: { // ranks 17..32 (lrf_bcd32.hip)
+                    const BcdLaunch a{X, pl, blr, nbr, fb.vf, fb.wf, fb.bf, U0, U, fb.pp, fb.qp, gpr, mode};
+                    int rcu = bcd32_update_u(c, rs, a, ch);
+                    if (rcu) return rcu;
+                    continue;
                 }
+                }
+#undef LRF_BY_MODE
 #undef LRF_LAUNCH_W
 #undef LRF_LAUNCH_WG
+#undef LRF_LAUNCH_W16
                 LAUNCH_CHECK();
             }
         }
@@ -248,10 +215,16 @@ static int run_bcd(lrf_ctx* c, const float* X, const Tables& t, int K, int lo, i
     return fam_join_streams(c, runs.size());
 }
 
-// Whether the kernel families of a call may run on streams of their own (run_init forks, run_bcd joins): not when the call's
-// iterations 2..K run in the persistent kernel — one launch for all families, behind a first iteration whose family kernels
-// run one after the other (side by side they were SLOWER: k_bcd_w32f 305 us and k_bcd_w16<1> 80 us alone, 590 us together).
-static bool plan_fam_parallel(lrf_ctx* c, const Tables& t, int K, int lo, int hi) { return !bcdp_plan(c, plan_runs(t), K, lo, hi).use; }
+// a call that initialises and iterates at once: run_init may leave the families forked for run_bcd to join
+static int init_then_bcd(lrf_ctx* c, const float* X, const Tables& t, const BcdPlan& plan, const int8_t* sign, int gram_exp, int8_t* U, int8_t* V)
+{
+    int rc = run_init(c, X, t, plan, sign, gram_exp);
+    if (rc) {
+        (void)fam_join_streams(c, 3);
+        return rc;
+    }
+    return run_bcd(c, X, plan, nullptr, U, V);
+}
 
 // ---- C ABI ------------------------------------------------------------------------------------
 extern "C" {
@@ -320,16 +293,16 @@ static int any_bcd_from_init(lrf_ctx* c, const float* X, long x_batch, int B, in
 }
 
 // k_init on the uploaded table, then its factors as fp32 into c->any_e2 (U0 at [0], V0 behind it): offsets from the table
-static int init_to_fp32(lrf_ctx* c, const float* X, const Tables& t, const int8_t* sign, size_t u0_floats, size_t v0_floats, float** U0,
+static int init_to_fp32(lrf_ctx* c, const float* X, const Tables& t, const BcdPlan& plan, const int8_t* sign, size_t u0_floats, size_t v0_floats, float** U0,
                         float** V0, int gram_exp)
 {
-    int rc = run_init(c, X, t, sign, gram_exp);
+    int rc = run_init(c, X, t, plan, sign, gram_exp);
     if (rc) return rc;
     if ((rc = ensure(c, c->any_e2, (u0_floats + v0_floats) * sizeof(float)))) return rc;
     *U0 = (float*)c->any_e2.p;
     *V0 = *U0 + u0_floats;
     hipLaunchKernelGGL(k_emit_init, dim3((unsigned)t.blocks.size()), dim3(256), 0, c->stream, X, (const PlaneDesc*)c->planes.p,
-                       (const BlockDesc*)c->blocks.p, (const float*)c->vf.p, (const float*)c->wf.p, *U0, *V0, table_rp(t));
+                       (const BlockDesc*)c->blocks.p, (const float*)c->vf.p, (const float*)c->wf.p, *U0, *V0, plan.rp);
     LAUNCH_CHECK();
     return LRF_OK;
 }
@@ -346,21 +319,14 @@ int lrf_qmf_decompose_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int6
     LRF_ON_DEVICE(c);
     Tables t;
     uniform_tables(t, B, M, R, sign != nullptr);
-    if ((rc = upload_tables(c, t))) return rc;
+    const BcdPlan plan = plan_bcd(t.planes, K, lo, hi, PLAN_FIRST_W0, plan_settings(c));
+    if ((rc = upload_tables(c, t, plan))) return rc;
     if (R > LRF_BIG_TO_ANY_RANK) {
         float *U0, *V0;
-        if ((rc = init_to_fp32(c, X, t, sign, (size_t)B * M * R, (size_t)B * 64 * R, &U0, &V0, LRF_GRAM_EXP_FROM_DATA))) return rc;
+        if ((rc = init_to_fp32(c, X, t, plan, sign, (size_t)B * M * R, (size_t)B * 64 * R, &U0, &V0, LRF_GRAM_EXP_FROM_DATA))) return rc;
         return any_bcd_from_init(c, X, M * 64, (int)B, (int)M, R, K, lo, hi, U0, V0, U, M * R, V, 64L * R);
     }
-    c->fam_parallel = plan_fam_parallel(c, t, K, lo, hi); // run_init is followed by run_bcd at once: the kernel families of the call may run side by side
-    c->init_parallel = !c->fam_parallel;
-    rc = run_init(c, X, t, sign, LRF_GRAM_EXP_FROM_DATA);
-    c->fam_parallel = c->init_parallel = false;
-    if (rc) {
-        (void)fam_join_streams(c, 3);
-        return rc;
-    }
-    return run_bcd(c, X, t, K, lo, hi, 1, nullptr, U, V);
+    return init_then_bcd(c, X, t, plan, sign, LRF_GRAM_EXP_FROM_DATA, U, V);
 }
 
 int lrf_qmf_bcd_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64_t N, int R, int K, int lo, int hi,
@@ -374,11 +340,12 @@ int lrf_qmf_bcd_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64_t N,
     LRF_ON_DEVICE(c);
     Tables t;
     uniform_tables(t, B, M, R, false);
-    if ((rc = upload_tables(c, t))) return rc;
+    const BcdPlan plan = plan_bcd(t.planes, K, lo, hi, PLAN_FIRST_U0, plan_settings(c));
+    if ((rc = upload_tables(c, t, plan))) return rc;
     hipLaunchKernelGGL(k_load_v0, dim3((unsigned)t.planes.size()), dim3(256), 0, c->stream, (const PlaneDesc*)c->planes.p, V0,
-                       (float*)c->vf.p, table_rp(t));
+                       (float*)c->vf.p, plan.rp);
     LAUNCH_CHECK();
-    return run_bcd(c, X, t, K, lo, hi, 2, U0, U, V);
+    return run_bcd(c, X, plan, U0, U, V);
 }
 
 int lrf_qmf_svd_init_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64_t N, int R, const int8_t* sign,
@@ -392,10 +359,11 @@ int lrf_qmf_svd_init_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64
     LRF_ON_DEVICE(c);
     Tables t;
     uniform_tables(t, B, M, R, sign != nullptr);
-    if ((rc = upload_tables(c, t))) return rc;
-    if ((rc = run_init(c, X, t, sign, LRF_GRAM_EXP_FROM_DATA))) return rc;
+    const BcdPlan plan = plan_bcd(t.planes, 0, 0, 0, PLAN_INIT_ONLY, plan_settings(c));
+    if ((rc = upload_tables(c, t, plan))) return rc;
+    if ((rc = run_init(c, X, t, plan, sign, LRF_GRAM_EXP_FROM_DATA))) return rc;
     hipLaunchKernelGGL(k_emit_init, dim3((unsigned)t.blocks.size()), dim3(256), 0, c->stream, X, (const PlaneDesc*)c->planes.p,
-                       (const BlockDesc*)c->blocks.p, (const float*)c->vf.p, (const float*)c->wf.p, U0, V0, table_rp(t));
+                       (const BlockDesc*)c->blocks.p, (const float*)c->vf.p, (const float*)c->wf.p, U0, V0, plan.rp);
     LAUNCH_CHECK();
     return LRF_OK;
 }
@@ -432,7 +400,8 @@ int encode_rgb_prepare(lrf_ctx* c, int64_t B, int64_t H, int64_t W, const int R[
                       with_sign ? (int)(b * s_img + soff[ch]) : -1);
             if (fuse_gram && ch == 0) ep.t.planes.back().gram_fused = 1;
         }
-    return upload_tables(c, ep.t);
+    ep.bcd = plan_bcd(ep.t.planes, K, lo, hi, PLAN_FIRST_W0, plan_settings(c));
+    return upload_tables(c, ep.t, ep.bcd);
 }
 
 extern "C" {
@@ -453,24 +422,16 @@ int lrf_qmf_encode_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64_t H, 
     float* X = (float*)c->x.p;
     if ((rc = fuse ? planes_gram_from_rgb(c, rgb, H, W, g, t, X) : lrf_qmf_planes_from_rgb_u8(c, rgb, B, H, W, X))) return rc;
     if (c->planes_done) HIP_TRY(hipEventRecord(c->planes_done, c->stream)); // the RGB bytes are not read again
-    if (table_rmax(t) > LRF_BIG_TO_ANY_RANK) {
+    if (ep.bcd.rmax > LRF_BIG_TO_ANY_RANK) {
         float *U0, *V0;
-        if ((rc = init_to_fp32(c, X, t, sign, (size_t)u0c[3], (size_t)v0c[3], &U0, &V0, LRF_PLANES_GRAM_EXP))) return rc;
+        if ((rc = init_to_fp32(c, X, t, ep.bcd, sign, (size_t)u0c[3], (size_t)v0c[3], &U0, &V0, LRF_PLANES_GRAM_EXP))) return rc;
         for (int ch = 0; ch < 3; ch++)
             if ((rc = any_bcd_from_init(c, X + g.p[ch].xoff, g.img_floats, (int)B, g.p[ch].M, R[ch], K, lo, hi, U0 + u0c[ch],
                                         V0 + v0c[ch], U + uoff[ch], u_img, V + voff[ch], v_img)))
                 return rc;
         return LRF_OK;
     }
-    c->fam_parallel = plan_fam_parallel(c, t, K, lo, hi); // run_init is followed by run_bcd at once: the kernel families of the call may run side by side
-    c->init_parallel = !c->fam_parallel;
-    rc = run_init(c, X, t, sign, LRF_PLANES_GRAM_EXP);
-    c->fam_parallel = c->init_parallel = false;
-    if (rc) {
-        (void)fam_join_streams(c, 3);
-        return rc;
-    }
-    return run_bcd(c, X, t, K, lo, hi, 1, nullptr, U, V);
+    return init_then_bcd(c, X, t, ep.bcd, sign, LRF_PLANES_GRAM_EXP, U, V);
 }
 
 // One batch at Q rank triples in one call (BASELINE config 3: an R-D sweep of 24 images x qualities 1..32; the reference's loop
@@ -509,12 +470,13 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64
         uq[q + 1] = uq[q] + B * u_img[q];
         vq[q + 1] = vq[q] + B * v_img[q];
     }
-    // The plane table: Q x B x 3 planes on B x 3 matrices.  Order: by kernel family (so that plan_runs finds at most three runs),
+    // The plane table: Q x B x 3 planes on B x 3 matrices.  Order: by kernel family (so that plan_bcd finds at most three runs),
     // inside a family the planes that compute an initialisation first (run_init launches k_init for a run's leading planes), then
     // luma before chroma; a call too small to split its families keeps one run: all initialising planes first.
     long nblk_img = 0;
     for (int ch = 0; ch < 3; ch++) nblk_img += (g.p[ch].M + LRF_KC - 1) / LRF_KC;
-    const bool split = plan_splits((long)Q * B * nblk_img, rmax_t);
+    const PlanSettings settings = plan_settings(c);
+    const bool split = plan_splits((long)Q * B * nblk_img, rmax_t, settings);
     const long s_img = rmaxc[0] + rmaxc[1] + rmaxc[2];
     const long soff[3] = {0, rmaxc[0], (long)rmaxc[0] + rmaxc[1]};
     struct Spec { int q, ch; long b; };
@@ -543,19 +505,12 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64
         t.planes[pi].init_src = base_index[(size_t)sp.b * 3 + sp.ch];
         if (fuse && sp.ch == 0 && t.planes[pi].init_src == (int)pi) t.planes[pi].gram_fused = 1; // one luma plane per image
     }
-    if ((rc = upload_tables(c, t))) return rc;
+    const BcdPlan plan = plan_bcd(t.planes, K, lo, hi, PLAN_FIRST_W0, settings, true);
+    if ((rc = upload_tables(c, t, plan))) return rc;
     float* X = (float*)c->x.p;
     if ((rc = fuse ? planes_gram_from_rgb(c, rgb, H, W, g, t, X) : lrf_qmf_planes_from_rgb_u8(c, rgb, B, H, W, X))) return rc;
     if (c->planes_done) HIP_TRY(hipEventRecord(c->planes_done, c->stream));
-    c->fam_parallel = false; // one stream: the shared initialisations tie the families together
-    c->init_parallel = true;
-    rc = run_init(c, X, t, sign, LRF_PLANES_GRAM_EXP);
-    c->init_parallel = false;
-    if (rc) {
-        (void)fam_join_streams(c, 3);
-        return rc;
-    }
-    return run_bcd(c, X, t, K, lo, hi, 1, nullptr, U, V);
+    return init_then_bcd(c, X, t, plan, sign, LRF_PLANES_GRAM_EXP, U, V);
 }
 
 // which decode body serves a geometry and a rank triple (lrf_qmf_decode_rgb_u8 and lrf_qmf_sweep_sse_rgb_u8 share it)

@@ -2,8 +2,9 @@
 //
 // Service knobs (every build): test hooks that move a size threshold so that small test inputs reach the large-call
 // kernels, and the pipe's schedule overrides.  Read once per process.
-//   LRF_PERSIST              0: never k_bcd_p; 1: k_bcd_p from LRF_BCDW_MIN_BLOCKS blocks on       (run_bcd)
-//   LRF_FAMILY_SPLIT_BLOCKS  blocks from which a call's rank families run on kernels of their own  (plan_runs)
+// The first four are the launch plan's (PlanSettings, lrf_plan.h: plan_settings_env reads them, plan_bcd decides by them).
+//   LRF_PERSIST              0: never k_bcd_p; 1: k_bcd_p from LRF_BCDW_MIN_BLOCKS blocks on
+//   LRF_FAMILY_SPLIT_BLOCKS  blocks from which a call's rank families run on kernels of their own  (plan_splits)
 //   LRF_BCDW16_MIN_BLOCKS / LRF_BCDW32_MIN_BLOCKS  blocks from which the wave kernels of ranks 9..16 / 17..32 run
 //   LRF_DEBUG_INIT_SWEEPS    stops k_init after a stage / forces the Sturm replacement loop       (tests/test_hip_parity.py)
 //   LRF_PIPE_BULK / LRF_PIPE_TAIL  the pipe's piece sizes                                          (tests/test_pipeline.py)

@@ -1,5 +1,5 @@
 // lrf_host.h — what the host-side translation units of liblrf_hip.so share: error convention, device guard, the context,
-// descriptor tables and the launch plan of a call.  lrf_ctx.hip defines the functions declared here unless noted.
+// descriptor tables (their builder and the launch plan of a call: lrf_plan.h).  lrf_ctx.hip defines the functions declared here unless noted.
 #ifndef LRF_HOST_H
 #define LRF_HOST_H
 #include <hip/hip_runtime.h>
@@ -18,18 +18,12 @@
 #include "../../include/lrf_hip.h"
 #include "lrf_internal.h"
 #include "lrf_env.h"
+#include "lrf_plan.h"
 
 // the planes qmf_encode forms hold YCbCr samples, 0 or in [0.114, 255.5]: all below 2^8 and exact on the grid 2^(8-35)
 // (run_init: selects k_gram64's integer digit extraction; callers with arbitrary X pass LRF_GRAM_EXP_FROM_DATA)
 #define LRF_PLANES_GRAM_EXP 8
-// largest rank of the 64-column BCD kernels (k_bcd_w <= 8, k_bcd <= 16, k_bcd_mid <= 32); above it the any-shape kernels iterate
-#define LRF_BIG_TO_ANY_RANK 32
 #define LRF_TABLE_SETS 6 // descriptor-table sets a context keeps resident (upload_tables)
-#define LRF_BCDW_MIN_BLOCKS 1024 // smaller rank <= 8 runs iterate on the workgroup kernel k_bcd (run_bcd)
-#define LRF_BCDW16_MIN_BLOCKS 1024 // likewise for rank <= 16 runs and k_bcd_w16
-#define LRF_PERSIST_MIN_BLOCKS 3584 // a call of this many blocks runs its iterations in one launch (k_bcd_p) ...
-#define LRF_PERSIST_MIN_BLOCKS_ONE_FAMILY 2304 // ... of this many when all its planes are of one rank family (lrf_bcd_persist.hip)
-#define LRF_BCDW32_MIN_BLOCKS 128  // likewise for rank 17..32 runs and k_bcd_w32 / k_bcd_w32f (12 images: 1.06 -> 0.99 ms at (20,10,10))
 
 int set_err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 const char* last_err();
@@ -83,7 +77,7 @@ struct lrf_ctx {
     DevBuf metrics; // lrf_image_metrics_u8: a float64 slot per (image, channel, tile), then (max, 255 - min) per image
     DevBuf sse_tab; // lrf_qmf_sweep_sse_rgb_u8: its table of rank triples (SseItem) ...
     std::vector<char> sse_key; // ... and the bytes now resident there (calls that repeat a sweep skip the synchronising upload)
-    DevBuf vf16, wf16, bf16, pp16, qp16; // the pitch-16 tables of a call that mixes kernel families (plan_runs)
+    DevBuf vf16, wf16, bf16, pp16, qp16; // the pitch-16 tables of a call that mixes kernel families (BcdPlan::mixed)
     // host staging for descriptor tables (pinned)
     void* h_stage = nullptr;
     size_t h_stage_cap = 0;
@@ -107,16 +101,11 @@ struct lrf_ctx {
     unsigned long tstamp = 0;
     unsigned attr_done = 0;      // hipFuncSetAttribute call sites already executed for this context's device (bit per site)
     unsigned attr_persist = 0;   // likewise, one bit per instantiation of k_bcd_p (lrf_bcd_persist.hip)
-    // Kernel families of one call on streams of their own (run_init / run_bcd): the runs of plan_runs touch disjoint planes, so
-    // the whole chain of a run — initialisation, b table, K x (U update, V update) — is independent of the other runs'; the
-    // first run stays on `stream`, the others fork behind the Gram pass and are joined at the end of run_bcd.  Created on
-    // first use (a call with 1024 blocks or more — 256 with a rank above 16 — that mixes rank families); never while kernel profiling is on.
+    // Kernel families of one call on streams of their own (BcdPlan::streams; run_init forks, run_bcd joins): the first run stays
+    // on `stream`, the others fork behind the Gram pass.  Created on first use; never to the call's end while kernel profiling is on.
     hipStream_t fam_stream[2] = {nullptr, nullptr};
     hipEvent_t fam_fork = nullptr, fam_join[2] = {nullptr, nullptr};
-    bool fam_parallel = false;   // set by the fused entry points whose run_init is followed by run_bcd at once
     bool fam_forked = false;     // run_init forked: run_bcd uses the same streams and joins
-    bool init_parallel = false;  // set by the fused entry points of a call whose iterations run in k_bcd_p: only the
-                                 // initialisation kernels of its families (per-matrix latency chains) run side by side
     hipEvent_t planes_done = nullptr; // set by a pipe: recorded after the planes kernel of lrf_qmf_encode_rgb_u8 (input buffer free)
     // the persistent iteration kernel (k_bcd_p, default for large rank <= 8 calls): its queue head, tickets and flags; its error
     // word is page-locked host memory the kernel writes directly — the sequence number of the first launch whose poll expired.
@@ -168,47 +157,18 @@ struct Prof {
 void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M);
 int make_geom(int64_t H, int64_t W, ImageGeom* g);
 
-// ---- descriptor tables ------------------------------------------------------------------------
-struct Tables {
-    std::vector<PlaneDesc> planes;
-    std::vector<BlockDesc> blocks;
-    std::vector<GramChunk> gchunks; // the chunks k_gram64 computes first, then those of the gram_fused planes (k_planes16_gram)
-    int ngram_rest = 0;             // how many of them k_gram64 computes (finish_gram_chunks)
-};
-
-void add_plane(Tables& t, long x_off, long u_off, long v_off, long u0_off, long v0_off, int M, int R, int sign_off);
+// ---- descriptor tables and the launch plan (lrf_plan.h: device-free) ----------------------------
 int check_params(int64_t M, int64_t N, int R, int K, int lo, int hi);
-int table_rmax(const Tables& t);
-int table_rp(const Tables& t); // padded rank of the V / W / partial tables: 16 (one MFMA tile) or LRF_RPB
-int upload_tables(lrf_ctx* c, Tables& t);
+PlanSettings plan_settings(const lrf_ctx* c); // the process's settings with the context's device
+int upload_tables(lrf_ctx* c, Tables& t, const BcdPlan& plan);
 
-// ---- kernel families of a call -----------------------------------------------------------------
-// A run: consecutive planes (and their blocks) that iterate on one kernel family — 0: rank <= 8 (k_bcd_w), 1: rank <= 16
-// (k_bcd<., 16>), 2: rank <= 32 (k_bcd_mid) — with that family's table pitch (16 or LRF_RPB).  A small call takes ONE family,
-// the one its largest rank needs: its launches are latency chains per block and a second launch per iteration costs more than
-// a faster kernel saves.  From 1024 blocks on (256 with a rank above 16: plan_runs) every plane
-// goes to its own family (256 images: (16,8,8) 4.05 -> 3.78 ms, (20,10,10) 7.07 -> see DESIGN.md); the planes of the fused
-// encode are ordered by channel, so that is at most three runs.  Pitch-16 runs of a call whose table pitch is LRF_RPB use
-// the second table set (vf16 ...): the regions of the two pitches would overlap in one buffer.
-struct FamRun {
-    int plane0, nplanes, block0, nblocks, rmax, fam, pitch;
-    int rmin;        // smallest rank of the run (k_bcd_w32 takes runs whose ranks are all 17..32)
-    bool any_native; // some plane of the run is small enough for ATen's native order of `uu @ bb` ((R-1) M < 400)
-    int nbase;       // leading planes of the run that compute their own SVD initialisation (all of them, except in a sweep call:
-                     // there the other planes take their columns from a plane of the same matrix, PlaneDesc::init_src)
-};
-inline int fam_of_rank(int R) { return LRF_FAM_OF_RANK(R); }
-bool plan_splits(long nblocks, int rmax_t); // whether a call of that size gives every plane the kernel family of its own rank
-bool bcd_wave_variant();
-std::vector<FamRun> plan_runs(const Tables& t);
-bool plan_is_mixed(const std::vector<FamRun>& runs);
 // the V / W / b / partial tables a run uses
 struct FamBufs {
     float *vf, *wf, *bf, *pp, *qp;
 };
 FamBufs run_bufs(lrf_ctx* c, const FamRun& r, bool mixed);
 hipStream_t run_stream(lrf_ctx* c, size_t run_idx);
-int fam_fork_streams(lrf_ctx* c, size_t nruns, bool stage_only = false);
+int fam_fork_streams(lrf_ctx* c, FamStreams layout, size_t nruns);
 int fam_join_streams(lrf_ctx* c, size_t nruns);
 
 // ---- the 64-column encoder (lrf_encode8.hip)
@@ -218,6 +178,7 @@ int fam_join_streams(lrf_ctx* c, size_t nruns);
 struct EncodePlan {
     ImageGeom g;
     Tables t;
+    BcdPlan bcd; // of the call that initialises and iterates (first_mode 1)
     long u_img = 0, v_img = 0, uoff[3], voff[3], u0c[4] = {0, 0, 0, 0}, v0c[4] = {0, 0, 0, 0};
 };
 int encode_rgb_prepare(lrf_ctx* c, int64_t B, int64_t H, int64_t W, const int R[3], int K, int lo, int hi, bool with_sign, bool fuse_gram,
@@ -241,20 +202,12 @@ struct BcdLaunch {
 };
 // ranks 17..32 (lrf_bcd32.hip: k_bprep_big, k_bcd_w32 / k_bcd_w32f / k_bcd_mid, k_vupdate_mid)
 int bcd32_bprep(hipStream_t rs, const PlaneDesc* pl, const float* vf, float* bf, int nplanes, int plane0);
-int bcd32_update_u(lrf_ctx* c, hipStream_t rs, const BcdLaunch& a, const FamRun& r, long mx_bound);
+int bcd32_update_u(lrf_ctx* c, hipStream_t rs, const BcdLaunch& a, BcdChoice ch); // ch: k_bcd_mid, k_bcd_w32 or k_bcd_w32f
 int bcd32_update_v(lrf_ctx* c, hipStream_t rs, const PlaneDesc* pl, const float* pp, const float* qp, float* vf, float* bf, int8_t* V, float lo,
                    float hi, int last, int nplanes, int plane0);
-bool bcd32_wave_kernels_apply(const FamRun& r, bool exact_int, long mx_bound, int mode); // k_bcd_w32 (mode 0) / k_bcd_w32f (mode 1) take the run
-// iterations 2..K of a whole call in one launch (lrf_bcd_persist.hip: k_bcd_p<F16, NP32>)
-struct PersistPlan {
-    bool use = false;
-    bool f16 = false; // planes of ranks 9..16 occur
-    int np32 = 0;     // pairs of rank columns of the planes of ranks 17..32 (0: none)
-    bool first = false; // the launch may carry the call's first iteration too (ranks <= 16)
-};
-PersistPlan bcdp_plan(lrf_ctx* c, const std::vector<FamRun>& runs, int K, int lo, int hi);
-int bcdp_launch(lrf_ctx* c, const PersistPlan& pp, const float* X, const PlaneDesc* pl, const BlockDesc* bl, int nblocks, int nplanes, int plane0,
-                const FamBufs& t16, const FamBufs& t64, int8_t* U, int8_t* V, GsParams gp, int niter, bool first);
+// the plan's persistent launch (lrf_bcd_persist.hip: k_bcd_p<F16, NP32, FIRST>): iterations 2..K of a whole call, or all K
+int bcdp_launch(lrf_ctx* c, const BcdPlan& plan, const float* X, const PlaneDesc* pl, const BlockDesc* bl, int nblocks, int nplanes, int plane0,
+                const FamBufs& t16, const FamBufs& t64, int8_t* U, int8_t* V, GsParams gp);
 
 // ---- the any-shape path (lrf_any.hip: other patch sizes, patch=False, the RGB colour space, ranks 33..64 of the 64-column path)
 int any_workspace(lrf_ctx* c, int B, int M, int N, int R);

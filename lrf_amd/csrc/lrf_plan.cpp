@@ -1,0 +1,162 @@
+// lrf_plan.cpp — the launch plan of a call of the 64-column path (lrf_plan.h): every rule that picks a kernel, the persistent
+// launch or a stream layout lives in plan_bcd, every bound is written once.  Host C++ only.
+#include "lrf_plan.h"
+
+#include <string.h>
+
+#include "lrf_env.h"
+
+void add_plane(Tables& t, long x_off, long u_off, long v_off, long u0_off, long v0_off, int M, int R, int sign_off)
+{
+    PlaneDesc pd;
+    memset(&pd, 0, sizeof(pd));
+    pd.x_off = x_off; pd.u_off = u_off; pd.v_off = v_off; pd.u0_off = u0_off; pd.v0_off = v0_off;
+    pd.M = M; pd.R = R;
+    pd.blk0 = (int)t.blocks.size();
+    pd.nblk = (M + LRF_KC - 1) / LRF_KC;
+    pd.native_t2_u = ((long)(R - 1) * M < 400) ? 1 : 0;
+    pd.sign_off = sign_off;
+    int pi = (int)t.planes.size();
+    pd.init_src = pi; // (a sweep call's table builder points the lower-rank planes of a matrix at its largest-rank plane)
+    for (int b = 0; b < pd.nblk; b++) t.blocks.push_back(BlockDesc{pi, b * LRF_KC, b, 0});
+    pd.gch0 = 0; // the Gram chunks are cut when the table is complete (finish_gram_chunks)
+    pd.ngch = 0;
+    t.planes.push_back(pd);
+}
+
+const PlanSettings& plan_settings_env()
+{
+    static const PlanSettings s{(int)env_long("LRF_PERSIST", -1), env_long("LRF_FAMILY_SPLIT_BLOCKS", -1),
+                                env_long("LRF_BCDW16_MIN_BLOCKS", LRF_BCDW16_MIN_BLOCKS), env_long("LRF_BCDW32_MIN_BLOCKS", LRF_BCDW32_MIN_BLOCKS),
+                                dev_flag("LRF_BCD_WG"), dev_flag("LRF_NO_FAMILY_SPLIT"), dev_flag("LRF_NO_FAMILY_STREAMS"), dev_flag("LRF_NO_BCDW32"),
+                                dev_flag("LRF_GENERIC_GS"), dev_flag("LRF_NO_PERSIST_FIRST"), dev_flag("LRF_NO_INIT_FORK"), false};
+    return s;
+}
+
+// A small call takes ONE family, the one its largest rank needs: its launches are latency chains per block and a second launch
+// per iteration costs more than a faster kernel saves.  Since the families of a call run side by side on streams of their own
+// (round 3) — or in one persistent launch (round 5) — the split pays from 1024 blocks on (64 x 512x768: (16,8,8) 0.93 -> 0.89 ms,
+// (20,10,10) 2.04 -> 1.36 with k_bcd_w32 on the luma run; 256 images: (16,8,8) 4.05 -> 3.78 ms); calls with a rank above 16
+// split from 256 blocks (24 images: (20,10,10) 1.27 -> 1.04 ms, 12 images 1.06 -> 0.99).
+bool plan_splits(long nblocks, int rmax_t, const PlanSettings& s)
+{
+    const long min_blocks = s.family_split_blocks >= 0 ? s.family_split_blocks : (rmax_t > 16 ? 256 : 1024);
+    return !s.no_family_split && !s.bcd_wg && rmax_t <= LRF_BIG_TO_ANY_RANK && nblocks >= min_blocks;
+}
+
+// What the wave kernel of a run's family asks of the numbers (its size thresholds and switches: bcd_kernel), by the mode of
+// the U update — 0: iterations >= 2 (old U from int8); 1: the first, old U = X W0; 2: the first, old U = the caller's U0.
+//   mode 0: every term and partial sum of `uu @ bb` is an exact integer in fp32 for the largest rank of the run (exact_int:
+//           (R - 1) 64 mx^3 < 2^24), so the order of that sum is immaterial, which lets ranks 9..16 (gs_row_lds) and 17..32
+//           (k_bcd_w32) replace the reference's dependent chain by independent fmas, bit for bit; ranks 17..32 also need |b|
+//           within int16 (64 mx^2 <= 32767): the lane = row Gauss-Seidel on int16 pairs;
+//   mode 1: no plane small enough for ATen's native order of `uu @ bb`; ranks 17..32: one rank for the whole run (k_bcd_w32f).
+// Ranks <= 8 (k_bcd_w) keep the reference's order: any bounds, any mode.
+static bool wave_numbers_ok(const FamRun& r, int mode, bool int16_b)
+{
+    if (r.fam == 0) return true;
+    if (mode == 0) return r.exact_int && (r.fam == 1 || int16_b);
+    if (mode == 1) return !r.any_native && (r.fam == 1 || r.rmin == r.rmax);
+    return false;
+}
+
+static BcdChoice bcd_kernel(const FamRun& r, int mode, bool int16_b, const PlanSettings& s)
+{
+    const bool ok = !s.bcd_wg && wave_numbers_ok(r, mode, int16_b);
+    // k_bcd_w (one wave per block, no barriers) for rank <= 8 runs of LRF_BCDW_MIN_BLOCKS blocks or more: with fewer than a
+    // wave per SIMD what counts is the latency of ONE block, and there the four waves of the workgroup kernel k_bcd share a
+    // block's sub-tile (one 512x768 image: 27.9 -> 17.0 us per launch, 8 images 28.5 -> 18.2, 32 images 31.7 -> 27.6; equal at 48)
+    if (r.fam == 0) return BcdChoice{ok && r.nblocks >= LRF_BCDW_MIN_BLOCKS ? BCD_K_W : BCD_K_WG8, 0};
+    // ranks 9..16 (and the lower-rank planes of such a run)
+    if (r.fam == 1) return BcdChoice{ok && r.nblocks >= s.bcdw16_min_blocks ? BCD_K_W16 : BCD_K_WG16, 0};
+    // ranks 17..32: a run whose planes all have such ranks, else the workgroup kernel k_bcd_mid (small runs, wide bounds, caller's U0)
+    if (!ok || s.no_bcdw32 || r.rmin < 17 || r.nblocks < s.bcdw32_min_blocks) return BcdChoice{BCD_K_MID, 0};
+    return mode == 0 ? BcdChoice{BCD_K_W32, (r.rmax + 1) >> 1} : BcdChoice{BCD_K_W32F, r.rmax};
+}
+
+BcdPlan plan_bcd(const std::vector<PlaneDesc>& planes, int K, int lo, int hi, int first_mode, const PlanSettings& s, bool sweep)
+{
+    BcdPlan p;
+    p.K = K; p.lo = lo; p.hi = hi; p.first_mode = first_mode;
+    long nblocks = 0;
+    for (const PlaneDesc& pd : planes) {
+        p.rmax = pd.R > p.rmax ? pd.R : p.rmax;
+        nblocks += pd.nblk;
+    }
+    p.rp = p.rmax <= 16 ? 16 : LRF_RPB;
+    p.split = plan_splits(nblocks, p.rmax, s);
+    // the runs: the planes of the fused encode are ordered by channel (a sweep's by family), so that is at most three
+    int blk = 0;
+    for (int pi = 0; pi < (int)planes.size(); pi++) {
+        const PlaneDesc& pd = planes[pi];
+        const int fam = p.split ? fam_of_rank(pd.R) : (p.rmax > 16 ? 2 : fam_of_rank(p.rmax));
+        if (p.runs.empty() || p.runs.back().fam != fam)
+            p.runs.push_back(FamRun{pi, 0, blk, 0, 1, fam, fam == 2 ? LRF_RPB : 16, pd.R, false, 0, false, {BCD_K_WG8, 0}, {BCD_K_WG8, 0}});
+        FamRun& r = p.runs.back();
+        r.any_native = r.any_native || pd.native_t2_u != 0;
+        if (pd.init_src == pi && r.nbase == r.nplanes) r.nbase++; // (the table builders put a run's self-initialising planes first)
+        r.nplanes++;
+        r.nblocks += pd.nblk;
+        r.rmax = pd.R > r.rmax ? pd.R : r.rmax;
+        r.rmin = pd.R < r.rmin ? pd.R : r.rmin;
+        blk += pd.nblk;
+    }
+    bool p16 = false, p64 = false;
+    for (const FamRun& r : p.runs) (r.pitch == 16 ? p16 : p64) = true;
+    p.mixed = p16 && p64;
+    if (first_mode == PLAN_INIT_ONLY || p.rmax > LRF_BIG_TO_ANY_RANK) return p; // (ranks 33..64 iterate on the any-shape kernels)
+
+    const long mx = bounds_mx(lo, hi);
+    const bool int16_b = 64 * mx * mx <= 32767;
+    for (FamRun& r : p.runs) {
+        r.exact_int = !s.generic_gs && (long)(r.rmax - 1) * 64 * mx * mx * mx < (1L << 24);
+        r.first = bcd_kernel(r, first_mode, int16_b, s);
+        r.later = bcd_kernel(r, 0, int16_b, s);
+    }
+
+    // Iterations 2..K of a large call in ONE launch (k_bcd_p<F16, NP32>): the U updates of all iterations and planes pulled from
+    // a queue, each matrix's V update done by the last of its blocks to finish.  The persistent kernel takes a call when
+    //   * the device is the part its in-launch hand-offs were validated on (gfx950);
+    //   * every plane sits on the kernel family of its own rank (the split plan) and the families' wave kernels accept the
+    //     numbers for iterations >= 2 (wave_numbers_ok), with one pair count NP for all planes of ranks 17..32; no plane of
+    //     ranks above 8 small enough for ATen's native order of `uu @ bb`;
+    //   * the call has LRF_PERSIST_MIN_BLOCKS blocks or more (256 x 512x768 at ranks <= 8: 2.05 -> 1.92 ms per step; 48 / 64 such
+    //     images lose 15 %: a round and a half of the 2048 wave slots; tools/dev_persist_threshold.py) — from
+    //     LRF_PERSIST_MIN_BLOCKS_ONE_FAMILY when all planes are of one rank family (96 x 512x768: (7,3,3) 0.96 -> 0.92 ms, (12,12,12)
+    //     1.25 -> 1.13, (20,20,20) 1.83 -> 1.72; calls that mix families lose at 96 and 128 images: tools/run_r05_o.sh).
+    //     LRF_PERSIST=0 turns it off, =1 lowers the threshold to LRF_BCDW_MIN_BLOCKS (tests).
+    bool persist = s.persist_arch && s.persist != 0 && !s.bcd_wg && K >= 2 && !p.runs.empty();
+    bool f16 = false;
+    int np32 = 0;
+    for (const FamRun& r : p.runs) {
+        if (fam_of_rank(r.rmin) != r.fam || fam_of_rank(r.rmax) != r.fam) persist = false; // a small call: one family for all planes
+        if (r.fam == 0) continue;
+        if (!wave_numbers_ok(r, 0, int16_b) || r.any_native) persist = false;
+        if (r.fam == 1) {
+            f16 = true;
+        } else {
+            const int np = (r.rmax + 1) >> 1;
+            if (r.rmin < 2 * np - 1 || (np32 != 0 && np32 != np)) persist = false;
+            np32 = np;
+        }
+    }
+    const long min_blocks = p.runs.size() == 1 ? LRF_PERSIST_MIN_BLOCKS_ONE_FAMILY : LRF_PERSIST_MIN_BLOCKS;
+    if (persist && nblocks >= (s.persist == 1 ? LRF_BCDW_MIN_BLOCKS : min_blocks)) {
+        p.persist = true;
+        p.persist_f16 = f16 || np32 != 0;
+        p.persist_np32 = np32;
+        // ... and the first iteration as well (k_bcd_p<.., 0, true>: ranks <= 16 only) when its old U is X @ W0 of the
+        // initialisation just run: then the b tables are the last launch before k_bcd_p
+        p.persist_first = np32 == 0 && !s.no_persist_first && first_mode == PLAN_FIRST_W0;
+    }
+
+    // Streams.  The runs touch disjoint planes, so the whole chain of a run — initialisation, b table, K x (U update, V update)
+    // — is independent of the other runs': a call that initialises and iterates (first_mode 1) forks them for its whole length.
+    // Not when its iterations run in the persistent kernel — one launch for all families, behind a first iteration whose family
+    // kernels run one after the other (side by side they were SLOWER: k_bcd_w32f 305 us and k_bcd_w16<1> 80 us alone, 590 us
+    // together) — and not in a sweep call, whose shared initialisations tie the families together: those fork for the
+    // initialisation kernels only (run_init says why that pays).
+    if (first_mode == PLAN_FIRST_W0 && !s.no_family_streams)
+        p.streams = !(p.persist || sweep) ? FAM_STREAMS_CALL : (s.no_init_fork ? FAM_STREAMS_NONE : FAM_STREAMS_INIT);
+    return p;
+}

@@ -1,0 +1,78 @@
+// lrf_plan.h — the descriptor tables of a call of the 64-column path and its launch plan: which kernel iterates which planes,
+// whether one persistent launch takes the iterations, how the kernel families share streams.  Decided once per call by
+// plan_bcd (lrf_plan.cpp), executed by run_init / run_bcd (lrf_encode8.hip), bcd32_update_u (lrf_bcd32.hip) and bcdp_launch
+// (lrf_bcd_persist.hip).  No device, no context, no HIP: the host compiler alone builds it (tests/test_bcd_plan.py does).
+#ifndef LRF_PLAN_H
+#define LRF_PLAN_H
+#include <stdlib.h>
+
+#include <vector>
+
+#include "lrf_internal.h"
+
+// largest rank of the 64-column BCD kernels (k_bcd_w <= 8, k_bcd <= 16, k_bcd_mid <= 32); above it the any-shape kernels iterate
+#define LRF_BIG_TO_ANY_RANK 32
+#define LRF_BCDW_MIN_BLOCKS 1024 // smaller rank <= 8 runs iterate on the workgroup kernel k_bcd (plan_bcd)
+#define LRF_BCDW16_MIN_BLOCKS 1024 // likewise for rank <= 16 runs and k_bcd_w16
+#define LRF_BCDW32_MIN_BLOCKS 128  // likewise for rank 17..32 runs and k_bcd_w32 / k_bcd_w32f (12 images: 1.06 -> 0.99 ms at (20,10,10))
+#define LRF_PERSIST_MIN_BLOCKS 3584 // a call of this many blocks runs its iterations in one launch (k_bcd_p) ...
+#define LRF_PERSIST_MIN_BLOCKS_ONE_FAMILY 2304 // ... of this many when all its planes are of one rank family
+
+// ---- descriptor tables ------------------------------------------------------------------------
+struct Tables {
+    std::vector<PlaneDesc> planes;
+    std::vector<BlockDesc> blocks;
+    std::vector<GramChunk> gchunks; // the chunks k_gram64 computes first, then those of the gram_fused planes (k_planes16_gram)
+    int ngram_rest = 0;             // how many of them k_gram64 computes (finish_gram_chunks)
+};
+void add_plane(Tables& t, long x_off, long u_off, long v_off, long u0_off, long v0_off, int M, int R, int sign_off);
+
+// ---- what the plan depends on besides the call: read once per process (plan_settings_env), persist_arch from the device
+struct PlanSettings {
+    int persist = -1;              // LRF_PERSIST                    (these four: the test hooks of lrf_env.h)
+    long family_split_blocks = -1; // LRF_FAMILY_SPLIT_BLOCKS
+    long bcdw16_min_blocks = LRF_BCDW16_MIN_BLOCKS, bcdw32_min_blocks = LRF_BCDW32_MIN_BLOCKS; // the variables of these names
+    // developer switches (-DLRF_DEV builds only): LRF_BCD_WG (the workgroup kernels instead of the wave kernels), LRF_NO_FAMILY_SPLIT,
+    // LRF_NO_FAMILY_STREAMS, LRF_NO_BCDW32 (k_bcd_mid instead), LRF_GENERIC_GS (never the exact-integer Gauss-Seidel), LRF_NO_PERSIST_FIRST, LRF_NO_INIT_FORK
+    bool bcd_wg = false, no_family_split = false, no_family_streams = false, no_bcdw32 = false, generic_gs = false, no_persist_first = false, no_init_fork = false;
+    bool persist_arch = false; // the device is the part the in-launch hand-offs of k_bcd_p were validated on (gfx950)
+};
+const PlanSettings& plan_settings_env(); // the environment's part (persist_arch false)
+
+// ---- the plan ---------------------------------------------------------------------------------
+inline int fam_of_rank(int R) { return LRF_FAM_OF_RANK(R); }
+inline long bounds_mx(int lo, int hi) { return labs((long)lo) > labs((long)hi) ? labs((long)lo) : labs((long)hi); } // mx = max(|lo|, |hi|)
+
+// the U-update kernels; arg: the pair count NP of k_bcd_w32<NP>, the rank of k_bcd_w32f<R>, 0 otherwise
+enum BcdKernel { BCD_K_WG8, BCD_K_WG16, BCD_K_MID, BCD_K_W, BCD_K_W16, BCD_K_W32, BCD_K_W32F };
+struct BcdChoice { BcdKernel k; int arg; };
+// A run: consecutive planes (and their blocks) that iterate on one kernel family — 0: rank <= 8, 1: rank <= 16, 2: rank <= 32
+// — with that family's table pitch (16 or LRF_RPB).  Pitch-16 runs of a call whose table pitch is LRF_RPB use the second
+// table set (vf16 ...): the regions of the two pitches would overlap in one buffer.
+struct FamRun {
+    int plane0, nplanes, block0, nblocks, rmax, fam, pitch;
+    int rmin;        // smallest rank of the run (k_bcd_w32 takes runs whose ranks are all 17..32)
+    bool any_native; // some plane of the run is small enough for ATen's native order of `uu @ bb` ((R-1) M < 400)
+    int nbase;       // leading planes of the run that compute their own SVD initialisation (all of them, except in a sweep call:
+                     // there the other planes take their columns from a plane of the same matrix, PlaneDesc::init_src)
+    bool exact_int;  // GsParams::exact_int of the run's launches
+    BcdChoice first, later; // the U update of the first iteration (old U by the plan's first_mode) and of iterations >= 2
+};
+enum FamStreams { FAM_STREAMS_NONE, FAM_STREAMS_INIT, FAM_STREAMS_CALL }; // the runs on streams of their own: never / the initialisation kernels / to the call's end
+enum { PLAN_INIT_ONLY = 0, PLAN_FIRST_W0 = 1, PLAN_FIRST_U0 = 2 }; // first_mode: no iterations (runs and pitches only) / old U = X W0 of the initialisation / the caller's U0
+struct BcdPlan {
+    int K = 0, lo = 0, hi = 0, first_mode = PLAN_INIT_ONLY;
+    std::vector<FamRun> runs;
+    int rmax = 1, rp = 16; // largest rank of the table; padded rank of its V / W / partial tables: 16 (one MFMA tile) or LRF_RPB
+    bool split = false, mixed = false; // every plane on the kernel family of its own rank (plan_splits); runs of both table pitches occur
+    // persist: one launch of k_bcd_p<f16, np32, first> for iterations 2..K — or all K (first: the call's first iteration inside too)
+    bool persist = false, persist_first = false;
+    bool persist_f16 = false;   // planes of ranks 9..16 occur (the instantiations with ranks 17..32 carry that body too: their chroma planes)
+    int persist_np32 = 0;       // pairs of rank columns of the planes of ranks 17..32 (0: none)
+    FamStreams streams = FAM_STREAMS_NONE;
+};
+// whether a call of that size gives every plane the kernel family of its own rank (the sweep entry point orders its planes by it)
+bool plan_splits(long nblocks, int rmax_t, const PlanSettings& s);
+// reads R, nblk, native_t2_u and init_src of the planes.  sweep: lrf_qmf_encode_sweep_rgb_u8's table
+BcdPlan plan_bcd(const std::vector<PlaneDesc>& planes, int K, int lo, int hi, int first_mode, const PlanSettings& s, bool sweep = false);
+#endif

@@ -1,5 +1,6 @@
 // lrf_unity.hip — the whole library as ONE translation unit, for the variant builds of the tools and tests (stamps, ablations,
-// failure injection: `make unity VARIANT=... DEFS=...`).  The shipped library is built from its eight units separately.
+// failure injection: `make unity VARIANT=... DEFS=...`).  The shipped library is built from its units separately.
+#include "lrf_plan.cpp"
 #include "lrf_ctx.hip"
 #include "lrf_pipe.hip"
 #include "lrf_encode8.hip"

@@ -18,7 +18,7 @@ D = (-16, 15)
 
 # ---- section 1: 256 x 512x768 -------------------------------------------------------------------------------------------
 # (ranks, bounds, K, (persistent launches, LRF_K_BCD regions), the k_bcd_p instantiation <F16, NP32, FIRST> it runs)
-# regions: 0 = the first iteration inside the launch (run_bcd's persist_first: ranks <= 16), 1 = outside (a rank above 16),
+# regions: 0 = the first iteration inside the launch (BcdPlan::persist_first: ranks <= 16), 1 = outside (a rank above 16),
 # K = no persistent launch (every iteration is a region).  (22,11,11), (28,14,14), (30,15,15): the pair counts 11, 14, 15.
 BATCH = (256, 512, 768)
 BATCH_CASES = [
@@ -34,7 +34,7 @@ BATCH_CASES = [
     # two iterations / a single iteration inside the launch; K < 2: no persistent launch
     ((16, 8, 8), D, 2, (1, 0), "<true,0,true>"), ((26, 13, 13), D, 2, (1, 1), "<true,13,false>"), ((7, 3, 3), D, 1, (0, 1), None),
 ]
-# ---- section 4: the two thresholds of bcdp_plan straddled (24 blocks an image): prefixes of section 1's batch
+# ---- section 4: the two thresholds of plan_bcd straddled (24 blocks an image): prefixes of section 1's batch
 # (ranks, images below, images at the threshold)
 THRESHOLD_CASES = [((7, 3, 3), 95, 96), ((12, 12, 12), 95, 96), ((16, 8, 8), 149, 150)]
 # ---- section 5: repeat runs next to other GPU work
@@ -63,7 +63,7 @@ def caller_inst(kind, R):
 
 
 # ---- section 6: the fused sweep on BASELINE config 3's 24 images.  Qualities 1..32 give luma ranks 17, 18, 19 and 20 in one
-# run of planes: two pair counts (9 and 10), which bcdp_plan declines (one NP32 per launch) — ten launch-per-iteration rounds;
+# run of planes: two pair counts (9 and 10), which plan_bcd declines (one NP32 per launch) — ten launch-per-iteration rounds;
 # qualities 1..25 stop at rank 16: one persistent launch with the first iteration inside.
 SWEEP_CASES = [(list(range(1, 33)), (0, 10), None), (list(range(1, 26)), (1, 0), "<true,0,true>")]
 

@@ -1,5 +1,5 @@
-"""GPU suite (-m gpu): the persistent iteration kernel k_bcd_p (lrf_bcdp_kernel.hip; which calls take it: bcdp_plan,
-lrf_bcd_persist.hip) where it ships — on the default thresholds, at production batch sizes — against the CPU oracle, EVERY
+"""GPU suite (-m gpu): the persistent iteration kernel k_bcd_p (lrf_bcdp_kernel.hip; which calls take it: plan_bcd,
+lrf_plan.cpp) where it ships — on the default thresholds, at production batch sizes — against the CPU oracle, EVERY
 image of every batch bit for bit.  A wrong hand-off inside the launch gives silently stale factors which the poll-expiry
 error word does not see; only this comparison does.
 
@@ -8,7 +8,7 @@ run): the LRF_PERSIST switch and the threshold hooks are read once per process, 
 REMOVED, so that what runs is what a user gets.  The parent never initialises HIP.  Every case asserts
   (a) the path, from the context's kernel timers: the number of LRF_K_BCD_PERSIST launches and of LRF_K_BCD regions (0: the
       first iteration inside the launch; 1: outside; K: no persistent launch) — the tables in the worker give, per case, what
-      bcdp_plan / run_bcd say on reading and the k_bcd_p instantiation <F16, NP32, FIRST> that makes it; all twelve occur;
+      plan_bcd says on reading and the k_bcd_p instantiation <F16, NP32, FIRST> that makes it; all twelve occur;
   (b) int8 U and V of every image equal the oracle's (np.array_equal; a failure names case, image, plane, count and first
       index of the differing entries);
   (c) ctx.synchronize() / ctx.check() raise nothing afterwards.
@@ -119,7 +119,7 @@ def test_caller_given_initial_factors_and_uniform_tables(kind, M, R, K):
 @pytest.mark.parametrize("qualities, path", [c[:2] for c in W.SWEEP_CASES], ids=[f"q{c[0][0]}..{c[0][-1]}" for c in W.SWEEP_CASES])
 def test_fused_sweep_every_image_and_rank_triple_equals_oracle(qualities, path):
     """qmf_encode_sweep on BASELINE config 3's 24 images: every stream parsed, the factors of every (image, distinct rank
-    triple) pair against the oracle.  Qualities 1..32 hold luma ranks 17..20 — two pair counts in one run, which bcdp_plan
+    triple) pair against the oracle.  Qualities 1..32 hold luma ranks 17..20 — two pair counts in one run, which plan_bcd
     declines: the launch-per-iteration kernels; qualities 1..25 (ranks <= 16) iterate in one persistent launch."""
     d = _child("sweep")[("sweep", f"sweep q={qualities[0]}..{qualities[-1]}")]
     _check(d, path, 24, planes=3 * d["pairs"])
