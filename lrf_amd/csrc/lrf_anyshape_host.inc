@@ -15,77 +15,52 @@ static int any_check(int64_t B, int64_t M, int64_t N, int R, int lo, int hi)
     return LRF_OK;
 }
 
-// C [B][I][R] = A' Bm with the reference's order (k_any_prod + k_any_fold); native: ATen's small-product kernel
+// C [B][I][R] = A' Bm with the reference's order (k_any_prod + k_any_fold); native: ATen's small-product kernel.  Which kernel,
+// its grid and loop counts: plan_any_prod (lrf_plan.cpp)
 static int any_prod(lrf_ctx* c, const float* A, long a_batch, long sai, long sak, const float* Bm, long b_batch, float* C, int B,
                     int I, int D, int R, bool native)
 {
-    const int nblk = (D + LRF_KC - 1) / LRF_KC;
+    static const bool prod_small = dev_flag("LRF_ANY_PROD_SMALL");
+    const AnyProdPlan p = plan_any_prod(I, D, R, B, sai, sak, native, prod_small);
+    const int nblk = p.nblk;
     float* P = C;
     if (nblk > 1) {
         int rc = ensure(c, c->any_p, (size_t)B * nblk * I * R * sizeof(float));
         if (rc) return rc;
         P = (float*)c->any_p.p;
     }
-    static const bool prod_small = dev_flag("LRF_ANY_PROD_SMALL");
-    if (!native && !prod_small && R <= 16) { // thin products (4 x 4 patches): operands straight from global memory
-        if (I <= 16 && D > 64) {
-            hipLaunchKernelGGL(k_any_prod_thin_long, dim3((unsigned)nblk, (unsigned)B), dim3(64), 0, c->stream, A, a_batch, sai, sak, Bm, b_batch,
-                               P, I, D, R, nblk);
-            LAUNCH_CHECK();
-            if (nblk > 1) {
-                const long IR = (long)I * R;
-                hipLaunchKernelGGL(k_any_fold, dim3((unsigned)((IR + 255) / 256), (unsigned)B), dim3(256), 0, c->stream, (const float*)P, C, IR, nblk);
-                LAUNCH_CHECK();
-            }
-            return LRF_OK;
-        }
-        if (D <= 64 && I >= 256) {
-            const long nt16 = (I + 15) / 16;
-            int tpw = 1;
-            while (tpw < 16 && nt16 * (long)B / (2 * tpw) >= 8192) tpw *= 2;
-            const dim3 grid((unsigned)((nt16 + tpw - 1) / tpw), (unsigned)B);
-            if (D <= 16)
-                hipLaunchKernelGGL(k_any_prod_thin_short<4>, grid, dim3(64), 0, c->stream, A, a_batch, sai, sak, Bm, b_batch, P, I, D, R, tpw);
-            else if (D <= 32)
-                hipLaunchKernelGGL(k_any_prod_thin_short<8>, grid, dim3(64), 0, c->stream, A, a_batch, sai, sak, Bm, b_batch, P, I, D, R, tpw);
-            else
-                hipLaunchKernelGGL(k_any_prod_thin_short<16>, grid, dim3(64), 0, c->stream, A, a_batch, sai, sak, Bm, b_batch, P, I, D, R, tpw);
-            LAUNCH_CHECK();
-            return LRF_OK;
-        }
+    if (p.refused) return set_err(LRF_ENOTSUP, "contraction of length %d with rank %d exceeds the launch grid", D, R);
+    const dim3 grid(p.gx, p.gy, p.gz), block((unsigned)p.threads);
+    switch (p.k) {
+    case ANY_PROD_THIN_LONG:
+        hipLaunchKernelGGL(k_any_prod_thin_long, grid, block, 0, c->stream, A, a_batch, sai, sak, Bm, b_batch, P, I, D, R, nblk);
+        break;
+    case ANY_PROD_THIN_SHORT4:
+        hipLaunchKernelGGL(k_any_prod_thin_short<4>, grid, block, 0, c->stream, A, a_batch, sai, sak, Bm, b_batch, P, I, D, R, p.tpw);
+        break;
+    case ANY_PROD_THIN_SHORT8:
+        hipLaunchKernelGGL(k_any_prod_thin_short<8>, grid, block, 0, c->stream, A, a_batch, sai, sak, Bm, b_batch, P, I, D, R, p.tpw);
+        break;
+    case ANY_PROD_THIN_SHORT16:
+        hipLaunchKernelGGL(k_any_prod_thin_short<16>, grid, block, 0, c->stream, A, a_batch, sai, sak, Bm, b_batch, P, I, D, R, p.tpw);
+        break;
+    case ANY_PROD_BIG:
+        hipLaunchKernelGGL(k_any_prod_big, grid, block, 0, c->stream, A, a_batch, sai, sak, Bm, b_batch, P, I, D, R, nblk);
+        break;
+    case ANY_PROD_TILED:
+        hipLaunchKernelGGL(k_any_prod, grid, block, 0, c->stream, A, a_batch, sai, sak, Bm, b_batch, P, I, D, R, nblk, p.native ? 1 : 0, p.tiles);
+        break;
     }
-    const bool fits32 = (double)I * (double)sai + 32.0 * (double)sak + (double)LRF_KC * (double)sak < 2147483648.0 && (double)LRF_KC * R < 2147483648.0;
-    if (!native && D > 32 && I > 64 && R > 16 && fits32 && !prod_small) { // the 128 x 64 tiled kernel
-        const unsigned gyb = (unsigned)(((R + 63) / 64) * nblk);
-        if (gyb > 65535u) return set_err(LRF_ENOTSUP, "contraction of length %d with rank %d exceeds the launch grid", D, R);
-        hipLaunchKernelGGL(k_any_prod_big, dim3((unsigned)((I + 127) / 128), gyb, (unsigned)B), dim3(256), 0, c->stream, A, a_batch, sai, sak,
-                           Bm, b_batch, P, I, D, R, nblk);
-        LAUNCH_CHECK();
-        if (nblk > 1) {
-            const long IR = (long)I * R;
-            hipLaunchKernelGGL(k_any_fold, dim3((unsigned)((IR + 255) / 256), (unsigned)B), dim3(256), 0, c->stream, (const float*)P, C, IR, nblk);
-            LAUNCH_CHECK();
-        }
-        return LRF_OK;
-    }
-    const unsigned gy = (unsigned)(((R + 31) / 32) * nblk);
-    if (gy > 65535u) return set_err(LRF_ENOTSUP, "contraction of length %d with rank %d exceeds the launch grid", D, R);
-    // 64-row tiles per workgroup: more for tall matrices with a short contraction, as long as ~4096 workgroups remain
-    const long ntile = (I + 63) / 64;
-    int tiles = 1;
-    while (tiles < 8 && D <= 64 && ntile * gy * (long)B / (2 * tiles) >= 4096) tiles *= 2;
-    hipLaunchKernelGGL(k_any_prod, dim3((unsigned)((ntile + tiles - 1) / tiles), gy, (unsigned)B), dim3(256), 0, c->stream, A, a_batch, sai,
-                       sak, Bm, b_batch, P, I, D, R, nblk, native ? 1 : 0, tiles);
     LAUNCH_CHECK();
-    if (nblk > 1) {
-        const long IR = (long)I * R;
-        hipLaunchKernelGGL(k_any_fold, dim3((unsigned)((IR + 255) / 256), (unsigned)B), dim3(256), 0, c->stream, (const float*)P, C, IR, nblk);
+    if (p.fold) {
+        hipLaunchKernelGGL(k_any_fold, dim3(p.fold_gx, (unsigned)B), dim3(256), 0, c->stream, (const float*)P, C, (long)I * R, nblk);
         LAUNCH_CHECK();
     }
     return LRF_OK;
 }
 
-// CoordinateDescent.update_u (lrf/factorization/qmf.py:93-126) for the factor F [B][rows][R]; `trans`: x.mT (update_v, :128-139)
+// CoordinateDescent.update_u (lrf/factorization/qmf.py:93-126) for the factor F [B][rows][R]; `trans`: x.mT (update_v, :128-139).
+// The native flags of the two products and the Gauss-Seidel variant: plan_any_update (lrf_plan.cpp)
 static int any_update(lrf_ctx* c, const float* X, long x_batch, int B, int M, int N, int R, bool trans, float* F, const float* Fix,
                       float lo, float hi, float l1 = 0.f, float l2 = 0.f, float eps = LRF_EPS, bool int_rows = false)
 {
@@ -95,25 +70,27 @@ static int any_update(lrf_ctx* c, const float* X, long x_batch, int B, int M, in
     int rc;
     // a = x @ v  (or x.mT @ u)
     if ((rc = any_prod(c, X, x_batch, trans ? 1 : N, trans ? N : 1, Fix, (long)depth * R, a, B, rows, depth, R,
-                       (long)depth * rows * R < 400)))
+                       (long)depth * rows * R < LRF_ANY_NATIVE_BELOW)))
         return rc;
     // b = v.mT @ v
-    if ((rc = any_prod(c, Fix, (long)depth * R, 1, R, Fix, (long)depth * R, bm, B, R, depth, R, (long)depth * R * R < 400))) return rc;
+    if ((rc = any_prod(c, Fix, (long)depth * R, 1, R, Fix, (long)depth * R, bm, B, R, depth, R, (long)depth * R * R < LRF_ANY_NATIVE_BELOW)))
+        return rc;
     static const bool gs_f32 = dev_flag("LRF_ANY_GS_F32");
-    const int native_gs = ((long)(R - 1) * rows < 400) ? 1 : 0;
-    const dim3 ggrid((unsigned)((rows + 63) / 64), (unsigned)B);
-    if (int_rows && !gs_f32) { // F holds integers of the int8 range: byte rows in LDS
-        const size_t lds = (((size_t)64 * 4 * (((R + 3) >> 2) | 1) + 15) & ~(size_t)15) + (size_t)R * sizeof(float);
-        hipLaunchKernelGGL((k_any_gs<int8_t, true>), ggrid, dim3(64), lds, c->stream, (const float*)a, (const float*)bm, F, rows, R, native_gs, lo,
-                           hi, l1, l2, eps);
-    } else {
-        const size_t rows_lds = ((size_t)64 * (R | 1) * sizeof(float) + 15) & ~(size_t)15;
-        if (rows_lds + (size_t)R * sizeof(float) <= 160 * 1024)
-            hipLaunchKernelGGL((k_any_gs<float, true>), ggrid, dim3(64), rows_lds + (size_t)R * sizeof(float), c->stream, (const float*)a,
-                               (const float*)bm, F, rows, R, native_gs, lo, hi, l1, l2, eps);
-        else
-            hipLaunchKernelGGL((k_any_gs<float, false>), ggrid, dim3(64), rows_lds, c->stream, (const float*)a, (const float*)bm, F, rows, R,
-                               native_gs, lo, hi, l1, l2, eps);
+    const AnyGsPlan g = plan_any_gs(rows, R, B, int_rows, gs_f32);
+    const dim3 ggrid(g.gx, g.gy);
+    switch (g.k) {
+    case ANY_GS_I8: // F holds integers of the int8 range: byte rows in LDS
+        hipLaunchKernelGGL((k_any_gs<int8_t, true>), ggrid, dim3(64), g.lds, c->stream, (const float*)a, (const float*)bm, F, rows, R, g.native_gs,
+                           lo, hi, l1, l2, eps);
+        break;
+    case ANY_GS_F32_LDS:
+        hipLaunchKernelGGL((k_any_gs<float, true>), ggrid, dim3(64), g.lds, c->stream, (const float*)a, (const float*)bm, F, rows, R, g.native_gs,
+                           lo, hi, l1, l2, eps);
+        break;
+    case ANY_GS_F32_NOLDS:
+        hipLaunchKernelGGL((k_any_gs<float, false>), ggrid, dim3(64), g.lds, c->stream, (const float*)a, (const float*)bm, F, rows, R, g.native_gs,
+                           lo, hi, l1, l2, eps);
+        break;
     }
     LAUNCH_CHECK();
     return LRF_OK;
@@ -128,8 +105,8 @@ int any_workspace(lrf_ctx* c, int B, int M, int N, int R)
     if ((rc = ensure(c, c->any_a, (size_t)B * mx * R * sizeof(float)))) return rc;
     if ((rc = ensure(c, c->any_b, (size_t)B * R * R * sizeof(float)))) return rc;
     if (!(c->attr_done & (1u << 8))) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_any_gs<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_any_gs<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_any_gs<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LRF_ANY_GS_MAX_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_any_gs<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LRF_ANY_GS_MAX_LDS));
         HIP_TRY(hipFuncSetAttribute((const void*)k_any_gs<int8_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
         c->attr_done |= 1u << 8;
     }
@@ -300,9 +277,7 @@ static int any_run_init(lrf_ctx* c, const float* X, int B, int M, int N, int R, 
     if ((rc = ensure(c, c->any_e2, (size_t)B * n * R * sizeof(float)))) return rc;
     float* E2 = (float*)c->any_e2.p;
     const size_t per = sizeof(double) * ((size_t)n * n + (size_t)3 * n * Rc);
-    long chunk = (long)(((size_t)2 << 30) / per);
-    if (chunk < 1) chunk = 1;
-    if (chunk > B) chunk = B;
+    const long chunk = plan_any_init_chunk(n, Rc, B);
     if ((rc = ensure(c, c->any_g, (size_t)chunk * per))) return rc;
     double* G = (double*)c->any_g.p;
     double* Z = G + (size_t)chunk * n * n;

@@ -160,3 +160,81 @@ BcdPlan plan_bcd(const std::vector<PlaneDesc>& planes, int K, int lo, int hi, in
         p.streams = !(p.persist || sweep) ? FAM_STREAMS_CALL : (s.no_init_fork ? FAM_STREAMS_NONE : FAM_STREAMS_INIT);
     return p;
 }
+
+// ---- the any-shape path ---------------------------------------------------------------------------------------------------
+AnyProdPlan plan_any_prod(int I, int D, int R, int B, long sai, long sak, bool native, bool prod_small)
+{
+    AnyProdPlan p;
+    p.nblk = (D + LRF_KC - 1) / LRF_KC;
+    p.fold = p.nblk > 1;
+    p.fold_gx = (unsigned)(((long)I * R + 255) / 256);
+    p.tpw = p.tiles = 1;
+    p.native = false;
+    p.refused = false;
+    if (!native && !prod_small && R <= 16) { // thin products (4 x 4 patches): operands straight from global memory
+        if (I <= 16 && D > 64) {
+            p.k = ANY_PROD_THIN_LONG;
+            p.gx = (unsigned)p.nblk; p.gy = (unsigned)B; p.gz = 1; p.threads = 64;
+            return p;
+        }
+        if (D <= 64 && I >= 256) {
+            const long nt16 = (I + 15) / 16;
+            while (p.tpw < 16 && nt16 * (long)B / (2 * p.tpw) >= 8192) p.tpw *= 2;
+            p.k = D <= 16 ? ANY_PROD_THIN_SHORT4 : D <= 32 ? ANY_PROD_THIN_SHORT8 : ANY_PROD_THIN_SHORT16;
+            p.gx = (unsigned)((nt16 + p.tpw - 1) / p.tpw); p.gy = (unsigned)B; p.gz = 1; p.threads = 64;
+            p.fold = false; // (D <= 64 < LRF_KC: one block, the kernel writes the result)
+            return p;
+        }
+    }
+    const bool fits32 = (double)I * (double)sai + 32.0 * (double)sak + (double)LRF_KC * (double)sak < 2147483648.0 && (double)LRF_KC * R < 2147483648.0;
+    if (!native && D > 32 && I > 64 && R > 16 && fits32 && !prod_small) { // the 128 x 64 tiled kernel
+        p.k = ANY_PROD_BIG;
+        p.gx = (unsigned)((I + 127) / 128); p.gy = (unsigned)(((R + 63) / 64) * p.nblk); p.gz = (unsigned)B; p.threads = 256;
+        p.refused = p.gy > 65535u;
+        return p;
+    }
+    p.k = ANY_PROD_TILED;
+    p.native = native;
+    p.gy = (unsigned)(((R + 31) / 32) * p.nblk);
+    p.refused = p.gy > 65535u;
+    // 64-row tiles per workgroup: more for tall matrices with a short contraction, as long as ~4096 workgroups remain
+    const long ntile = (I + 63) / 64;
+    while (p.tiles < 8 && D <= 64 && ntile * p.gy * (long)B / (2 * p.tiles) >= 4096) p.tiles *= 2;
+    p.gx = (unsigned)((ntile + p.tiles - 1) / p.tiles); p.gz = (unsigned)B; p.threads = 256;
+    return p;
+}
+
+AnyGsPlan plan_any_gs(int rows, int R, int B, bool int_rows, bool gs_f32)
+{
+    AnyGsPlan g;
+    g.native_gs = ((long)(R - 1) * rows < LRF_ANY_NATIVE_BELOW) ? 1 : 0;
+    g.gx = (unsigned)((rows + 63) / 64); g.gy = (unsigned)B;
+    if (int_rows && !gs_f32) { // the factor holds integers of the int8 range: byte rows in LDS
+        g.k = ANY_GS_I8;
+        g.lds = (((size_t)64 * 4 * (((R + 3) >> 2) | 1) + 15) & ~(size_t)15) + (size_t)R * sizeof(float);
+        return g;
+    }
+    const size_t rows_lds = ((size_t)64 * (R | 1) * sizeof(float) + 15) & ~(size_t)15;
+    const bool diag = rows_lds + (size_t)R * sizeof(float) <= LRF_ANY_GS_MAX_LDS;
+    g.k = diag ? ANY_GS_F32_LDS : ANY_GS_F32_NOLDS;
+    g.lds = diag ? rows_lds + (size_t)R * sizeof(float) : rows_lds;
+    return g;
+}
+
+AnyUpdatePlan plan_any_update(int B, int M, int N, int R, bool trans, bool int_rows, bool prod_small, bool gs_f32)
+{
+    const int rows = trans ? N : M, depth = trans ? M : N;
+    AnyUpdatePlan u;
+    u.a = plan_any_prod(rows, depth, R, B, trans ? 1 : N, trans ? N : 1, (long)depth * rows * R < LRF_ANY_NATIVE_BELOW, prod_small);
+    u.b = plan_any_prod(R, depth, R, B, 1, R, (long)depth * R * R < LRF_ANY_NATIVE_BELOW, prod_small);
+    u.gs = plan_any_gs(rows, R, B, int_rows, gs_f32);
+    return u;
+}
+
+long plan_any_init_chunk(int n, int Rc, long B)
+{
+    const size_t per = sizeof(double) * ((size_t)n * n + (size_t)3 * n * Rc);
+    long chunk = (long)(LRF_ANY_INIT_WORK_BYTES / per);
+    if (chunk < 1) chunk = 1;
+    return chunk > B ? B : chunk;
+}

@@ -75,4 +75,39 @@ struct BcdPlan {
 bool plan_splits(long nblocks, int rmax_t, const PlanSettings& s);
 // reads R, nblk, native_t2_u and init_src of the planes.  sweep: lrf_qmf_encode_sweep_rgb_u8's table
 BcdPlan plan_bcd(const std::vector<PlaneDesc>& planes, int K, int lo, int hi, int first_mode, const PlanSettings& s, bool sweep = false);
+
+// ---- the any-shape path (lrf_anyshape_host.inc executes these; tests/test_any_plan.py reads them on the CPU) ----------------
+#define LRF_ANY_GS_MAX_LDS (160 * 1024) // dynamic LDS of k_any_gs<float, .>
+#define LRF_ANY_NATIVE_BELOW 400        // products of fewer multiply-adds take ATen's small-product order
+#define LRF_ANY_INIT_WORK_BYTES ((size_t)2 << 30) // Gram matrices and eigen-solver work space of one chunk of any_run_init
+// One product C [B][I][R] = A' Bm over a contraction of length D (any_prod).  THIN_LONG: k_any_prod_thin_long; THIN_SHORT4 /
+// 8 / 16: k_any_prod_thin_short<4 | 8 | 16>; BIG: k_any_prod_big; TILED: k_any_prod
+enum AnyProdKernel { ANY_PROD_THIN_LONG, ANY_PROD_THIN_SHORT4, ANY_PROD_THIN_SHORT8, ANY_PROD_THIN_SHORT16, ANY_PROD_BIG, ANY_PROD_TILED };
+struct AnyProdPlan {
+    AnyProdKernel k;
+    int nblk;            // blocks of LRF_KC of the contraction; above one the kernel writes partial sums ...
+    bool fold;           // ... and k_any_fold, grid (fold_gx, B) of 256 threads, adds them in block order
+    int tpw, tiles;      // 16-row tiles per wave (THIN_SHORT*) / 64-row tiles per workgroup (TILED); 1 for the others
+    unsigned gx, gy, gz; // the product kernel's grid ...
+    int threads;         // ... and workgroup size
+    unsigned fold_gx;
+    bool native;         // TILED in ATen's order (the caller's flag, where the product stays on k_any_prod)
+    bool refused;        // the contraction's blocks times the rank's column tiles exceed the launch grid: no launch
+};
+AnyProdPlan plan_any_prod(int I, int D, int R, int B, long sai, long sak, bool native, bool prod_small);
+// The Gauss-Seidel sweep over the rows of a factor (any_update).  GS_I8: k_any_gs<int8_t, true>; GS_F32_LDS: k_any_gs<float, true>;
+// GS_F32_NOLDS: k_any_gs<float, false> (the diagonal no longer fits next to the rows)
+enum AnyGsKernel { ANY_GS_I8, ANY_GS_F32_LDS, ANY_GS_F32_NOLDS };
+struct AnyGsPlan {
+    AnyGsKernel k;
+    unsigned gx, gy; // 64 threads
+    size_t lds;
+    int native_gs;   // (R - 1) rows < LRF_ANY_NATIVE_BELOW
+};
+AnyGsPlan plan_any_gs(int rows, int R, int B, bool int_rows, bool gs_f32);
+// One factor update of B matrices [M][N] at rank R (any_update; trans: the V update): a = x @ v (or x.mT @ u), b = v.mT @ v, the sweep
+struct AnyUpdatePlan { AnyProdPlan a, b; AnyGsPlan gs; };
+AnyUpdatePlan plan_any_update(int B, int M, int N, int R, bool trans, bool int_rows, bool prod_small, bool gs_f32);
+// matrices per chunk of any_run_init: n = min(M, N), Rc = min(R, n)
+long plan_any_init_chunk(int n, int Rc, long B);
 #endif

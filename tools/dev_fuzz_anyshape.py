@@ -24,7 +24,7 @@ for case in range(cases):
     R = int(rng.integers(1, max(2, min(M, N, 70)) + 1))
     if rng.integers(0, 6) == 0:
         R = int(min(M, N) + rng.integers(0, 4))       # ranks at / beyond the side
-    R = max(1, min(R, 120))
+    R = max(1, min(R, 639 if kind == 4 else 120))  # around 512: up to LRF_ANY_MAX_RANK (include/lrf_hip.h), ranks at the side included
     K = int(rng.integers(1, 4))
     lo, hi = [(-16, 15), (-128, 127), (-8, 7)][int(rng.integers(0, 3))]
     style = rng.integers(0, 3)
