@@ -223,6 +223,34 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* ctx, const uint8_t* rgb, int64_t B, int
 int lrf_qmf_decode_rgb_u8(lrf_ctx* ctx, const int8_t* U, const int8_t* V, int64_t B, int64_t H, int64_t W,
                           const int R[3], uint8_t* rgb);
 
+/*
+ * The same decode (lrf/compression/qmf.py:295-353) for a list of n images that differ in size and in ranks, in one call: what a
+ * per-image quality choice or a dataset of mixed sizes hands to a decoder.
+ *   images  [n] descriptors in host memory
+ *   U, V    device buffers of u_len / v_len int8 elements; image i's factors start at u_off / v_off and are laid out as
+ *           lrf_qmf_encode_rgb_u8 writes ONE image: [M_Y,R_Y] [M_Cb,R_Cb] [M_Cr,R_Cr], and three [64,R_c]
+ *   rgb     device buffer of rgb_len bytes; image i is written as [3][H][W] at rgb_off
+ * Image i's bytes are those the uniform decoder writes when called for that image alone (B = 1, U + u_off, V + v_off,
+ * rgb + rgb_off), for every geometry and rank it accepts: the kernels run the same device functions.  They do not depend on
+ * the image's place in the list or on the other images.
+ * Launches: the images whose sides are multiples of 16 (with rgb + rgb_off a multiple of 8) and whose ranks are within
+ * (32,16,16) share one launch whatever their ranks; the other images the tiled decoder covers take one launch per rank-bound
+ * class (at most five); one launch each for the images only the rank <= 8 kernel and the general kernel serve: at most eight.
+ * Asynchronous on the context's stream and timed under LRF_K_DECODE, except that the first call of a new list uploads a table
+ * (the descriptors and an entry per workgroup) and waits for the stream; lrf_ctx_trim releases the table.
+ * Everything is validated on the host before any launch.  LRF_EINVAL: a NULL pointer, n outside [1,65535], a rank outside
+ * [1,64], a size the uniform decoder refuses, a negative offset, an image whose U, V or rgb range leaves its buffer, 2^31 or
+ * more workgroups in one launch.
+ */
+typedef struct {
+    int64_t H, W;         /* image size */
+    int R[3];             /* ranks Y, Cb, Cr, each 1..64 */
+    int64_t u_off, v_off; /* int8 elements from U / V to this image's factors */
+    int64_t rgb_off;      /* bytes from rgb to this image's [3][H][W] output */
+} lrf_ragged_image;
+int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_image* images /* host */, const int8_t* U, int64_t u_len,
+                                 const int8_t* V, int64_t v_len, uint8_t* rgb, int64_t rgb_len);
+
 /* ---- scoring (the third stage of the reference's experiment loop) ----------------------------- */
 
 /*

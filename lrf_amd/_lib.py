@@ -31,6 +31,11 @@ class QmfOpts(ctypes.Structure):
                 ("l1_ratio", ctypes.c_double), ("factors", c_int), ("eps", ctypes.c_double), ("w_init", c_int)]
 
 
+class RaggedImage(ctypes.Structure):
+    """lrf_ragged_image (include/lrf_hip.h)"""
+    _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int * 3), ("u_off", c_i64), ("v_off", c_i64), ("rgb_off", c_i64)]
+
+
 def load():
     """Loads liblrf_hip.so; raises ImportError when it has not been built (see __graft_entry__.build)."""
     global _lib
@@ -76,6 +81,7 @@ def load():
                                                     c_int, c_void_p, c_void_p, c_void_p]
         lib.lrf_qmf_decode_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, ctypes.POINTER(c_int),
                                               c_void_p]
+        lib.lrf_qmf_decode_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
         lib.lrf_image_metrics_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
         lib.lrf_qmf_sweep_sse_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int), c_void_p]
         lib.lrf_svd_encode_rgb_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -121,7 +127,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -228,6 +234,37 @@ def check_sweep_sse_args(rgb, factors, triples):
         if tuple(U.shape) != (B, nu) or tuple(V.shape) != (B, nv) or U.device != dev or V.device != dev:
             raise ValueError(f"factor buffers do not match the geometry at ranks {tuple(t)}: expected int8 U {(B, nu)} and V {(B, nv)} on "
                              f"{dev}, got {tuple(U.shape)} on {U.device} and {tuple(V.shape)} on {V.device}")
+
+
+def check_ragged_args(U, V, images):
+    """The argument checks of lrf_qmf_decode_ragged_rgb_u8 on its tensors, before any device is touched.  U, V: flat int8 tensors
+    on one device; images: 1 to 65535 tuples (H, W, ranks, u_off, v_off), every rank in 1..64, every image's factors inside U and
+    V (the kernels index them from the tuple alone: anything else would be an out-of-bounds read).  TypeError for anything but
+    int8 tensors, ValueError for everything else.  -> [(H, W, [R_Y, R_Cb, R_Cr], u_off, v_off)] as integers."""
+    import torch
+    if not isinstance(U, torch.Tensor) or not isinstance(V, torch.Tensor) or U.dtype != torch.int8 or V.dtype != torch.int8:
+        raise TypeError("factors must be int8 tensors")
+    if U.dim() != 1 or V.dim() != 1 or U.device != V.device or not U.is_contiguous() or not V.is_contiguous():
+        raise ValueError(f"U and V must be flat contiguous tensors on one device, got {tuple(U.shape)} on {U.device} and {tuple(V.shape)} on {V.device}")
+    if images is None or len(images) < 1 or len(images) > 65535:
+        raise ValueError("decode_ragged needs 1 to 65535 images")
+    out = []
+    for i, im in enumerate(images):
+        if len(im) != 5 or len(im[2]) != 3:
+            raise ValueError(f"image {i}: (H, W, (R_Y, R_Cb, R_Cr), u_off, v_off) expected")
+        H, W, ranks, u_off, v_off = im
+        if any(int(x) != x for x in (H, W, u_off, v_off)) or any(int(r) != r for r in ranks):
+            raise ValueError(f"image {i}: integers expected")
+        H, W, u_off, v_off, ranks = int(H), int(W), int(u_off), int(v_off), [int(r) for r in ranks]
+        if H < 1 or W < 1 or H >= 2 ** 31 or W >= 2 ** 31 or min(ranks) < 1 or max(ranks) > 64:
+            raise ValueError(f"image {i}: size {H}x{W} or ranks {ranks} out of range (ranks 1..64)")
+        dims = plane_dims(H, W)
+        nu, nv = sum(d[4] * r for d, r in zip(dims, ranks)), 64 * sum(ranks)
+        if u_off < 0 or v_off < 0 or u_off + nu > U.numel() or v_off + nv > V.numel():
+            raise ValueError(f"image {i}: its factors (U {nu} elements at {u_off}, V {nv} at {v_off}) leave the buffers of "
+                             f"{U.numel()} and {V.numel()} elements")
+        out.append((H, W, ranks, u_off, v_off))
+    return out
 
 
 def _dptr(t):
@@ -446,6 +483,26 @@ class Context:
         self.use_torch_stream()
         check(self._lib.lrf_qmf_decode_rgb_u8(self._h, _dptr(U), _dptr(V), B, H, W, R, _dptr(rgb)))
         return rgb
+
+    def decode_ragged(self, U, V, images):
+        """Images that differ in size and ranks in one call (lrf_qmf_decode_ragged_rgb_u8).  U, V: flat int8 CUDA tensors; images:
+        [(H, W, ranks, u_off, v_off)], image i's factors at U[u_off:], V[v_off:] in encode_rgb's layout of one image -> a list
+        of uint8 CUDA tensors [3,H_i,W_i]: views of one buffer, each starting at a multiple of 16 bytes (so that images whose
+        sides are multiples of 16 keep the decoder made for them)."""
+        import torch
+        ims = check_ragged_args(U, V, images)
+        if not (U.is_cuda and U.device.index == self.device):
+            raise ValueError(f"decode_ragged needs its tensors on cuda:{self.device}, got {U.device}")
+        desc = (RaggedImage * len(ims))()
+        off = 0
+        for d, (H, W, ranks, u_off, v_off) in zip(desc, ims):
+            d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, off
+            d.R[0], d.R[1], d.R[2] = ranks
+            off = (off + 3 * H * W + 15) // 16 * 16
+        rgb = torch.empty((off,), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_decode_ragged_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(rgb), rgb.numel()))
+        return [rgb[d.rgb_off:d.rgb_off + 3 * d.H * d.W].view(3, d.H, d.W) for d in desc]
 
     def image_metrics(self, a, b, want_ssim=True):
         """uint8 CUDA tensors a, b [B,C,H,W] -> (sse int64 [B], ssim float64 [B] or None) on the device (lrf_image_metrics_u8):

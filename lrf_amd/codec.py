@@ -300,6 +300,10 @@ def _pack_lib():
                                                     ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64)]
         lib.lrf_pack_free.argtypes = [ctypes.c_void_p]
         lib.lrf_pack_free.restype = None
+        lib.lrf_pack_unpack_qmf_factors_ragged.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int),
+                                                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+                                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
         lib.lrf_pack_unpack_qmf_factors.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
                                                     ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
@@ -885,6 +889,103 @@ def qmf_decode_batch(streams: Sequence[bytes], device=None) -> torch.Tensor:
     if m0["dtype"] != "uint8":
         raise NotImplementedError("HIP decode writes uint8 images")
     return ctx.decode_rgb(U, V, H, W, m0["rank"])
+
+
+def _ragged_branch(meta) -> str:
+    """'' for a stream of the default branch (YCbCr, 8x8 patches, chroma (0.5, 0.5), uint8), else the name of its branch"""
+    if meta["color space"] != "YCbCr":
+        return f"the {meta['color space']} colour space"
+    if not meta["patch"]:
+        return "patch=False"
+    if list(meta["patch size"]) != [8, 8]:
+        return f"patch size {tuple(meta['patch size'])}"
+    H, W = meta["original size"][0]
+    dims = _lib.plane_dims(int(H), int(W))
+    for c in range(3):
+        if list(meta["original size"][c]) != [dims[c][0], dims[c][1]] or list(meta["padded size"][c]) != [dims[c][2], dims[c][3]]:
+            return "a chroma scale other than (0.5, 0.5)"
+    if meta["dtype"] != "uint8":
+        return f"dtype {meta['dtype']}"
+    return ""
+
+
+def unpack_ragged_native(blobs, Ms, Rs, u_off, v_off, u_len, v_len, threads: int = 0):
+    """lrf_pack_unpack_qmf_factors_ragged: the factor payloads of n streams of differing (M, R) -> (U int8 [u_len], V int8 [v_len],
+    rc); U and V are None unless rc == 0.  Raises OSError where liblrf_pack.so cannot be used."""
+    import ctypes
+    lib = _pack_lib()
+    n = len(blobs)
+    U, V = np.empty((u_len,), dtype=np.int8), np.empty((v_len,), dtype=np.int8)
+    rc = lib.lrf_pack_unpack_qmf_factors_ragged(
+        (ctypes.c_char_p * n)(*blobs), (ctypes.c_int64 * n)(*[len(b) for b in blobs]), n,
+        (ctypes.c_int64 * (3 * n))(*[int(m) for M in Ms for m in M]), (ctypes.c_int * (3 * n))(*[int(r) for R in Rs for r in R]),
+        (ctypes.c_int64 * n)(*u_off), (ctypes.c_int64 * n)(*v_off), int(threads),
+        U.ctypes.data_as(ctypes.c_void_p), u_len, V.ctypes.data_as(ctypes.c_void_p), v_len)
+    return (U, V, 0) if rc == 0 else (None, None, rc)
+
+
+def _factors_ragged(streams: Sequence[bytes]):
+    """-> ([(H, W, ranks, u_off, v_off)], U int8 flat, V int8 flat) on the host, every stream checked: the branch
+    (NotImplementedError), the ranks, and the factor shapes against the metadata (ValueError).  No GPU is touched."""
+    if isinstance(streams, (bytes, bytearray, str)) or len(streams) < 1:
+        raise ValueError("qmf_decode_ragged takes a non-empty list of byte streams")
+    for i, s in enumerate(streams):
+        if not isinstance(s, (bytes, bytearray)):
+            raise TypeError(f"stream {i} is {type(s).__name__}, not bytes")
+    images, blobs, Ms, uo, vo = [], [], [], 0, 0
+    for i, s in enumerate(streams):
+        encoded_metadata, encoded_factors = separate_bytes(bytes(s), 2)
+        meta = bytes_to_dict(encoded_metadata)
+        branch = _ragged_branch(meta)
+        if branch:
+            raise NotImplementedError(f"stream {i}: qmf_decode_ragged covers the YCbCr / 8x8-patch / chroma (0.5, 0.5) / uint8 branch only, "
+                                      f"this stream is of {branch} (qmf_decode takes it)")
+        H, W = (int(x) for x in meta["original size"][0])
+        ranks = [int(r) for r in meta["rank"]]
+        if len(ranks) != 3 or min(ranks) < 1:
+            raise ValueError(f"stream {i} metadata: 'rank' must hold three positive integers")
+        M = [d[4] for d in _lib.plane_dims(H, W)]
+        images.append((H, W, ranks, uo, vo))
+        blobs.append(encoded_factors)
+        Ms.append(M)
+        uo += sum(m * r for m, r in zip(M, ranks))
+        vo += 64 * sum(ranks)
+    # untrusted metadata, nothing of the payload validated yet: a deflate stream expands by at most ~1032x, so a stream that
+    # claims more factor bytes than its payload could inflate to never gets its buffers (_factors_native's bound)
+    sizes = [sum(m * r for m, r in zip(M, im[2])) + 64 * sum(im[2]) for M, im in zip(Ms, images)]
+    U = V = None
+    if max(max(im[2]) for im in images) <= 64 and all(n <= 1040 * len(b) + 4096 for n, b in zip(sizes, blobs)):
+        try:
+            U, V, _ = unpack_ragged_native(blobs, Ms, [im[2] for im in images], [im[3] for im in images], [im[4] for im in images], uo, vo)
+        except OSError:
+            pass
+    if U is None:  # the library is absent or refused a stream: this module's parser names the defect (or parses what is valid)
+        Us, Vs = [], []
+        import zlib
+        for i, s in enumerate(streams):
+            try:
+                _, u1, v1 = _factors_python([bytes(s)])
+            except (zlib.error, KeyError, IndexError, TypeError) as e:  # cut short or corrupt inside the container
+                raise ValueError(f"stream {i}: its payload does not hold the factors its metadata describes ({e})") from e
+            Us.append(u1[0])
+            Vs.append(v1[0])
+        U, V = np.concatenate(Us), np.concatenate(Vs)
+    for i, im in enumerate(images):
+        if max(im[2]) > 64:
+            raise ValueError(f"stream {i}: ranks {im[2]} above 64")
+    return images, U, V
+
+
+def qmf_decode_ragged(streams: Sequence[bytes], device=None) -> list:
+    """Decodes streams that differ in size and ranks — what qmf_encode_target writes for a batch, or a dataset of mixed sizes —
+    in one call: -> a list of uint8 CUDA tensors [3,H_i,W_i] in input order (views of one buffer), each equal to
+    qmf_decode of its stream.  The default branch only (YCbCr, 8x8 patches, chroma (0.5, 0.5), uint8): a stream of another
+    branch raises NotImplementedError naming it.  One host-to-device copy of all U factors, one of all V, one kernel call."""
+    images, Uh, Vh = _factors_ragged(streams)
+    ctx = _lib.context(device)
+    U = torch.from_numpy(Uh).cuda(ctx.device)
+    V = torch.from_numpy(Vh).cuda(ctx.device)
+    return ctx.decode_ragged(U, V, images)
 
 
 def _qmf_decode_rgbspace(encoded_image: bytes, device=None) -> torch.Tensor:

@@ -7,6 +7,7 @@
 #include "lrf_bcdw_kernel.hip"
 #include "lrf_bcdw16_kernel.hip"
 #include "lrf_sweep_sse_kernel.hip"
+#include "lrf_decode_ragged_kernel.hip"
 
 // gram_exp: the fixed-point grid exponent of the exact Gram matrix (max|x| < 2^gram_exp) when the caller knows it — 8 for the
 // planes of qmf_encode — or LRF_GRAM_EXP_FROM_DATA: one more pass over X finds it per matrix
@@ -513,8 +514,8 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64
     return init_then_bcd(c, X, t, plan, sign, LRF_PLANES_GRAM_EXP, U, V);
 }
 
-// which decode body serves a geometry and a rank triple (lrf_qmf_decode_rgb_u8 and lrf_qmf_sweep_sse_rgb_u8 share it)
-enum { DEC_TILE16 = 0, DEC_STRIP = 1, DEC_R8 = 2, DEC_ANY = 3 };
+// which decode body serves a geometry and a rank triple (lrf_qmf_decode_rgb_u8, lrf_qmf_decode_ragged_rgb_u8 and
+// lrf_qmf_sweep_sse_rgb_u8 share it; the kinds DEC_*: lrf_plan.h)
 struct DecodePlan {
     int kind;
     int cls; // tiled kinds: index of the rank bounds (chroma, luma) = (4,8) (8,8) (8,16) (16,16) (16,32)
@@ -541,11 +542,7 @@ static DecodePlan decode_plan(const ImageGeom& g, int64_t H, int64_t W, const in
     return DecodePlan{(R[0] <= 8 && R[1] <= 8 && R[2] <= 8) ? DEC_R8 : DEC_ANY, 0};
 }
 // groups of four pixels per thread of k_decode8 / k_sse8: as many as leave the call ~2048 workgroups (small calls keep one group per thread)
-static long decode8_reps(long images, long n4)
-{
-    const long reps = images * ((n4 + 255) / 256) / 2048;
-    return reps < 1 ? 1 : (reps > 16 ? 16 : reps);
-}
+static long decode8_reps(long images, long n4) { return decode8_reps_of(images * ((n4 + 255) / 256)); }
 
 int lrf_qmf_decode_rgb_u8(lrf_ctx* c, const int8_t* U, const int8_t* V, int64_t B, int64_t H, int64_t W, const int R[3],
                           uint8_t* rgb)
@@ -594,6 +591,88 @@ int lrf_qmf_decode_rgb_u8(lrf_ctx* c, const int8_t* U, const int8_t* V, int64_t 
         hipLaunchKernelGGL(k_decode, dim3((unsigned)((n4 + 255) / 256), (unsigned)B), dim3(256), 0, c->stream, U, V, (int)H, (int)W,
                            g, R[0], R[1], R[2], u_img, v_img, rgb);
     LAUNCH_CHECK();
+    return LRF_OK;
+}
+
+// A list of images that differ in size and ranks in one call (kernels: lrf_decode_ragged_kernel.hip; the launches:
+// plan_decode_ragged).  Everything the kernels index with is checked here, before any launch.
+int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
+                                 int64_t v_len, uint8_t* rgb, int64_t rgb_len)
+{
+    if (!c || !images || !U || !V || !rgb) return set_err(LRF_EINVAL, "NULL argument");
+    if (n < 1 || n > 65535) return set_err(LRF_EINVAL, "n=%ld out of range [1,65535]", (long)n);
+    std::vector<RaggedDesc> descs((size_t)n);
+    std::vector<RaggedWork> work((size_t)n);
+    memset((void*)descs.data(), 0, descs.size() * sizeof(RaggedDesc)); // (the bytes are the table's key: padding included)
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_ragged_image& im = images[i];
+        RaggedDesc& d = descs[(size_t)i];
+        if (im.H < 1 || im.W < 1 || im.H > INT32_MAX || im.W > INT32_MAX) return set_err(LRF_EINVAL, "image %ld: size %ldx%ld out of range", (long)i, (long)im.H, (long)im.W);
+        int rc = make_geom(im.H, im.W, &d.g);
+        if (rc) return rc;
+        for (int ch = 0; ch < 3; ch++)
+            if (im.R[ch] < 1 || im.R[ch] > 64) return set_err(LRF_EINVAL, "image %ld: rank %d out of range", (long)i, im.R[ch]);
+        if (im.u_off < 0 || im.v_off < 0 || im.rgb_off < 0) return set_err(LRF_EINVAL, "image %ld: negative offset", (long)i);
+        long u_img = 0, v_img = 0;
+        for (int ch = 0; ch < 3; ch++) {
+            u_img += (long)d.g.p[ch].M * im.R[ch];
+            v_img += 64L * im.R[ch];
+        }
+        // (every term is checked against the length before it is added to an offset: no sum can wrap)
+        if (u_img > u_len || im.u_off > u_len - u_img) return set_err(LRF_EINVAL, "image %ld: its U factors leave the buffer of %ld elements", (long)i, (long)u_len);
+        if (v_img > v_len || im.v_off > v_len - v_img) return set_err(LRF_EINVAL, "image %ld: its V factors leave the buffer of %ld elements", (long)i, (long)v_len);
+        if (rgb_len < 3 || im.H * im.W > rgb_len / 3 || im.rgb_off > rgb_len - 3 * im.H * im.W)
+            return set_err(LRF_EINVAL, "image %ld: its output leaves the buffer of %ld bytes", (long)i, (long)rgb_len);
+        const DecodePlan plan = decode_plan(d.g, im.H, im.W, im.R, ((reinterpret_cast<uintptr_t>(rgb) + (uintptr_t)im.rgb_off) & 7) == 0);
+        d.u_off = im.u_off; d.v_off = im.v_off; d.rgb_off = im.rgb_off;
+        d.H = (int)im.H; d.W = (int)im.W;
+        d.R0 = im.R[0]; d.R1 = im.R[1]; d.R2 = im.R[2];
+        d.kind = plan.kind; d.cls = plan.cls;
+        d.per_strip = (d.g.p[0].nw + 31) / 32;
+        RaggedWork& w = work[(size_t)i];
+        w.kind = plan.kind; w.cls = plan.cls;
+        if (plan.kind == DEC_TILE16) w.units = (long)(im.H / 16) * d.per_strip;
+        else if (plan.kind == DEC_STRIP) w.units = (long)((d.g.p[0].nh + 1) / 2) * d.per_strip;
+        else w.units = (long)im.H * ((im.W + 3) / 4);
+    }
+    const RaggedPlan plan = plan_decode_ragged(work);
+    if (plan.too_many) return set_err(LRF_EINVAL, "%ld work items in one launch: split the list", plan.too_many);
+    LRF_ON_DEVICE(c);
+    // the table: descriptors, then blocks (a function of the descriptors: they alone are the key)
+    const size_t db = descs.size() * sizeof(RaggedDesc), bb = plan.blocks.size() * sizeof(RaggedBlock);
+    if (c->ragged_key.size() != db || memcmp(c->ragged_key.data(), descs.data(), db) != 0 || !c->ragged_tab.p) {
+        c->ragged_key.clear();
+        std::vector<char> tab(db + bb);
+        memcpy(tab.data(), descs.data(), db);
+        memcpy(tab.data() + db, plan.blocks.data(), bb);
+        int rc = upload(c, c->ragged_tab, tab.data(), tab.size());
+        if (rc) return rc;
+        c->ragged_key.assign((const char*)descs.data(), (const char*)descs.data() + db);
+    }
+    const RaggedDesc* d_desc = (const RaggedDesc*)c->ragged_tab.p;
+    const RaggedBlock* d_blk = (const RaggedBlock*)((const char*)c->ragged_tab.p + db);
+    Prof p(c, LRF_K_DECODE);
+    for (const RaggedLaunch& l : plan.launches) {
+        const dim3 grid((unsigned)l.nblocks);
+        const RaggedBlock* bl = d_blk + l.block0;
+        if (l.kind == DEC_TILE16)
+            hipLaunchKernelGGL((k_decode_ragged_tiled<false, -1>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl);
+        else if (l.kind == DEC_STRIP) {
+#define LRF_RAGGED_STRIP(CLS) hipLaunchKernelGGL((k_decode_ragged_tiled<true, CLS>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl)
+            switch (l.cls) {
+            case 0: LRF_RAGGED_STRIP(0); break;
+            case 1: LRF_RAGGED_STRIP(1); break;
+            case 2: LRF_RAGGED_STRIP(2); break;
+            case 3: LRF_RAGGED_STRIP(3); break;
+            default: LRF_RAGGED_STRIP(4); break;
+            }
+#undef LRF_RAGGED_STRIP
+        } else if (l.kind == DEC_R8)
+            hipLaunchKernelGGL(k_decode8_ragged, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, l.reps);
+        else
+            hipLaunchKernelGGL(k_decode_ragged_any, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl);
+        LAUNCH_CHECK();
+    }
     return LRF_OK;
 }
 

@@ -77,6 +77,8 @@ struct lrf_ctx {
     DevBuf metrics; // lrf_image_metrics_u8: a float64 slot per (image, channel, tile), then (max, 255 - min) per image
     DevBuf sse_tab; // lrf_qmf_sweep_sse_rgb_u8: its table of rank triples (SseItem) ...
     std::vector<char> sse_key; // ... and the bytes now resident there (calls that repeat a sweep skip the synchronising upload)
+    DevBuf ragged_tab; // lrf_qmf_decode_ragged_rgb_u8: the image descriptors (RaggedDesc), behind them the block table ...
+    std::vector<char> ragged_key; // ... and the descriptor bytes now resident there
     DevBuf vf16, wf16, bf16, pp16, qp16; // the pitch-16 tables of a call that mixes kernel families (BcdPlan::mixed)
     // host staging for descriptor tables (pinned)
     void* h_stage = nullptr;

@@ -74,6 +74,22 @@ struct GramChunk {
     int nrows;
 };
 
+// ---- the ragged decode (lrf_qmf_decode_ragged_rgb_u8; kernels: lrf_decode_ragged_kernel.hip) ----
+// One image of the call, as the kernels read it (uniform loads: the index comes from the workgroup's table entry).
+struct RaggedDesc {
+    ImageGeom g;
+    long u_off, v_off; // int8 elements from U / V to the image's factors
+    long rgb_off;      // bytes from rgb to the image's [3][H][W]
+    int H, W;
+    int R0, R1, R2;
+    int kind, cls;     // the decode body that serves it and, for the tiled ones, the index of its rank bounds (decode_plan)
+    int per_strip;     // tiled bodies: workgroups per 16-row strip
+};
+// One workgroup of a launch: which image, and which tile (tiled bodies) or group of 256 x reps pixel quads inside it
+struct RaggedBlock {
+    int image, tile;
+};
+
 struct GsParams {
     float lo, hi;      // clamp
     float flimit;      // |q~| >= flimit: certainly outside [lo,hi] after rounding

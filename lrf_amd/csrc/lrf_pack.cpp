@@ -390,4 +390,69 @@ int lrf_pack_unpack_qmf_factors(const uint8_t* const* factor_blobs, const int64_
     return status.load();
 }
 
+/* The same for streams that differ in (M, R): every stream's factors into one flat U and one flat V, at the offsets the caller
+ * names (the layout lrf_qmf_decode_ragged_rgb_u8 reads). */
+int lrf_pack_unpack_qmf_factors_ragged(const uint8_t* const* factor_blobs, const int64_t* blob_len, int64_t n, const int64_t* M /* [n][3] */,
+                                       const int* R /* [n][3] */, const int64_t* u_off, const int64_t* v_off, int threads, int8_t* U,
+                                       int64_t u_len, int8_t* V, int64_t v_len)
+{
+    if (!factor_blobs || !blob_len || !M || !R || !u_off || !v_off || !U || !V || n < 1 || u_len < 1 || v_len < 1) return -1;
+    struct Item {
+        Span z;
+        int8_t* dst; // first element of the column in the row-major destination
+        int64_t rows;
+        int cols;
+    };
+    std::vector<Item> items;
+    std::vector<Span> mats, parts, fibers;
+    for (int64_t b = 0; b < n; b++) {
+        const int64_t* Mb = M + 3 * b;
+        const int* Rb = R + 3 * b;
+        int64_t usz = 0, vsz = 0;
+        for (int c = 0; c < 3; c++) {
+            // (each stream's share is bounded by the buffer before it is added up: M R <= u_len keeps the sums far from wrapping)
+            if (Mb[c] < 1 || Rb[c] < 1 || Mb[c] > u_len / Rb[c] || 64 * (int64_t)Rb[c] > v_len) return -1;
+            usz += Mb[c] * Rb[c];
+            vsz += 64 * (int64_t)Rb[c];
+        }
+        if (u_off[b] < 0 || v_off[b] < 0 || usz > u_len || u_off[b] > u_len - usz || vsz > v_len || v_off[b] > v_len - vsz) return -1;
+        if (!factor_blobs[b] || blob_len[b] < 0) return -1;
+        if (!separate(Span{factor_blobs[b], (size_t)blob_len[b]}, 6, mats)) return -6;
+        int8_t* u = U + u_off[b];
+        int8_t* v = V + v_off[b];
+        for (int c = 0; c < 3; c++) {
+            for (int f = 0; f < 2; f++) {
+                const int64_t rows = f ? 64 : Mb[c];
+                int8_t* dst = f ? v : u;
+                if (!separate(mats[(size_t)(2 * c + f)], 2, parts) || !header_is(parts[0], Rb[c])) return -6;
+                if (!separate(parts[1], Rb[c], fibers)) return -6;
+                for (int r = 0; r < Rb[c]; r++) items.push_back(Item{fibers[(size_t)r], dst + r, rows, Rb[c]});
+            }
+            u += Mb[c] * Rb[c];
+            v += 64 * Rb[c];
+        }
+    }
+    std::atomic<int64_t> next(0);
+    std::atomic<int> status(0);
+    const int64_t nitems = (int64_t)items.size();
+    auto work = [&]() {
+        std::vector<unsigned char> col;
+        for (;;) {
+            const int64_t it = next.fetch_add(1);
+            if (it >= nitems || status.load() != 0) return;
+            const Item& w = items[(size_t)it];
+            col.resize((size_t)w.rows);
+            uLongf got = (uLongf)w.rows;
+            if (uncompress(col.data(), &got, w.z.p, (uLong)w.z.n) != Z_OK || (int64_t)got != w.rows) { status.store(-6); return; }
+            for (int64_t i = 0; i < w.rows; i++) w.dst[i * w.cols] = (int8_t)col[(size_t)i];
+        }
+    };
+    unsigned hw = std::thread::hardware_concurrency();
+    int nt = threads > 0 ? threads : (int)(hw ? (hw > 64 ? 64 : hw) : 1);
+    if (nt > nitems) nt = (int)nitems;
+    if (nt > 1) worker_pool().run(nt - 1, work);
+    else work();
+    return status.load();
+}
+
 } // extern "C"

@@ -238,3 +238,50 @@ long plan_any_init_chunk(int n, int Rc, long B)
     if (chunk < 1) chunk = 1;
     return chunk > B ? B : chunk;
 }
+
+// ---- the launches of a ragged decode -----------------------------------------------------------------------------------------
+// All DEC_TILE16 images share one launch (the 16-aligned body under a class switch keeps the registers of its largest class);
+// the strip body does not (204 registers under a switch), so DEC_STRIP images take one launch per class present; DEC_R8 and
+// DEC_ANY one each.  A workgroup finds its work through blocks[blockIdx.x].
+RaggedPlan plan_decode_ragged(const std::vector<RaggedWork>& images)
+{
+    RaggedPlan p;
+    const int nslots = 3 + LRF_DEC_CLASSES;
+    auto slot_of = [](const RaggedWork& w) { return w.kind == DEC_TILE16 ? 0 : (w.kind == DEC_STRIP ? 1 + w.cls : (w.kind == DEC_R8 ? 1 + LRF_DEC_CLASSES : 2 + LRF_DEC_CLASSES)); };
+    long quads8 = 0; // DEC_R8: groups of 256 pixel quads of the whole launch
+    for (const RaggedWork& w : images)
+        if (w.kind == DEC_R8) quads8 += (w.units + 255) / 256;
+    const long reps = decode8_reps_of(quads8);
+    auto blocks_of = [&](const RaggedWork& w) {
+        if (w.kind == DEC_R8) return (w.units + 256 * reps - 1) / (256 * reps);
+        if (w.kind == DEC_ANY) return (w.units + 255) / 256;
+        return w.units;
+    };
+    std::vector<long> count((size_t)nslots, 0);
+    for (const RaggedWork& w : images) count[(size_t)slot_of(w)] += blocks_of(w);
+    long total = 0;
+    for (int s = 0; s < nslots; s++) {
+        if (count[(size_t)s] >= (1L << 31)) {
+            p.too_many = count[(size_t)s];
+            return p;
+        }
+        total += count[(size_t)s];
+    }
+    p.blocks.reserve((size_t)total);
+    for (int s = 0; s < nslots; s++) {
+        if (!count[(size_t)s]) continue;
+        RaggedLaunch l;
+        l.kind = s == 0 ? DEC_TILE16 : (s <= LRF_DEC_CLASSES ? DEC_STRIP : (s == 1 + LRF_DEC_CLASSES ? DEC_R8 : DEC_ANY));
+        l.cls = l.kind == DEC_TILE16 ? -1 : (l.kind == DEC_STRIP ? s - 1 : 0);
+        l.block0 = (long)p.blocks.size();
+        l.nblocks = count[(size_t)s];
+        l.reps = l.kind == DEC_R8 ? (int)reps : 1;
+        for (size_t i = 0; i < images.size(); i++) {
+            if (slot_of(images[i]) != s) continue;
+            const long nb = blocks_of(images[i]);
+            for (long t = 0; t < nb; t++) p.blocks.push_back(RaggedBlock{(int)i, (int)t});
+        }
+        p.launches.push_back(l);
+    }
+    return p;
+}

@@ -76,6 +76,35 @@ bool plan_splits(long nblocks, int rmax_t, const PlanSettings& s);
 // reads R, nblk, native_t2_u and init_src of the planes.  sweep: lrf_qmf_encode_sweep_rgb_u8's table
 BcdPlan plan_bcd(const std::vector<PlaneDesc>& planes, int K, int lo, int hi, int first_mode, const PlanSettings& s, bool sweep = false);
 
+// ---- decode: which body serves an image, and the launches of a ragged call (lrf_qmf_decode_ragged_rgb_u8) ------------------
+enum { DEC_TILE16 = 0, DEC_STRIP = 1, DEC_R8 = 2, DEC_ANY = 3 }; // decode_plan (lrf_encode8.hip) decides
+#define LRF_DEC_CLASSES 5 // rank-bound classes of the tiled bodies
+// groups of four pixels per thread of k_decode8 / k_sse8 for a launch of `groups256` groups of 256 pixel quads: as many as leave
+// it ~2048 workgroups (small launches keep one group per thread)
+inline long decode8_reps_of(long groups256)
+{
+    const long reps = groups256 / 2048;
+    return reps < 1 ? 1 : (reps > 16 ? 16 : reps);
+}
+// One image of a ragged call as decode_plan classified it.  units: its tiles (DEC_TILE16, DEC_STRIP) or its pixel quads
+// H ceil(W / 4) (DEC_R8, DEC_ANY)
+struct RaggedWork {
+    int kind, cls;
+    long units;
+};
+struct RaggedLaunch {
+    int kind;
+    int cls;              // DEC_STRIP: the launch's class; DEC_TILE16: -1 (the kernel switches on the image's class); else 0
+    long block0, nblocks; // its workgroups: entries block0 .. block0 + nblocks - 1 of the block table
+    int reps;             // DEC_R8: pixel quads per thread (decode8_reps_of the launch's total), else 1
+};
+struct RaggedPlan {
+    std::vector<RaggedLaunch> launches; // order: DEC_TILE16, DEC_STRIP by class, DEC_R8, DEC_ANY; at most 3 + LRF_DEC_CLASSES
+    std::vector<RaggedBlock> blocks;    // per launch the images in call order, an image's tiles ascending
+    long too_many = 0;                  // != 0: a launch would have this many (>= 2^31) workgroups; no table is built
+};
+RaggedPlan plan_decode_ragged(const std::vector<RaggedWork>& images);
+
 // ---- the any-shape path (lrf_anyshape_host.inc executes these; tests/test_any_plan.py reads them on the CPU) ----------------
 #define LRF_ANY_GS_MAX_LDS (160 * 1024) // dynamic LDS of k_any_gs<float, .>
 #define LRF_ANY_NATIVE_BELOW 400        // products of fewer multiply-adds take ATen's small-product order
