@@ -251,6 +251,38 @@ typedef struct {
 int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_image* images /* host */, const int8_t* U, int64_t u_len,
                                  const int8_t* V, int64_t v_len, uint8_t* rgb, int64_t rgb_len);
 
+/*
+ * The fused encode (lrf/compression/qmf.py:227-262) for a list of n images that differ in size and in ranks, in one call: what a
+ * dataset of mixed sizes or a per-image quality choice hands to an encoder.
+ *   images  [n] descriptors in host memory
+ *   rgb     device buffer of rgb_len bytes; image i is read as [3][H][W] at rgb_off
+ *   sign    optional device buffer of sign_len int8; image i's R[0]+R[1]+R[2] signs (as lrf_qmf_encode_rgb_u8's) start at
+ *           sign_off; a sign_off of -1, or a NULL sign, gives the image the default signs
+ *   U, V    device buffers of u_len / v_len int8 elements; image i's factors are written at u_off / v_off, laid out as
+ *           lrf_qmf_encode_rgb_u8 writes ONE image: [M_Y,R_Y] [M_Cb,R_Cb] [M_Cr,R_Cr], and three [64,R_c]
+ * Image i's U / V bytes are exactly those lrf_qmf_encode_rgb_u8 writes when called for that image alone (B = 1) with the same
+ * R, K, lo, hi and signs: the planes kernels run the same device functions, every BCD kernel family computes the same bits, the
+ * Gram matrix is exact.  They do not depend on the image's place in the list or on the other images.
+ * Launches of the planes stage: the images whose sides are multiples of 16 (with rgb + rgb_off a multiple of 8) share one, the
+ * others take one per pooling-window size (2 or 3 by the parity of H and of W): at most five, timed under LRF_K_PLANES.  From
+ * there on the call is one table of 3 n matrices — large launches per rank family, the persistent kernel from its usual block
+ * counts — whatever the sizes.  Asynchronous on the context's stream, except that the first call of a new list uploads its
+ * tables and waits for the stream; lrf_ctx_trim releases them.
+ * Everything is validated on the host before any launch or write.  LRF_EINVAL: a NULL pointer, n outside [1,65535], a size or
+ * rank or bounds lrf_qmf_encode_rgb_u8 refuses with it, a negative offset, an image whose pixels, signs or factors leave their
+ * buffer, factor ranges of two images that overlap.  LRF_ENOTSUP: a rank above 32 (encode those images with
+ * lrf_qmf_encode_rgb_u8), an image of 2^31 / 3 pixels or more, 2^31 or more blocks in the call.
+ */
+typedef struct {
+    int64_t H, W;                   /* image size */
+    int R[3];                       /* ranks Y, Cb, Cr, each 1..32 */
+    int64_t rgb_off;                /* bytes from rgb to this image's [3][H][W] input */
+    int64_t u_off, v_off, sign_off; /* int8 elements from U / V / sign to this image's factors / signs; sign_off -1: default signs */
+} lrf_ragged_encode_image;
+int lrf_qmf_encode_ragged_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_encode_image* images /* host */, const uint8_t* rgb, int64_t rgb_len,
+                                 int K, int lo, int hi, const int8_t* sign /* optional, flat */, int64_t sign_len, int8_t* U, int64_t u_len,
+                                 int8_t* V, int64_t v_len);
+
 /* ---- scoring (the third stage of the reference's experiment loop) ----------------------------- */
 
 /*

@@ -36,6 +36,11 @@ class RaggedImage(ctypes.Structure):
     _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int * 3), ("u_off", c_i64), ("v_off", c_i64), ("rgb_off", c_i64)]
 
 
+class RaggedEncodeImage(ctypes.Structure):
+    """lrf_ragged_encode_image (include/lrf_hip.h)"""
+    _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int * 3), ("rgb_off", c_i64), ("u_off", c_i64), ("v_off", c_i64), ("sign_off", c_i64)]
+
+
 def load():
     """Loads liblrf_hip.so; raises ImportError when it has not been built (see __graft_entry__.build)."""
     global _lib
@@ -82,6 +87,8 @@ def load():
         lib.lrf_qmf_decode_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, ctypes.POINTER(c_int),
                                               c_void_p]
         lib.lrf_qmf_decode_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_encode_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedEncodeImage), c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64,
+                                                     c_void_p, c_i64, c_void_p, c_i64]
         lib.lrf_image_metrics_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
         lib.lrf_qmf_sweep_sse_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int), c_void_p]
         lib.lrf_svd_encode_rgb_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -127,7 +134,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -264,6 +271,40 @@ def check_ragged_args(U, V, images):
             raise ValueError(f"image {i}: its factors (U {nu} elements at {u_off}, V {nv} at {v_off}) leave the buffers of "
                              f"{U.numel()} and {V.numel()} elements")
         out.append((H, W, ranks, u_off, v_off))
+    return out
+
+
+def check_encode_ragged_args(rgb, images, sign=None):
+    """The argument checks of lrf_qmf_encode_ragged_rgb_u8 on its tensors, before any device is touched.  rgb: a flat uint8 tensor;
+    images: 1 to 65535 tuples (H, W, ranks, rgb_off[, sign_off]) with every rank in 1..32 and every image's bytes inside rgb (the
+    kernels index them from the tuple alone); sign: None or a flat int8 tensor on rgb's device, an image's sign_off (-1 or absent:
+    the default signs) naming where its sum(ranks) signs start.  TypeError for tensors of another type, ValueError for everything
+    else.  -> [(H, W, [R_Y, R_Cb, R_Cr], rgb_off, sign_off)] as integers."""
+    import torch
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8:
+        raise TypeError("encode_ragged takes its pixels as a uint8 tensor")
+    if sign is not None and (not isinstance(sign, torch.Tensor) or sign.dtype != torch.int8):
+        raise TypeError("encode_ragged takes its signs as an int8 tensor")
+    if rgb.dim() != 1 or not rgb.is_contiguous() or (sign is not None and (sign.dim() != 1 or not sign.is_contiguous() or sign.device != rgb.device)):
+        raise ValueError("rgb (and sign) must be flat contiguous tensors on one device")
+    if images is None or len(images) < 1 or len(images) > 65535:
+        raise ValueError("encode_ragged needs 1 to 65535 images")
+    out = []
+    for i, im in enumerate(images):
+        if len(im) not in (4, 5) or len(im[2]) != 3:
+            raise ValueError(f"image {i}: (H, W, (R_Y, R_Cb, R_Cr), rgb_off[, sign_off]) expected")
+        H, W, ranks, rgb_off = im[:4]
+        sign_off = im[4] if len(im) == 5 and im[4] is not None else -1
+        if any(int(x) != x for x in (H, W, rgb_off, sign_off)) or any(int(r) != r for r in ranks):
+            raise ValueError(f"image {i}: integers expected")
+        H, W, rgb_off, sign_off, ranks = int(H), int(W), int(rgb_off), int(sign_off), [int(r) for r in ranks]
+        if H < 1 or W < 1 or 3 * H * W >= 2 ** 31 or min(ranks) < 1 or max(ranks) > 32:
+            raise ValueError(f"image {i}: size {H}x{W} or ranks {ranks} out of range (ranks 1..32, fewer than 2^31 / 3 pixels)")
+        if rgb_off < 0 or rgb_off + 3 * H * W > rgb.numel():
+            raise ValueError(f"image {i}: its {3 * H * W} bytes at {rgb_off} leave the buffer of {rgb.numel()} bytes")
+        if sign_off < -1 or (sign_off >= 0 and (sign is None or sign_off + sum(ranks) > sign.numel())):
+            raise ValueError(f"image {i}: its {sum(ranks)} signs at {sign_off} leave the sign buffer")
+        out.append((H, W, ranks, rgb_off, sign_off))
     return out
 
 
@@ -503,6 +544,31 @@ class Context:
         self.use_torch_stream()
         check(self._lib.lrf_qmf_decode_ragged_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(rgb), rgb.numel()))
         return [rgb[d.rgb_off:d.rgb_off + 3 * d.H * d.W].view(3, d.H, d.W) for d in desc]
+
+    def encode_ragged(self, rgb, images, K, lo, hi, sign=None):
+        """Images that differ in size and ranks in one encode (lrf_qmf_encode_ragged_rgb_u8).  rgb: a flat uint8 CUDA tensor;
+        images: [(H, W, ranks, rgb_off[, sign_off])], image i's [3,H,W] bytes at rgb[rgb_off:]; sign: None or a flat int8 CUDA
+        tensor -> (U, V, u_off, v_off): two flat int8 CUDA tensors and, per image, where its factors start in them, each image
+        in encode_rgb's layout of one image, the images back to back in call order."""
+        import torch
+        ims = check_encode_ragged_args(rgb, images, sign)
+        if not (rgb.is_cuda and rgb.device.index == self.device):
+            raise ValueError(f"encode_ragged needs its tensors on cuda:{self.device}, got {rgb.device}")
+        desc = (RaggedEncodeImage * len(ims))()
+        u_off, v_off, uo, vo = [], [], 0, 0
+        for d, (H, W, ranks, rgb_off, sign_off) in zip(desc, ims):
+            d.H, d.W, d.rgb_off, d.u_off, d.v_off, d.sign_off = H, W, rgb_off, uo, vo, sign_off
+            d.R[0], d.R[1], d.R[2] = ranks
+            u_off.append(uo)
+            v_off.append(vo)
+            uo += sum(dm[4] * r for dm, r in zip(plane_dims(H, W), ranks))
+            vo += 64 * sum(ranks)
+        U = torch.empty((uo,), dtype=torch.int8, device=rgb.device)
+        V = torch.empty((vo,), dtype=torch.int8, device=rgb.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_encode_ragged_rgb_u8(self._h, len(ims), desc, _dptr(rgb), rgb.numel(), int(K), int(lo), int(hi), _dptr(sign),
+                                                     0 if sign is None else sign.numel(), _dptr(U), uo, _dptr(V), vo))
+        return U, V, u_off, v_off
 
     def image_metrics(self, a, b, want_ssim=True):
         """uint8 CUDA tensors a, b [B,C,H,W] -> (sse int64 [B], ssim float64 [B] or None) on the device (lrf_image_metrics_u8):

@@ -304,6 +304,10 @@ def _pack_lib():
                                                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int),
                                                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
                                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
+        lib.lrf_pack_qmf_streams_ragged.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
+                                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64),
+                                                    ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64)]
         lib.lrf_pack_unpack_qmf_factors.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
                                                     ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
@@ -449,6 +453,169 @@ def qmf_encode_batch(images: torch.Tensor, rank=None, quality=None, bounds=(-16,
     if workers <= 1 or images.shape[0] == 1:
         return [pack(b) for b in range(images.shape[0])]
     return list(_pack_pool(workers).map(pack, range(images.shape[0])))
+
+
+def _stream_metadata(image_hw, ranks, bounds, patch_size=(8, 8), dtype_name="uint8") -> bytes:
+    """the metadata block pack_image writes for one image of the default branch"""
+    dims = _lib.plane_dims(*image_hw)
+    return dict_to_bytes({
+        "dtype": dtype_name, "color space": "YCbCr", "patch": True, "bounds": bounds, "patch size": patch_size,
+        "original size": [[d[0], d[1]] for d in dims], "padded size": [[d[2], d[3]] for d in dims], "rank": list(ranks)})
+
+
+def pack_streams_ragged_native(Uh: np.ndarray, Vh: np.ndarray, sizes, triples, u_off, v_off, bounds, threads: int = 0):
+    """lrf_pack_qmf_streams_ragged: flat int8 U / V holding n images of sizes[i] = (H, W) and ranks triples[i] at u_off[i] /
+    v_off[i] -> (n byte streams, each byte-identical to pack_image of that image, 0), or (None, rc) when the library refuses the
+    layout.  Raises OSError where liblrf_pack.so cannot be used."""
+    import ctypes
+    lib = _pack_lib()
+    n = len(sizes)
+    Uh = np.ascontiguousarray(Uh, dtype=np.int8).reshape(-1)
+    Vh = np.ascontiguousarray(Vh, dtype=np.int8).reshape(-1)
+    metas = [_stream_metadata(hw, t, bounds) for hw, t in zip(sizes, triples)]
+    out = (ctypes.c_void_p * max(n, 1))()
+    lens = (ctypes.c_int64 * max(n, 1))()
+    rc = lib.lrf_pack_qmf_streams_ragged(
+        Uh.ctypes.data_as(ctypes.c_void_p), Uh.size, Vh.ctypes.data_as(ctypes.c_void_p), Vh.size, n,
+        (ctypes.c_int64 * max(3 * n, 1))(*[int(d[4]) for hw in sizes for d in _lib.plane_dims(*hw)]),
+        (ctypes.c_int * max(3 * n, 1))(*[int(r) for t in triples for r in t]), (ctypes.c_int64 * max(n, 1))(*[int(x) for x in u_off]),
+        (ctypes.c_int64 * max(n, 1))(*[int(x) for x in v_off]), (ctypes.c_char_p * max(n, 1))(*metas),
+        (ctypes.c_int64 * max(n, 1))(*[len(m) for m in metas]), int(threads), out, lens)
+    if rc:
+        return None, rc
+    streams = []
+    for b in range(n):
+        streams.append(ctypes.string_at(out[b], lens[b]))
+        lib.lrf_pack_free(out[b])
+    return streams, 0
+
+
+def _per_image(value, n, name, one):
+    """`value` as a list of n entries: `one(value)` says whether it is a single entry meant for every image"""
+    if value is None or one(value):
+        return [value] * n
+    value = list(value)
+    if len(value) != n:
+        raise ValueError(f"qmf_encode_ragged: '{name}' must be one value or one per image ({n}), got {len(value)} entries")
+    return value
+
+
+def _check_encode_ragged_args(images, rank, quality, ranks, num_iters, init_sign):
+    """qmf_encode_ragged's refusals, raised before a GPU is asked for -> ([(H, W)], [rank triple per image], [sign per image: None or int8 array])"""
+    if isinstance(images, torch.Tensor) and images.dim() != 4:
+        raise ValueError(f"qmf_encode_ragged takes a sequence of [3,H,W] images, got a tensor of shape {tuple(images.shape)}")
+    if isinstance(images, (bytes, str)) or len(images) < 1:
+        raise ValueError("qmf_encode_ragged takes a non-empty sequence of images")
+    n = len(images)
+    for i, im in enumerate(images):
+        if not isinstance(im, torch.Tensor):
+            raise TypeError(f"qmf_encode_ragged: image {i} is {type(im).__name__}, not a tensor")
+        if im.dtype != torch.uint8:
+            raise NotImplementedError(f"qmf_encode_ragged: image {i} is {im.dtype}; the HIP path takes uint8 images")
+        if im.dim() != 3 or im.shape[0] != 3 or im.shape[1] < 1 or im.shape[2] < 1:
+            raise ValueError(f"qmf_encode_ragged: image {i} must be [3,H,W], got {tuple(im.shape)}")
+    if num_iters < 1:
+        raise NotImplementedError("qmf_encode_ragged: num_iters = 0 (the truncated initialisation) is outside the fused encoder (qmf_encode takes it)")
+    if sum(x is not None for x in (rank, quality, ranks)) != 1:
+        raise ValueError("qmf_encode_ragged: give exactly one of 'rank', 'quality' and 'ranks'")
+    scalar = lambda v: not isinstance(v, Iterable)
+    triple = lambda v: len(v) == 3 and all(scalar(x) for x in v)
+    rank_l = _per_image(rank, n, "rank", scalar)
+    quality_l = _per_image(quality, n, "quality", scalar)
+    ranks_l = _per_image(None if ranks is None else list(ranks), n, "ranks", triple)
+    sizes = [(int(im.shape[1]), int(im.shape[2])) for im in images]
+    triples = []
+    for i, hw in enumerate(sizes):
+        r = rank_l[i] if ranks_l[i] is None else list(ranks_l[i])
+        if r is None and quality_l[i] is None:
+            raise ValueError(f"qmf_encode_ragged: image {i} has neither a rank nor a quality")
+        if isinstance(r, list) and len(r) != 3:
+            raise ValueError(f"qmf_encode_ragged: image {i}: a rank triple has three entries, got {len(r)}")
+        t = [int(x) for x in qmf_ranks(hw, r, quality_l[i])]
+        if min(t) < 1:
+            raise ValueError(f"qmf_encode_ragged: image {i}: ranks {t} must be >= 1")
+        triples.append(t)
+    one_sign = lambda v: isinstance(v, (np.ndarray, torch.Tensor)) or (len(v) > 0 and all(x is not None and scalar(x) for x in v))
+    signs = []
+    for i, sg in enumerate(_per_image(init_sign, n, "init_sign", one_sign)):
+        if sg is not None:
+            sg = np.ascontiguousarray(torch.as_tensor(sg, dtype=torch.int8).reshape(-1).numpy())
+            if sg.size != sum(triples[i]):
+                raise ValueError(f"qmf_encode_ragged: image {i}: init_sign holds {sg.size} signs, its ranks {triples[i]} need {sum(triples[i])}")
+        signs.append(sg)
+    return sizes, triples, signs
+
+
+def qmf_encode_ragged(images, rank=None, quality=None, ranks=None, bounds=(-16, 15), num_iters: int = 10, init_sign=None,
+                      pack_workers: Optional[int] = None) -> list:
+    """qmf_encode of a list of uint8 images [3,H_i,W_i] (host or device) that differ in size and in ranks, in one GPU call
+    (lrf_qmf_encode_ragged_rgb_u8) -> one byte stream per image, stream i byte-identical to
+    qmf_encode_batch(images[i][None], ...)[0] with that image's parameters.  Default branch only (YCbCr, 8x8 patches, uint8,
+    num_iters >= 1).
+
+    rank (an integer: (r, r // 2, r // 2) as in qmf_encode), quality, ranks (a (Y, Cb, Cr) triple) and init_sign (sum(ranks)
+    signs) are each one value for all images or one entry per image; every entry goes through qmf_ranks((H_i, W_i), ...).
+
+    Host images are gathered in one page-locked buffer, each at a multiple of 16 bytes (so that images whose sides are multiples
+    of 16 keep the planes kernel made for them), and go up in one copy; then one C call, one copy of all factors back and one
+    call of the native packer over all columns of all images.  Images whose triple has a rank above 32 are encoded one by one
+    through qmf_encode_batch and put back in place.  For a list of equal sizes and ranks qmf_encode_batch is the call to use."""
+    sizes, triples, signs = _check_encode_ragged_args(images, rank, quality, ranks, num_iters, init_sign)
+    n = len(sizes)
+    streams = [None] * n
+    fused = [i for i in range(n) if max(triples[i]) <= 32]
+    for i in range(n):
+        if i not in fused:
+            streams[i] = qmf_encode_batch(images[i][None], rank=list(triples[i]), bounds=bounds, num_iters=num_iters, init_sign=signs[i],
+                                          pack_workers=pack_workers)[0]
+    if not fused:
+        return streams
+    on_dev = [images[i] for i in fused if images[i].is_cuda]
+    ctx = _lib.context(on_dev[0].device.index if on_dev else None)
+    dev = torch.device("cuda", ctx.device)
+    offs, off = [], 0
+    for i in fused:
+        offs.append(off)
+        off = (off + 3 * sizes[i][0] * sizes[i][1] + 15) // 16 * 16
+    if on_dev:  # pixels already in HBM: gathered there
+        flat = torch.empty((off,), dtype=torch.uint8, device=dev)
+        for i, o in zip(fused, offs):
+            flat[o:o + images[i].numel()].view(images[i].shape).copy_(images[i])
+    else:
+        stage = torch.empty((off,), dtype=torch.uint8).pin_memory()
+        for i, o in zip(fused, offs):
+            stage[o:o + images[i].numel()].view(images[i].shape).copy_(images[i])
+        flat = stage.to(dev, non_blocking=True)
+    sign, sign_offs = None, [-1] * len(fused)
+    if any(signs[i] is not None for i in fused):
+        so = 0
+        for k, i in enumerate(fused):
+            if signs[i] is not None:
+                sign_offs[k] = so
+                so += signs[i].size
+        sign = torch.from_numpy(np.concatenate([signs[i] for i in fused if signs[i] is not None])).to(dev)
+    lo, hi = math.ceil(bounds[0]), math.floor(bounds[1])
+    U, V, u_off, v_off = ctx.encode_ragged(flat, [(sizes[i][0], sizes[i][1], triples[i], o, s) for i, o, s in zip(fused, offs, sign_offs)],
+                                           num_iters, lo, hi, sign)
+    Uh, Vh = (t.numpy() for t in ctx.to_host(U, V))  # waits for the stream, then raises if a launch of this call gave up
+    packed = None
+    if pack_workers != "python" and not (isinstance(pack_workers, int) and pack_workers < 0):
+        try:
+            packed, rc = pack_streams_ragged_native(Uh, Vh, [sizes[i] for i in fused], [triples[i] for i in fused], u_off, v_off, bounds,
+                                                    threads=pack_workers or default_pack_threads())
+            if rc:
+                raise RuntimeError(f"lrf_pack_qmf_streams_ragged failed ({rc})")
+        except OSError:  # liblrf_pack.so missing or linked against another zlib: the Python container code, same bytes
+            packed = None
+    if packed is None:
+        packed = []
+        for k, i in enumerate(fused):
+            nu, nv = sum(d[4] * r for d, r in zip(_lib.plane_dims(*sizes[i]), triples[i])), 64 * sum(triples[i])
+            packed.append(pack_image(split_factors(Uh[u_off[k]:u_off[k] + nu], Vh[v_off[k]:v_off[k] + nv], sizes[i], triples[i]), sizes[i],
+                                     triples[i], bounds, (8, 8), "uint8"))
+    for i, s_ in zip(fused, packed):
+        streams[i] = s_
+    return streams
 
 
 def qmf_encode(image: torch.Tensor, rank=None, quality=None, color_space: str = "YCbCr",

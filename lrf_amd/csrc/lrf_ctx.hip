@@ -69,42 +69,14 @@ void fold_events(lrf_ctx* c)
 }
 
 // ---- geometry ---------------------------------------------------------------------------------
-void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M)
-{
-    // F.interpolate(scale_factor=0.5): output size = floor(input * 0.5) (lrf/compression/qmf.py:230)
-    int64_t ph = c ? (int64_t)floor((double)H * 0.5) : H, pw = c ? (int64_t)floor((double)W * 0.5) : W;
-    *h = ph;
-    *w = pw;
-    *hp = ph + (8 - ph % 8) % 8;
-    *wp = pw + (8 - pw % 8) % 8;
-    *M = (*hp / 8) * (*wp / 8);
-}
-
+// (plane_dims, geom_of: lrf_plan.cpp)
 int make_geom(int64_t H, int64_t W, ImageGeom* g)
 {
-    long xoff = 0;
-    for (int c = 0; c < 3; c++) {
-        int64_t h, w, hp, wp, M;
-        plane_dims(H, W, c, &h, &w, &hp, &wp, &M);
-        if (h < 1 || w < 1) return set_err(LRF_EINVAL, "image %ldx%ld too small", (long)H, (long)W);
-        // reflect padding needs pad < size (torch raises otherwise)
-        if ((hp - h) / 2 >= h || (hp - h) - (hp - h) / 2 >= h || (wp - w) / 2 >= w || (wp - w) - (wp - w) / 2 >= w)
-            return set_err(LRF_EINVAL, "reflect padding larger than the plane (%ldx%ld)", (long)h, (long)w);
-        PlaneGeom& p = g->p[c];
-        p.h = (int)h; p.w = (int)w; p.hp = (int)hp; p.wp = (int)wp;
-        p.top = (int)((hp - h) / 2); p.left = (int)((wp - w) / 2);
-        p.top_crop = p.top; p.left_crop = p.left;
-        p.nw = (int)(wp / 8);
-        p.nh = (int)(hp / 8);
-        p.pr0 = c ? g->p[c - 1].pr0 + g->p[c - 1].nh : 0;
-        p.M = (int)M;
-        p.xoff = xoff;
-        p.o4 = xoff / 4;
-        xoff += M * 64;
-    }
-    g->img_floats = xoff;
-    g->tot4 = xoff / 4;
-    return LRF_OK;
+    int64_t h, w;
+    const int bad = geom_of(H, W, g, &h, &w);
+    if (bad == 0) return LRF_OK;
+    if (bad < 10) return set_err(LRF_EINVAL, "image %ldx%ld too small", (long)H, (long)W);
+    return set_err(LRF_EINVAL, "reflect padding larger than the plane (%ldx%ld)", (long)h, (long)w);
 }
 
 // ---- descriptor tables (add_plane: lrf_plan.cpp) ------------------------------------------------
@@ -320,7 +292,7 @@ void lrf_ctx_destroy(lrf_ctx* c)
     DevBuf* bufs[] = {&c->gchunks, &c->gpart, &c->gexp, &c->planes, &c->blocks, &c->vf, &c->wf, &c->bf, &c->ppart, &c->qpart, &c->x, &c->sign,
                       &c->sx, &c->sg, &c->svn, &c->swn, &c->suf, &c->smm,
                       &c->any_uf, &c->any_vf, &c->any_a, &c->any_b, &c->any_p, &c->any_e2, &c->any_g, &c->any_td,
-                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab};
+                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& a : c->talt) {
@@ -382,7 +354,7 @@ size_t lrf_ctx_workspace_bytes(const lrf_ctx* c)
     const DevBuf* bufs[] = {&c->gchunks, &c->gpart, &c->gexp, &c->planes, &c->blocks, &c->vf, &c->wf, &c->bf, &c->ppart, &c->qpart, &c->x, &c->sign,
                             &c->sx, &c->sg, &c->svn, &c->swn, &c->suf, &c->smm,
                             &c->any_uf, &c->any_vf, &c->any_a, &c->any_b, &c->any_p, &c->any_e2, &c->any_g, &c->any_td,
-                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab};
+                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab};
     size_t total = 0;
     for (const DevBuf* b : bufs) total += b->cap;
     for (const auto& a : c->talt) total += a.planes.cap + a.blocks.cap + a.gchunks.cap;
@@ -397,7 +369,7 @@ int lrf_ctx_trim(lrf_ctx* c)
     DevBuf* bufs[] = {&c->gchunks, &c->gpart, &c->gexp, &c->planes, &c->blocks, &c->vf,
                       &c->wf, &c->bf, &c->ppart, &c->qpart, &c->x, &c->sign, &c->sx, &c->sg, &c->svn, &c->swn, &c->suf, &c->smm,
                       &c->any_uf, &c->any_vf, &c->any_a, &c->any_b, &c->any_p, &c->any_e2, &c->any_g, &c->any_td,
-                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab};
+                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab};
     for (DevBuf* b : bufs) {
         if (b->p) HIP_TRY(hipFree(b->p));
         b->p = nullptr;

@@ -8,6 +8,7 @@
 #include "lrf_bcdw16_kernel.hip"
 #include "lrf_sweep_sse_kernel.hip"
 #include "lrf_decode_ragged_kernel.hip"
+#include "lrf_planes_ragged_kernel.hip"
 
 // gram_exp: the fixed-point grid exponent of the exact Gram matrix (max|x| < 2^gram_exp) when the caller knows it — 8 for the
 // planes of qmf_encode — or LRF_GRAM_EXP_FROM_DATA: one more pass over X finds it per matrix
@@ -512,6 +513,102 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64
     if ((rc = fuse ? planes_gram_from_rgb(c, rgb, H, W, g, t, X) : lrf_qmf_planes_from_rgb_u8(c, rgb, B, H, W, X))) return rc;
     if (c->planes_done) HIP_TRY(hipEventRecord(c->planes_done, c->stream));
     return init_then_bcd(c, X, t, plan, sign, LRF_PLANES_GRAM_EXP, U, V);
+}
+
+// A list of images that differ in size and ranks in one encode (planes kernels: lrf_planes_ragged_kernel.hip; the tables:
+// plan_encode_ragged).  Behind the planes stage the call is its plane table: Gram pass, initialisation and iterations read
+// PlaneDesc / BlockDesc as in every other call, chosen by the same plan_bcd.  Everything the kernels index with is checked here,
+// before anything is launched or written.
+int lrf_qmf_encode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_encode_image* images, const uint8_t* rgb, int64_t rgb_len, int K, int lo,
+                                 int hi, const int8_t* sign, int64_t sign_len, int8_t* U, int64_t u_len, int8_t* V, int64_t v_len)
+{
+    if (!c || !images || !rgb || !U || !V) return set_err(LRF_EINVAL, "NULL argument");
+    if (n < 1 || n > 65535) return set_err(LRF_EINVAL, "n=%ld out of range [1,65535]", (long)n);
+    if (rgb_len < 1 || u_len < 1 || v_len < 1 || (sign && sign_len < 1)) return set_err(LRF_EINVAL, "a buffer length below 1");
+    if (sign && sign_len > INT32_MAX) return set_err(LRF_ENOTSUP, "sign_len=%ld: sign offsets are 32-bit", (long)sign_len);
+    std::vector<EncRaggedImage> ims((size_t)n);
+    struct Range { long off, len; };
+    std::vector<Range> ur((size_t)n), vr((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_ragged_encode_image& im = images[i];
+        if (im.H < 1 || im.W < 1 || im.H > INT32_MAX || im.W > INT32_MAX) return set_err(LRF_EINVAL, "image %ld: size %ldx%ld out of range", (long)i, (long)im.H, (long)im.W);
+        ImageGeom g;
+        int rc = make_geom(im.H, im.W, &g);
+        if (rc) return rc;
+        for (int ch = 0; ch < 3; ch++)
+            if ((rc = check_params(g.p[ch].M, 64, im.R[ch], K, lo, hi))) return rc;
+        for (int ch = 0; ch < 3; ch++)
+            if (im.R[ch] > LRF_BIG_TO_ANY_RANK)
+                return set_err(LRF_ENOTSUP, "image %ld: rank %d > %d (ranks above it iterate on the any-shape kernels: lrf_qmf_encode_rgb_u8 per image)", (long)i, im.R[ch], LRF_BIG_TO_ANY_RANK);
+        if (im.rgb_off < 0 || im.u_off < 0 || im.v_off < 0 || im.sign_off < -1) return set_err(LRF_EINVAL, "image %ld: negative offset", (long)i);
+        if (im.H * im.W * 3 >= (1L << 31)) return set_err(LRF_ENOTSUP, "image %ld: too large for 32-bit pixel indexing", (long)i);
+        // (every term is checked against the length before it is added to an offset: no sum can wrap)
+        const long bytes = 3 * im.H * im.W;
+        long u_img = 0, v_img = 0, s_img = 0;
+        for (int ch = 0; ch < 3; ch++) {
+            u_img += (long)g.p[ch].M * im.R[ch];
+            v_img += 64L * im.R[ch];
+            s_img += im.R[ch];
+        }
+        if (bytes > rgb_len || im.rgb_off > rgb_len - bytes) return set_err(LRF_EINVAL, "image %ld: its pixels leave the buffer of %ld bytes", (long)i, (long)rgb_len);
+        if (u_img > u_len || im.u_off > u_len - u_img) return set_err(LRF_EINVAL, "image %ld: its U factors leave the buffer of %ld elements", (long)i, (long)u_len);
+        if (v_img > v_len || im.v_off > v_len - v_img) return set_err(LRF_EINVAL, "image %ld: its V factors leave the buffer of %ld elements", (long)i, (long)v_len);
+        const bool own_sign = sign && im.sign_off >= 0;
+        if (own_sign && (s_img > sign_len || im.sign_off > sign_len - s_img)) return set_err(LRF_EINVAL, "image %ld: its signs leave the buffer of %ld elements", (long)i, (long)sign_len);
+        EncRaggedImage& e = ims[(size_t)i];
+        e.H = im.H; e.W = im.W;
+        for (int ch = 0; ch < 3; ch++) e.R[ch] = im.R[ch];
+        e.rgb_off = im.rgb_off; e.u_off = im.u_off; e.v_off = im.v_off;
+        e.sign_off = own_sign ? im.sign_off : -1;
+        e.aligned8 = ((reinterpret_cast<uintptr_t>(rgb) + (uintptr_t)im.rgb_off) & 7) == 0;
+        ur[(size_t)i] = Range{im.u_off, u_img};
+        vr[(size_t)i] = Range{im.v_off, v_img};
+    }
+    for (std::vector<Range>* r : {&ur, &vr}) { // no two images may share output bytes
+        std::sort(r->begin(), r->end(), [](const Range& a, const Range& b) { return a.off < b.off; });
+        for (size_t i = 1; i < r->size(); i++)
+            if ((*r)[i].off - (*r)[i - 1].off < (*r)[i - 1].len) return set_err(LRF_EINVAL, "the %s ranges of two images overlap (at element %ld)", r == &ur ? "U" : "V", (*r)[i].off);
+    }
+    const PlanSettings settings = plan_settings(c);
+    EncRaggedPlan plan = plan_encode_ragged(ims, settings);
+    if (plan.too_many) return set_err(LRF_ENOTSUP, "%ld blocks in one call: split the list", plan.too_many);
+    LRF_ON_DEVICE(c);
+    int rc = ensure(c, c->x, (size_t)plan.x_floats * sizeof(float));
+    if (rc) return rc;
+    const BcdPlan bcd = plan_bcd(plan.t.planes, K, lo, hi, PLAN_FIRST_W0, settings);
+    if ((rc = upload_tables(c, plan.t, bcd))) return rc;
+    // the planes table: descriptors, then workgroups (a function of the descriptors: they alone are the key)
+    const size_t db = plan.descs.size() * sizeof(EncRaggedDesc), bb = plan.blocks.size() * sizeof(RaggedBlock);
+    if (c->enc_ragged_key.size() != db || memcmp(c->enc_ragged_key.data(), plan.descs.data(), db) != 0 || !c->enc_ragged_tab.p) {
+        c->enc_ragged_key.clear();
+        std::vector<char> tab(db + bb);
+        memcpy(tab.data(), plan.descs.data(), db);
+        memcpy(tab.data() + db, plan.blocks.data(), bb);
+        if ((rc = upload(c, c->enc_ragged_tab, tab.data(), tab.size()))) return rc;
+        c->enc_ragged_key.assign((const char*)plan.descs.data(), (const char*)plan.descs.data() + db);
+    }
+    const EncRaggedDesc* d_desc = (const EncRaggedDesc*)c->enc_ragged_tab.p;
+    const RaggedBlock* d_blk = (const RaggedBlock*)((const char*)c->enc_ragged_tab.p + db);
+    float* X = (float*)c->x.p;
+    {
+        Prof p(c, LRF_K_PLANES);
+        for (const EncRaggedLaunch& l : plan.launches) {
+            const RaggedBlock* bl = d_blk + l.block0;
+#define LRF_RAGGED_STRIP(KH, KW) \
+    hipLaunchKernelGGL((k_planes_strip_ragged<KH, KW>), dim3((unsigned)(8 * l.xcd_chunk)), dim3(256), 0, c->stream, rgb, X, d_desc, bl, (int)l.nblocks, l.xcd_chunk)
+            switch (l.body) {
+            case ENC_TILE16: hipLaunchKernelGGL(k_planes16_ragged, dim3((unsigned)l.nblocks), dim3(256), 0, c->stream, rgb, X, d_desc, bl); break;
+            case ENC_STRIP22: LRF_RAGGED_STRIP(2, 2); break;
+            case ENC_STRIP23: LRF_RAGGED_STRIP(2, 3); break;
+            case ENC_STRIP32: LRF_RAGGED_STRIP(3, 2); break;
+            default: LRF_RAGGED_STRIP(3, 3); break;
+            }
+#undef LRF_RAGGED_STRIP
+            LAUNCH_CHECK();
+        }
+    }
+    if (c->planes_done) HIP_TRY(hipEventRecord(c->planes_done, c->stream)); // the RGB bytes are not read again
+    return init_then_bcd(c, X, plan.t, bcd, sign, LRF_PLANES_GRAM_EXP, U, V);
 }
 
 // which decode body serves a geometry and a rank triple (lrf_qmf_decode_rgb_u8, lrf_qmf_decode_ragged_rgb_u8 and

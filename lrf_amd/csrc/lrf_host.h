@@ -79,6 +79,8 @@ struct lrf_ctx {
     std::vector<char> sse_key; // ... and the bytes now resident there (calls that repeat a sweep skip the synchronising upload)
     DevBuf ragged_tab; // lrf_qmf_decode_ragged_rgb_u8: the image descriptors (RaggedDesc), behind them the block table ...
     std::vector<char> ragged_key; // ... and the descriptor bytes now resident there
+    DevBuf enc_ragged_tab; // lrf_qmf_encode_ragged_rgb_u8: the image descriptors (EncRaggedDesc), behind them the workgroup table ...
+    std::vector<char> enc_ragged_key; // ... and the descriptor bytes now resident there
     DevBuf vf16, wf16, bf16, pp16, qp16; // the pitch-16 tables of a call that mixes kernel families (BcdPlan::mixed)
     // host staging for descriptor tables (pinned)
     void* h_stage = nullptr;
@@ -156,7 +158,6 @@ struct Prof {
 #define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
 
 // ---- geometry (lrf_ctx.hip)
-void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M);
 int make_geom(int64_t H, int64_t W, ImageGeom* g);
 
 // ---- descriptor tables and the launch plan (lrf_plan.h: device-free) ----------------------------

@@ -90,6 +90,18 @@ struct RaggedBlock {
     int image, tile;
 };
 
+// ---- the ragged encode (lrf_qmf_encode_ragged_rgb_u8; kernels: lrf_planes_ragged_kernel.hip) ----
+// One image of the call, as the planes kernels read it (uniform loads, like RaggedDesc; the workgroup table is RaggedBlock's:
+// image, unit = strip * per_strip + column group)
+struct EncRaggedDesc {
+    ImageGeom g;
+    long rgb_off;      // bytes from rgb to the image's [3][H][W]
+    long x_off;        // floats from the X workspace to the image's three matrices
+    int H, W;
+    int body;          // ENC_* (lrf_plan.h): the planes body that serves it
+    int per_strip;     // workgroups per 16-row strip
+};
+
 struct GsParams {
     float lo, hi;      // clamp
     float flimit;      // |q~| >= flimit: certainly outside [lo,hi] after rounding

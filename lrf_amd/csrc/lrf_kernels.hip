@@ -133,17 +133,16 @@ __global__ __launch_bounds__(256) void k_planes(const uint8_t* __restrict__ rgb,
 // aligned rows): every RGB byte is read once.  One workgroup per 16-row strip; a thread takes a 2 x 8 pixel block
 // (six 8-byte loads) and produces its sixteen luma samples and its four Cb and four Cr samples with the arithmetic and
 // orders of k_planes (ycc_of; the window sum is row-major: (0,0), (0,1), (1,0), (1,1)).
-__global__ __launch_bounds__(256) void k_planes16(const uint8_t* __restrict__ rgb, int H, int W, ImageGeom g,
-                                                  float* __restrict__ X)
+// The work of one workgroup — unit = strip * per_strip + column group of image `img`, whose matrices start at Xi — as a device
+// function: k_planes16 runs it for (blockIdx.y, blockIdx.x), k_planes16_ragged (lrf_planes_ragged_kernel.hip) for a table entry.
+// Ls: luma staging of 2 * 32 * 64 floats, [h = patch row 0/1 of the strip][patch 0..31][16 float4], float4 slot q stored at q ^ swz(h, q)
+__device__ __forceinline__ void planes16_unit(const uint8_t* __restrict__ img, float* __restrict__ Xi, int H, int W, const ImageGeom& g, int unit,
+                                              float* __restrict__ Ls)
 {
-    // luma staging: [h = patch row 0/1 of the strip][patch 0..31][16 float4], float4 slot q stored at q ^ swz(h, q)
-    __shared__ __attribute__((aligned(16))) float Ls[2 * 32 * 64];
     const int hw = H * W, nwl = g.p[0].nw, nwc = g.p[1].nw;
     const int per_strip = (nwl + 31) / 32; // workgroups per strip: 32 luma patches (256 blocks of 2 x 8 pixels) each
-    const int strip = blockIdx.x / per_strip;
-    const int ww0 = (blockIdx.x - strip * per_strip) * 32;
-    const uint8_t* img = rgb + (long)blockIdx.y * 3 * H * W;
-    float* Xi = X + (long)blockIdx.y * g.img_floats;
+    const int strip = unit / per_strip;
+    const int ww0 = (unit - strip * per_strip) * 32;
     const int tid = threadIdx.x;
     const int wwl = tid >> 3, ww = ww0 + wwl, rp = tid & 7; // 8-pixel column block, row pair inside the strip
     if (ww < nwl) {
@@ -205,6 +204,12 @@ __global__ __launch_bounds__(256) void k_planes16(const uint8_t* __restrict__ rg
             *reinterpret_cast<f32x4*>(Xi + g.p[0].xoff + ((long)(2 * strip + h) * nwl + ww0) * 64 + rem * 4) = v;
         }
     }
+}
+__global__ __launch_bounds__(256) void k_planes16(const uint8_t* __restrict__ rgb, int H, int W, ImageGeom g,
+                                                  float* __restrict__ X)
+{
+    __shared__ __attribute__((aligned(16))) float Ls[2 * 32 * 64];
+    planes16_unit(rgb + (long)blockIdx.y * 3 * H * W, X + (long)blockIdx.y * g.img_floats, H, W, g, (int)blockIdx.x, Ls);
 }
 
 // K1 for every other size, in one pass over the image (CLIC-sized 1365 x 2048: the odd height means 3-row pooling windows,
@@ -290,22 +295,18 @@ __device__ __forceinline__ void strip_chroma(const uint32_t (&lo)[KH][3], const 
     }
 }
 
+// one workgroup's work — bid = strip * per_strip + column group of image `img` — as a device function: k_planes_strip runs it
+// for (blockIdx.y, its XCD-dealt block), k_planes_strip_ragged (lrf_planes_ragged_kernel.hip) for a table entry.  Ls: as in planes16_unit
 template <int KH, int KW>
-__global__ __launch_bounds__(256) void k_planes_strip(const uint8_t* __restrict__ rgb, int H, int W, ImageGeom g,
-                                                      float* __restrict__ X, int per_strip, int nblk, int xcd_chunk)
+__device__ __forceinline__ void planes_strip_unit(const uint8_t* __restrict__ img, float* __restrict__ Xi, int H, int W, const ImageGeom& g, int bid,
+                                                  int per_strip, float* __restrict__ Ls)
 {
-    __shared__ __attribute__((aligned(16))) float Ls[2 * 32 * 64]; // luma staging, as in k_planes16
     typedef uint64_t __attribute__((aligned(1))) u64u;
-    // blocks are dealt to the XCDs round-robin: XCD j gets the contiguous range [j chunk, (j + 1) chunk) of (strip, column group)
-    const int bid = xcd_chunk ? (int)(blockIdx.x & 7) * xcd_chunk + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (bid >= nblk) return;
     const int hw = H * W;
     const PlaneGeom pl = g.p[0], pc = g.p[1];
     const int nwl = pl.nw, nwc = pc.nw;
     const int strip = bid / per_strip;
     const int ww0 = (bid - strip * per_strip) * 32;
-    const uint8_t* img = rgb + (long)blockIdx.y * 3 * H * W;
-    float* Xi = X + (long)blockIdx.y * g.img_floats;
     const int tid = threadIdx.x;
     const int wwl = tid >> 3, ww = ww0 + wwl, rp = tid & 7; // 8-column block of padded luma pixels, row pair inside the strip
     float* Lp = Ls + ((rp >> 2) * 32 + wwl) * 64;
@@ -502,6 +503,16 @@ __global__ __launch_bounds__(256) void k_planes_strip(const uint8_t* __restrict_
             *reinterpret_cast<f32x4*>(Xi + g.p[0].xoff + ((long)(2 * strip + h) * nwl + ww0) * 64 + rem * 4) = v;
         }
     }
+}
+template <int KH, int KW>
+__global__ __launch_bounds__(256) void k_planes_strip(const uint8_t* __restrict__ rgb, int H, int W, ImageGeom g,
+                                                      float* __restrict__ X, int per_strip, int nblk, int xcd_chunk)
+{
+    __shared__ __attribute__((aligned(16))) float Ls[2 * 32 * 64]; // luma staging, as in k_planes16
+    // blocks are dealt to the XCDs round-robin: XCD j gets the contiguous range [j chunk, (j + 1) chunk) of (strip, column group)
+    const int bid = xcd_chunk ? (int)(blockIdx.x & 7) * xcd_chunk + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    if (bid >= nblk) return;
+    planes_strip_unit<KH, KW>(rgb + (long)blockIdx.y * 3 * H * W, X + (long)blockIdx.y * g.img_floats, H, W, g, bid, per_strip, Ls);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -210,6 +210,84 @@ int lrf_pack_qmf_streams(const int8_t* U, int64_t u_stride, const int8_t* V, int
     return 0;
 }
 
+/* The same container for n images that differ in (M, R) — what lrf_qmf_encode_ragged_rgb_u8 writes — from one flat U and one flat
+ * V: all columns of all images go over the thread pool together (include/lrf_pack_ragged.h). */
+int lrf_pack_qmf_streams_ragged(const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len, int64_t n, const int64_t* M /* [n][3] */,
+                                const int* R /* [n][3] */, const int64_t* u_off, const int64_t* v_off, const char* const* metadata,
+                                const int64_t* metadata_len, int threads, uint8_t** out, int64_t* out_len)
+{
+    if (!U || !V || !M || !R || !u_off || !v_off || !metadata || !metadata_len || !out || !out_len || n < 1 || u_len < 1 || v_len < 1) return -6;
+    struct Item {
+        const int8_t* A; // the row-major matrix the column is taken from
+        int64_t rows;
+        int cols, col;
+    };
+    std::vector<Item> items;
+    std::vector<size_t> first((size_t)n + 1, 0); // image b's columns: items first[b] .. first[b + 1] - 1
+    for (int64_t b = 0; b < n; b++) {
+        const int64_t* Mb = M + 3 * b;
+        const int* Rb = R + 3 * b;
+        int64_t usz = 0, vsz = 0;
+        for (int c = 0; c < 3; c++) {
+            // (each image's share is bounded by the buffer before it is added up: M R <= u_len keeps the sums far from wrapping)
+            if (Mb[c] < 1 || Rb[c] < 1 || Mb[c] > u_len / Rb[c] || 64 * (int64_t)Rb[c] > v_len) return -6;
+            usz += Mb[c] * Rb[c];
+            vsz += 64 * (int64_t)Rb[c];
+        }
+        if (u_off[b] < 0 || v_off[b] < 0 || usz > u_len || u_off[b] > u_len - usz || vsz > v_len || v_off[b] > v_len - vsz) return -6;
+        if (!metadata[b] || metadata_len[b] < 0) return -6;
+        const int8_t* u = U + u_off[b];
+        const int8_t* v = V + v_off[b];
+        for (int c = 0; c < 3; c++) {
+            for (int r = 0; r < Rb[c]; r++) items.push_back(Item{u, Mb[c], Rb[c], r});
+            for (int r = 0; r < Rb[c]; r++) items.push_back(Item{v, 64, Rb[c], r});
+            u += Mb[c] * Rb[c];
+            v += 64 * Rb[c];
+        }
+        first[(size_t)b + 1] = items.size();
+    }
+    const int64_t nitems = (int64_t)items.size();
+    unsigned hw = std::thread::hardware_concurrency();
+    int nt = threads > 0 ? threads : (int)(hw ? (hw > 64 ? 64 : hw) : 1);
+    if (nt > nitems) nt = (int)nitems;
+    std::vector<std::string> fibers((size_t)nitems);
+    std::atomic<int64_t> next(0);
+    std::atomic<int> status(0);
+    auto work = [&]() {
+        for (;;) {
+            const int64_t it = next.fetch_add(1);
+            if (it >= nitems || status.load() != 0) return;
+            const Item& w = items[(size_t)it];
+            const int rc = compress_column(w.A, w.rows, w.cols, w.col, fibers[(size_t)it]);
+            if (rc) { status.store(rc); return; }
+        }
+    };
+    for (int64_t b = 0; b < n; b++) out[b] = nullptr;
+    if (nt > 1) worker_pool().run(nt - 1, work);
+    else work();
+    if (status.load() != 0) return status.load();
+    for (int64_t b = 0; b < n; b++) {
+        const int* Rb = R + 3 * b;
+        std::vector<std::string> enc;
+        size_t at = first[(size_t)b];
+        for (int c = 0; c < 3; c++)
+            for (int f = 0; f < 2; f++) {
+                enc.push_back(assemble_matrix(std::vector<std::string>(fibers.begin() + at, fibers.begin() + at + Rb[c])));
+                at += (size_t)Rb[c];
+            }
+        std::string stream = combine({std::string(metadata[b], (size_t)metadata_len[b]), combine(enc)});
+        uint8_t* p = (uint8_t*)malloc(stream.size() ? stream.size() : 1);
+        if (!p) {
+            for (int64_t j = 0; j < b; j++) { free(out[j]); out[j] = nullptr; }
+            return -4;
+        }
+        memcpy(p, stream.data(), stream.size());
+        out[b] = p;
+        out_len[b] = (int64_t)stream.size();
+    }
+    return 0;
+}
+
 /* The streams of the other patch sizes and of patch=False (lrf/compression/qmf.py:232-286): six factor arrays per batch,
  * F[f] = [B][rows[f]][cols[f]] int8 (u_Y, v_Y, u_Cb, v_Cb, u_Cr, v_Cr).  whole == 0: every factor as encode_matrix does
  * (per-column zlib, utils.py:354-390); whole != 0: the patch=False form — the reference keeps the plane's channel axis, so the

@@ -2,6 +2,7 @@
 // launch or a stream layout lives in plan_bcd, every bound is written once.  Host C++ only.
 #include "lrf_plan.h"
 
+#include <math.h>
 #include <string.h>
 
 #include "lrf_env.h"
@@ -282,6 +283,122 @@ RaggedPlan plan_decode_ragged(const std::vector<RaggedWork>& images)
             for (long t = 0; t < nb; t++) p.blocks.push_back(RaggedBlock{(int)i, (int)t});
         }
         p.launches.push_back(l);
+    }
+    return p;
+}
+
+// ---- geometry -----------------------------------------------------------------------------------------------------------------
+void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M)
+{
+    // F.interpolate(scale_factor=0.5): output size = floor(input * 0.5) (lrf/compression/qmf.py:230)
+    int64_t ph = c ? (int64_t)floor((double)H * 0.5) : H, pw = c ? (int64_t)floor((double)W * 0.5) : W;
+    *h = ph;
+    *w = pw;
+    *hp = ph + (8 - ph % 8) % 8;
+    *wp = pw + (8 - pw % 8) % 8;
+    *M = (*hp / 8) * (*wp / 8);
+}
+
+int geom_of(int64_t H, int64_t W, ImageGeom* g, int64_t* bad_h, int64_t* bad_w)
+{
+    long xoff = 0;
+    for (int c = 0; c < 3; c++) {
+        int64_t h, w, hp, wp, M;
+        plane_dims(H, W, c, &h, &w, &hp, &wp, &M);
+        *bad_h = h;
+        *bad_w = w;
+        if (h < 1 || w < 1) return c + 1;
+        // reflect padding needs pad < size (torch raises otherwise)
+        if ((hp - h) / 2 >= h || (hp - h) - (hp - h) / 2 >= h || (wp - w) / 2 >= w || (wp - w) - (wp - w) / 2 >= w) return 10 + c + 1;
+        PlaneGeom& p = g->p[c];
+        p.h = (int)h; p.w = (int)w; p.hp = (int)hp; p.wp = (int)wp;
+        p.top = (int)((hp - h) / 2); p.left = (int)((wp - w) / 2);
+        p.top_crop = p.top; p.left_crop = p.left;
+        p.nw = (int)(wp / 8);
+        p.nh = (int)(hp / 8);
+        p.pr0 = c ? g->p[c - 1].pr0 + g->p[c - 1].nh : 0;
+        p.M = (int)M;
+        p.xoff = xoff;
+        p.o4 = xoff / 4;
+        xoff += M * 64;
+    }
+    g->img_floats = xoff;
+    g->tot4 = xoff / 4;
+    return 0;
+}
+
+// ---- the tables of a ragged encode ----------------------------------------------------------------------------------------------
+// The planes stage: all ENC_TILE16 images share one launch, the others one launch per window size present.  A workgroup finds
+// its work through blocks[i].  Behind it the call is the table of its planes: everything from the Gram pass on reads PlaneDesc.
+EncRaggedPlan plan_encode_ragged(const std::vector<EncRaggedImage>& images, const PlanSettings& s)
+{
+    EncRaggedPlan p;
+    const size_t n = images.size();
+    p.descs.resize(n);
+    memset((void*)p.descs.data(), 0, n * sizeof(EncRaggedDesc)); // (the bytes are the device table's key: padding included)
+    long count[LRF_ENC_BODIES] = {0, 0, 0, 0, 0}, bcd_blocks = 0;
+    std::vector<long> units(n);
+    int rmax_t = 1;
+    for (size_t i = 0; i < n; i++) {
+        const EncRaggedImage& im = images[i];
+        EncRaggedDesc& d = p.descs[i];
+        int64_t bh, bw;
+        (void)geom_of(im.H, im.W, &d.g, &bh, &bw); // (validated by the caller)
+        const ImageGeom& g = d.g;
+        d.rgb_off = im.rgb_off;
+        d.x_off = p.x_floats;
+        p.x_floats += g.img_floats;
+        d.H = (int)im.H; d.W = (int)im.W;
+        if (im.H % 16 == 0 && im.W % 16 == 0 && im.aligned8) {
+            d.body = ENC_TILE16;
+            d.per_strip = (g.p[0].nw + 31) / 32;
+            units[i] = (im.H / 16) * d.per_strip;
+        } else { // k_planes16's tiling laid over the padded planes (lrf_qmf_planes_from_rgb_u8)
+            d.body = ENC_STRIP22 + 2 * (int)(im.H & 1) + (int)(im.W & 1);
+            const int ncols = g.p[0].nw > 2 * g.p[1].nw ? g.p[0].nw : 2 * g.p[1].nw;
+            const int nstrips = (g.p[0].nh + 1) / 2 > g.p[1].nh ? (g.p[0].nh + 1) / 2 : g.p[1].nh;
+            d.per_strip = (ncols + 31) / 32;
+            units[i] = (long)nstrips * d.per_strip;
+        }
+        count[d.body] += units[i];
+        for (int ch = 0; ch < 3; ch++) {
+            bcd_blocks += (g.p[ch].M + LRF_KC - 1) / LRF_KC;
+            rmax_t = im.R[ch] > rmax_t ? im.R[ch] : rmax_t;
+        }
+    }
+    long total = 0;
+    for (int b = 0; b < LRF_ENC_BODIES; b++) total += count[b];
+    if (bcd_blocks >= (1L << 31) || total >= (1L << 31)) {
+        p.too_many = bcd_blocks > total ? bcd_blocks : total;
+        p.descs.clear();
+        p.x_floats = 0;
+        return p;
+    }
+    p.blocks.reserve((size_t)total);
+    for (int b = 0; b < LRF_ENC_BODIES; b++) {
+        if (!count[b]) continue;
+        p.launches.push_back(EncRaggedLaunch{b, (long)p.blocks.size(), count[b], b == ENC_TILE16 ? 0 : (int)((count[b] + 7) / 8)});
+        for (size_t i = 0; i < n; i++) {
+            if (p.descs[i].body != b) continue;
+            for (long u = 0; u < units[i]; u++) p.blocks.push_back(RaggedBlock{(int)i, (int)u});
+        }
+    }
+    p.split = plan_splits(bcd_blocks, rmax_t, s);
+    p.order.reserve(3 * n);
+    for (int fam = 0; fam < (p.split ? 3 : 1); fam++)
+        for (int ch = 0; ch < 3; ch++)
+            for (size_t i = 0; i < n; i++)
+                if (!p.split || fam_of_rank(images[i].R[ch]) == fam) p.order.push_back(EncRaggedPlane{(int)i, ch});
+    for (const EncRaggedPlane& o : p.order) {
+        const EncRaggedImage& im = images[(size_t)o.image];
+        const ImageGeom& g = p.descs[(size_t)o.image].g;
+        long uo = im.u_off, vo = im.v_off, so = im.sign_off;
+        for (int c2 = 0; c2 < o.ch; c2++) {
+            uo += (long)g.p[c2].M * im.R[c2];
+            vo += 64L * im.R[c2];
+            so += im.R[c2];
+        }
+        add_plane(p.t, p.descs[(size_t)o.image].x_off + g.p[o.ch].xoff, uo, vo, 0, 0, g.p[o.ch].M, im.R[o.ch], im.sign_off < 0 ? -1 : (int)so);
     }
     return p;
 }

@@ -4,6 +4,7 @@
 // (lrf_bcd_persist.hip).  No device, no context, no HIP: the host compiler alone builds it (tests/test_bcd_plan.py does).
 #ifndef LRF_PLAN_H
 #define LRF_PLAN_H
+#include <stdint.h>
 #include <stdlib.h>
 
 #include <vector>
@@ -104,6 +105,45 @@ struct RaggedPlan {
     long too_many = 0;                  // != 0: a launch would have this many (>= 2^31) workgroups; no table is built
 };
 RaggedPlan plan_decode_ragged(const std::vector<RaggedWork>& images);
+
+// ---- geometry of the default branch (lrf/compression/qmf.py:230-242): plain arithmetic, so it lives with the plans --------------
+void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M);
+// 0, or the number (1..3) of the first plane the reference could not form — 10 + that number when its reflect padding would
+// exceed the plane, else the plane is empty — with that plane's size in *bad_h / *bad_w (make_geom words the refusal)
+int geom_of(int64_t H, int64_t W, ImageGeom* g, int64_t* bad_h, int64_t* bad_w);
+
+// ---- encode: the tables of a ragged call (lrf_qmf_encode_ragged_rgb_u8) -------------------------------------------------------
+// the planes body that serves an image: k_planes16's when both sides are multiples of 16 and its bytes start at a multiple of 8,
+// else k_planes_strip<KH, KW>'s with window sizes 2 (even side) or 3 (odd side): ENC_STRIP22 + 2 (H & 1) + (W & 1)
+enum { ENC_TILE16 = 0, ENC_STRIP22 = 1, ENC_STRIP23 = 2, ENC_STRIP32 = 3, ENC_STRIP33 = 4 };
+#define LRF_ENC_BODIES 5
+// One image as the entry point hands it over, every field validated there.  sign_off: -1 = the default signs
+struct EncRaggedImage {
+    long H, W;
+    int R[3];
+    long rgb_off, u_off, v_off, sign_off;
+    bool aligned8; // rgb + rgb_off is a multiple of 8
+};
+struct EncRaggedLaunch {
+    int body;
+    long block0, nblocks; // its workgroups: entries block0 .. block0 + nblocks - 1 of the workgroup table
+    int xcd_chunk;        // strip bodies: ceil(nblocks / 8), the grid is 8 * xcd_chunk (k_planes_strip_ragged); ENC_TILE16: 0
+};
+struct EncRaggedPlane { int image, ch; };
+struct EncRaggedPlan {
+    std::vector<EncRaggedDesc> descs;      // per image; x_off = the running sum of img_floats
+    std::vector<EncRaggedLaunch> launches; // by body, ENC_TILE16 first: at most LRF_ENC_BODIES
+    std::vector<RaggedBlock> blocks;       // per launch the images in call order, an image's units ascending
+    Tables t;                              // the plane / block tables plan_bcd and run_init / run_bcd take
+    std::vector<EncRaggedPlane> order;     // which (image, channel) plane i of the table is
+    bool split = false;                    // plan_splits of the whole call: the table is ordered by kernel family
+    long x_floats = 0;                     // the X workspace
+    long too_many = 0;                     // != 0: the call has this many (>= 2^31) BCD blocks or planes workgroups; nothing is built
+};
+// Plane order: by kernel family when the call splits (plan_bcd then finds at most three runs), inside a family — or in the
+// whole table of a call that does not split — luma before Cb before Cr, images in call order.  Every plane computes its own
+// initialisation, so each run's leading planes are its self-initialising ones, as plan_bcd assumes.
+EncRaggedPlan plan_encode_ragged(const std::vector<EncRaggedImage>& images, const PlanSettings& s);
 
 // ---- the any-shape path (lrf_anyshape_host.inc executes these; tests/test_any_plan.py reads them on the CPU) ----------------
 #define LRF_ANY_GS_MAX_LDS (160 * 1024) // dynamic LDS of k_any_gs<float, .>

@@ -23,12 +23,12 @@ LIBTSAN=$(gcc -print-file-name=libtsan.so)
   echo "# CPU sanitizer runs, $(date -u +%Y-%m-%dT%H:%MZ), gcc $(gcc -dumpversion), $(python3 -c 'import sys; print("python", sys.version.split()[0])')"
   echo "## 1. liblrf_pack.so with AddressSanitizer + UBSan: tests/test_container_abi.py + the packer tests of tests/test_anyshape.py"
   ASAN_OPTIONS=detect_leaks=0:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1 LD_PRELOAD="$LIBASAN $LIBUBSAN" LRF_PACK_LIB=$REPO/$ASAN_LIB \
-    python3 -m pytest tests/test_container_abi.py tests/test_anyshape.py -q -m "not gpu" -k "native or repack or unpack or pack or fork or crafted or stream or abi or container" -p no:cacheprovider 2>&1 | tail -4
+    python3 -m pytest tests/test_container_abi.py tests/test_anyshape.py tests/test_encode_ragged_host.py -q -m "not gpu" -k "native or repack or unpack or pack or fork or crafted or stream or abi or container" -p no:cacheprovider 2>&1 | tail -4
   echo "## 2. liblrf_pack.so with ThreadSanitizer: the same tests without the fork test (TSan cannot follow a fork of a"
   echo "##    multi-threaded process: that test hangs under it and runs under ASan above); OPENBLAS_NUM_THREADS=1 keeps numpy's own"
   echo "##    (uninstrumented) BLAS threads out of the report"
   OPENBLAS_NUM_THREADS=1 TSAN_OPTIONS=report_signal_unsafe=0:halt_on_error=0:die_after_fork=0 LD_PRELOAD="$LIBTSAN" LRF_PACK_LIB=$REPO/$TSAN_LIB \
-    timeout 900 python3 -m pytest tests/test_container_abi.py tests/test_anyshape.py -q -m "not gpu" --timeout 300 \
+    timeout 900 python3 -m pytest tests/test_container_abi.py tests/test_anyshape.py tests/test_encode_ragged_host.py -q -m "not gpu" --timeout 300 \
     -k "(native or repack or unpack or pack or crafted or stream or abi or container) and not fork" -p no:cacheprovider 2>&1 | tail -6
   echo "## 3. the oracle with AddressSanitizer + UBSan: tests/test_oracle_golden.py tests/test_qmf_kwargs.py tests/test_identity_rate.py"
   ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=print_stacktrace=1 LD_PRELOAD="$LIBASAN $LIBUBSAN" LRF_ORACLE_SO=$REPO/oracle/_build/liblrf_oracle_san.so \
