@@ -252,6 +252,36 @@ int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_image
                                  const int8_t* V, int64_t v_len, uint8_t* rgb, int64_t rgb_len);
 
 /*
+ * Windows of compressed images straight from their factors: n_crops windows of one size (h, w) out of a list of images that
+ * differ in size and in ranks, in one call — the decode of lrf/compression/qmf.py:329-351, lrf/factorization/qmf.py:216-223,
+ * lrf/compression/utils.py:50-73,98-105,135-182 followed by a slice, without the pixels outside the slice.  A pixel depends on
+ * one row of U per plane and on the three V tables, so a window costs its own patches only: what a training loader that keeps
+ * a dataset resident as int8 factors asks for at every step.
+ *   images  [n_images] descriptors in host memory, as for lrf_qmf_decode_ragged_rgb_u8 (rgb_off is ignored)
+ *   crops   [n_crops] windows in host memory: rows y0 .. y0 + h - 1, columns x0 .. x0 + w - 1 of image `image`
+ *   rgb     device buffer of rgb_len bytes; crop j is written as [3][h][w] at 3 h w j
+ * Crop j = (image i, y0, x0) equals decode(image i)[:, y0:y0+h, x0:x0+w] byte for byte, decode being what
+ * lrf_qmf_decode_rgb_u8 writes for that image alone, for every geometry and rank triple that decoder accepts: the kernels run
+ * the same device functions at the image's coordinates.  A crop's bytes depend on nothing else in the call.
+ * Launches: one per rank-bound class present among the images the tiled decoders cover (at most five), one each for those only
+ * the rank <= 8 kernel and the general kernel serve: at most seven.
+ * Asynchronous on the context's stream and timed under LRF_K_DECODE.  The image descriptors stay on the device between calls,
+ * keyed on their bytes (the first call of a new image list uploads them and waits for the stream; lrf_ctx_trim releases
+ * them).  The crop list does not: it travels stream-ordered through pinned staging slots the context owns, and a slot is
+ * reused only after an event says its copy has run, so calls with fresh lists follow each other without a stream wait.
+ * Everything is validated on the host before any launch, and a refused call writes nothing.  LRF_EINVAL: a NULL pointer,
+ * n_images outside [1,65535], n_crops outside [1,2^20], h or w below 1, a crop whose image index is out of range or whose
+ * rectangle leaves its image, a rank outside [1,64], a size the uniform decoder refuses, a negative offset, a U, V or rgb range
+ * that leaves its buffer, 2^31 or more workgroups in one launch.
+ */
+typedef struct {
+    int32_t image, y0, x0;
+} lrf_crop;
+int lrf_qmf_decode_crops_rgb_u8(lrf_ctx* ctx, int64_t n_images, const lrf_ragged_image* images /* host; rgb_off ignored */, const int8_t* U,
+                                int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops, const lrf_crop* crops /* host */, int64_t h,
+                                int64_t w, uint8_t* rgb /* [n_crops][3][h][w] */, int64_t rgb_len);
+
+/*
  * The fused encode (lrf/compression/qmf.py:227-262) for a list of n images that differ in size and in ranks, in one call: what a
  * dataset of mixed sizes or a per-image quality choice hands to an encoder.
  *   images  [n] descriptors in host memory

@@ -1155,6 +1155,49 @@ def qmf_decode_ragged(streams: Sequence[bytes], device=None) -> list:
     return ctx.decode_ragged(U, V, images)
 
 
+class ResidentFactors:
+    """The factors of a list of streams resident on one device (qmf_load_factors): flat int8 U and V, the image table decode_ragged
+    takes, and the images' sizes.  A dataset kept this way costs its int8 factors, not its pixels; .decode() gives whole images,
+    .decode_crops(crops, size) windows of them."""
+
+    def __init__(self, ctx, U, V, images):
+        self._ctx, self.U, self.V, self.images = ctx, U, V, images
+        self.sizes = [(im[0], im[1]) for im in images]
+
+    def __len__(self):
+        return len(self.images)
+
+    def decode(self) -> list:
+        """every image: what qmf_decode_ragged gives for the streams"""
+        return self._ctx.decode_ragged(self.U, self.V, self.images)
+
+    def decode_crops(self, crops, size) -> torch.Tensor:
+        """crops: integers [n, 3] of (image, y0, x0) on the host; size: (h, w) -> uint8 CUDA [n, 3, h, w]"""
+        return self._ctx.decode_crops(self.U, self.V, self.images, crops, size)
+
+
+def _resident(images, Uh, Vh, device) -> ResidentFactors:
+    ctx = _lib.context(device)
+    return ResidentFactors(ctx, torch.from_numpy(Uh).cuda(ctx.device), torch.from_numpy(Vh).cuda(ctx.device), images)
+
+
+def qmf_load_factors(streams: Sequence[bytes], device=None) -> ResidentFactors:
+    """Parses and validates the streams once (the default branch only, as qmf_decode_ragged: a stream of another branch raises
+    NotImplementedError naming it) and uploads their factors once -> ResidentFactors."""
+    return _resident(*_factors_ragged(streams), device)
+
+
+def qmf_decode_crops(source, crops, size, device=None) -> torch.Tensor:
+    """Windows of compressed images without decoding the images: source is a list of streams (parsed and uploaded for this call)
+    or the ResidentFactors of qmf_load_factors (nothing but the crop list travels); crops: integers [n, 3] of (image, y0, x0) on
+    the host; size: (h, w) -> uint8 CUDA [n, 3, h, w], crop j equal to qmf_decode(stream)[:, y0:y0+h, x0:x0+w]."""
+    if not isinstance(source, ResidentFactors):
+        images, Uh, Vh = _factors_ragged(source)
+        _lib.check_crop_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, crops, size)  # refused before a GPU is asked for
+        source = _resident(images, Uh, Vh, device)
+    return source.decode_crops(crops, size)
+
+
 def _qmf_decode_rgbspace(encoded_image: bytes, device=None) -> torch.Tensor:
     """RGB colour-space branch of qmf_decode (lrf/compression/qmf.py:309-323) -> uint8 CUDA tensor [3,H,W]."""
     encoded_metadata, encoded_factors = separate_bytes(encoded_image, 2)

@@ -8,6 +8,7 @@
 #include "lrf_bcdw16_kernel.hip"
 #include "lrf_sweep_sse_kernel.hip"
 #include "lrf_decode_ragged_kernel.hip"
+#include "lrf_decode_crops_kernel.hip"
 #include "lrf_planes_ragged_kernel.hip"
 
 // gram_exp: the fixed-point grid exponent of the exact Gram matrix (max|x| < 2^gram_exp) when the caller knows it — 8 for the
@@ -768,6 +769,121 @@ int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* 
             hipLaunchKernelGGL(k_decode8_ragged, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, l.reps);
         else
             hipLaunchKernelGGL(k_decode_ragged_any, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl);
+        LAUNCH_CHECK();
+    }
+    return LRF_OK;
+}
+
+// The crop table of one call on its way to the device: stream-ordered, no wait for the stream.  The pinned staging slots take
+// turns; a slot is written again only after the event recorded behind its last copy says that copy has run (a wait for that
+// one copy at most, LRF_CROP_SLOTS calls back).  The device table is one buffer: the copy of a call is ordered behind the
+// kernels of the call before it on the same stream.
+static int stage_crop_table(lrf_ctx* c, const std::vector<CropEntry>& table)
+{
+    const size_t bytes = table.size() * sizeof(CropEntry);
+    int rc = ensure(c, c->crop_tab, bytes);
+    if (rc) return rc;
+    lrf_ctx::CropSlot& s = c->crop_slot[c->crop_next];
+    c->crop_next = (c->crop_next + 1) % LRF_CROP_SLOTS;
+    if (!s.copied) HIP_TRY(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+    else if (s.in_flight) HIP_TRY(hipEventSynchronize(s.copied));
+    s.in_flight = false;
+    if (bytes > s.cap) {
+        if (s.h) HIP_TRY(hipHostFree(s.h));
+        s.h = nullptr;
+        s.cap = 0;
+        HIP_TRY(hipHostMalloc(&s.h, bytes + bytes / 2, hipHostMallocDefault));
+        s.cap = bytes + bytes / 2;
+    }
+    memcpy(s.h, table.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(c->crop_tab.p, s.h, bytes, hipMemcpyHostToDevice, c->stream));
+    s.in_flight = true;
+    HIP_TRY(hipEventRecord(s.copied, c->stream));
+    return LRF_OK;
+}
+
+// n_crops windows of one size (h, w) out of a list of images that differ in size and ranks (kernels:
+// lrf_decode_crops_kernel.hip; the launches: plan_decode_crops).  Everything the kernels index with is checked here, before
+// any launch.  The image descriptors stay resident between calls (their bytes are the key); the crop list does not.
+int lrf_qmf_decode_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
+                                int64_t v_len, int64_t n_crops, const lrf_crop* crops, int64_t h, int64_t w, uint8_t* rgb, int64_t rgb_len)
+{
+    if (!c || !images || !U || !V || !crops || !rgb) return set_err(LRF_EINVAL, "NULL argument");
+    if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
+    if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
+    if (h < 1 || w < 1 || h > INT32_MAX || w > INT32_MAX) return set_err(LRF_EINVAL, "crop size %ldx%ld out of range", (long)h, (long)w);
+    std::vector<RaggedDesc> descs((size_t)n_images);
+    std::vector<RaggedWork> work((size_t)n_images);
+    memset((void*)descs.data(), 0, descs.size() * sizeof(RaggedDesc)); // (the bytes are the table's key: padding included)
+    for (int64_t i = 0; i < n_images; i++) {
+        const lrf_ragged_image& im = images[i];
+        RaggedDesc& d = descs[(size_t)i];
+        if (im.H < 1 || im.W < 1 || im.H > INT32_MAX || im.W > INT32_MAX) return set_err(LRF_EINVAL, "image %ld: size %ldx%ld out of range", (long)i, (long)im.H, (long)im.W);
+        int rc = make_geom(im.H, im.W, &d.g);
+        if (rc) return rc;
+        for (int ch = 0; ch < 3; ch++)
+            if (im.R[ch] < 1 || im.R[ch] > 64) return set_err(LRF_EINVAL, "image %ld: rank %d out of range", (long)i, im.R[ch]);
+        if (im.u_off < 0 || im.v_off < 0) return set_err(LRF_EINVAL, "image %ld: negative offset", (long)i);
+        long u_img = 0, v_img = 0;
+        for (int ch = 0; ch < 3; ch++) {
+            u_img += (long)d.g.p[ch].M * im.R[ch];
+            v_img += 64L * im.R[ch];
+        }
+        if (u_img > u_len || im.u_off > u_len - u_img) return set_err(LRF_EINVAL, "image %ld: its U factors leave the buffer of %ld elements", (long)i, (long)u_len);
+        if (v_img > v_len || im.v_off > v_len - v_img) return set_err(LRF_EINVAL, "image %ld: its V factors leave the buffer of %ld elements", (long)i, (long)v_len);
+        const DecodePlan plan = decode_plan(d.g, im.H, im.W, im.R, true); // (the windowed tiled body stores at any alignment)
+        d.u_off = im.u_off; d.v_off = im.v_off; // (rgb_off: 0, the output is the crops')
+        d.H = (int)im.H; d.W = (int)im.W;
+        d.R0 = im.R[0]; d.R1 = im.R[1]; d.R2 = im.R[2];
+        d.kind = plan.kind; d.cls = plan.cls;
+        d.per_strip = (d.g.p[0].nw + 31) / 32;
+        work[(size_t)i] = RaggedWork{plan.kind, plan.cls, 0};
+    }
+    // (h * w <= rgb_len / 3 first: then 3 h w cannot wrap)
+    if (rgb_len < 3 || h > rgb_len / 3 / w || n_crops > rgb_len / (3 * h * w))
+        return set_err(LRF_EINVAL, "%ld crops of 3x%ldx%ld leave the output buffer of %ld bytes", (long)n_crops, (long)h, (long)w, (long)rgb_len);
+    std::vector<CropEntry> list((size_t)n_crops);
+    for (int64_t j = 0; j < n_crops; j++) {
+        const lrf_crop& cr = crops[j];
+        if (cr.image < 0 || cr.image >= n_images) return set_err(LRF_EINVAL, "crop %ld: image %d out of range [0,%ld)", (long)j, cr.image, (long)n_images);
+        const lrf_ragged_image& im = images[cr.image];
+        if (cr.y0 < 0 || cr.x0 < 0 || h > im.H || w > im.W || cr.y0 > im.H - h || cr.x0 > im.W - w)
+            return set_err(LRF_EINVAL, "crop %ld: %ldx%ld at (%d,%d) leaves image %d of %ldx%ld", (long)j, (long)h, (long)w, cr.y0, cr.x0, cr.image, (long)im.H,
+                           (long)im.W);
+        list[(size_t)j] = CropEntry{cr.image, cr.y0, cr.x0, (int)j};
+    }
+    const CropPlan plan = plan_decode_crops(work, list, (int)h, (int)w);
+    if (plan.too_many) return set_err(LRF_EINVAL, "%ld workgroups in one launch: split the list", plan.too_many);
+    LRF_ON_DEVICE(c);
+    const size_t db = descs.size() * sizeof(RaggedDesc);
+    if (c->crop_desc_key.size() != db || memcmp(c->crop_desc_key.data(), descs.data(), db) != 0 || !c->crop_desc.p) {
+        c->crop_desc_key.clear();
+        int rc = upload(c, c->crop_desc, descs.data(), db);
+        if (rc) return rc;
+        c->crop_desc_key.assign((const char*)descs.data(), (const char*)descs.data() + db);
+    }
+    const RaggedDesc* d_desc = (const RaggedDesc*)c->crop_desc.p;
+    Prof p(c, LRF_K_DECODE);
+    int rc = stage_crop_table(c, plan.table);
+    if (rc) return rc;
+    const CropEntry* d_crop = (const CropEntry*)c->crop_tab.p;
+    for (const CropLaunch& l : plan.launches) {
+        const dim3 grid((unsigned)(l.ncrops * l.wgs));
+        const CropEntry* ce = d_crop + l.crop0;
+        if (l.kind == DEC_STRIP) {
+#define LRF_CROPS_TILED(CLS) hipLaunchKernelGGL((k_decode_crops_tiled<CLS>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs)
+            switch (l.cls) {
+            case 0: LRF_CROPS_TILED(0); break;
+            case 1: LRF_CROPS_TILED(1); break;
+            case 2: LRF_CROPS_TILED(2); break;
+            case 3: LRF_CROPS_TILED(3); break;
+            default: LRF_CROPS_TILED(4); break;
+            }
+#undef LRF_CROPS_TILED
+        } else if (l.kind == DEC_R8)
+            hipLaunchKernelGGL(k_decode8_crops, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs);
+        else
+            hipLaunchKernelGGL(k_decode_crops_any, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs);
         LAUNCH_CHECK();
     }
     return LRF_OK;

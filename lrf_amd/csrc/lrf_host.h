@@ -24,6 +24,7 @@
 // (run_init: selects k_gram64's integer digit extraction; callers with arbitrary X pass LRF_GRAM_EXP_FROM_DATA)
 #define LRF_PLANES_GRAM_EXP 8
 #define LRF_TABLE_SETS 6 // descriptor-table sets a context keeps resident (upload_tables)
+#define LRF_CROP_SLOTS 4 // pinned staging slots of lrf_qmf_decode_crops_rgb_u8's crop table
 
 int set_err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 const char* last_err();
@@ -79,6 +80,17 @@ struct lrf_ctx {
     std::vector<char> sse_key; // ... and the bytes now resident there (calls that repeat a sweep skip the synchronising upload)
     DevBuf ragged_tab; // lrf_qmf_decode_ragged_rgb_u8: the image descriptors (RaggedDesc), behind them the block table ...
     std::vector<char> ragged_key; // ... and the descriptor bytes now resident there
+    DevBuf crop_desc; // lrf_qmf_decode_crops_rgb_u8: the image descriptors (RaggedDesc) ...
+    std::vector<char> crop_desc_key; // ... and the descriptor bytes now resident there
+    DevBuf crop_tab;  // the crop table (CropEntry) of the call in flight; filled stream-ordered from the pinned slots below, which take turns
+    struct CropSlot {
+        void* h = nullptr; // page-locked
+        size_t cap = 0;
+        hipEvent_t copied = nullptr; // recorded behind the slot's copy: the slot is written again only after it
+        bool in_flight = false;
+    };
+    CropSlot crop_slot[LRF_CROP_SLOTS];
+    int crop_next = 0;
     DevBuf enc_ragged_tab; // lrf_qmf_encode_ragged_rgb_u8: the image descriptors (EncRaggedDesc), behind them the workgroup table ...
     std::vector<char> enc_ragged_key; // ... and the descriptor bytes now resident there
     DevBuf vf16, wf16, bf16, pp16, qp16; // the pitch-16 tables of a call that mixes kernel families (BcdPlan::mixed)

@@ -90,6 +90,13 @@ struct RaggedBlock {
     int image, tile;
 };
 
+// ---- the decode of windows (lrf_qmf_decode_crops_rgb_u8; kernels: lrf_decode_crops_kernel.hip) ----
+// One window of the call's (h, w), as the kernels read it (a uniform load per workgroup); the image: an index into RaggedDesc
+struct CropEntry {
+    int image, y0, x0; // the window's origin inside the image
+    int out;           // which [3][h][w] of the output it fills: its place in the caller's list
+};
+
 // ---- the ragged encode (lrf_qmf_encode_ragged_rgb_u8; kernels: lrf_planes_ragged_kernel.hip) ----
 // One image of the call, as the planes kernels read it (uniform loads, like RaggedDesc; the workgroup table is RaggedBlock's:
 // image, unit = strip * per_strip + column group)

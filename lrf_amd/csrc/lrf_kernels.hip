@@ -1496,27 +1496,20 @@ __device__ __forceinline__ float recon_at(const int8_t* __restrict__ Uc, const i
 // to 8 columns), a thread keeps the u row of the patch it is in and reloads it only when the patch changes (four
 // horizontally adjacent pixels touch at most two luma and two chroma patches), and the four output bytes of a
 // channel leave as one dword.  Same arithmetic and order as k_decode.
-// Ui / Vi: the image's factors; bx: the workgroup's index inside the image; Vs: 3 x 64 x 8 floats of LDS.
-template <class Sink>
-__device__ __forceinline__ void decode8_body(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0,
-                                             int R1, int R2, int bx, int reps, float (*Vs)[64 * 8], Sink& sink)
+// decode8_stage_v: the V tables into LDS (Vs: 3 x 64 x 8 floats); decode8_quad: the pixels (y, x0 .. xlim - 1), at most four, of the
+// image — xlim = W for a whole image, the window's right edge for a crop (lrf_decode_crops_kernel.hip); y, x0 and the
+// chroma sampling are in image coordinates either way.
+__device__ __forceinline__ void decode8_stage_v(const int8_t* (&Vc)[3], const int (&Rc)[3], float (*Vs)[64 * 8])
 {
-    const int8_t* Uc[3] = {Ui, Ui + (long)g.p[0].M * R0, Ui + (long)g.p[0].M * R0 + (long)g.p[1].M * R1};
-    const int8_t* Vc[3] = {Vi, Vi + 64 * R0, Vi + 64 * R0 + 64 * R1};
-    const int Rc[3] = {R0, R1, R2};
     for (int e = threadIdx.x; e < 3 * 64 * 8; e += 256) {
         int c = e >> 9, n = (e >> 3) & 63, r = e & 7;
         Vs[c][n * 8 + r] = (r < Rc[c]) ? (float)Vc[c][n * Rc[c] + r] : 0.f;
     }
-    __syncthreads();
-    int w4 = (W + 3) >> 2;
-    // `reps` groups of four pixels per thread (the host picks up to 16 for large calls): the V table above (six dependent byte
-    // loads per thread and a barrier) is then staged once for up to 16384 pixels instead of 1024 — with one group per thread
-    // that prologue, not the arithmetic, set the pace (512 x 1365x2048: 4.8 -> 3.4 ms)
-    for (int rep = 0; rep < reps; rep++) {
-    long o = ((long)bx * reps + rep) * 256 + threadIdx.x;
-    if (o >= (long)H * w4) return;
-    int y = (int)(o / w4), x0 = (int)(o - (long)y * w4) * 4;
+}
+template <class Sink>
+__device__ __forceinline__ void decode8_quad(const int8_t* (&Uc)[3], const int (&Rc)[3], int H, int W, const ImageGeom& g, int y, int x0, int xlim,
+                                             float (*Vs)[64 * 8], Sink& sink)
+{
     float sh = (float)g.p[1].h / (float)H, sw = (float)g.p[1].w / (float)W;
     int sy = (int)floorf((float)y * sh);
     if (sy > g.p[1].h - 1) sy = g.p[1].h - 1;
@@ -1541,7 +1534,7 @@ __device__ __forceinline__ void decode8_body(const int8_t* __restrict__ Ui, cons
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         int x = x0 + i;
-        if (x >= W) break;
+        if (x >= xlim) break;
         int sx = (int)floorf((float)x * sw);
         if (sx > g.p[1].w - 1) sx = g.p[1].w - 1;
         const float c0 = recon(0, yyl, x + g.p[0].left_crop) + 0.f;
@@ -1558,12 +1551,32 @@ __device__ __forceinline__ void decode8_body(const int8_t* __restrict__ Ui, cons
     }
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
-        if (x0 + 3 < W) {
+        if (x0 + 3 < xlim) {
             sink.put4(ch, y, x0, packed[ch]);
         } else {
-            for (int i = 0; x0 + i < W; i++) sink.put1(ch, y, x0 + i, (uint8_t)(packed[ch] >> (8 * i)));
+            for (int i = 0; x0 + i < xlim; i++) sink.put1(ch, y, x0 + i, (uint8_t)(packed[ch] >> (8 * i)));
         }
     }
+}
+// Ui / Vi: the image's factors; bx: the workgroup's index inside the image; Vs: 3 x 64 x 8 floats of LDS.
+template <class Sink>
+__device__ __forceinline__ void decode8_body(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0,
+                                             int R1, int R2, int bx, int reps, float (*Vs)[64 * 8], Sink& sink)
+{
+    const int8_t* Uc[3] = {Ui, Ui + (long)g.p[0].M * R0, Ui + (long)g.p[0].M * R0 + (long)g.p[1].M * R1};
+    const int8_t* Vc[3] = {Vi, Vi + 64 * R0, Vi + 64 * R0 + 64 * R1};
+    const int Rc[3] = {R0, R1, R2};
+    decode8_stage_v(Vc, Rc, Vs);
+    __syncthreads();
+    int w4 = (W + 3) >> 2;
+    // `reps` groups of four pixels per thread (the host picks up to 16 for large calls): the V table above (six dependent byte
+    // loads per thread and a barrier) is then staged once for up to 16384 pixels instead of 1024 — with one group per thread
+    // that prologue, not the arithmetic, set the pace (512 x 1365x2048: 4.8 -> 3.4 ms)
+    for (int rep = 0; rep < reps; rep++) {
+        long o = ((long)bx * reps + rep) * 256 + threadIdx.x;
+        if (o >= (long)H * w4) return;
+        int y = (int)(o / w4), x0 = (int)(o - (long)y * w4) * 4;
+        decode8_quad(Uc, Rc, H, W, g, y, x0, W, Vs, sink);
     }
 }
 
@@ -1756,20 +1769,22 @@ __global__ __launch_bounds__(256) void k_decode16(const int8_t* __restrict__ U, 
 // lrf/compression/utils.py:98-105): the two rows of a thread usually share it (then the chroma sums are computed once, as
 // in k_decode16), otherwise the second row's are computed separately, from the u rows of its own chroma patch.
 // Same arithmetic as k_decode8 / k_decode16.
+// decode_strip_core: the thread's place — strip, luma patch column ww, row pair rp — and the image pixels it keeps are its
+// caller's: rows [ylo, yhi) and columns [xlo, xhi) of the image, all of it for a whole-image decode (decode_strip_tile), a
+// window for a crop (lrf_decode_crops_kernel.hip; keep: the thread's pixels meet the window).  Coordinates, chroma sampling
+// included, are the image's in both.
 template <int RC, int RL, class Sink> // rank bounds of the chroma planes (4, 8, 16) and of luma (8, 16, 32)
-__device__ __forceinline__ void decode_strip_tile(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0,
-                                                  int R1, int R2, int bx, int per_strip, float* __restrict__ VsL, float* __restrict__ VsC, Sink& sink)
+__device__ __forceinline__ void decode_strip_core(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0,
+                                                  int R1, int R2, int strip, int ww, int rp, bool keep, int ylo, int yhi, int xlo, int xhi,
+                                                  float* __restrict__ VsL, float* __restrict__ VsC, Sink& sink)
 {
     const int8_t* Uc[3] = {Ui, Ui + (long)g.p[0].M * R0, Ui + (long)g.p[0].M * R0 + (long)g.p[1].M * R1};
     const int8_t* Vc[3] = {Vi, Vi + 64 * R0, Vi + 64 * R0 + 64 * R1};
     const int Rc[3] = {R0, R1, R2};
     const PlaneGeom pl = g.p[0], pc = g.p[1];
     const int nwl = pl.nw, nwc = pc.nw;
-    const int strip = bx / per_strip;
-    const int ww = (bx - strip * per_strip) * 32 + (threadIdx.x & 31);
-    const int rp = threadIdx.x >> 5; // row pair inside the strip: padded luma rows 16 strip + 2 rp, + 1
     const int prow = 2 * strip + (rp >> 2);
-    const bool live = ww < nwl && prow < pl.nh;
+    const bool live = keep && ww < nwl && prow < pl.nh;
     const int wwc = ww < nwl ? ww : nwl - 1, prc = prow < pl.nh ? prow : pl.nh - 1;
     // image rows / columns of this thread and their chroma samples (padded chroma coordinates)
     const int y0 = 16 * strip + 2 * rp - pl.top_crop, x0 = 8 * wwc - pl.left_crop;
@@ -1801,7 +1816,7 @@ __device__ __forceinline__ void decode_strip_tile(const int8_t* __restrict__ Ui,
     float cb[4], cr[4];
     // samples (padded row qq, padded columns cx .. cx + 3) of both planes
     decode_chroma4<RC>(ub, ur, VsC, (q[0] & 7) * 8 + (cx & 7), cb, cr);
-    const bool xfull = x0 >= 0 && x0 + 8 <= W;
+    const bool xfull = x0 >= xlo && x0 + 8 <= xhi;
 #pragma unroll
     for (int rr = 0; rr < 2; rr++) {
         const int y = y0 + rr;
@@ -1814,7 +1829,7 @@ __device__ __forceinline__ void decode_strip_tile(const int8_t* __restrict__ Ui,
             }
             decode_chroma4<RC>(ub, ur, VsC, (q[1] & 7) * 8 + (cx & 7), cb, cr);
         }
-        if (y < 0 || y >= H) continue;
+        if (y < ylo || y >= yhi) continue;
         uint2 pk[3];
         decode_row8<RL>(ul, VsL, (2 * (rp & 3) + rr) * 8, cb, cr, pk);
         if (xfull) {
@@ -1824,10 +1839,20 @@ __device__ __forceinline__ void decode_strip_tile(const int8_t* __restrict__ Ui,
             for (int k = 0; k < 3; k++) {
                 const unsigned long long w = ((unsigned long long)pk[k].y << 32) | pk[k].x;
                 for (int j = 0; j < 8; j++)
-                    if (x0 + j >= 0 && x0 + j < W) sink.put1(k, y, x0 + j, (uint8_t)(w >> (8 * j)));
+                    if (x0 + j >= xlo && x0 + j < xhi) sink.put1(k, y, x0 + j, (uint8_t)(w >> (8 * j)));
             }
         }
     }
+}
+
+// bx: the workgroup's tile inside the image; a thread owns padded luma rows 16 strip + 2 rp, + 1 of one patch
+template <int RC, int RL, class Sink>
+__device__ __forceinline__ void decode_strip_tile(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0,
+                                                  int R1, int R2, int bx, int per_strip, float* __restrict__ VsL, float* __restrict__ VsC, Sink& sink)
+{
+    const int strip = bx / per_strip;
+    decode_strip_core<RC, RL>(Ui, Vi, H, W, g, R0, R1, R2, strip, (bx - strip * per_strip) * 32 + (int)(threadIdx.x & 31), (int)(threadIdx.x >> 5), true, 0, H, 0, W,
+                              VsL, VsC, sink);
 }
 
 template <int RC, int RL>
@@ -1841,15 +1866,11 @@ __global__ __launch_bounds__(256) void k_decode_strip(const int8_t* __restrict__
     decode_strip_tile<RC, RL>(U + (long)blockIdx.y * u_img, V + (long)blockIdx.y * v_img, H, W, g, R0, R1, R2, (int)blockIdx.x, per_strip, VsL, VsC, sink);
 }
 
-// every geometry and rank: bx = the workgroup's index inside the image (256 groups of four pixels each)
+// every geometry and rank.  decode_quad: the pixels (y, x0 .. xlim - 1), at most four, of the image (xlim = W, or a window's right edge)
 template <class Sink>
-__device__ __forceinline__ void decode_body(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0, int R1,
-                                            int R2, long bx, Sink& sink)
+__device__ __forceinline__ void decode_quad(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0, int R1,
+                                            int R2, int y, int x0, int xlim, Sink& sink)
 {
-    int w4 = (W + 3) >> 2;
-    long o = bx * 256 + threadIdx.x;
-    if (o >= (long)H * w4) return;
-    int y = (int)(o / w4), x0 = (int)(o - (long)y * w4) * 4;
     const int8_t* Uc[3] = {Ui, Ui + (long)g.p[0].M * R0, Ui + (long)g.p[0].M * R0 + (long)g.p[1].M * R1};
     const int8_t* Vc[3] = {Vi, Vi + 64 * R0, Vi + 64 * R0 + 64 * R1};
     const int Rc[3] = {R0, R1, R2};
@@ -1860,7 +1881,7 @@ __device__ __forceinline__ void decode_body(const int8_t* __restrict__ Ui, const
     if (sy > g.p[1].h - 1) sy = g.p[1].h - 1;
     for (int i = 0; i < 4; i++) {
         int x = x0 + i;
-        if (x >= W) break;
+        if (x >= xlim) break;
         int sx = (int)floorf((float)x * sw);
         if (sx > g.p[1].w - 1) sx = g.p[1].w - 1;
         float c[3];
@@ -1877,6 +1898,17 @@ __device__ __forceinline__ void decode_body(const int8_t* __restrict__ Ui, const
             sink.put1(ch, y, x, (uint8_t)acc); // truncation (to_dtype)
         }
     }
+}
+// bx = the workgroup's index inside the image (256 groups of four pixels each)
+template <class Sink>
+__device__ __forceinline__ void decode_body(const int8_t* __restrict__ Ui, const int8_t* __restrict__ Vi, int H, int W, const ImageGeom& g, int R0, int R1,
+                                            int R2, long bx, Sink& sink)
+{
+    int w4 = (W + 3) >> 2;
+    long o = bx * 256 + threadIdx.x;
+    if (o >= (long)H * w4) return;
+    int y = (int)(o / w4), x0 = (int)(o - (long)y * w4) * 4;
+    decode_quad(Ui, Vi, H, W, g, R0, R1, R2, y, x0, W, sink);
 }
 
 __global__ __launch_bounds__(256) void k_decode(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W,

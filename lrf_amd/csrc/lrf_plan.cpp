@@ -287,6 +287,43 @@ RaggedPlan plan_decode_ragged(const std::vector<RaggedWork>& images)
     return p;
 }
 
+// ---- the launches of a decode of windows -----------------------------------------------------------------------------------------
+// One launch per rank-bound class of the tiled body present (the strip body under a class switch: 204 registers), one each for
+// DEC_R8 and DEC_ANY.  The table is a stable sort of the call's list by launch.
+CropPlan plan_decode_crops(const std::vector<RaggedWork>& images, const std::vector<CropEntry>& crops, int h, int w)
+{
+    CropPlan p;
+    const int nslots = LRF_DEC_CLASSES + 2;
+    auto slot_of = [&](const CropEntry& e) {
+        const RaggedWork& im = images[(size_t)e.image];
+        return im.kind == DEC_TILE16 || im.kind == DEC_STRIP ? im.cls : (im.kind == DEC_R8 ? LRF_DEC_CLASSES : LRF_DEC_CLASSES + 1);
+    };
+    std::vector<long> count((size_t)nslots, 0);
+    for (const CropEntry& e : crops) count[(size_t)slot_of(e)]++;
+    const long wgs_tiled = crop_tiled_wgs(h, w), wgs_quad = crop_quad_wgs(h, w);
+    for (int s = 0; s < nslots; s++) {
+        const long wgs = s < LRF_DEC_CLASSES ? wgs_tiled : wgs_quad;
+        if (count[(size_t)s] && (wgs >= (1L << 31) || count[(size_t)s] * wgs >= (1L << 31))) {
+            p.too_many = wgs >= (1L << 31) ? wgs : count[(size_t)s] * wgs;
+            return p;
+        }
+    }
+    p.table.reserve(crops.size());
+    for (int s = 0; s < nslots; s++) {
+        if (!count[(size_t)s]) continue;
+        CropLaunch l;
+        l.kind = s < LRF_DEC_CLASSES ? DEC_STRIP : (s == LRF_DEC_CLASSES ? DEC_R8 : DEC_ANY);
+        l.cls = s < LRF_DEC_CLASSES ? s : 0;
+        l.crop0 = (long)p.table.size();
+        l.ncrops = count[(size_t)s];
+        l.wgs = s < LRF_DEC_CLASSES ? wgs_tiled : wgs_quad;
+        for (size_t j = 0; j < crops.size(); j++)
+            if (slot_of(crops[j]) == s) p.table.push_back(CropEntry{crops[j].image, crops[j].y0, crops[j].x0, (int)j});
+        p.launches.push_back(l);
+    }
+    return p;
+}
+
 // ---- geometry -----------------------------------------------------------------------------------------------------------------
 void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M)
 {

@@ -106,6 +106,80 @@ struct RaggedPlan {
 };
 RaggedPlan plan_decode_ragged(const std::vector<RaggedWork>& images);
 
+// ---- decode of windows: the launches of lrf_qmf_decode_crops_rgb_u8 and which pixels a thread answers for --------------------
+// The windows of a call share one size (h, w), so a launch's grid is uniform: (workgroups per window) x (its windows), the
+// workgroups per window being the worst case over the alignments a window can have inside its image; workgroups a window's
+// alignment leaves without pixels exit.  The functions below say which image pixels thread `tid` of workgroup `wg` of a window
+// keeps: the kernels store exactly those, and tests/test_decode_crops_plan.py checks on the CPU that they tile every window.
+#ifdef __HIPCC__
+#define LRF_HD __host__ __device__
+#else
+#define LRF_HD
+#endif
+struct CropSpan { int y, x, ny, nx; }; // image rows y .. y + ny - 1, columns x .. x + nx - 1; ny == 0 or nx == 0: none
+// Tiled body: the tiles of decode_strip_tile (16 padded luma rows x 32 luma patches, a thread two rows of one patch), laid from
+// the strip and the patch column that hold the window's origin.  h rows touch at most floor((h + 14) / 16) + 1 strips, w
+// columns at most floor((w + 6) / 8) + 1 patches.
+LRF_HD inline int crop_tiled_per_strip(int w) { return (((w + 6) >> 3) + 1 + 31) / 32; }
+LRF_HD inline long crop_tiled_wgs(int h, int w) { return (long)(((h + 14) >> 4) + 1) * crop_tiled_per_strip(w); }
+struct CropTile {
+    int strip, ww, rp; // padded luma rows 16 strip + 2 rp, + 1 of luma patch column ww
+    CropSpan px;       // what of them lies inside the window
+};
+// top, left: the luma plane's padding above and left of the image (PlaneGeom::top_crop, left_crop)
+LRF_HD inline CropTile crop_tile_of(int top, int left, int y0, int x0, int h, int w, int wg, int tid)
+{
+    const int per_strip = crop_tiled_per_strip(w), s = wg / per_strip;
+    CropTile t;
+    t.strip = ((y0 + top) >> 4) + s;
+    t.ww = ((x0 + left) >> 3) + (wg - s * per_strip) * 32 + (tid & 31);
+    t.rp = tid >> 5;
+    const long ya = 16L * t.strip + 2 * t.rp - top, xa = 8L * t.ww - left; // (long: a tile past the window may pass 2^31)
+    const long ylo = ya > y0 ? ya : y0, yhi = ya + 2 < (long)y0 + h ? ya + 2 : (long)y0 + h;
+    const long xlo = xa > x0 ? xa : x0, xhi = xa + 8 < (long)x0 + w ? xa + 8 : (long)x0 + w;
+    t.px.ny = yhi > ylo ? (int)(yhi - ylo) : 0;
+    t.px.nx = xhi > xlo ? (int)(xhi - xlo) : 0;
+    t.px.y = t.px.ny ? (int)ylo : y0;
+    t.px.x = t.px.nx ? (int)xlo : x0;
+    return t;
+}
+// whether workgroup wg of a window holds any of its pixels (its first thread's rows and columns start inside the window's)
+LRF_HD inline bool crop_tile_wg_live(int top, int left, int y0, int x0, int h, int w, int wg)
+{
+    const int per_strip = crop_tiled_per_strip(w), s = wg / per_strip;
+    const long ya = 16L * (((y0 + top) >> 4) + s) - top, xa = 8L * (((x0 + left) >> 3) + (wg - s * per_strip) * 32) - left;
+    return ya < (long)y0 + h && xa < (long)x0 + w;
+}
+// Quad bodies (rank <= 8 and general): the window's pixel quads, row by row, 256 to a workgroup
+LRF_HD inline long crop_quad_wgs(int h, int w) { return ((long)h * ((w + 3) >> 2) + 255) / 256; }
+LRF_HD inline CropSpan crop_quad_of(int y0, int x0, int h, int w, int wg, int tid)
+{
+    const int w4 = (w + 3) >> 2;
+    const long o = (long)wg * 256 + tid;
+    CropSpan q = {y0, x0, 0, 0};
+    if (o >= (long)h * w4) return q;
+    const int r = (int)(o / w4), c = (int)(o - (long)r * w4) * 4;
+    q.y = y0 + r;
+    q.x = x0 + c;
+    q.ny = 1;
+    q.nx = w - c < 4 ? w - c : 4;
+    return q;
+}
+// One launch: windows crop0 .. crop0 + ncrops - 1 of the sorted table, wgs workgroups each (grid.x = ncrops * wgs).
+// kind: DEC_STRIP (the tiled body, images decode_plan gives DEC_TILE16 or DEC_STRIP; cls: its rank-bound class), DEC_R8, DEC_ANY
+struct CropLaunch {
+    int kind, cls;
+    long crop0, ncrops;
+    long wgs;
+};
+struct CropPlan {
+    std::vector<CropLaunch> launches; // order: tiled by class, DEC_R8, DEC_ANY; at most LRF_DEC_CLASSES + 2
+    std::vector<CropEntry> table;     // the windows grouped by launch, call order inside a group; out = the place in the call
+    long too_many = 0;                // != 0: a launch would have this many (>= 2^31) workgroups; no table is built
+};
+// images: (kind, cls) per image as decode_plan classified it (units unused); crops: (image, y0, x0) in call order, validated
+CropPlan plan_decode_crops(const std::vector<RaggedWork>& images, const std::vector<CropEntry>& crops, int h, int w);
+
 // ---- geometry of the default branch (lrf/compression/qmf.py:230-242): plain arithmetic, so it lives with the plans --------------
 void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M);
 // 0, or the number (1..3) of the first plane the reference could not form — 10 + that number when its reflect padding would
