@@ -1,5 +1,8 @@
 """Randomised HIP-vs-oracle parity sweep of the BCD from given initial factors (bit for bit): the 64-column path
-(lrf_qmf_bcd_f32) and the RGB colour-space path (lrf_qmf_rgbspace_encode_u8 with init)."""
+(lrf_qmf_bcd_f32) and the RGB colour-space path (lrf_qmf_rgbspace_encode_u8 with init).
+`python tools/dev_fuzz_bcd.py <seed> <cases> int`: integer data instead — random cases from the generators of tests/exact_bcd.py
+(rounding ties, zero denominators, clamps) through lrf_qmf_bcd_f32 against reference_bcd; a draw whose sums would reach 2^24
+is skipped.  For long developer runs; the suite's own integer cases are the table of tests/exact_bcd.py."""
 import os, sys, random
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -10,6 +13,27 @@ oracle.build()
 rnd = random.Random(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
 ctx = _lib.context(0)
 bad = 0
+if sys.argv[3:4] == ["int"]:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import exact_bcd as E
+    for i in range(int(sys.argv[2])):
+        lo, hi = rnd.choice([(-16, 15), (-8, 7), (-3, 5), (-4, 4), (-128, 127), (-32, 31), (-25, 25)])
+        c = E.Case(rnd.choice([1, 2, 7, 130, 1030]), rnd.choice([1, 17, 48, 130, 384, 400, 777]), rnd.randint(1, 40), rnd.choice([3, 4, 6]), lo, hi,
+                   rnd.choice([1, 2, 6, 12]), rnd.choice([2, 4, 6, 10]), N=rnd.choice([64, 64, 64, 16, 192]), zero_x=rnd.random() < 0.3,
+                   zero_v=rnd.random() < 0.3)
+        c.seed = 7000 + i
+        X, U0, V0 = c.inputs()
+        try:
+            Uw, Vw, st = E.reference_bcd(X, U0, V0, c.K, lo, hi)
+        except AssertionError as e:
+            print(f"[{i}] {c.id}: skipped ({e})")
+            continue
+        U, V = ctx.bcd(*(torch.from_numpy(t).float().cuda() for t in (X, U0, V0)), c.K, lo, hi)
+        Uh, Vh = ctx.to_host(U, V)
+        ok = np.array_equal(Uh.numpy(), Uw) and np.array_equal(Vh.numpy(), Vw)
+        print(f"[{i}] {c.id} x{c.gen['xmax']}: ties U {E.share(st['u']):.1f} % V {E.share(st['v']):.1f} %: {'ok' if ok else 'FAIL'}", flush=True)
+        bad += not ok
+    sys.exit(1 if bad else 0)
 for i in range(int(sys.argv[2]) if len(sys.argv) > 2 else 30):
     H = rnd.choice([16, 24, 64, 99, 173, 256]); W = rnd.choice([16, 56, 96, 130, 264, 384])
     K = rnd.choice([1, 2, 5, 10]); bounds = rnd.choice([(-16, 15), (-8, 7), (-128, 127)])
