@@ -491,6 +491,23 @@ int lrf_qmf_decode_any_hw_u8(lrf_ctx* ctx, const int8_t* U0, const int8_t* V0, c
                              const int8_t* V2, int64_t B, int64_t H, int64_t W, int64_t hc, int64_t wc, int p, int q, const int R[3],
                              uint8_t* rgb);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Deflate of factor columns on the device: every column of n int8 matrices becomes a zlib stream (RFC 1950 / 1951, Huffman
+ * only — literals and end-of-block, no matches) that any inflate reads.  The format, the choice between a dynamic, a fixed and
+ * stored blocks, the code-length builder and the header's run-length rule are defined once, in lrf_amd/csrc/lrf_deflate_shared.h;
+ * liblrf_pack.so restates the coder on the host from the same file (include/lrf_pack_deflate.h) and gives the same bytes.
+ * Matrix i is [rows, cols] int8, row-major, at src + src_off (the layout lrf_qmf_encode_rgb_u8 and the ragged encoder write).
+ * Column j's stream goes to the slot dst + dst_off + j * bound(rows), bound(len) = 2 + 5 * ceil(len / 65535) + len + 4 being the
+ * most a stream can take (stored blocks), and its length to out_len[len_off + j]; no byte of a slot behind that length is written.
+ * Everything is checked on the host before a launch: 1 <= n <= 2^20, 1 <= rows <= 2^30, 1 <= cols <= 4096, every range against
+ * src_len, dst_len and out_len_count, no two matrices sharing slot bytes or length entries.  `mats` is host memory and free again
+ * on return; the table goes to the device stream-ordered and the call does not wait for the stream.  One workgroup per column.
+ */
+typedef struct { int64_t src_off, rows, cols, dst_off, len_off; } lrf_deflate_matrix;
+int64_t lrf_deflate_bound(int64_t len);
+int lrf_deflate_columns_i8(lrf_ctx* ctx, const int8_t* src, int64_t src_len, int64_t n, const lrf_deflate_matrix* mats /* host */,
+                           uint8_t* dst, int64_t dst_len, int32_t* out_len /* device */, int64_t out_len_count);
+
 #ifdef __cplusplus
 }
 #endif

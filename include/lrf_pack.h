@@ -54,4 +54,5 @@ const char* lrf_pack_zlib_version(void);
 /* the unpacker for streams that differ in size and ranks: a header of its own (tests/test_container_abi.py pins the list of
  * functions this file declares) */
 #include "lrf_pack_ragged.h"
+#include "lrf_pack_deflate.h"
 #endif

@@ -96,6 +96,9 @@ def load():
                                                     c_i64, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_encode_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedEncodeImage), c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64,
                                                      c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_deflate_bound.restype = c_i64
+        lib.lrf_deflate_bound.argtypes = [c_i64]
+        lib.lrf_deflate_columns_i8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64]
         lib.lrf_image_metrics_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
         lib.lrf_qmf_sweep_sse_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int), c_void_p]
         lib.lrf_svd_encode_rgb_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -141,7 +144,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -354,6 +357,36 @@ def check_encode_ragged_args(rgb, images, sign=None):
             raise ValueError(f"image {i}: its {sum(ranks)} signs at {sign_off} leave the sign buffer")
         out.append((H, W, ranks, rgb_off, sign_off))
     return out
+
+
+def deflate_bound(length):
+    """bytes of the slot a column of `length` bytes gets: 2 + 5 * ceil(length / 65535) + length + 4 (host-only arithmetic; works
+    on integers and on integer arrays alike)"""
+    return 2 + 5 * ((length + 65534) // 65535) + length + 4
+
+
+def deflate_table(mats):
+    """The table lrf_deflate_columns_i8 takes, as an int64 array [n, 5] of (src_off, rows, cols, dst_off, len_off), from an
+    integer array-like [n, 3] of (src_off, rows, cols): slots and length entries back to back in call order -> (table, bytes
+    of all slots, number of columns).  Host-only arithmetic."""
+    m = np.asarray(mats, dtype=np.int64).reshape(-1, 3)
+    if m.shape[0] < 1 or bool((m[:, 1:] < 1).any()) or bool((m[:, 0] < 0).any()):
+        raise ValueError("deflate_columns needs at least one matrix (src_off >= 0, rows >= 1, cols >= 1)")
+    slots = m[:, 2] * deflate_bound(m[:, 1])
+    table = np.empty((m.shape[0], 5), dtype=np.int64)
+    table[:, :3] = m
+    table[:, 3] = np.cumsum(slots) - slots
+    table[:, 4] = np.cumsum(m[:, 2]) - m[:, 2]
+    return table, int(slots.sum()), int(m[:, 2].sum())
+
+
+def deflate_column_offsets(table):
+    """per column of a table (deflate_table's layout) where its slot starts: int64 [number of columns], matrices in table order"""
+    t = np.asarray(table, dtype=np.int64).reshape(-1, 5)
+    cols = t[:, 2]
+    first = np.cumsum(cols) - cols
+    within = np.arange(int(cols.sum()), dtype=np.int64) - np.repeat(first, cols)
+    return np.repeat(t[:, 3], cols) + within * np.repeat(deflate_bound(t[:, 1]), cols)
 
 
 def _dptr(t):
@@ -637,6 +670,33 @@ class Context:
         check(self._lib.lrf_qmf_encode_ragged_rgb_u8(self._h, len(ims), desc, _dptr(rgb), rgb.numel(), int(K), int(lo), int(hi), _dptr(sign),
                                                      0 if sign is None else sign.numel(), _dptr(U), uo, _dptr(V), vo))
         return U, V, u_off, v_off
+
+    def deflate_columns_into(self, src, table, slots, lens):
+        """lrf_deflate_columns_i8 with every offset named by the caller: src a flat int8 CUDA tensor, table an int64 array [n, 5]
+        of (src_off, rows, cols, dst_off, len_off) on the host, slots a flat uint8 and lens a flat int32 CUDA tensor.  The
+        library checks every range before it launches (ValueError).  Asynchronous on torch's current stream."""
+        import torch
+        for t, dt in ((src, torch.int8), (slots, torch.uint8), (lens, torch.int32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt:
+                raise TypeError("deflate_columns takes an int8 source, uint8 slots and int32 lengths")
+            if t.dim() != 1 or not t.is_contiguous() or not (t.is_cuda and t.device.index == self.device):
+                raise ValueError(f"deflate_columns needs flat contiguous tensors on cuda:{self.device}")
+        table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 5)
+        self.use_torch_stream()
+        check(self._lib.lrf_deflate_columns_i8(self._h, _dptr(src), src.numel(), table.shape[0], c_void_p(table.ctypes.data), _dptr(slots),
+                                               slots.numel(), _dptr(lens), lens.numel()))
+
+    def deflate_columns(self, src, mats):
+        """The zlib stream of every column of int8 matrices, written on the device (lrf_deflate_columns_i8).  src: a flat int8
+        CUDA tensor; mats: [(src_off, rows, cols)], matrix i row-major [rows, cols] at src[src_off:] -> (slots, lens): a flat
+        uint8 and a flat int32 CUDA tensor laid out as deflate_table(mats) says (column j of matrix i: lens[len_off_i + j]
+        bytes at slots[dst_off_i + j * deflate_bound(rows_i):]).  Asynchronous on torch's current stream."""
+        import torch
+        table, nbytes, ncols = deflate_table(mats)
+        slots = torch.empty((nbytes,), dtype=torch.uint8, device=src.device)
+        lens = torch.empty((ncols,), dtype=torch.int32, device=src.device)
+        self.deflate_columns_into(src, table, slots, lens)
+        return slots, lens
 
     def image_metrics(self, a, b, want_ssim=True):
         """uint8 CUDA tensors a, b [B,C,H,W] -> (sse int64 [B], ssim float64 [B] or None) on the device (lrf_image_metrics_u8):

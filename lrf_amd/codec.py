@@ -166,7 +166,7 @@ def _check_target_args(images, psnr, qualities, num_iters):
 
 
 def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
-                      pack_workers: Optional[int] = None) -> dict:
+                      pack_workers: Optional[int] = None, deflate: str = "host") -> dict:
     """Per image of a batch [B,3,H,W], the smallest-quality stream that reaches `psnr` dB (one number, or one per image).
 
     Default branch only (YCbCr, 8x8 patches, uint8, num_iters >= 1).  Every distinct rank triple of `qualities` is factorised on
@@ -178,7 +178,11 @@ def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds
     Returns {"streams": B byte streams, stream i byte-identical to qmf_encode_batch(images[i:i+1], quality=quality[i])[0];
     "quality": the chosen quality per image (the lowest of those that share its rank triple); "psnr": float64 [B], the chosen
     stream's PSNR, what psnr_batch gives for its decode; "reached": bool [B]; "table": float64 [Q,B], the PSNR of every
-    (quality of `qualities`, image) pair}.  The tensors are host tensors."""
+    (quality of `qualities`, image) pair}.  The tensors are host tensors.
+
+    deflate="device": the winners' columns are deflated on the GPU (as in qmf_encode_batch) and only their streams' bytes come
+    to the host; the streams then hold the same factors as the default call's but are not byte-identical to them."""
+    on_device = _deflate_on_device(deflate)
     qualities, target = _check_target_args(images, psnr, qualities, num_iters)
     H, W = images.shape[-2:]
     B = images.shape[0]
@@ -204,6 +208,14 @@ def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds
         if rows.numel() == 0:
             continue
         sel = rows.to(dev.device)
+        if on_device:
+            Us, Vs = factors[t][0].index_select(0, sel), factors[t][1].index_select(0, sel)
+            k = rows.numel()
+            packed = streams_from_device_factors(ctx, Us, Vs, [(H, W)] * k, [t] * k, np.arange(k, dtype=np.int64) * Us.shape[1],
+                                                 np.arange(k, dtype=np.int64) * Vs.shape[1], bounds, _pack_threads(pack_workers))
+            for b, s_ in zip(rows.tolist(), packed):
+                streams[b] = s_
+            continue
         Uh, Vh = (x.numpy() for x in ctx.to_host(factors[t][0].index_select(0, sel), factors[t][1].index_select(0, sel)))
         packed = pack_streams_native(Uh, Vh, (H, W), list(t), bounds, (8, 8), "uint8", threads=pack_workers or default_pack_threads())
         for b, s in zip(rows.tolist(), packed):
@@ -311,6 +323,15 @@ def _pack_lib():
         lib.lrf_pack_unpack_qmf_factors.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
                                                     ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
+        # the Huffman-only deflate coder of factor columns (include/lrf_pack_deflate.h)
+        lib.lrf_pack_deflate_bound.restype = ctypes.c_int64
+        lib.lrf_pack_deflate_bound.argtypes = [ctypes.c_int64]
+        lib.lrf_pack_deflate_column_i8.restype = ctypes.c_int64
+        lib.lrf_pack_deflate_column_i8.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
+        lib.lrf_pack_qmf_streams_deflated.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_char_p),
+                                                      ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                                      ctypes.POINTER(ctypes.c_int64)]
         # Byte identity with the reference (CPython's zlib module at level 9) needs the same deflate implementation:
         # a Python built against another zlib (conda, zlib-ng) would make the native streams valid but different.
         import zlib
@@ -400,14 +421,92 @@ def _pack_pool(workers):
     return _PACK_POOL
 
 
+def _deflate_on_device(deflate, patch=True, patch_size=(8, 8)) -> bool:
+    """the `deflate` keyword of the encoders: "host" (False) or "device" (True); ValueError for anything else,
+    NotImplementedError for the branches the device coder does not serve yet"""
+    if deflate not in ("host", "device"):
+        raise ValueError(f"deflate must be 'host' or 'device', got {deflate!r}")
+    if deflate == "device" and (not patch or tuple(patch_size) != (8, 8)):
+        raise NotImplementedError("deflate='device' covers the 8x8-patch branch only (patch=False packs a factor as one long fiber)")
+    return deflate == "device"
+
+
+def _pack_threads(pack_workers) -> int:
+    return pack_workers if isinstance(pack_workers, int) and pack_workers > 0 else default_pack_threads()
+
+
+def streams_from_device_factors(ctx, U, V, sizes, triples, u_off, v_off, bounds, threads: int = 0) -> list:
+    """The one way factors become streams with deflate="device": U, V flat int8 CUDA tensors holding n images of sizes[i] =
+    (H, W) and ranks triples[i] at u_off[i] / v_off[i] (encode_rgb's layout of one image each).  Every column is deflated where
+    it lies (lrf_deflate_columns_i8, one call for the U matrices and one for the V matrices into the same slots and lengths),
+    the slots and the lengths come to the host in one copy each (ctx.to_host: a failed launch raises here) and
+    lrf_pack_qmf_streams_deflated folds them into the containers.  The streams are not byte-identical to the zlib-9 ones; they
+    hold the same factors and every inflate reads them."""
+    import ctypes
+    lib = _pack_lib()
+    n = len(sizes)
+    m_of, meta_of = {}, {}
+    for hw, t in zip(sizes, triples):
+        if tuple(hw) not in m_of:
+            m_of[tuple(hw)] = [int(d[4]) for d in _lib.plane_dims(*hw)]
+        if (tuple(hw), tuple(t)) not in meta_of:
+            meta_of[(tuple(hw), tuple(t))] = _stream_metadata(hw, list(t), bounds)
+    Ms = np.array([m_of[tuple(hw)] for hw in sizes], dtype=np.int64).reshape(n, 3)
+    Rs = np.array([[int(r) for r in t] for t in triples], dtype=np.int64).reshape(n, 3)
+    mats = np.empty((n, 3, 2, 3), dtype=np.int64)  # (src_off, rows, cols) in stream order: image, plane, U before V
+    mats[:, :, 0, 0] = np.asarray(u_off, dtype=np.int64).reshape(n, 1) + np.cumsum(Ms * Rs, axis=1) - Ms * Rs
+    mats[:, :, 0, 1] = Ms
+    mats[:, :, 1, 0] = np.asarray(v_off, dtype=np.int64).reshape(n, 1) + 64 * (np.cumsum(Rs, axis=1) - Rs)
+    mats[:, :, 1, 1] = 64
+    mats[:, :, :, 2] = Rs[:, :, None]
+    table, nbytes, ncols = _lib.deflate_table(mats.reshape(-1, 3))
+    slots = torch.empty((nbytes,), dtype=torch.uint8, device=U.device)
+    lens = torch.empty((ncols,), dtype=torch.int32, device=U.device)
+    by_factor = table.reshape(n, 3, 2, 5)
+    ctx.deflate_columns_into(U.reshape(-1), by_factor[:, :, 0].reshape(-1, 5), slots, lens)
+    ctx.deflate_columns_into(V.reshape(-1), by_factor[:, :, 1].reshape(-1, 5), slots, lens)
+    slots_h, lens_h = (t.numpy() for t in ctx.to_host(slots, lens))
+    col_off = _lib.deflate_column_offsets(table)
+    metas = [meta_of[(tuple(hw), tuple(t))] for hw, t in zip(sizes, triples)]
+    meta_len = np.array([len(m) for m in metas], dtype=np.int64)
+    R32 = np.ascontiguousarray(Rs, dtype=np.int32)
+    out = (ctypes.c_void_p * n)()
+    out_len = (ctypes.c_int64 * n)()
+    rc = lib.lrf_pack_qmf_streams_deflated(slots_h.ctypes.data, slots_h.size, n, Ms.ctypes.data, R32.ctypes.data, col_off.ctypes.data,
+                                           lens_h.ctypes.data, ncols, (ctypes.c_char_p * n)(*metas), meta_len.ctypes.data, int(threads), out, out_len)
+    if rc:
+        raise RuntimeError(f"lrf_pack_qmf_streams_deflated failed ({rc})")
+    streams = []
+    for b in range(n):
+        streams.append(ctypes.string_at(out[b], out_len[b]))
+        lib.lrf_pack_free(out[b])
+    return streams
+
+
 def qmf_encode_batch(images: torch.Tensor, rank=None, quality=None, bounds=(-16, 15), num_iters: int = 10,
-                     init_sign=None, pack_workers: Optional[int] = None, patch: bool = True, patch_size=(8, 8)) -> list:
+                     init_sign=None, pack_workers: Optional[int] = None, patch: bool = True, patch_size=(8, 8), deflate: str = "host") -> list:
     """Batched qmf_encode (YCbCr branch) -> list of byte streams, one per image.  The factorisation of the whole batch
     runs on the GPU; for the default 8x8 patches the byte containers are packed by liblrf_pack.so on native host threads
     (`pack_workers` None / 0: as many as this process may use, default_pack_threads), or, with pack_workers="python", by the Python container code on a
-    thread pool.  Other patch sizes and patch=False go through the any-shape kernels (container packed in Python)."""
+    thread pool.  Other patch sizes and patch=False go through the any-shape kernels (container packed in Python).
+
+    deflate="device": the columns are deflated on the GPU (Huffman-only zlib streams, lrf_deflate_columns_i8) while the factors
+    are still there, and the host only folds them into the container: same factors, other bytes, read by every decoder.  8x8
+    patches only (NotImplementedError otherwise).  A host tensor then takes the context path (upload, factorise, deflate), not
+    the pipelined encoder: wiring the pipe's slots to the coder is a follow-up."""
     assert (rank, quality) != (None, None), "Either 'rank' or 'quality' must be specified."
     H, W = images.shape[-2:]
+    on_device = _deflate_on_device(deflate, patch, patch_size)
+    if on_device:
+        if images.dtype != torch.uint8:
+            raise NotImplementedError("HIP path takes uint8 images")
+        ctx = _lib.context(images.device.index if images.is_cuda else None)
+        dev = images if images.is_cuda else images.cuda(ctx.device)
+        ranks = qmf_ranks((H, W), rank, quality)
+        U, V = qmf_factorize_batch(dev, ranks, num_iters, bounds, init_sign)
+        B = U.shape[0]
+        return streams_from_device_factors(ctx, U, V, [(H, W)] * B, [ranks] * B, np.arange(B, dtype=np.int64) * U.shape[1],
+                                           np.arange(B, dtype=np.int64) * V.shape[1], bounds, _pack_threads(pack_workers))
     if (not images.is_cuda) and patch and tuple(patch_size) == (8, 8) and images.dtype == torch.uint8 and num_iters >= 1 \
             and pack_workers != "python" and not (isinstance(pack_workers, int) and pack_workers < 0):
         # host tensor in, byte streams out: the pipelined encoder, the container of each finished sub-batch packed by
@@ -547,7 +646,7 @@ def _check_encode_ragged_args(images, rank, quality, ranks, num_iters, init_sign
 
 
 def qmf_encode_ragged(images, rank=None, quality=None, ranks=None, bounds=(-16, 15), num_iters: int = 10, init_sign=None,
-                      pack_workers: Optional[int] = None) -> list:
+                      pack_workers: Optional[int] = None, deflate: str = "host") -> list:
     """qmf_encode of a list of uint8 images [3,H_i,W_i] (host or device) that differ in size and in ranks, in one GPU call
     (lrf_qmf_encode_ragged_rgb_u8) -> one byte stream per image, stream i byte-identical to
     qmf_encode_batch(images[i][None], ...)[0] with that image's parameters.  Default branch only (YCbCr, 8x8 patches, uint8,
@@ -559,7 +658,11 @@ def qmf_encode_ragged(images, rank=None, quality=None, ranks=None, bounds=(-16, 
     Host images are gathered in one page-locked buffer, each at a multiple of 16 bytes (so that images whose sides are multiples
     of 16 keep the planes kernel made for them), and go up in one copy; then one C call, one copy of all factors back and one
     call of the native packer over all columns of all images.  Images whose triple has a rank above 32 are encoded one by one
-    through qmf_encode_batch and put back in place.  For a list of equal sizes and ranks qmf_encode_batch is the call to use."""
+    through qmf_encode_batch and put back in place.  For a list of equal sizes and ranks qmf_encode_batch is the call to use.
+
+    deflate="device": as in qmf_encode_batch — the columns are deflated on the GPU and only folded into the containers on the
+    host; the streams hold the same factors but are not the zlib-9 bytes."""
+    on_device = _deflate_on_device(deflate)
     sizes, triples, signs = _check_encode_ragged_args(images, rank, quality, ranks, num_iters, init_sign)
     n = len(sizes)
     streams = [None] * n
@@ -567,7 +670,7 @@ def qmf_encode_ragged(images, rank=None, quality=None, ranks=None, bounds=(-16, 
     for i in range(n):
         if i not in fused:
             streams[i] = qmf_encode_batch(images[i][None], rank=list(triples[i]), bounds=bounds, num_iters=num_iters, init_sign=signs[i],
-                                          pack_workers=pack_workers)[0]
+                                          pack_workers=pack_workers, deflate=deflate)[0]
     if not fused:
         return streams
     on_dev = [images[i] for i in fused if images[i].is_cuda]
@@ -597,6 +700,12 @@ def qmf_encode_ragged(images, rank=None, quality=None, ranks=None, bounds=(-16, 
     lo, hi = math.ceil(bounds[0]), math.floor(bounds[1])
     U, V, u_off, v_off = ctx.encode_ragged(flat, [(sizes[i][0], sizes[i][1], triples[i], o, s) for i, o, s in zip(fused, offs, sign_offs)],
                                            num_iters, lo, hi, sign)
+    if on_device:
+        packed = streams_from_device_factors(ctx, U, V, [sizes[i] for i in fused], [triples[i] for i in fused], u_off, v_off, bounds,
+                                             _pack_threads(pack_workers))
+        for i, s_ in zip(fused, packed):
+            streams[i] = s_
+        return streams
     Uh, Vh = (t.numpy() for t in ctx.to_host(U, V))  # waits for the stream, then raises if a launch of this call gave up
     packed = None
     if pack_workers != "python" and not (isinstance(pack_workers, int) and pack_workers < 0):

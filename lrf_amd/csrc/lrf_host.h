@@ -93,6 +93,9 @@ struct lrf_ctx {
     int crop_next = 0;
     DevBuf enc_ragged_tab; // lrf_qmf_encode_ragged_rgb_u8: the image descriptors (EncRaggedDesc), behind them the workgroup table ...
     std::vector<char> enc_ragged_key; // ... and the descriptor bytes now resident there
+    DevBuf deflate_tab; // lrf_deflate_columns_i8: the matrix table (DeflateMat) of the call in flight, filled stream-ordered from ...
+    CropSlot deflate_slot[LRF_CROP_SLOTS]; // ... pinned slots of its own, which take turns as the crop table's do
+    int deflate_next = 0;
     DevBuf vf16, wf16, bf16, pp16, qp16; // the pitch-16 tables of a call that mixes kernel families (BcdPlan::mixed)
     // host staging for descriptor tables (pinned)
     void* h_stage = nullptr;

@@ -1,11 +1,13 @@
 // lrf_pack.cpp — host-side packer of liblrf_pack.so (include/lrf_pack.h).  No GPU code.
 #include "../../include/lrf_pack.h"
+#include "lrf_deflate_shared.h"
 
 #include <zlib.h>
 
 #include <pthread.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -531,6 +533,112 @@ int lrf_pack_unpack_qmf_factors_ragged(const uint8_t* const* factor_blobs, const
     if (nt > 1) worker_pool().run(nt - 1, work);
     else work();
     return status.load();
+}
+
+/* ---- the Huffman-only deflate coder of factor columns (include/lrf_pack_deflate.h; the format: lrf_deflate_shared.h) ---- */
+
+int64_t lrf_pack_deflate_bound(int64_t len) { return len < 1 ? -1 : lrfd_bound(len); }
+
+int64_t lrf_pack_deflate_column_i8(const int8_t* src, int64_t rows, int64_t stride, uint8_t* dst, int64_t cap)
+{
+    if (!src || !dst || rows < 1 || rows > LRFD_MAX_ROWS || stride < 1) return -1;
+    lrfd_work k;
+    uint8_t hdr[LRFD_HDR_MAX];
+    memset(&k, 0, sizeof(k));
+    memset(hdr, 0, sizeof(hdr));
+    uint64_t a = 0, b = 0; // Adler-32: A = 1 + sum d, B = rows + sum (rows - i) d_i
+    for (int64_t i = 0; i < rows; i++) {
+        const uint32_t d = (uint8_t)src[i * stride];
+        k.freq[d]++;
+        a += d;
+        b = (b + (uint64_t)((rows - i) % LRFD_ADLER) * d) % LRFD_ADLER;
+    }
+    k.freq[256] = 1;
+    lrfd_plan(&k, rows, hdr);
+    if (k.stream_len > cap) return -7;
+    uint8_t trailer[4];
+    lrfd_adler_bytes((uint32_t)((1 + a) % LRFD_ADLER), (uint32_t)((rows % LRFD_ADLER + b) % LRFD_ADLER), trailer);
+    if (k.form == LRFD_STORED) {
+        dst[0] = hdr[0];
+        dst[1] = hdr[1];
+        const int64_t nblocks = (rows + LRFD_STORED_MAX - 1) / LRFD_STORED_MAX;
+        for (int64_t blk = 0; blk < nblocks; blk++) lrfd_stored_block_header(rows, blk, dst + 2 + blk * (LRFD_STORED_MAX + 5));
+        for (int64_t i = 0; i < rows; i++) dst[lrfd_stored_pos(i)] = (uint8_t)src[i * stride];
+    } else {
+        memset(dst, 0, (size_t)k.stream_len - 4);
+        memcpy(dst, hdr, (k.hdr_bits + 7) / 8);
+        uint64_t pos = k.hdr_bits;
+        for (int64_t i = 0; i < rows; i++) {
+            const uint8_t d = (uint8_t)src[i * stride];
+            lrfd_put_bits(dst, pos, k.code[d], k.len[d]);
+            pos += k.len[d];
+        }
+        lrfd_put_bits(dst, pos, k.code[256], k.len[256]);
+    }
+    memcpy(dst + k.stream_len - 4, trailer, 4);
+    return k.stream_len;
+}
+
+int lrf_pack_qmf_streams_deflated(const uint8_t* slots, int64_t slots_len, int64_t n, const int64_t* M /* [n][3] */, const int* R /* [n][3] */,
+                                  const int64_t* col_off, const int32_t* col_len, int64_t ncols, const char* const* metadata,
+                                  const int64_t* metadata_len, int threads, uint8_t** out, int64_t* out_len)
+{
+    if (!slots || !M || !R || !col_off || !col_len || !metadata || !metadata_len || !out || !out_len || n < 1 || slots_len < 1 || ncols < 1) return -6;
+    std::vector<int64_t> first((size_t)n + 1, 0); // image b's columns: first[b] .. first[b + 1] - 1
+    for (int64_t b = 0; b < n; b++) {
+        int64_t c_img = 0;
+        for (int c = 0; c < 3; c++) {
+            if (M[3 * b + c] < 1 || R[3 * b + c] < 1) return -6;
+            c_img += 2 * (int64_t)R[3 * b + c];
+        }
+        if (!metadata[b] || metadata_len[b] < 0 || c_img > ncols - first[(size_t)b]) return -6;
+        first[(size_t)b + 1] = first[(size_t)b] + c_img;
+    }
+    if (first[(size_t)n] != ncols) return -6;
+    std::vector<std::pair<int64_t, int64_t>> ranges((size_t)ncols);
+    for (int64_t k = 0; k < ncols; k++) {
+        if (col_len[k] < 1 || col_off[k] < 0 || col_len[k] > slots_len || col_off[k] > slots_len - col_len[k]) return -6;
+        ranges[(size_t)k] = {col_off[k], (int64_t)col_len[k]};
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t k = 1; k < ranges.size(); k++)
+        if (ranges[k].first - ranges[k - 1].first < ranges[k - 1].second) return -6;
+    std::vector<std::string> streams((size_t)n);
+    std::atomic<int64_t> next(0);
+    auto work = [&]() {
+        for (;;) {
+            const int64_t b = next.fetch_add(1);
+            if (b >= n) return;
+            const int* Rb = R + 3 * b;
+            std::vector<std::string> enc;
+            int64_t at = first[(size_t)b];
+            for (int c = 0; c < 3; c++)
+                for (int f = 0; f < 2; f++) {
+                    std::vector<std::string> fibers;
+                    for (int r = 0; r < Rb[c]; r++, at++) fibers.emplace_back((const char*)slots + col_off[at], (size_t)col_len[at]);
+                    enc.push_back(assemble_matrix(fibers));
+                }
+            streams[(size_t)b] = combine({std::string(metadata[b], (size_t)metadata_len[b]), combine(enc)});
+        }
+    };
+    unsigned hw = std::thread::hardware_concurrency();
+    int nt = threads > 0 ? threads : (int)(hw ? (hw > 64 ? 64 : hw) : 1);
+    if (nt > n) nt = (int)n;
+    if (nt > 1) worker_pool().run(nt - 1, work);
+    else work();
+    for (int64_t b = 0; b < n; b++) out[b] = nullptr;
+    for (int64_t b = 0; b < n; b++) {
+        const std::string& stream = streams[(size_t)b];
+        uint8_t* p = (uint8_t*)malloc(stream.size() ? stream.size() : 1);
+        if (!p) {
+            for (int64_t j = 0; j < b; j++) { free(out[j]); out[j] = nullptr; }
+            return -4;
+        }
+        memcpy(p, stream.data(), stream.size());
+        out[b] = p;
+        out_len[b] = (int64_t)stream.size();
+    }
+    return 0;
 }
 
 } // extern "C"

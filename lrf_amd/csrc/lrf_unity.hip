@@ -9,3 +9,4 @@
 #include "lrf_bcd_persist.hip"
 #include "lrf_any.hip"
 #include "lrf_metrics.hip"
+#include "lrf_deflate.hip"
