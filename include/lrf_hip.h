@@ -87,6 +87,10 @@ int lrf_ctx_trim(lrf_ctx* ctx);
 #define LRF_K_METRICS 8      /* scoring: squared error + SSIM of image pairs (lrf_image_metrics_u8) and the squared error of a sweep from its
                                 factors (lrf_qmf_sweep_sse_rgb_u8); the whole launch sequence of a call counts as one */
 #define LRF_K_COUNT 9
+/* Ids behind LRF_K_COUNT: launches that are not a step of the codec's own encode / decode / scoring sequences (LRF_K_COUNT stays the
+ * number of those); timed and read exactly like the ids above.  LRF_K_SLOTS is the number of timers a context keeps. */
+#define LRF_K_INFLATE LRF_K_COUNT /* 9: the inflate of factor columns (lrf_inflate_columns_i8: one launch per call) */
+#define LRF_K_SLOTS (LRF_K_COUNT + 1)
 int lrf_ctx_profile(lrf_ctx* ctx, int enable);
 /* The same for a subset of the kernels: bit (1 << LRF_K_x) per kernel id, 0 = off.  An event pair costs a few
  * microseconds of stream time per launch (0.15 ms per 22-launch encode when every kernel is timed); bench.py times
@@ -507,6 +511,43 @@ typedef struct { int64_t src_off, rows, cols, dst_off, len_off; } lrf_deflate_ma
 int64_t lrf_deflate_bound(int64_t len);
 int lrf_deflate_columns_i8(lrf_ctx* ctx, const int8_t* src, int64_t src_len, int64_t n, const lrf_deflate_matrix* mats /* host */,
                            uint8_t* dst, int64_t dst_len, int32_t* out_len /* device */, int64_t out_len_count);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Inflate of factor columns on the device: the reverse of the call above, for ANY zlib stream (RFC 1950 / 1951: stored, fixed
+ * and dynamic blocks, matches up to distance 32,768, several blocks, the Adler-32) — the reference's level-9 streams as well as
+ * lrf_deflate_columns_i8's.  The decoder is defined once, in lrf_amd/csrc/lrf_inflate_shared.h; liblrf_pack.so restates it on the
+ * host from the same file (include/lrf_pack_inflate.h: lrf_pack_inflate_column_i8) and gives the same bytes and the same status.
+ * `src` (device, src_len bytes) holds the streams: stream k is the col_len[k] bytes at src + col_off[k] (host arrays of ncols
+ * entries).  Matrix i is [rows, cols] int8, row-major, at dst + dst_off; its column j is inflated from stream first + j and must
+ * come to exactly `rows` bytes.  status[k] (device, ncols entries) becomes 0 or the LRFI_E_* of stream k; a refused stream leaves
+ * unspecified bytes in its own column's elements and touches nothing else.
+ * Everything is checked on the host before the launch, and a failed check (LRF_EINVAL) writes nothing: no NULL pointer,
+ * 1 <= n <= 2^20, 1 <= rows <= 2^30, 1 <= cols <= 4096, every stream range inside src_len with col_len >= 8, every matrix inside
+ * dst_len, no two matrices sharing dst bytes or stream indices, ncols equal to the sum of cols.  `mats`, `col_off` and `col_len`
+ * are free again on return; the column table goes to the device stream-ordered and the call does not wait for the stream.  One
+ * launch, one lane per stream (lrf_plan.h: plan_inflate orders them), timed under LRF_K_INFLATE.
+ */
+#define LRFI_E_HEADER 1     /* CMF / FLG: CM != 8, CINFO > 7, not a multiple of 31, or FDICT set */
+#define LRFI_E_BTYPE 2      /* block type 3 */
+#define LRFI_E_STORED 3     /* stored block: NLEN is not the complement of LEN */
+#define LRFI_E_COUNTS 4     /* dynamic block: HLIT > 286 or HDIST > 30 */
+#define LRFI_E_OVERSUB 5    /* an over-subscribed set of code lengths */
+#define LRFI_E_INCOMPLETE 6 /* an incomplete set other than a single code of one bit */
+#define LRFI_E_REPEAT 7     /* a repeat code with nothing to repeat, or one running past the lengths */
+#define LRFI_E_NOEOB 8      /* dynamic block: no code for the end-of-block symbol */
+#define LRFI_E_CODE 9       /* a bit pattern that is no code */
+#define LRFI_E_LENSYM 10    /* literal/length symbol 286 or 287 */
+#define LRFI_E_DISTSYM 11   /* distance symbol 30 or 31 */
+#define LRFI_E_FAR 12       /* a distance reaching before the output's start */
+#define LRFI_E_OVERRUN 13   /* more output than `rows` */
+#define LRFI_E_SHORT 14     /* the stream ends with less output than `rows` */
+#define LRFI_E_INPUT 15     /* the input is exhausted */
+#define LRFI_E_ADLER 16     /* the Adler-32 does not match */
+#define LRFI_E_CAP 17       /* the iteration cap (8 src_len + rows + 64) was reached: cannot happen while every step consumes or produces */
+typedef struct { int64_t dst_off, rows, cols, first; } lrf_inflate_matrix;
+int lrf_inflate_columns_i8(lrf_ctx* ctx, const uint8_t* src, int64_t src_len, int64_t n, const lrf_inflate_matrix* mats /* host */,
+                           const int64_t* col_off /* host */, const int32_t* col_len /* host */, int64_t ncols, int8_t* dst, int64_t dst_len,
+                           int32_t* status /* device */);
 
 #ifdef __cplusplus
 }

@@ -55,4 +55,5 @@ const char* lrf_pack_zlib_version(void);
  * functions this file declares) */
 #include "lrf_pack_ragged.h"
 #include "lrf_pack_deflate.h"
+#include "lrf_pack_inflate.h"
 #endif

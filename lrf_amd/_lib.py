@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "liblrf_hip.so")
 
 LRF_MAX_RANK = 64
 LRF_K_PLANES, LRF_K_INIT, LRF_K_BCD, LRF_K_VUPDATE, LRF_K_DECODE, LRF_K_GRAM, LRF_K_BCD_PERSIST, LRF_K_PLANES_GRAM, LRF_K_METRICS = range(9)
+LRF_K_INFLATE = 9  # behind LRF_K_COUNT (include/lrf_hip.h): timed like the others, no step of bench.py's sequences (not in KERNEL_NAMES)
 KERNEL_NAMES = {LRF_K_PLANES: "k_planes", LRF_K_GRAM: "k_gram", LRF_K_INIT: "k_init", LRF_K_BCD: "k_bcd",
                 LRF_K_VUPDATE: "k_vupdate", LRF_K_DECODE: "k_decode", LRF_K_BCD_PERSIST: "k_bcd_persist",
                 LRF_K_PLANES_GRAM: "k_planes_gram", LRF_K_METRICS: "k_metrics"}
@@ -99,6 +100,7 @@ def load():
         lib.lrf_deflate_bound.restype = c_i64
         lib.lrf_deflate_bound.argtypes = [c_i64]
         lib.lrf_deflate_columns_i8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_inflate_columns_i8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p]
         lib.lrf_image_metrics_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
         lib.lrf_qmf_sweep_sse_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int), c_void_p]
         lib.lrf_svd_encode_rgb_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -144,7 +146,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -387,6 +389,21 @@ def deflate_column_offsets(table):
     first = np.cumsum(cols) - cols
     within = np.arange(int(cols.sum()), dtype=np.int64) - np.repeat(first, cols)
     return np.repeat(t[:, 3], cols) + within * np.repeat(deflate_bound(t[:, 1]), cols)
+
+
+def inflate_table(mats):
+    """The table lrf_inflate_columns_i8 takes, as an int64 array [n, 4] of (dst_off, rows, cols, first), from an integer
+    array-like [n, 2] of (rows, cols): the matrices back to back in the destination and their streams in call order -> (table,
+    bytes of all matrices, number of columns).  Host-only arithmetic."""
+    m = np.asarray(mats, dtype=np.int64).reshape(-1, 2)
+    if m.shape[0] < 1 or bool((m < 1).any()):
+        raise ValueError("inflate_columns needs at least one matrix (rows >= 1, cols >= 1)")
+    size = m[:, 0] * m[:, 1]
+    table = np.empty((m.shape[0], 4), dtype=np.int64)
+    table[:, 0] = np.cumsum(size) - size
+    table[:, 1:3] = m
+    table[:, 3] = np.cumsum(m[:, 1]) - m[:, 1]
+    return table, int(size.sum()), int(m[:, 1].sum())
 
 
 def _dptr(t):
@@ -697,6 +714,28 @@ class Context:
         lens = torch.empty((ncols,), dtype=torch.int32, device=src.device)
         self.deflate_columns_into(src, table, slots, lens)
         return slots, lens
+
+    def inflate_columns_into(self, src, table, col_off, col_len, dst, status):
+        """lrf_inflate_columns_i8 with every offset named by the caller: src a flat uint8 CUDA tensor holding the zlib streams,
+        table an int64 array [n, 4] of (dst_off, rows, cols, first) on the host, col_off (int64) and col_len (int32) host arrays
+        with one entry per stream, dst a flat int8 and status a flat int32 CUDA tensor with one entry per stream (0, or the
+        LRFI_E_* of include/lrf_hip.h).  The library checks every range before it launches (ValueError).  Asynchronous on
+        torch's current stream."""
+        import torch
+        for t, dt in ((src, torch.uint8), (dst, torch.int8), (status, torch.int32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt:
+                raise TypeError("inflate_columns takes a uint8 source, an int8 destination and int32 statuses")
+            if t.dim() != 1 or not t.is_contiguous() or not (t.is_cuda and t.device.index == self.device):
+                raise ValueError(f"inflate_columns needs flat contiguous tensors on cuda:{self.device}")
+        table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 4)
+        col_off = np.ascontiguousarray(col_off, dtype=np.int64).reshape(-1)
+        col_len = np.ascontiguousarray(col_len, dtype=np.int32).reshape(-1)
+        if col_off.shape != col_len.shape or status.numel() != col_off.shape[0]:
+            raise ValueError(f"inflate_columns: {col_off.shape[0]} offsets, {col_len.shape[0]} lengths and {status.numel()} statuses")
+        self.use_torch_stream()
+        check(self._lib.lrf_inflate_columns_i8(self._h, _dptr(src), src.numel(), table.shape[0], c_void_p(table.ctypes.data),
+                                               c_void_p(col_off.ctypes.data), c_void_p(col_len.ctypes.data), col_off.shape[0], _dptr(dst),
+                                               dst.numel(), _dptr(status)))
 
     def image_metrics(self, a, b, want_ssim=True):
         """uint8 CUDA tensors a, b [B,C,H,W] -> (sse int64 [B], ssim float64 [B] or None) on the device (lrf_image_metrics_u8):

@@ -332,6 +332,13 @@ def _pack_lib():
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_char_p),
                                                       ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                                       ctypes.POINTER(ctypes.c_int64)]
+        # the inflate of factor columns (include/lrf_pack_inflate.h)
+        lib.lrf_pack_inflate_column_i8.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
+        lib.lrf_pack_inflate_max_distance.restype = ctypes.c_int64
+        lib.lrf_pack_inflate_max_distance.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
+        lib.lrf_pack_index_qmf_columns_ragged.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_int64]
         # Byte identity with the reference (CPython's zlib module at level 9) needs the same deflate implementation:
         # a Python built against another zlib (conda, zlib-ng) would make the native streams valid but different.
         import zlib
@@ -1139,15 +1146,139 @@ def _factors_native(streams: Sequence[bytes]):
     return (metas, U, V) if rc == 0 else None
 
 
-def qmf_decode_batch(streams: Sequence[bytes], device=None) -> torch.Tensor:
+def _check_inflate(inflate) -> bool:
+    """True for inflate="device", False for "host"; anything else is refused"""
+    if inflate not in ("host", "device"):
+        raise ValueError(f'inflate must be "host" or "device", got {inflate!r}')
+    return inflate == "device"
+
+
+_FACTOR_NAMES = ("u_Y", "v_Y", "u_Cb", "v_Cb", "u_Cr", "v_Cr")
+
+
+def index_columns_native(blobs, Ms, Rs):
+    """lrf_pack_index_qmf_columns_ragged: where the columns' zlib streams lie in the factor payloads of n streams -> (col_off int64
+    [ncols] within each column's own blob, col_len int32 [ncols], rc); the arrays are None unless rc == 0.  Raises OSError where
+    liblrf_pack.so cannot be used."""
+    import ctypes
+    lib = _pack_lib()
+    n = len(blobs)
+    ncols = 2 * sum(int(r) for R in Rs for r in R)
+    col_off, col_len = np.empty((ncols,), dtype=np.int64), np.empty((ncols,), dtype=np.int32)
+    rc = lib.lrf_pack_index_qmf_columns_ragged(
+        (ctypes.c_char_p * n)(*blobs), (ctypes.c_int64 * n)(*[len(b) for b in blobs]), n,
+        (ctypes.c_int64 * (3 * n))(*[int(m) for M in Ms for m in M]), (ctypes.c_int * (3 * n))(*[int(r) for R in Rs for r in R]),
+        col_off.ctypes.data, col_len.ctypes.data, ncols)
+    return (col_off, col_len, 0) if rc == 0 else (None, None, rc)
+
+
+def _factors_ragged_device(streams: Sequence[bytes], device=None):
+    """_factors_ragged with the columns inflated on the device (inflate="device") -> (ctx, [(H, W, ranks, u_off, v_off)], U, V):
+    flat int8 CUDA tensors in the layout the ragged decoder reads.  The metadata is parsed and checked as _factors_ragged does
+    (the branch: NotImplementedError; the ranks, the 1040x expansion bound, ranks <= 64: ValueError); the host only walks the
+    container headers (lrf_pack_index_qmf_columns_ragged).  The factor payloads travel as ONE buffer in one copy,
+    lrf_inflate_columns_i8 fills U and V, the statuses come back in one small copy, and a stream that does not inflate raises
+    ValueError naming stream, factor and column before any decode kernel is launched.  OSError without liblrf_pack.so."""
+    if isinstance(streams, (bytes, bytearray, str)) or len(streams) < 1:
+        raise ValueError("qmf_decode_ragged takes a non-empty list of byte streams")
+    for i, s in enumerate(streams):
+        if not isinstance(s, (bytes, bytearray)):
+            raise TypeError(f"stream {i} is {type(s).__name__}, not bytes")
+    lib_error = None
+    try:
+        _pack_lib()
+    except OSError as e:
+        lib_error = e
+    if lib_error is not None:
+        raise OSError(f'inflate="device" needs liblrf_pack.so to walk the container headers: {lib_error}')
+    images, blobs, Ms, uo, vo = [], [], [], 0, 0
+    for i, s in enumerate(streams):
+        encoded_metadata, encoded_factors = separate_bytes(bytes(s), 2)
+        meta = bytes_to_dict(encoded_metadata)
+        branch = _ragged_branch(meta)
+        if branch:
+            raise NotImplementedError(f"stream {i}: qmf_decode_ragged covers the YCbCr / 8x8-patch / chroma (0.5, 0.5) / uint8 branch only, "
+                                      f"this stream is of {branch} (qmf_decode takes it)")
+        H, W = (int(x) for x in meta["original size"][0])
+        ranks = [int(r) for r in meta["rank"]]
+        if len(ranks) != 3 or min(ranks) < 1:
+            raise ValueError(f"stream {i} metadata: 'rank' must hold three positive integers")
+        if max(ranks) > 64:
+            raise ValueError(f"stream {i}: ranks {ranks} above 64")
+        M = [d[4] for d in _lib.plane_dims(H, W)]
+        # untrusted metadata: a deflate stream expands by at most ~1032x (_factors_native's bound)
+        if sum(m * r for m, r in zip(M, ranks)) + 64 * sum(ranks) > 1040 * len(encoded_factors) + 4096:
+            raise ValueError(f"stream {i}: its payload of {len(encoded_factors)} bytes cannot hold the factors its metadata describes")
+        images.append((H, W, ranks, uo, vo))
+        blobs.append(encoded_factors)
+        Ms.append(M)
+        uo += sum(m * r for m, r in zip(M, ranks))
+        vo += 64 * sum(ranks)
+    v0 = (uo + 255) // 256 * 256  # V starts at a multiple of 256 bytes of the one buffer, as a tensor of its own would
+    Rs = [im[2] for im in images]
+    col_off, col_len, rc = index_columns_native(blobs, Ms, Rs)
+    if rc != 0:  # name the first stream the walk refuses
+        for i in range(len(blobs)):
+            if index_columns_native(blobs[i:i + 1], Ms[i:i + 1], Rs[i:i + 1])[2] != 0:
+                raise ValueError(f"stream {i}: its payload is not six int8 factors packed column by column with the ranks its metadata names")
+        raise ValueError("the streams' payloads are not int8 factors packed column by column")
+    # the column table: matrix (image, plane, u or v), its streams in the container's order u_Y, v_Y, u_Cb, v_Cb, u_Cr, v_Cr
+    mats = np.empty((6 * len(images), 4), dtype=np.int64)
+    base = np.empty((len(images),), dtype=np.int64)
+    first = at = 0
+    for i, ((H, W, ranks, u_off, v_off), M) in enumerate(zip(images, Ms)):
+        base[i] = at
+        at += len(blobs[i])
+        for c in range(3):
+            mats[6 * i + 2 * c] = (u_off, M[c], ranks[c], first)
+            mats[6 * i + 2 * c + 1] = (v0 + v_off, 64, ranks[c], first + ranks[c])
+            first += 2 * ranks[c]
+            u_off += M[c] * ranks[c]
+            v_off += 64 * ranks[c]
+    col_off += np.repeat(base, [2 * sum(r) for r in Rs])
+    short = np.flatnonzero(col_len < 8)
+    if short.size:
+        raise ValueError(_inflate_refusal(int(short[0]), Rs, f"{int(col_len[short[0]])} bytes are no zlib stream"))
+    ctx = _lib.context(device)
+    src = torch.frombuffer(bytearray(b"".join(blobs)), dtype=torch.uint8).cuda(ctx.device)
+    buf = torch.empty((v0 + vo,), dtype=torch.int8, device=src.device)
+    status = torch.empty((col_off.shape[0],), dtype=torch.int32, device=src.device)
+    ctx.inflate_columns_into(src, mats, col_off, col_len, buf, status)
+    st = status.cpu().numpy()
+    failed = np.flatnonzero(st)
+    if failed.size:
+        raise ValueError(_inflate_refusal(int(failed[0]), Rs, f"inflate status {int(st[failed[0]])} (LRFI_E_*, include/lrf_hip.h): "
+                                          "the column's zlib stream is corrupt, or the container was cut short"))
+    return ctx, images, buf[:uo], buf[v0:]
+
+
+def _inflate_refusal(k, Rs, what) -> str:
+    """the message for column k of a call's column table"""
+    for i, R in enumerate(Rs):
+        for f in range(6):
+            if k < R[f // 2]:
+                return f"stream {i}: column {k} of factor {_FACTOR_NAMES[f]} does not inflate to its rows: {what}"
+            k -= R[f // 2]
+    raise AssertionError("column index outside the table")
+
+
+def qmf_decode_batch(streams: Sequence[bytes], device=None, inflate: str = "host") -> torch.Tensor:
     """Decodes streams of equal geometry and ranks -> uint8 CUDA tensor [B,3,H,W].  Streams of the other branches (another
-    patch size, patch=False, another chroma scale, the RGB colour space) are decoded one by one and stacked."""
+    patch size, patch=False, another chroma scale, the RGB colour space) are decoded one by one and stacked.
+    inflate="device": the columns' zlib streams are inflated on the GPU (_factors_ragged_device) instead of on host threads."""
+    on_device = _check_inflate(inflate)
     m_first = bytes_to_dict(separate_bytes(streams[0], 2)[0])
     H0, W0 = (m_first["original size"][0] if m_first["color space"] == "YCbCr" else (0, 0))
     if m_first["color space"] != "YCbCr" or not m_first["patch"] or list(m_first["patch size"]) != [8, 8] \
             or list(m_first["original size"][1]) != [H0 // 2, W0 // 2]:
         one = _qmf_decode_rgbspace if m_first["color space"] == "RGB" else _qmf_decode_anyshape
         return torch.stack([one(s) for s in streams])
+    if on_device:
+        ctx, images, U, V = _factors_ragged_device(streams, device)
+        H, W, ranks = images[0][:3]
+        if any((im[0], im[1], im[2]) != (H, W, ranks) for im in images[1:]):
+            raise ValueError("streams differ in geometry or ranks")
+        return ctx.decode_rgb(U.view(len(images), -1), V.view(len(images), -1), H, W, ranks)
     got = _factors_native(streams)
     metas, Uh, Vh = got if got is not None else _factors_python(streams)
     m0 = metas[0]
@@ -1252,11 +1383,15 @@ def _factors_ragged(streams: Sequence[bytes]):
     return images, U, V
 
 
-def qmf_decode_ragged(streams: Sequence[bytes], device=None) -> list:
+def qmf_decode_ragged(streams: Sequence[bytes], device=None, inflate: str = "host") -> list:
     """Decodes streams that differ in size and ranks — what qmf_encode_target writes for a batch, or a dataset of mixed sizes —
     in one call: -> a list of uint8 CUDA tensors [3,H_i,W_i] in input order (views of one buffer), each equal to
     qmf_decode of its stream.  The default branch only (YCbCr, 8x8 patches, chroma (0.5, 0.5), uint8): a stream of another
-    branch raises NotImplementedError naming it.  One host-to-device copy of all U factors, one of all V, one kernel call."""
+    branch raises NotImplementedError naming it.  One host-to-device copy of all U factors, one of all V, one kernel call.
+    inflate="device": the streams' payloads go up in one copy and are inflated on the GPU (_factors_ragged_device)."""
+    if _check_inflate(inflate):
+        ctx, images, U, V = _factors_ragged_device(streams, device)
+        return ctx.decode_ragged(U, V, images)
     images, Uh, Vh = _factors_ragged(streams)
     ctx = _lib.context(device)
     U = torch.from_numpy(Uh).cuda(ctx.device)
@@ -1290,16 +1425,25 @@ def _resident(images, Uh, Vh, device) -> ResidentFactors:
     return ResidentFactors(ctx, torch.from_numpy(Uh).cuda(ctx.device), torch.from_numpy(Vh).cuda(ctx.device), images)
 
 
-def qmf_load_factors(streams: Sequence[bytes], device=None) -> ResidentFactors:
+def qmf_load_factors(streams: Sequence[bytes], device=None, inflate: str = "host") -> ResidentFactors:
     """Parses and validates the streams once (the default branch only, as qmf_decode_ragged: a stream of another branch raises
-    NotImplementedError naming it) and uploads their factors once -> ResidentFactors."""
+    NotImplementedError naming it) and uploads their factors once -> ResidentFactors.  inflate="device": the compressed payloads
+    are uploaded instead and inflated on the GPU."""
+    if _check_inflate(inflate):
+        ctx, images, U, V = _factors_ragged_device(streams, device)
+        return ResidentFactors(ctx, U, V, images)
     return _resident(*_factors_ragged(streams), device)
 
 
-def qmf_decode_crops(source, crops, size, device=None) -> torch.Tensor:
+def qmf_decode_crops(source, crops, size, device=None, inflate: str = "host") -> torch.Tensor:
     """Windows of compressed images without decoding the images: source is a list of streams (parsed and uploaded for this call)
     or the ResidentFactors of qmf_load_factors (nothing but the crop list travels); crops: integers [n, 3] of (image, y0, x0) on
-    the host; size: (h, w) -> uint8 CUDA [n, 3, h, w], crop j equal to qmf_decode(stream)[:, y0:y0+h, x0:x0+w]."""
+    the host; size: (h, w) -> uint8 CUDA [n, 3, h, w], crop j equal to qmf_decode(stream)[:, y0:y0+h, x0:x0+w].
+    inflate="device" (a list of streams only): their columns are inflated on the GPU."""
+    on_device = _check_inflate(inflate)
+    if on_device and not isinstance(source, ResidentFactors):
+        ctx, images, U, V = _factors_ragged_device(source, device)
+        source = ResidentFactors(ctx, U, V, images)
     if not isinstance(source, ResidentFactors):
         images, Uh, Vh = _factors_ragged(source)
         _lib.check_crop_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, crops, size)  # refused before a GPU is asked for

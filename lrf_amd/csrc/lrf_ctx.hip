@@ -54,7 +54,7 @@ int upload(lrf_ctx* c, DevBuf& b, const void* src, size_t bytes)
 
 void fold_events(lrf_ctx* c)
 {
-    for (int k = 0; k < LRF_K_COUNT; k++) {
+    for (int k = 0; k < LRF_K_SLOTS; k++) {
         for (auto& pr : c->ev[k]) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
@@ -292,7 +292,7 @@ void lrf_ctx_destroy(lrf_ctx* c)
     DevBuf* bufs[] = {&c->gchunks, &c->gpart, &c->gexp, &c->planes, &c->blocks, &c->vf, &c->wf, &c->bf, &c->ppart, &c->qpart, &c->x, &c->sign,
                       &c->sx, &c->sg, &c->svn, &c->swn, &c->suf, &c->smm,
                       &c->any_uf, &c->any_vf, &c->any_a, &c->any_b, &c->any_p, &c->any_e2, &c->any_g, &c->any_td,
-                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->crop_desc, &c->crop_tab, &c->deflate_tab};
+                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->crop_desc, &c->crop_tab, &c->deflate_tab, &c->inflate_tab};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& a : c->talt) {
@@ -306,6 +306,10 @@ void lrf_ctx_destroy(lrf_ctx* c)
         if (s.copied) (void)hipEventDestroy(s.copied);
     }
     for (auto& s : c->deflate_slot) {
+        if (s.h) (void)hipHostFree(s.h);
+        if (s.copied) (void)hipEventDestroy(s.copied);
+    }
+    for (auto& s : c->inflate_slot) {
         if (s.h) (void)hipHostFree(s.h);
         if (s.copied) (void)hipEventDestroy(s.copied);
     }
@@ -362,7 +366,7 @@ size_t lrf_ctx_workspace_bytes(const lrf_ctx* c)
     const DevBuf* bufs[] = {&c->gchunks, &c->gpart, &c->gexp, &c->planes, &c->blocks, &c->vf, &c->wf, &c->bf, &c->ppart, &c->qpart, &c->x, &c->sign,
                             &c->sx, &c->sg, &c->svn, &c->swn, &c->suf, &c->smm,
                             &c->any_uf, &c->any_vf, &c->any_a, &c->any_b, &c->any_p, &c->any_e2, &c->any_g, &c->any_td,
-                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->crop_desc, &c->crop_tab, &c->deflate_tab};
+                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->crop_desc, &c->crop_tab, &c->deflate_tab, &c->inflate_tab};
     size_t total = 0;
     for (const DevBuf* b : bufs) total += b->cap;
     for (const auto& a : c->talt) total += a.planes.cap + a.blocks.cap + a.gchunks.cap;
@@ -377,7 +381,7 @@ int lrf_ctx_trim(lrf_ctx* c)
     DevBuf* bufs[] = {&c->gchunks, &c->gpart, &c->gexp, &c->planes, &c->blocks, &c->vf,
                       &c->wf, &c->bf, &c->ppart, &c->qpart, &c->x, &c->sign, &c->sx, &c->sg, &c->svn, &c->swn, &c->suf, &c->smm,
                       &c->any_uf, &c->any_vf, &c->any_a, &c->any_b, &c->any_p, &c->any_e2, &c->any_g, &c->any_td,
-                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->crop_desc, &c->crop_tab, &c->deflate_tab};
+                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->crop_desc, &c->crop_tab, &c->deflate_tab, &c->inflate_tab};
     for (DevBuf* b : bufs) {
         if (b->p) HIP_TRY(hipFree(b->p));
         b->p = nullptr;
@@ -415,7 +419,7 @@ int lrf_ctx_profile_kernels(lrf_ctx* c, unsigned mask)
 
 int lrf_ctx_kernel_time(lrf_ctx* c, int id, double* total_ms, long* launches)
 {
-    if (!c || id < 0 || id >= LRF_K_COUNT) return set_err(LRF_EINVAL, "bad kernel id");
+    if (!c || id < 0 || id >= LRF_K_SLOTS) return set_err(LRF_EINVAL, "bad kernel id");
     HIP_TRY(hipStreamSynchronize(c->stream));
     fold_events(c);
     if (total_ms) *total_ms = c->acc_ms[id];
@@ -428,7 +432,7 @@ int lrf_ctx_profile_reset(lrf_ctx* c)
     if (!c) return set_err(LRF_EINVAL, "ctx is NULL");
     HIP_TRY(hipStreamSynchronize(c->stream));
     fold_events(c);
-    for (int k = 0; k < LRF_K_COUNT; k++) { c->acc_ms[k] = 0; c->acc_n[k] = 0; }
+    for (int k = 0; k < LRF_K_SLOTS; k++) { c->acc_ms[k] = 0; c->acc_n[k] = 0; }
     return LRF_OK;
 }
 

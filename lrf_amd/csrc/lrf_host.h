@@ -96,6 +96,9 @@ struct lrf_ctx {
     DevBuf deflate_tab; // lrf_deflate_columns_i8: the matrix table (DeflateMat) of the call in flight, filled stream-ordered from ...
     CropSlot deflate_slot[LRF_CROP_SLOTS]; // ... pinned slots of its own, which take turns as the crop table's do
     int deflate_next = 0;
+    DevBuf inflate_tab; // lrf_inflate_columns_i8: the column table (InflateCol) of the call in flight, filled stream-ordered from ...
+    CropSlot inflate_slot[LRF_CROP_SLOTS]; // ... pinned slots of its own
+    int inflate_next = 0;
     DevBuf vf16, wf16, bf16, pp16, qp16; // the pitch-16 tables of a call that mixes kernel families (BcdPlan::mixed)
     // host staging for descriptor tables (pinned)
     void* h_stage = nullptr;
@@ -103,10 +106,10 @@ struct lrf_ctx {
     // profiling
     bool profile = false;
     unsigned profile_mask = ~0u; // kernel ids (bit per LRF_K_*) that get event pairs while `profile` is on
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[LRF_K_COUNT];
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[LRF_K_SLOTS];
     std::vector<hipEvent_t> ev_pool;
-    double acc_ms[LRF_K_COUNT] = {0};
-    long acc_n[LRF_K_COUNT] = {0};
+    double acc_ms[LRF_K_SLOTS] = {0};
+    long acc_n[LRF_K_SLOTS] = {0};
     int init_sweeps = 0; // developer aid: stop k_init after stage n (0 = run everything)
     std::vector<char> table_key; // bytes of the descriptor tables now resident on the device (planes / blocks)
     // earlier tables, least recently used one replaced: calls that alternate between a few geometries (a pipeline slot sees

@@ -1,6 +1,7 @@
 // lrf_pack.cpp — host-side packer of liblrf_pack.so (include/lrf_pack.h).  No GPU code.
 #include "../../include/lrf_pack.h"
 #include "lrf_deflate_shared.h"
+#include "lrf_inflate_shared.h"
 
 #include <zlib.h>
 
@@ -637,6 +638,58 @@ int lrf_pack_qmf_streams_deflated(const uint8_t* slots, int64_t slots_len, int64
         memcpy(p, stream.data(), stream.size());
         out[b] = p;
         out_len[b] = (int64_t)stream.size();
+    }
+    return 0;
+}
+
+/* ---- the inflate of factor columns (include/lrf_pack_inflate.h; the decoder: lrf_inflate_shared.h) ---- */
+
+int lrf_pack_inflate_column_i8(const uint8_t* src, int64_t src_len, int8_t* dst, int64_t rows, int64_t stride)
+{
+    if (!src || !dst || src_len < 0 || rows < 1 || rows > LRFI_MAX_ROWS || stride < 1) return -1;
+    uint16_t tab[LRFI_TAB_N];
+    return lrfi_inflate(src, src_len, dst, rows, stride, lrfi_tab{tab, 1}, nullptr);
+}
+
+int64_t lrf_pack_inflate_max_distance(const uint8_t* src, int64_t src_len, int64_t rows)
+{
+    if (!src || src_len < 0 || rows < 1 || rows > LRFI_MAX_ROWS) return -1;
+    int8_t* out = (int8_t*)malloc((size_t)rows); // (no exception may cross the C ABI)
+    if (!out) return -4;
+    uint16_t tab[LRFI_TAB_N];
+    int64_t far = 0;
+    const int rc = lrfi_inflate(src, src_len, out, rows, 1, lrfi_tab{tab, 1}, &far);
+    free(out);
+    return rc ? -(int64_t)rc : far;
+}
+
+int lrf_pack_index_qmf_columns_ragged(const uint8_t* const* factor_blobs, const int64_t* blob_len, int64_t n, const int64_t* M /* [n][3] */,
+                                      const int* R /* [n][3] */, int64_t* col_off, int32_t* col_len, int64_t ncols)
+{
+    if (!factor_blobs || !blob_len || !M || !R || !col_off || !col_len || n < 1 || ncols < 1) return -1;
+    int64_t total = 0;
+    for (int64_t b = 0; b < n; b++)
+        for (int c = 0; c < 3; c++) {
+            if (M[3 * b + c] < 1 || R[3 * b + c] < 1 || 2 * (int64_t)R[3 * b + c] > ncols - total) return -1;
+            total += 2 * (int64_t)R[3 * b + c];
+        }
+    if (total != ncols) return -1;
+    std::vector<Span> mats, parts, fibers;
+    int64_t k = 0;
+    for (int64_t b = 0; b < n; b++) {
+        const int* Rb = R + 3 * b;
+        if (!factor_blobs[b] || blob_len[b] < 0) return -1;
+        if (!separate(Span{factor_blobs[b], (size_t)blob_len[b]}, 6, mats)) return -6;
+        for (int c = 0; c < 3; c++)
+            for (int f = 0; f < 2; f++) {
+                if (!separate(mats[(size_t)(2 * c + f)], 2, parts) || !header_is(parts[0], Rb[c])) return -6;
+                if (!separate(parts[1], Rb[c], fibers)) return -6;
+                for (int r = 0; r < Rb[c]; r++, k++) {
+                    if (fibers[(size_t)r].n > (size_t)INT32_MAX) return -6;
+                    col_off[k] = (int64_t)(fibers[(size_t)r].p - factor_blobs[b]);
+                    col_len[k] = (int32_t)fibers[(size_t)r].n;
+                }
+            }
     }
     return 0;
 }

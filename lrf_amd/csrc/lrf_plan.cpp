@@ -3,6 +3,7 @@
 #include "lrf_plan.h"
 
 #include <math.h>
+#include <algorithm>
 #include <string.h>
 
 #include "lrf_env.h"
@@ -438,4 +439,20 @@ EncRaggedPlan plan_encode_ragged(const std::vector<EncRaggedImage>& images, cons
         add_plane(p.t, p.descs[(size_t)o.image].x_off + g.p[o.ch].xoff, uo, vo, 0, 0, g.p[o.ch].M, im.R[o.ch], im.sign_off < 0 ? -1 : (int)so);
     }
     return p;
+}
+
+// ---- inflate of factor columns -------------------------------------------------------------------------------------------------
+std::vector<InflateSlot> plan_inflate(const std::vector<InflateMatDim>& mats)
+{
+    std::vector<int> order(mats.size());
+    for (size_t i = 0; i < mats.size(); i++) order[i] = (int)i;
+    std::sort(order.begin(), order.end(), [&](int a, int b) {
+        if (mats[(size_t)a].rows != mats[(size_t)b].rows) return mats[(size_t)a].rows > mats[(size_t)b].rows;
+        if (mats[(size_t)a].cols != mats[(size_t)b].cols) return mats[(size_t)a].cols > mats[(size_t)b].cols;
+        return a < b;
+    });
+    std::vector<InflateSlot> slots;
+    for (int m : order)
+        for (int j = 0; j < mats[(size_t)m].cols; j++) slots.push_back(InflateSlot{m, j});
+    return slots;
 }

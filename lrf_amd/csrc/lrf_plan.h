@@ -180,6 +180,15 @@ struct CropPlan {
 // images: (kind, cls) per image as decode_plan classified it (units unused); crops: (image, y0, x0) in call order, validated
 CropPlan plan_decode_crops(const std::vector<RaggedWork>& images, const std::vector<CropEntry>& crops, int h, int w);
 
+// ---- inflate of factor columns: which lane decodes which column (lrf_inflate_columns_i8; tests/test_inflate_plan.py) ----------
+// One lane per stream, 64 consecutive slots to a wave.  The slots are the matrices' columns, matrix after matrix, a matrix's
+// columns ascending — so a wave's lanes hold adjacent columns of one matrix (adjacent bytes of every row) until the matrix
+// ends — and the matrices by descending `rows`: the long U columns start first and share no wave with the 64-row V columns
+// except where the two groups meet.  Ties: more columns first, then the order of the call.
+struct InflateMatDim { long rows; int cols; };
+struct InflateSlot { int mat, col; };
+std::vector<InflateSlot> plan_inflate(const std::vector<InflateMatDim>& mats);
+
 // ---- geometry of the default branch (lrf/compression/qmf.py:230-242): plain arithmetic, so it lives with the plans --------------
 void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M);
 // 0, or the number (1..3) of the first plane the reference could not form — 10 + that number when its reflect padding would

@@ -10,3 +10,4 @@
 #include "lrf_any.hip"
 #include "lrf_metrics.hip"
 #include "lrf_deflate.hip"
+#include "lrf_inflate.hip"
