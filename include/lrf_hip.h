@@ -513,6 +513,20 @@ int lrf_deflate_columns_i8(lrf_ctx* ctx, const int8_t* src, int64_t src_len, int
                            uint8_t* dst, int64_t dst_len, int32_t* out_len /* device */, int64_t out_len_count);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The lengths of those streams without the streams: out_len[len_off + j] becomes exactly what lrf_deflate_columns_i8 would write
+ * there for the same matrix, no other entry of out_len is written and no stream is written anywhere (dst_off is ignored).  A
+ * stream's length is a function of its column's byte counts alone (lrfd_measure of lrf_amd/csrc/lrf_deflate_shared.h, the first
+ * half of the coder's plan; liblrf_pack.so restates it on the host: lrf_pack_deflate_size_column_i8), so the kernel only counts:
+ * one workgroup per LRF_DEFLATE_CG consecutive columns of a matrix reads the matrix once and measures its columns side by side.
+ * The same host checks before the launch as above (n, rows, cols, negative offsets, every range against src_len and
+ * out_len_count, no two matrices sharing length entries), the same stream-ordered table, no wait for the stream; asynchronous
+ * and, like the call above, not timed under an LRF_K_* id.  LRF_ENOTSUP above INT32_MAX workgroups.
+ */
+#define LRF_DEFLATE_CG 8 /* columns per workgroup of the count */
+int lrf_deflate_sizes_i8(lrf_ctx* ctx, const int8_t* src, int64_t src_len, int64_t n, const lrf_deflate_matrix* mats /* host; dst_off ignored */,
+                         int32_t* out_len /* device */, int64_t out_len_count);
+
+/* ---------------------------------------------------------------------------------------------------
  * Inflate of factor columns on the device: the reverse of the call above, for ANY zlib stream (RFC 1950 / 1951: stored, fixed
  * and dynamic blocks, matches up to distance 32,768, several blocks, the Adler-32) — the reference's level-9 streams as well as
  * lrf_deflate_columns_i8's.  The decoder is defined once, in lrf_amd/csrc/lrf_inflate_shared.h; liblrf_pack.so restates it on the

@@ -21,6 +21,13 @@ int64_t lrf_pack_deflate_bound(int64_t len);
 int64_t lrf_pack_deflate_column_i8(const int8_t* src, int64_t rows, int64_t stride, uint8_t* dst, int64_t cap);
 
 /*
+ * The length lrf_pack_deflate_column_i8 would return for the same column (cap large enough), from the column's byte counts alone:
+ * no stream is written.  The CPU-testable definition of what lrf_deflate_sizes_i8 of liblrf_hip.so counts on the device.
+ * Returns -1 for a bad argument (NULL, rows outside [1, 2^30], stride < 1).
+ */
+int64_t lrf_pack_deflate_size_column_i8(const int8_t* src, int64_t rows, int64_t stride);
+
+/*
  * What lrf_pack_qmf_streams_ragged does, from columns that are deflated already: image b of n has M[3 b + c] rows and
  * R[3 b + c] columns in plane c and its stream opens with the metadata_len[b] bytes at metadata[b]; its columns — those of
  * u_Y, v_Y, u_Cb, v_Cb, u_Cr, v_Cr in this order, the images in call order, `ncols` in all — are the col_len[k] bytes at

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "liblrf_hip.so")
 
 LRF_MAX_RANK = 64
 LRF_K_PLANES, LRF_K_INIT, LRF_K_BCD, LRF_K_VUPDATE, LRF_K_DECODE, LRF_K_GRAM, LRF_K_BCD_PERSIST, LRF_K_PLANES_GRAM, LRF_K_METRICS = range(9)
+LRF_DEFLATE_CG = 8  # columns per workgroup of lrf_deflate_sizes_i8 (include/lrf_hip.h)
 LRF_K_INFLATE = 9  # behind LRF_K_COUNT (include/lrf_hip.h): timed like the others, no step of bench.py's sequences (not in KERNEL_NAMES)
 KERNEL_NAMES = {LRF_K_PLANES: "k_planes", LRF_K_GRAM: "k_gram", LRF_K_INIT: "k_init", LRF_K_BCD: "k_bcd",
                 LRF_K_VUPDATE: "k_vupdate", LRF_K_DECODE: "k_decode", LRF_K_BCD_PERSIST: "k_bcd_persist",
@@ -100,6 +101,7 @@ def load():
         lib.lrf_deflate_bound.restype = c_i64
         lib.lrf_deflate_bound.argtypes = [c_i64]
         lib.lrf_deflate_columns_i8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_deflate_sizes_i8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64]
         lib.lrf_inflate_columns_i8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p]
         lib.lrf_image_metrics_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
         lib.lrf_qmf_sweep_sse_rgb_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int), c_void_p]
@@ -146,7 +148,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -404,6 +406,20 @@ def inflate_table(mats):
     table[:, 1:3] = m
     table[:, 3] = np.cumsum(m[:, 1]) - m[:, 1]
     return table, int(size.sum()), int(m[:, 1].sum())
+
+
+def flat_views(ts):
+    """One flat tensor holding the int8 tensors `ts` back to back (the C layout of a sweep: triple after triple): where they
+    already are consecutive views of one buffer, as encode_sweep_rgb returns them, a view of it; a copy otherwise."""
+    import torch
+    p = ts[0].data_ptr()
+    for t in ts:
+        if not t.is_contiguous() or t.data_ptr() != p or t.untyped_storage().data_ptr() != ts[0].untyped_storage().data_ptr():
+            return torch.cat([x.reshape(-1) for x in ts])
+        p += t.numel()
+    if len(ts) == 1:
+        return ts[0].reshape(-1)
+    return torch.as_strided(ts[0], (p - ts[0].data_ptr(),), (1,))
 
 
 def _dptr(t):
@@ -715,6 +731,32 @@ class Context:
         self.deflate_columns_into(src, table, slots, lens)
         return slots, lens
 
+    def deflate_sizes_into(self, src, table, lens):
+        """lrf_deflate_sizes_i8 with every offset named by the caller: src a flat int8 CUDA tensor, table an int64 array [n, 5] of
+        (src_off, rows, cols, dst_off, len_off) on the host (deflate_table's layout; dst_off is not used), lens a flat int32
+        CUDA tensor.  lens[len_off + j] becomes what deflate_columns_into writes there; nothing else is written.  The library
+        checks every range before it launches (ValueError).  Asynchronous on torch's current stream."""
+        import torch
+        for t, dt in ((src, torch.int8), (lens, torch.int32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt:
+                raise TypeError("deflate_sizes takes an int8 source and int32 lengths")
+        for t in (src, lens):
+            if t.dim() != 1 or not t.is_contiguous() or not (t.is_cuda and t.device.index == self.device):
+                raise ValueError(f"deflate_sizes needs flat contiguous tensors on cuda:{self.device}")
+        table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 5)
+        self.use_torch_stream()
+        check(self._lib.lrf_deflate_sizes_i8(self._h, _dptr(src), src.numel(), table.shape[0], c_void_p(table.ctypes.data), _dptr(lens), lens.numel()))
+
+    def deflate_sizes(self, src, mats):
+        """The length of every column's zlib stream without the stream (lrf_deflate_sizes_i8).  src, mats: as deflate_columns
+        takes them -> lens, a flat int32 CUDA tensor equal to the one deflate_columns returns.  Asynchronous on torch's current
+        stream."""
+        import torch
+        table, _, ncols = deflate_table(mats)
+        lens = torch.empty((ncols,), dtype=torch.int32, device=src.device)
+        self.deflate_sizes_into(src, table, lens)
+        return lens
+
     def inflate_columns_into(self, src, table, col_off, col_len, dst, status):
         """lrf_inflate_columns_i8 with every offset named by the caller: src a flat uint8 CUDA tensor holding the zlib streams,
         table an int64 array [n, 4] of (dst_off, rows, cols, first) on the host, col_off (int64) and col_len (int32) host arrays
@@ -765,15 +807,7 @@ class Context:
         if not rgb.is_contiguous():
             raise ValueError("sweep_sse needs a contiguous image tensor")
         B, _, H, W = rgb.shape
-
-        def flat(ts):  # the C layout: triple after triple, back to back
-            p = ts[0].data_ptr()
-            for t in ts:
-                if not t.is_contiguous() or t.data_ptr() != p or t.untyped_storage().data_ptr() != ts[0].untyped_storage().data_ptr():
-                    return torch.cat([x.reshape(-1) for x in ts])
-                p += t.numel()
-            return ts[0]
-        U, V = flat([f[0] for f in factors]), flat([f[1] for f in factors])
+        U, V = flat_views([f[0] for f in factors]), flat_views([f[1] for f in factors])
         sse = torch.empty((len(triples), B), dtype=torch.int64, device=rgb.device)
         R = (c_int * (3 * len(triples)))(*[int(r) for t in triples for r in t])
         self.use_torch_stream()

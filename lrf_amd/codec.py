@@ -145,24 +145,52 @@ def select_target(sse: torch.Tensor, n: int, target: torch.Tensor):
     return table, torch.where(reached, first_ok, best), reached
 
 
-def _check_target_args(images, psnr, qualities, num_iters):
-    """qmf_encode_target's refusals, raised before a GPU is asked for -> (qualities as a list, target as float64 [B])"""
+def _check_sweep_args(images, qualities, num_iters, name):
+    """what qmf_encode_target and qmf_encode_budget refuse about images, qualities and num_iters -> qualities as a list"""
     if not isinstance(images, torch.Tensor):
-        raise TypeError(f"qmf_encode_target takes a tensor of images, got {type(images).__name__}")
+        raise TypeError(f"{name} takes a tensor of images, got {type(images).__name__}")
     if images.dtype != torch.uint8:
-        raise NotImplementedError("qmf_encode_target: the HIP path takes uint8 images")
+        raise NotImplementedError(f"{name}: the HIP path takes uint8 images")
     if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
-        raise ValueError(f"qmf_encode_target takes a batch [B,3,H,W], got {tuple(images.shape)}")
+        raise ValueError(f"{name} takes a batch [B,3,H,W], got {tuple(images.shape)}")
     if num_iters < 1:
-        raise NotImplementedError("qmf_encode_target: num_iters = 0 (the truncated initialisation) is outside the fused sweep")
+        raise NotImplementedError(f"{name}: num_iters = 0 (the truncated initialisation) is outside the fused sweep")
     qualities = list(qualities)
     if not qualities or any(not (0 <= q <= 100) for q in qualities):
-        raise ValueError("qmf_encode_target: 'qualities' must be a non-empty sequence of numbers between 0 and 100")
+        raise ValueError(f"{name}: 'qualities' must be a non-empty sequence of numbers between 0 and 100")
+    return qualities
+
+
+def _check_target_args(images, psnr, qualities, num_iters):
+    """qmf_encode_target's refusals, raised before a GPU is asked for -> (qualities as a list, target as float64 [B])"""
+    qualities = _check_sweep_args(images, qualities, num_iters, "qmf_encode_target")
     target = torch.as_tensor(psnr, dtype=torch.float64).reshape(-1)
     B = images.shape[0]
     if target.numel() not in (1, B) or bool(torch.isnan(target).any()):
         raise ValueError(f"qmf_encode_target: 'psnr' must be one number or one per image ({B}), got {target.numel()} values")
     return qualities, target.expand(B).contiguous()
+
+
+def _sweep_candidates(images, qualities, bounds, num_iters):
+    """Every distinct rank triple of `qualities` factorised and scored on the GPU: triples within rank 32 in one fused sweep,
+    larger ones one call each -> (ctx, the images on the device, triples, the lowest quality of each, {triple: (U, V)}, sse int64
+    [Q,B] on the device)."""
+    H, W = images.shape[-2:]
+    B = images.shape[0]
+    triples, lowest = target_candidates((H, W), qualities)
+    ctx = _lib.context(images.device.index if images.is_cuda else None)
+    dev = (images if images.is_cuda else images.cuda(ctx.device)).contiguous()
+    lo, hi = math.ceil(bounds[0]), math.floor(bounds[1])
+    fused = [t for t in triples if max(t) <= 32]
+    factors = dict(zip(fused, ctx.encode_sweep_rgb(dev, fused, num_iters, lo, hi, None))) if fused else {}
+    sse = torch.empty((len(triples), B), dtype=torch.int64, device=dev.device)
+    if fused:
+        sse[[triples.index(t) for t in fused]] = ctx.sweep_sse(dev, [factors[t] for t in fused], fused)
+    for i, t in enumerate(triples):
+        if t not in factors:  # a rank above 32: the per-triple encoder, scored by a sweep of one
+            factors[t] = qmf_factorize_batch(dev, list(t), num_iters, bounds)
+            sse[i] = ctx.sweep_sse(dev, [factors[t]], [t])[0]
+    return ctx, dev, triples, lowest, factors, sse
 
 
 def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
@@ -186,19 +214,7 @@ def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds
     qualities, target = _check_target_args(images, psnr, qualities, num_iters)
     H, W = images.shape[-2:]
     B = images.shape[0]
-    triples, lowest = target_candidates((H, W), qualities)
-    ctx = _lib.context(images.device.index if images.is_cuda else None)
-    dev = (images if images.is_cuda else images.cuda(ctx.device)).contiguous()
-    lo, hi = math.ceil(bounds[0]), math.floor(bounds[1])
-    fused = [t for t in triples if max(t) <= 32]
-    factors = dict(zip(fused, ctx.encode_sweep_rgb(dev, fused, num_iters, lo, hi, None))) if fused else {}
-    sse = torch.empty((len(triples), B), dtype=torch.int64, device=dev.device)
-    if fused:
-        sse[[triples.index(t) for t in fused]] = ctx.sweep_sse(dev, [factors[t] for t in fused], fused)
-    for i, t in enumerate(triples):
-        if t not in factors:  # a rank above 32: the per-triple encoder, scored by a sweep of one
-            factors[t] = qmf_factorize_batch(dev, list(t), num_iters, bounds)
-            sse[i] = ctx.sweep_sse(dev, [factors[t]], [t])[0]
+    ctx, dev, triples, lowest, factors, sse = _sweep_candidates(images, qualities, bounds, num_iters)
     table, index, reached = select_target(sse, 3 * H * W, target)
     chosen_psnr = table.gather(0, index.reshape(1, -1))[0]
     table, index, reached, chosen_psnr = table.cpu(), index.cpu(), reached.cpu(), chosen_psnr.cpu()
@@ -209,11 +225,7 @@ def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds
             continue
         sel = rows.to(dev.device)
         if on_device:
-            Us, Vs = factors[t][0].index_select(0, sel), factors[t][1].index_select(0, sel)
-            k = rows.numel()
-            packed = streams_from_device_factors(ctx, Us, Vs, [(H, W)] * k, [t] * k, np.arange(k, dtype=np.int64) * Us.shape[1],
-                                                 np.arange(k, dtype=np.int64) * Vs.shape[1], bounds, _pack_threads(pack_workers))
-            for b, s_ in zip(rows.tolist(), packed):
+            for b, s_ in zip(rows.tolist(), _device_streams_of_rows(ctx, factors[t], sel, (H, W), t, bounds, pack_workers)):
                 streams[b] = s_
             continue
         Uh, Vh = (x.numpy() for x in ctx.to_host(factors[t][0].index_select(0, sel), factors[t][1].index_select(0, sel)))
@@ -223,6 +235,166 @@ def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds
     row_of = [triples.index(tuple(qmf_ranks((H, W), None, q))) for q in qualities]
     return {"streams": streams, "quality": [lowest[i] for i in index.tolist()], "psnr": chosen_psnr, "reached": reached,
             "table": table[row_of]}
+
+
+def _device_streams_of_rows(ctx, pair, sel, image_hw, triple, bounds, pack_workers) -> list:
+    """the deflate="device" streams of the images `sel` (a device index tensor) of one triple's factors (U [B,nu], V [B,nv])"""
+    Us, Vs = pair[0].index_select(0, sel), pair[1].index_select(0, sel)
+    k = Us.shape[0]
+    return streams_from_device_factors(ctx, Us, Vs, [tuple(image_hw)] * k, [triple] * k, np.arange(k, dtype=np.int64) * Us.shape[1],
+                                       np.arange(k, dtype=np.int64) * Vs.shape[1], bounds, _pack_threads(pack_workers))
+
+
+def container_bytes(meta_len, ranks, column_lengths):
+    """len() of the container lrf_pack_qmf_streams_deflated folds from an image's deflated columns, by host arithmetic: the
+    metadata JSON of meta_len bytes, then six factors (u_Y, v_Y, u_Cb, v_Cb, u_Cr, v_Cr), each one JSON header {"num_fibers",
+    "mode", "dtype"} in front of its ranks[c] columns; combine_bytes puts four length bytes in front of every part but the last
+    (container.py).  column_lengths: integers [..., 2 sum(ranks)] (an array or a tensor, on any device), the lengths of an image's
+    column streams in any order -> their sum over the last axis plus the constant of (meta_len, ranks), computed once for all
+    images."""
+    ranks = [int(r) for r in ranks]
+    lens = column_lengths if isinstance(column_lengths, torch.Tensor) else np.asarray(column_lengths, dtype=np.int64)
+    if len(ranks) != 3 or min(ranks) < 1 or lens.shape[-1] != 2 * sum(ranks):
+        raise ValueError(f"container_bytes: three ranks >= 1 and 2 sum(ranks) column lengths expected, got {ranks} and {tuple(lens.shape)}")
+    const = 4 + int(meta_len) + 4 * 5  # the metadata's prefix; five of the six factors carry one
+    for r in ranks:  # per factor: the header and its prefix, a prefix for every column but the last
+        const += 2 * (4 + len(dict_to_bytes({"num_fibers": r, "mode": "col", "dtype": "int8"})) + 4 * (r - 1))
+    total = lens.sum(dim=-1, dtype=torch.int64) if isinstance(lens, torch.Tensor) else lens.sum(axis=-1, dtype=np.int64)
+    return total + const
+
+
+def qmf_stream_sizes(factors, triples, image_hw, bounds=(-16, 15)) -> torch.Tensor:
+    """The exact size of every stream of a sweep, counted on the GPU without producing one (lrf_deflate_sizes_i8).  factors: one
+    (U, V) pair of int8 CUDA tensors per rank triple of `triples`, as Context.encode_sweep_rgb returns them (for one triple:
+    [qmf_factorize_batch's pair], or the pair and the triple themselves) -> int64 CUDA tensor [Q, B], out[q][b] = len() of the
+    stream streams_from_device_factors (deflate="device") produces for image b at triple q.  One count over all U matrices and
+    one over all V matrices; the factors are taken where they lie when they are consecutive views of two flat buffers and
+    concatenated otherwise.  The column lengths are summed per (q, b) on the device and the container constant of triple q added."""
+    if len(factors) == 2 and isinstance(factors[0], torch.Tensor):
+        factors, triples = [factors], [triples]
+    triples = [tuple(int(r) for r in t) for t in triples]
+    H, W = image_hw
+    if not factors or len(factors) != len(triples):
+        raise ValueError("qmf_stream_sizes needs one (U, V) pair per rank triple")
+    Ms = np.array([d[4] for d in _lib.plane_dims(H, W)], dtype=np.int64)
+    B = factors[0][0].shape[0]
+    u_mats, v_mats, uo, vo = [], [], 0, 0
+    for (U, V), t in zip(factors, triples):
+        R = np.array(t, dtype=np.int64)
+        nu, nv = int((Ms * R).sum()), 64 * int(R.sum())
+        if not (isinstance(U, torch.Tensor) and isinstance(V, torch.Tensor) and U.dtype == torch.int8 and V.dtype == torch.int8):
+            raise TypeError("factors must be int8 tensors")
+        if len(t) != 3 or min(t) < 1 or tuple(U.shape) != (B, nu) or tuple(V.shape) != (B, nv):
+            raise ValueError(f"factor buffers do not match the geometry at ranks {t}: expected int8 U {(B, nu)} and V {(B, nv)}, got "
+                             f"{tuple(U.shape)} and {tuple(V.shape)}")
+        for mats, at, per_image, first, rows in ((u_mats, uo, nu, np.cumsum(Ms * R) - Ms * R, Ms),
+                                                 (v_mats, vo, nv, 64 * (np.cumsum(R) - R), np.full(3, 64, dtype=np.int64))):
+            m = np.empty((B, 3, 3), dtype=np.int64)  # (src_off, rows, cols): image after image, plane after plane
+            m[:, :, 0] = at + per_image * np.arange(B, dtype=np.int64).reshape(B, 1) + first
+            m[:, :, 1] = rows
+            m[:, :, 2] = R
+            mats.append(m.reshape(-1, 3))
+        uo += B * nu
+        vo += B * nv
+    ctx = _lib.context(factors[0][0].device.index)
+    u_len = ctx.deflate_sizes(_lib.flat_views([f[0] for f in factors]), np.concatenate(u_mats))
+    v_len = ctx.deflate_sizes(_lib.flat_views([f[1] for f in factors]), np.concatenate(v_mats))
+    out = torch.empty((len(triples), B), dtype=torch.int64, device=u_len.device)
+    at = 0
+    for q, t in enumerate(triples):  # the lengths lie triple after triple, image after image: [B, sum(ranks)] of each kind
+        n = B * sum(t)
+        cols = torch.cat([u_len[at:at + n].view(B, -1), v_len[at:at + n].view(B, -1)], dim=1)
+        out[q] = container_bytes(len(_stream_metadata((H, W), list(t), bounds)), t, cols)
+        at += n
+    return out
+
+
+def select_budget(size: torch.Tensor, sse: torch.Tensor, budget: torch.Tensor):
+    """The choice qmf_encode_budget makes, from exact sizes and exact squared errors: size, sse int64 [Q,B] (candidate q in
+    ascending quality, image b), budget int64 [B] in bytes -> (index int64 [B], reached bool [B]).  Per image, among the
+    candidates with size <= budget the one of the LOWEST sse wins; equal sse: the smaller size; equal in both: the lowest
+    quality.  Every candidate is looked at — nothing assumes that size or error is monotonic in quality.  Where no candidate fits,
+    the smallest stream wins (equal sizes: the lowest quality) and reached is False.  Evaluated on the device the tables live on."""
+    Q = size.shape[0]
+    big = torch.iinfo(torch.int64).max
+    rank = torch.arange(Q, dtype=torch.int64, device=size.device).reshape(Q, 1)
+    fits = size <= budget.to(size.device).reshape(1, -1)
+    reached = fits.any(dim=0)
+    best = fits & (sse == torch.where(fits, sse, big).min(dim=0).values)
+    best = best & (size == torch.where(best, size, big).min(dim=0).values)
+    smallest = size == size.min(dim=0).values
+    index = torch.where(torch.where(reached, best, smallest), rank, Q).min(dim=0).values
+    return index, reached
+
+
+def _check_budget_args(images, bpp, nbytes, qualities, num_iters):
+    """qmf_encode_budget's refusals, raised before a GPU is asked for -> (qualities as a list, budget as int64 [B] in bytes)"""
+    qualities = _check_sweep_args(images, qualities, num_iters, "qmf_encode_budget")
+    if (bpp is None) == (nbytes is None):
+        raise ValueError("qmf_encode_budget: give exactly one of 'bpp' and 'nbytes'")
+    B, _, H, W = images.shape
+    name, value = ("bpp", bpp) if bpp is not None else ("nbytes", nbytes)
+    v = torch.as_tensor(value).detach().cpu()
+    if v.dtype == torch.bool or v.is_complex():
+        raise TypeError(f"qmf_encode_budget: '{name}' must hold numbers, got {v.dtype}")
+    v = v.to(torch.float64).reshape(-1)
+    if v.numel() not in (1, B) or bool(torch.isnan(v).any()) or bool((v < 0).any()):
+        raise ValueError(f"qmf_encode_budget: '{name}' must be one number >= 0 or one per image ({B}), got {v.tolist() if v.numel() <= 8 else v.numel()}")
+    if bpp is not None:
+        v = v * H * W / 8  # bits per pixel become bytes once, in float64; everything after that is integers
+    budget = torch.floor(v).clamp(max=2.0 ** 62).to(torch.int64)
+    return qualities, budget.expand(B).contiguous()
+
+
+def qmf_encode_budget(images: torch.Tensor, bpp=None, nbytes=None, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
+                      pack_workers: Optional[int] = None) -> dict:
+    """Per image of a batch [B,3,H,W], the best stream that fits a byte budget: `nbytes` bytes, or `bpp` bits per pixel (=
+    floor(bpp H W / 8) bytes); one number, or one per image.
+
+    Default branch only (YCbCr, 8x8 patches, uint8, num_iters >= 1).  Every distinct rank triple of `qualities` is factorised
+    and scored on the GPU as in qmf_encode_target, and the size of every candidate's stream is COUNTED there, exact to the byte,
+    without producing it (qmf_stream_sizes: the device coder's streams have a length that follows from their columns' byte
+    counts alone; zlib-9 streams do not, so the budget is met by deflate="device" streams).  select_budget picks per image; only
+    the winners' factors are gathered and packed, B streams instead of Q x B, and every packed stream's length is compared with
+    the counted one (RuntimeError on a difference).
+
+    Returns {"streams": B byte streams, stream i byte-identical to qmf_encode_batch(images[i:i+1], quality=quality[i],
+    deflate="device")[0]; "quality": the chosen quality per image (the lowest of those that share its rank triple); "nbytes":
+    int64 [B], their lengths; "bpp": float64 [B], bits_per_pixel((H, W), stream); "psnr": float64 [B]; "reached": bool [B], False
+    where no candidate fits (the smallest stream is returned then); "size_table": int64 [len(qualities), B]; "table": float64
+    [len(qualities), B], the PSNR of every (quality, image) pair}.  The tensors are host tensors."""
+    from .metrics import bits_per_pixel, psnr_from_sse
+    qualities, budget = _check_budget_args(images, bpp, nbytes, qualities, num_iters)
+    H, W = images.shape[-2:]
+    B = images.shape[0]
+    ctx, dev, triples, lowest, factors, sse = _sweep_candidates(images, qualities, bounds, num_iters)
+    size = torch.empty_like(sse)
+    fused = [t for t in triples if max(t) <= 32]  # (their factors are views of two flat buffers: counted where they lie)
+    if fused:
+        size[[triples.index(t) for t in fused]] = qmf_stream_sizes([factors[t] for t in fused], fused, (H, W), bounds)
+    for i, t in enumerate(triples):
+        if max(t) > 32:
+            size[i] = qmf_stream_sizes([factors[t]], [t], (H, W), bounds)[0]
+    index, reached = select_budget(size, sse, budget)
+    table = psnr_from_sse(sse, 3 * H * W)[1]
+    chosen_psnr = table.gather(0, index.reshape(1, -1))[0]
+    counted = size.gather(0, index.reshape(1, -1))[0]
+    table, size, index, reached, chosen_psnr, counted = (x.cpu() for x in (table, size, index, reached, chosen_psnr, counted))
+    streams = [None] * B
+    for i, t in enumerate(triples):  # images choose different triples: one gather, one deflate and one fold per group
+        rows = torch.nonzero(index == i).reshape(-1)
+        if rows.numel() == 0:
+            continue
+        for b, s in zip(rows.tolist(), _device_streams_of_rows(ctx, factors[t], rows.to(dev.device), (H, W), t, bounds, pack_workers)):
+            streams[b] = s
+    for b, s in enumerate(streams):
+        if len(s) != int(counted[b]):
+            raise RuntimeError(f"qmf_encode_budget: image {b} at quality {lowest[int(index[b])]}: the stream has {len(s)} bytes, "
+                               f"{int(counted[b])} were counted")
+    row_of = [triples.index(tuple(qmf_ranks((H, W), None, q))) for q in qualities]
+    return {"streams": streams, "quality": [lowest[i] for i in index.tolist()], "nbytes": counted,
+            "bpp": torch.tensor([bits_per_pixel((H, W), s) for s in streams], dtype=torch.float64), "psnr": chosen_psnr,
+            "reached": reached, "size_table": size[row_of], "table": table[row_of]}
 
 
 def qmf_factorize_host(images: torch.Tensor, ranks: Sequence[int], num_iters: int = 10, bounds=(-16, 15), init_sign=None,

@@ -1,6 +1,7 @@
 // lrf_deflate_shared.h — the Huffman-only deflate coder of factor columns: everything that decides a stream's bytes, as plain
 // C++ that compiles as host code (lrf_pack.cpp: lrf_pack_deflate_column_i8, the CPU-testable definition) and as device code
-// (lrf_deflate_kernel.hip).  Both include this file and nothing else decides a byte, so the two cannot drift apart.
+// (lrf_deflate_kernel.hip; lrf_deflate_sizes_kernel.hip counts a stream's bytes without writing it).  All include this file and
+// nothing else decides a byte or a size, so they cannot drift apart.
 //
 // The stream (RFC 1950 around RFC 1951) of one column of `rows` bytes:
 //   header   0x78 0x01
@@ -11,7 +12,7 @@
 //              STORED   BTYPE 0 blocks of at most 65,535 bytes, as many as the length needs
 //   trailer  Adler-32, big-endian
 // Choice of form: the smallest total byte count; on equal counts STORED before FIXED before DYNAMIC (the cheaper one to write
-// and to read).  The counts are exact and known before a byte is written (lrfd_plan).
+// and to read).  The counts are exact and known before a byte is written (lrfd_measure, the first half of lrfd_plan).
 //
 // Code lengths (literals: at most 15 bits; the code-length alphabet: at most 7) come from one builder, lrfd_code_lengths:
 //   1. the used symbols in ascending (count, symbol) order — a strict order, so the sorting method cannot matter
@@ -59,6 +60,15 @@ struct lrfd_work {
     int32_t form;              // out: LRFD_DYNAMIC / LRFD_FIXED / LRFD_STORED
     uint32_t hdr_bits;         // out: bits of the stream in front of the first literal (zlib header included); STORED: 16
     int64_t stream_len;        // out: bytes of the whole stream
+};
+
+// what a caller that only counts keeps per column (lrfd_measure): 3,085 bytes instead of lrfd_work's 3,880
+struct lrfd_count {
+    uint32_t freq[LRFD_NLIT]; // in: counts of the column's bytes, freq[256] = 1
+    uint32_t w[LRFD_NLIT];    // scratch of the builder
+    uint16_t sym[LRFD_NLIT];  // scratch of the builder
+    uint8_t len[LRFD_NLIT];   // the literals' code lengths
+    uint8_t seq[LRFD_NSEQ];   // the run-length coded sequence (symbols only)
 };
 
 LRFD_HD inline int64_t lrfd_bound(int64_t len) { return 2 + 5 * ((len + LRFD_STORED_MAX - 1) / LRFD_STORED_MAX) + len + 4; }
@@ -178,59 +188,107 @@ LRFD_HD inline void lrfd_canonical(const uint8_t* len, int n, uint16_t* code)
     for (int s = 0; s < n; s++) code[s] = len[s] ? (uint16_t)lrfd_reverse(next[len[s]]++, len[s]) : 0;
 }
 
-// The plan of one column from its counts (k->freq, freq[256] = 1): the form, the exact length of the stream, the code table and
-// the bits in front of the first literal, written to hdr (LRFD_HDR_MAX bytes, zero on entry).
-LRFD_HD inline void lrfd_plan(lrfd_work* k, int64_t rows, uint8_t* hdr)
+// the RFC's order of the code-length code lengths in a dynamic block's header
+LRFD_HD inline int lrfd_cl_order(int i)
 {
     const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    lrfd_code_lengths(k->freq, LRFD_NLIT, LRFD_LIT_LIMIT, k->len, k->sym, k->w);
-    // the run-length coded sequence of the 258 lengths (the distance length 0 is the last)
+    return order[i];
+}
+
+// The run-length coded sequence of the 258 lengths (the distance length 0 is the last) by the greedy rule at the top: the
+// symbols of the code-length alphabet to seq and, where ext is not NULL, the value of each one's extra bits to ext -> how many
+LRFD_HD inline int lrfd_run_lengths(const uint8_t* len, uint8_t* seq, uint8_t* ext)
+{
     int nseq = 0;
     for (int i = 0; i < LRFD_NSEQ;) {
-        const int v = i < LRFD_NLIT ? k->len[i] : 0;
+        const int v = i < LRFD_NLIT ? len[i] : 0;
         int run = 1;
-        while (i + run < LRFD_NSEQ && (i + run < LRFD_NLIT ? k->len[i + run] : 0) == v) run++;
+        while (i + run < LRFD_NSEQ && (i + run < LRFD_NLIT ? len[i + run] : 0) == v) run++;
         i += run;
         if (v == 0) {
             while (run >= 11) {
                 const int t = run < 138 ? run : 138;
-                k->seq[nseq] = 18; k->ext[nseq++] = (uint8_t)(t - 11);
+                if (ext) ext[nseq] = (uint8_t)(t - 11);
+                seq[nseq++] = 18;
                 run -= t;
             }
-            if (run >= 3) { k->seq[nseq] = 17; k->ext[nseq++] = (uint8_t)(run - 3); run = 0; }
-            for (; run > 0; run--) { k->seq[nseq] = 0; k->ext[nseq++] = 0; }
+            if (run >= 3) {
+                if (ext) ext[nseq] = (uint8_t)(run - 3);
+                seq[nseq++] = 17;
+                run = 0;
+            }
+            for (; run > 0; run--) {
+                if (ext) ext[nseq] = 0;
+                seq[nseq++] = 0;
+            }
         } else {
-            k->seq[nseq] = (uint8_t)v; k->ext[nseq++] = 0;
+            if (ext) ext[nseq] = 0;
+            seq[nseq++] = (uint8_t)v;
             run--;
             while (run >= 3) {
                 const int t = run < 6 ? run : 6;
-                k->seq[nseq] = 16; k->ext[nseq++] = (uint8_t)(t - 3);
+                if (ext) ext[nseq] = (uint8_t)(t - 3);
+                seq[nseq++] = 16;
                 run -= t;
             }
-            for (; run > 0; run--) { k->seq[nseq] = (uint8_t)v; k->ext[nseq++] = 0; }
+            for (; run > 0; run--) {
+                if (ext) ext[nseq] = 0;
+                seq[nseq++] = (uint8_t)v;
+            }
         }
     }
+    return nseq;
+}
+
+// what lrfd_measure decides
+struct lrfd_measured {
+    int32_t form;       // LRFD_DYNAMIC / LRFD_FIXED / LRFD_STORED
+    int32_t nseq;       // entries of seq
+    int32_t hclen;      // code-length code lengths sent
+    int64_t stream_len; // bytes of the whole stream
+    uint8_t cllen[19];  // lengths of the code-length code
+};
+
+// The size of one column's stream from its counts alone (freq[LRFD_NLIT], freq[256] = 1): the literals' code lengths (len), the
+// run-length sequence (seq), the code-length code, the exact byte counts of the three forms and the tie rule.  Everything that
+// decides a size is here; no code, no extra bits and no header byte is touched, so a caller that only counts (k_deflate_sizes,
+// lrf_pack_deflate_size_column_i8) keeps an lrfd_count per column instead of an lrfd_work.  w, sym: scratch of LRFD_NLIT entries.
+LRFD_HD inline void lrfd_measure(const uint32_t* freq, uint32_t* w, uint16_t* sym, uint8_t* len, uint8_t* seq, int64_t rows, lrfd_measured* m)
+{
+    lrfd_code_lengths(freq, LRFD_NLIT, LRFD_LIT_LIMIT, len, sym, w);
+    const int nseq = lrfd_run_lengths(len, seq, nullptr);
     uint32_t clfreq[19];
-    uint8_t cllen[19];
-    uint16_t clcode[19];
     for (int s = 0; s < 19; s++) clfreq[s] = 0;
-    for (int i = 0; i < nseq; i++) clfreq[k->seq[i]]++;
-    lrfd_code_lengths(clfreq, 19, LRFD_CL_LIMIT, cllen, k->sym, k->w);
-    lrfd_canonical(cllen, 19, clcode);
+    for (int i = 0; i < nseq; i++) clfreq[seq[i]]++;
+    lrfd_code_lengths(clfreq, 19, LRFD_CL_LIMIT, m->cllen, sym, w);
     int hclen = 19;
-    while (hclen > 4 && cllen[order[hclen - 1]] == 0) hclen--;
+    while (hclen > 4 && m->cllen[lrfd_cl_order(hclen - 1)] == 0) hclen--;
     // exact bit counts of the three forms
     uint64_t dyn_bits = 3 + 5 + 5 + 4 + 3 * (uint64_t)hclen, fix_bits = 3;
-    for (int i = 0; i < nseq; i++) dyn_bits += cllen[k->seq[i]] + (k->seq[i] == 16 ? 2 : k->seq[i] == 17 ? 3 : k->seq[i] == 18 ? 7 : 0);
+    for (int i = 0; i < nseq; i++) dyn_bits += m->cllen[seq[i]] + (seq[i] == 16 ? 2 : seq[i] == 17 ? 3 : seq[i] == 18 ? 7 : 0);
     for (int s = 0; s < LRFD_NLIT; s++) {
-        dyn_bits += (uint64_t)k->freq[s] * k->len[s];
-        fix_bits += (uint64_t)k->freq[s] * (s < 144 ? 8 : s < 256 ? 9 : 7);
+        dyn_bits += (uint64_t)freq[s] * len[s];
+        fix_bits += (uint64_t)freq[s] * (s < 144 ? 8 : s < 256 ? 9 : 7);
     }
     const int64_t dyn_len = 2 + (int64_t)((dyn_bits + 7) / 8) + 4, fix_len = 2 + (int64_t)((fix_bits + 7) / 8) + 4;
-    k->form = LRFD_STORED;
-    k->stream_len = lrfd_bound(rows);
-    if (fix_len < k->stream_len) { k->form = LRFD_FIXED; k->stream_len = fix_len; }
-    if (dyn_len < k->stream_len) { k->form = LRFD_DYNAMIC; k->stream_len = dyn_len; }
+    m->form = LRFD_STORED;
+    m->stream_len = lrfd_bound(rows);
+    if (fix_len < m->stream_len) { m->form = LRFD_FIXED; m->stream_len = fix_len; }
+    if (dyn_len < m->stream_len) { m->form = LRFD_DYNAMIC; m->stream_len = dyn_len; }
+    m->nseq = nseq;
+    m->hclen = hclen;
+}
+
+// The plan of one column from its counts (k->freq, freq[256] = 1): the form, the exact length of the stream (lrfd_measure), then
+// the code table and the bits in front of the first literal, written to hdr (LRFD_HDR_MAX bytes, zero on entry).
+LRFD_HD inline void lrfd_plan(lrfd_work* k, int64_t rows, uint8_t* hdr)
+{
+    lrfd_measured m;
+    lrfd_measure(k->freq, k->w, k->sym, k->len, k->seq, rows, &m);
+    const uint8_t* cllen = m.cllen;
+    const int nseq = m.nseq, hclen = m.hclen;
+    k->form = m.form;
+    k->stream_len = m.stream_len;
     hdr[0] = 0x78;
     hdr[1] = 0x01;
     uint64_t pos = 16;
@@ -246,11 +304,14 @@ LRFD_HD inline void lrfd_plan(lrfd_work* k, int64_t rows, uint8_t* hdr)
         return;
     }
     lrfd_canonical(k->len, LRFD_NLIT, k->code);
+    uint16_t clcode[19];
+    lrfd_canonical(cllen, 19, clcode);
+    lrfd_run_lengths(k->len, k->seq, k->ext); // (the same sequence again, now with the extra bits)
     lrfd_put_bits(hdr, pos, 2, 2); pos += 2;
     lrfd_put_bits(hdr, pos, LRFD_NLIT - 257, 5); pos += 5; // HLIT
     lrfd_put_bits(hdr, pos, 0, 5); pos += 5;               // HDIST: one code
     lrfd_put_bits(hdr, pos, (uint32_t)(hclen - 4), 4); pos += 4;
-    for (int i = 0; i < hclen; i++) { lrfd_put_bits(hdr, pos, cllen[order[i]], 3); pos += 3; }
+    for (int i = 0; i < hclen; i++) { lrfd_put_bits(hdr, pos, cllen[lrfd_cl_order(i)], 3); pos += 3; }
     for (int i = 0; i < nseq; i++) {
         const int s = k->seq[i];
         lrfd_put_bits(hdr, pos, clcode[s], cllen[s]); pos += cllen[s];

@@ -580,6 +580,18 @@ int64_t lrf_pack_deflate_column_i8(const int8_t* src, int64_t rows, int64_t stri
     return k.stream_len;
 }
 
+int64_t lrf_pack_deflate_size_column_i8(const int8_t* src, int64_t rows, int64_t stride)
+{
+    if (!src || rows < 1 || rows > LRFD_MAX_ROWS || stride < 1) return -1;
+    lrfd_count k;
+    lrfd_measured m;
+    memset(&k, 0, sizeof(k));
+    for (int64_t i = 0; i < rows; i++) k.freq[(uint8_t)src[i * stride]]++;
+    k.freq[256] = 1;
+    lrfd_measure(k.freq, k.w, k.sym, k.len, k.seq, rows, &m);
+    return m.stream_len;
+}
+
 int lrf_pack_qmf_streams_deflated(const uint8_t* slots, int64_t slots_len, int64_t n, const int64_t* M /* [n][3] */, const int* R /* [n][3] */,
                                   const int64_t* col_off, const int32_t* col_len, int64_t ncols, const char* const* metadata,
                                   const int64_t* metadata_len, int threads, uint8_t** out, int64_t* out_len)
