@@ -286,6 +286,50 @@ int lrf_qmf_decode_crops_rgb_u8(lrf_ctx* ctx, int64_t n_images, const lrf_ragged
                                 int64_t w, uint8_t* rgb /* [n_crops][3][h][w] */, int64_t rgb_len);
 
 /*
+ * Compressed images at 1/2, 1/4 or 1/8 scale straight from their factors: the decode of lrf/compression/qmf.py:329-351,
+ * lrf/factorization/qmf.py:216-223, lrf/compression/utils.py:50-73,98-105,135-182 with an area pooling in front of its colour
+ * conversion (utils.py:50-73), without the full-resolution pixels.  lrf_scaled_dims: the scaled size, Hs = ceil(H / scale),
+ * Ws = ceil(W / scale); LRF_EINVAL for a scale outside {2, 4, 8}, a size outside [1,2^31) or a NULL pointer.
+ * Output pixel (i, j) covers image rows scale i .. min(scale i + scale, H) - 1 and the columns likewise (n pixels: the partial
+ * blocks at the bottom and right edge average the pixels that exist).  Per plane the integers the decoder holds before its
+ * colour conversion — luma at the pixel, chroma at its nearest-neighbour sample min(floor(float(y) * (float(h_c) / float(H))),
+ * h_c - 1) — are summed exactly (int32), the mean is float(sum) / float(n), and the means go through the decoder's colour
+ * chain, clamp and truncation.  A luma patch is u . V^T, so a block's sum is u . (the sum of those rows of V): the pooling
+ * moves onto a small table per image, the call reads the same U and writes 1 / scale^2 of the pixels.
+ *   images  [n] descriptors in host memory, as for lrf_qmf_decode_ragged_rgb_u8; image i is written as [3][Hs_i][Ws_i] at rgb_off
+ * Images whose sides are multiples of 16 and whose ranks lie inside the tiled decoders' bounds (32, 16, 16) take the tiled kernel,
+ * every other geometry and rank the general one; both give the bytes of the definition above, and an image's bytes depend on
+ * nothing else in the call.  Launches: one that builds the pooled tables, one per (scale, rank-bound class) of the tiled images
+ * and one per scale of the others: at most 1 + 5 + 1 here, 1 + 15 + 3 in the crops entry.
+ * Asynchronous on the context's stream and timed under LRF_K_DECODE.  The image descriptors stay on the device between calls,
+ * keyed on their bytes and shared with lrf_qmf_decode_crops_rgb_u8 (lrf_ctx_trim releases them); the item list travels
+ * stream-ordered through that entry's pinned staging slots.  Everything is validated on the host before any launch, and a
+ * refused call writes nothing.  LRF_EINVAL: a NULL pointer, n outside [1,65535], a scale outside {2, 4, 8}, a rank outside
+ * [1,64], a size the uniform decoder refuses, a negative offset, a U, V or rgb range that leaves its buffer, 2^31 or more
+ * workgroups in one launch.
+ */
+int lrf_scaled_dims(int64_t H, int64_t W, int scale, int64_t* Hs, int64_t* Ws);
+int lrf_qmf_decode_scaled_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_image* images /* host */, int scale, const int8_t* U, int64_t u_len,
+                                 const int8_t* V, int64_t v_len, uint8_t* rgb, int64_t rgb_len);
+
+/*
+ * Windows of scaled images: n_crops windows of one size (h, w), each out of the image `image` at its own scale — a loader takes
+ * each window from the level nearest the zoom it drew.  Window j = rows y0 .. y0 + h - 1, columns x0 .. x0 + w - 1 of the scaled
+ * image, equal byte for byte to that slice of what lrf_qmf_decode_scaled_rgb_u8 writes for the image at that scale (a whole
+ * image is the window (0, 0, Hs, Ws): the two entries share their kernels); written as [3][h][w] at 3 h w j.
+ * As lrf_qmf_decode_crops_rgb_u8 otherwise: images (rgb_off ignored), the resident descriptors, the staging slots, the
+ * validation before any launch.  LRF_EINVAL in addition to the list above: n_images outside [1,65535], n_crops outside
+ * [1,2^20], h or w below 1, a crop whose image index is out of range, whose scale is outside {2, 4, 8} or whose rectangle
+ * leaves its image's scaled size.
+ */
+typedef struct {
+    int32_t image, scale, y0, x0; /* y0, x0 in the scaled image */
+} lrf_scaled_crop;
+int lrf_qmf_decode_scaled_crops_rgb_u8(lrf_ctx* ctx, int64_t n_images, const lrf_ragged_image* images /* host; rgb_off ignored */, const int8_t* U,
+                                       int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops, const lrf_scaled_crop* crops /* host */,
+                                       int64_t h, int64_t w, uint8_t* rgb /* [n_crops][3][h][w] */, int64_t rgb_len);
+
+/*
  * The fused encode (lrf/compression/qmf.py:227-262) for a list of n images that differ in size and in ranks, in one call: what a
  * dataset of mixed sizes or a per-image quality choice hands to an encoder.
  *   images  [n] descriptors in host memory

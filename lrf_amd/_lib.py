@@ -43,6 +43,11 @@ class Crop(ctypes.Structure):
     _fields_ = [("image", ctypes.c_int32), ("y0", ctypes.c_int32), ("x0", ctypes.c_int32)]
 
 
+class ScaledCrop(ctypes.Structure):
+    """lrf_scaled_crop (include/lrf_hip.h)"""
+    _fields_ = [("image", ctypes.c_int32), ("scale", ctypes.c_int32), ("y0", ctypes.c_int32), ("x0", ctypes.c_int32)]
+
+
 class RaggedEncodeImage(ctypes.Structure):
     """lrf_ragged_encode_image (include/lrf_hip.h)"""
     _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int * 3), ("rgb_off", c_i64), ("u_off", c_i64), ("v_off", c_i64), ("sign_off", c_i64)]
@@ -96,6 +101,10 @@ def load():
         lib.lrf_qmf_decode_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_decode_crops_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_i64, ctypes.POINTER(Crop),
                                                     c_i64, c_i64, c_void_p, c_i64]
+        lib.lrf_scaled_dims.argtypes = [c_i64, c_i64, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
+        lib.lrf_qmf_decode_scaled_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_decode_scaled_crops_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_i64,
+                                                           ctypes.POINTER(ScaledCrop), c_i64, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_encode_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedEncodeImage), c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64,
                                                      c_void_p, c_i64, c_void_p, c_i64]
         lib.lrf_deflate_bound.restype = c_i64
@@ -148,7 +157,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -326,6 +335,75 @@ def check_crop_args(U, V, images, crops, size):
     if bad.size:
         j = bad[0]
         raise ValueError(f"crop {j}: {h}x{w} at ({boxes[j, 1]}, {boxes[j, 2]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]}")
+    return ims, np.ascontiguousarray(boxes, dtype=np.int32), (h, w)
+
+
+SCALES = (2, 4, 8)  # lrf_qmf_decode_scaled_rgb_u8
+
+
+def scaled_dims(H, W, scale):
+    """(ceil(H / scale), ceil(W / scale)): the size of an H x W image decoded at 1/scale (lrf_scaled_dims)"""
+    if isinstance(scale, bool) or int(scale) != scale or int(scale) not in SCALES:
+        raise ValueError(f"scale {scale!r}: 2, 4 or 8 expected")
+    if H < 1 or W < 1:
+        raise ValueError(f"size {H}x{W} out of range")
+    scale = int(scale)
+    return -(-int(H) // scale), -(-int(W) // scale)
+
+
+def check_scaled_args(U, V, images, scale=None, crops=None, size=None):
+    """The argument checks of lrf_qmf_decode_scaled_rgb_u8 (scale: 2, 4 or 8; crops and size None) and of
+    lrf_qmf_decode_scaled_crops_rgb_u8 (scale None; crops: an integer array-like [n, 4] of (image, scale, y0, x0) on the host,
+    1 <= n <= 2^20, y0 and x0 in the scaled image; size: (h, w), both >= 1; every window inside its image's scaled size), before
+    any device is touched.  U, V, images: as check_ragged_args takes them.  TypeError for factors that are not int8 tensors and
+    for scales, boxes or sizes that are not integers, ValueError for everything else.
+    -> (images as check_ragged_args returns them, scale) or (images, crops as an int32 array [n, 4], (h, w))."""
+    import numpy as np
+    ims = check_ragged_args(U, V, images)
+    if crops is None and size is None:
+        if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)):
+            raise TypeError(f"scale must be an integer, got {scale!r}")
+        if int(scale) not in SCALES:
+            raise ValueError(f"scale {scale}: 2, 4 or 8 expected")
+        return ims, int(scale)
+    if scale is not None or crops is None or size is None:
+        raise ValueError("give either a scale (whole images) or crops of (image, scale, y0, x0) and a size")
+    try:
+        h, w = size
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (h, w), got {size!r}") from None
+    if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in (h, w)):
+        raise TypeError(f"size must hold two integers, got {size!r}")
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"crop size {h}x{w}: both sides must be >= 1")
+    if hasattr(crops, "detach"):  # a torch tensor
+        if crops.is_cuda:
+            raise ValueError("crops live on the host: the call validates every box before it launches")
+        crops = crops.detach().numpy()
+    boxes = np.asarray(crops)
+    if boxes.size == 0:
+        raise ValueError("decode_scaled_crops needs 1 to 2^20 crops")
+    if boxes.dtype.kind not in "iu":
+        raise TypeError(f"crops must be integers (image, scale, y0, x0), got {boxes.dtype}")
+    if boxes.ndim != 2 or boxes.shape[1] != 4:
+        raise ValueError(f"crops must be [n, 4] (image, scale, y0, x0), got shape {tuple(boxes.shape)}")
+    if boxes.shape[0] > 2 ** 20:
+        raise ValueError("decode_scaled_crops needs 1 to 2^20 crops")
+    boxes = boxes.astype(np.int64)
+    bad = np.flatnonzero((boxes[:, 0] < 0) | (boxes[:, 0] >= len(ims)))
+    if bad.size:
+        raise ValueError(f"crop {bad[0]}: image {boxes[bad[0], 0]} out of range [0, {len(ims)})")
+    bad = np.flatnonzero(~np.isin(boxes[:, 1], SCALES))
+    if bad.size:
+        raise ValueError(f"crop {bad[0]}: scale {boxes[bad[0], 1]}: 2, 4 or 8 expected")
+    f = boxes[:, 1]
+    Hs = -(-np.array([im[0] for im in ims], dtype=np.int64)[boxes[:, 0]] // f)
+    Ws = -(-np.array([im[1] for im in ims], dtype=np.int64)[boxes[:, 0]] // f)
+    bad = np.flatnonzero((boxes[:, 2] < 0) | (boxes[:, 3] < 0) | (boxes[:, 2] + h > Hs) | (boxes[:, 3] + w > Ws))
+    if bad.size:
+        j = bad[0]
+        raise ValueError(f"crop {j}: {h}x{w} at ({boxes[j, 2]}, {boxes[j, 3]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]} at scale 1/{f[j]}")
     return ims, np.ascontiguousarray(boxes, dtype=np.int32), (h, w)
 
 
@@ -677,6 +755,47 @@ class Context:
         self.use_torch_stream()
         check(self._lib.lrf_qmf_decode_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
                                                     boxes.ctypes.data_as(ctypes.POINTER(Crop)), h, w, _dptr(rgb), rgb.numel()))
+        return rgb
+
+    def decode_scaled(self, U, V, images, scale):
+        """Images at 1/scale straight from the factors (lrf_qmf_decode_scaled_rgb_u8).  U, V, images: as decode_ragged takes them;
+        scale: 2, 4 or 8 -> a list of uint8 CUDA tensors [3, ceil(H_i / scale), ceil(W_i / scale)]: views of one buffer, each
+        starting at a multiple of 16 bytes.  Asynchronous on torch's current stream."""
+        import torch
+        ims, scale = check_scaled_args(U, V, images, scale)
+        if not (U.is_cuda and U.device.index == self.device):
+            raise ValueError(f"decode_scaled needs its tensors on cuda:{self.device}, got {U.device}")
+        desc = (RaggedImage * len(ims))()
+        sizes, off = [], 0
+        for d, (H, W, ranks, u_off, v_off) in zip(desc, ims):
+            hs, ws = scaled_dims(H, W, scale)
+            d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, off
+            d.R[0], d.R[1], d.R[2] = ranks
+            sizes.append((hs, ws))
+            off = (off + 3 * hs * ws + 15) // 16 * 16
+        rgb = torch.empty((off,), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_decode_scaled_rgb_u8(self._h, len(ims), desc, scale, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(rgb), rgb.numel()))
+        return [rgb[d.rgb_off:d.rgb_off + 3 * hs * ws].view(3, hs, ws) for d, (hs, ws) in zip(desc, sizes)]
+
+    def decode_scaled_crops(self, U, V, images, crops, size):
+        """Windows of scaled images straight from the factors (lrf_qmf_decode_scaled_crops_rgb_u8).  U, V, images: as decode_ragged
+        takes them; crops: an integer array-like [n, 4] of (image, scale, y0, x0) on the host, the scale per crop out of 2, 4, 8
+        and y0, x0 in the scaled image; size: (h, w) -> a uint8 CUDA tensor [n, 3, h, w], crop j equal to decode_scaled of its
+        image at its scale sliced [:, y0:y0+h, x0:x0+w].  Asynchronous on torch's current stream."""
+        import torch
+        ims, boxes, (h, w) = check_scaled_args(U, V, images, crops=crops, size=size)
+        if not (U.is_cuda and U.device.index == self.device):
+            raise ValueError(f"decode_scaled_crops needs its tensors on cuda:{self.device}, got {U.device}")
+        desc = (RaggedImage * len(ims))()
+        for d, (H, W, ranks, u_off, v_off) in zip(desc, ims):
+            d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, 0
+            d.R[0], d.R[1], d.R[2] = ranks
+        n = boxes.shape[0]
+        rgb = torch.empty((n, 3, h, w), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_decode_scaled_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
+                                                           boxes.ctypes.data_as(ctypes.POINTER(ScaledCrop)), h, w, _dptr(rgb), rgb.numel()))
         return rgb
 
     def encode_ragged(self, rgb, images, K, lo, hi, sign=None):

@@ -1571,10 +1571,65 @@ def qmf_decode_ragged(streams: Sequence[bytes], device=None, inflate: str = "hos
     return ctx.decode_ragged(U, V, images)
 
 
+def _crop_scales(scale, n):
+    """scale: one integer or one per crop, out of 1, 2, 4, 8 -> an int64 array [n]"""
+    sc = np.asarray(scale)
+    if sc.dtype.kind not in "iu" or sc.dtype == np.bool_:
+        raise TypeError(f"scale must be an integer or one integer per crop, got {scale!r}")
+    if sc.ndim == 0:
+        sc = np.full(n, int(sc), dtype=np.int64)
+    if sc.ndim != 1 or sc.shape[0] != n:
+        raise ValueError(f"scale must be one value or one per crop ({n}), got shape {tuple(sc.shape)}")
+    bad = np.flatnonzero(~np.isin(sc, (1, 2, 4, 8)))
+    if bad.size:
+        raise ValueError(f"crop {bad[0]}: scale {sc[bad[0]]}: 1, 2, 4 or 8 expected")
+    return sc.astype(np.int64)
+
+
+def _split_crops_by_scale(U, V, images, crops, size, scale):
+    """The crops of a call with per-crop scales, split for the two kernels calls and validated (no device is touched): ->
+    (where the full-scale crops stand in the call, their boxes [n1, 3], where the scaled ones stand, their boxes [n2, 4] of
+    (image, scale, y0, x0)); either part may be empty."""
+    if hasattr(crops, "detach"):
+        if crops.is_cuda:
+            raise ValueError("crops live on the host: the call validates every box before it launches")
+        crops = crops.detach().numpy()
+    boxes = np.asarray(crops)
+    if boxes.size == 0:
+        raise ValueError("decode_crops needs 1 to 2^20 crops")
+    if boxes.dtype.kind not in "iu":
+        raise TypeError(f"crops must be integers (image, y0, x0), got {boxes.dtype}")
+    if boxes.ndim != 2 or boxes.shape[1] != 3:
+        raise ValueError(f"crops must be [n, 3] (image, y0, x0), got shape {tuple(boxes.shape)}")
+    sc = _crop_scales(scale, boxes.shape[0])
+    full, scaled = np.flatnonzero(sc == 1), np.flatnonzero(sc != 1)
+    b1 = boxes[full]
+    b2 = np.concatenate([boxes[scaled, :1], sc[scaled, None].astype(boxes.dtype), boxes[scaled, 1:]], axis=1)
+    if full.size:
+        _lib.check_crop_args(U, V, images, b1, size)
+    if scaled.size:
+        _lib.check_scaled_args(U, V, images, crops=b2, size=size)
+    return full, b1, scaled, b2
+
+
+def _decode_crops_at_scales(ctx, U, V, images, crops, size, scale) -> torch.Tensor:
+    """entries at scale 1 take Context.decode_crops, the rest Context.decode_scaled_crops; merged in call order"""
+    full, b1, scaled, b2 = _split_crops_by_scale(U, V, images, crops, size, scale)
+    if not scaled.size:
+        return ctx.decode_crops(U, V, images, b1, size)
+    if not full.size:
+        return ctx.decode_scaled_crops(U, V, images, b2, size)
+    a, b = ctx.decode_crops(U, V, images, b1, size), ctx.decode_scaled_crops(U, V, images, b2, size)
+    out = torch.empty((full.size + scaled.size,) + tuple(a.shape[1:]), dtype=torch.uint8, device=a.device)
+    out[torch.from_numpy(full).to(a.device)] = a
+    out[torch.from_numpy(scaled).to(a.device)] = b
+    return out
+
+
 class ResidentFactors:
     """The factors of a list of streams resident on one device (qmf_load_factors): flat int8 U and V, the image table decode_ragged
     takes, and the images' sizes.  A dataset kept this way costs its int8 factors, not its pixels; .decode() gives whole images,
-    .decode_crops(crops, size) windows of them."""
+    .decode_crops(crops, size) windows of them, both also at 1/2, 1/4 or 1/8 scale (scale=)."""
 
     def __init__(self, ctx, U, V, images):
         self._ctx, self.U, self.V, self.images = ctx, U, V, images
@@ -1583,13 +1638,22 @@ class ResidentFactors:
     def __len__(self):
         return len(self.images)
 
-    def decode(self) -> list:
-        """every image: what qmf_decode_ragged gives for the streams"""
-        return self._ctx.decode_ragged(self.U, self.V, self.images)
+    def scaled_sizes(self, scale) -> list:
+        """the images' sizes at 1/scale: (ceil(H / scale), ceil(W / scale)); scale 1: their sizes"""
+        return list(self.sizes) if type(scale) is int and scale == 1 else [_lib.scaled_dims(H, W, scale) for H, W in self.sizes]
 
-    def decode_crops(self, crops, size) -> torch.Tensor:
-        """crops: integers [n, 3] of (image, y0, x0) on the host; size: (h, w) -> uint8 CUDA [n, 3, h, w]"""
-        return self._ctx.decode_crops(self.U, self.V, self.images, crops, size)
+    def decode(self, scale=1) -> list:
+        """every image: what qmf_decode_ragged gives for the streams; scale 2, 4, 8: what qmf_decode_scaled gives"""
+        if type(scale) is int and scale == 1:
+            return self._ctx.decode_ragged(self.U, self.V, self.images)
+        return self._ctx.decode_scaled(self.U, self.V, self.images, scale)
+
+    def decode_crops(self, crops, size, scale=1) -> torch.Tensor:
+        """crops: integers [n, 3] of (image, y0, x0) on the host; size: (h, w) -> uint8 CUDA [n, 3, h, w].  scale: 1, 2, 4, 8 or
+        one of them per crop: crop j is the window (y0, x0) of its image decoded at 1/scale_j, y0 and x0 in that scaled image"""
+        if type(scale) is int and scale == 1:
+            return self._ctx.decode_crops(self.U, self.V, self.images, crops, size)
+        return _decode_crops_at_scales(self._ctx, self.U, self.V, self.images, crops, size, scale)
 
 
 def _resident(images, Uh, Vh, device) -> ResidentFactors:
@@ -1607,20 +1671,46 @@ def qmf_load_factors(streams: Sequence[bytes], device=None, inflate: str = "host
     return _resident(*_factors_ragged(streams), device)
 
 
-def qmf_decode_crops(source, crops, size, device=None, inflate: str = "host") -> torch.Tensor:
+def qmf_decode_crops(source, crops, size, device=None, inflate: str = "host", scale=1) -> torch.Tensor:
     """Windows of compressed images without decoding the images: source is a list of streams (parsed and uploaded for this call)
     or the ResidentFactors of qmf_load_factors (nothing but the crop list travels); crops: integers [n, 3] of (image, y0, x0) on
     the host; size: (h, w) -> uint8 CUDA [n, 3, h, w], crop j equal to qmf_decode(stream)[:, y0:y0+h, x0:x0+w].
-    inflate="device" (a list of streams only): their columns are inflated on the GPU."""
+    inflate="device" (a list of streams only): their columns are inflated on the GPU.
+    scale: 1, 2, 4, 8 or one of them per crop: crop j is then that window of qmf_decode_scaled(stream, scale_j)."""
     on_device = _check_inflate(inflate)
     if on_device and not isinstance(source, ResidentFactors):
         ctx, images, U, V = _factors_ragged_device(source, device)
         source = ResidentFactors(ctx, U, V, images)
     if not isinstance(source, ResidentFactors):
         images, Uh, Vh = _factors_ragged(source)
-        _lib.check_crop_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, crops, size)  # refused before a GPU is asked for
+        if type(scale) is int and scale == 1:
+            _lib.check_crop_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, crops, size)  # refused before a GPU is asked for
+        else:
+            _split_crops_by_scale(torch.from_numpy(Uh), torch.from_numpy(Vh), images, crops, size, scale)
         source = _resident(images, Uh, Vh, device)
-    return source.decode_crops(crops, size)
+    return source.decode_crops(crops, size, scale)
+
+
+def qmf_decode_scaled(source, scale, device=None, inflate: str = "host") -> list:
+    """Thumbnails, previews, the coarse level a resampling loader starts from: the images at 1/2, 1/4 or 1/8 scale straight from
+    their factors, without the full-resolution pixels.  source: a list of streams or the ResidentFactors of qmf_load_factors;
+    scale: 2, 4 or 8 -> a list of uint8 CUDA tensors [3, ceil(H_i / scale), ceil(W_i / scale)] in input order.  Pixel (i, j) is
+    the decoder's image before its colour conversion averaged over the scale x scale block of image pixels it covers (the
+    partial blocks at the bottom and right edge over the pixels that exist), then converted, clamped and truncated: within
+    half a level on average of block-averaging qmf_decode's bytes, which truncates and clamps before it averages.  The default
+    branch only (YCbCr, 8x8 patches, chroma (0.5, 0.5), uint8): a stream of another branch raises NotImplementedError naming it.
+    inflate="device" (a list of streams only): their columns are inflated on the GPU."""
+    on_device = _check_inflate(inflate)
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)):
+        raise TypeError(f"scale must be an integer, got {scale!r}")
+    if int(scale) not in _lib.SCALES:
+        raise ValueError(f"scale {scale}: 2, 4 or 8 expected")
+    if isinstance(source, ResidentFactors):
+        return source.decode(int(scale))
+    if on_device:
+        ctx, images, U, V = _factors_ragged_device(source, device)
+        return ctx.decode_scaled(U, V, images, int(scale))
+    return _resident(*_factors_ragged(source), device).decode(int(scale))
 
 
 def _qmf_decode_rgbspace(encoded_image: bytes, device=None) -> torch.Tensor:

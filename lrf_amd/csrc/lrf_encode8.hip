@@ -9,6 +9,7 @@
 #include "lrf_sweep_sse_kernel.hip"
 #include "lrf_decode_ragged_kernel.hip"
 #include "lrf_decode_crops_kernel.hip"
+#include "lrf_decode_scaled_kernel.hip"
 #include "lrf_planes_ragged_kernel.hip"
 
 // gram_exp: the fixed-point grid exponent of the exact Gram matrix (max|x| < 2^gram_exp) when the caller knows it — 8 for the
@@ -778,9 +779,8 @@ int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* 
 // turns; a slot is written again only after the event recorded behind its last copy says that copy has run (a wait for that
 // one copy at most, LRF_CROP_SLOTS calls back).  The device table is one buffer: the copy of a call is ordered behind the
 // kernels of the call before it on the same stream.
-static int stage_crop_table(lrf_ctx* c, const std::vector<CropEntry>& table)
+static int stage_crop_bytes(lrf_ctx* c, const void* table, size_t bytes)
 {
-    const size_t bytes = table.size() * sizeof(CropEntry);
     int rc = ensure(c, c->crop_tab, bytes);
     if (rc) return rc;
     lrf_ctx::CropSlot& s = c->crop_slot[c->crop_next];
@@ -795,12 +795,13 @@ static int stage_crop_table(lrf_ctx* c, const std::vector<CropEntry>& table)
         HIP_TRY(hipHostMalloc(&s.h, bytes + bytes / 2, hipHostMallocDefault));
         s.cap = bytes + bytes / 2;
     }
-    memcpy(s.h, table.data(), bytes);
+    memcpy(s.h, table, bytes);
     HIP_TRY(hipMemcpyAsync(c->crop_tab.p, s.h, bytes, hipMemcpyHostToDevice, c->stream));
     s.in_flight = true;
     HIP_TRY(hipEventRecord(s.copied, c->stream));
     return LRF_OK;
 }
+static int stage_crop_table(lrf_ctx* c, const std::vector<CropEntry>& table) { return stage_crop_bytes(c, table.data(), table.size() * sizeof(CropEntry)); }
 
 // n_crops windows of one size (h, w) out of a list of images that differ in size and ranks (kernels:
 // lrf_decode_crops_kernel.hip; the launches: plan_decode_crops).  Everything the kernels index with is checked here, before
@@ -1004,3 +1005,5 @@ int lrf_debug_read_gram_stamps(lrf_ctx* c, unsigned long long* out_host, int n)
 #endif
 
 } // extern "C"
+
+#include "lrf_decode_scaled_host.inc"

@@ -91,6 +91,7 @@ struct lrf_ctx {
     };
     CropSlot crop_slot[LRF_CROP_SLOTS];
     int crop_next = 0;
+    DevBuf scaled_pool; // lrf_qmf_decode_scaled_*: the pooled V tables (int16) of the call in flight, written by its k_pool_v
     DevBuf enc_ragged_tab; // lrf_qmf_encode_ragged_rgb_u8: the image descriptors (EncRaggedDesc), behind them the workgroup table ...
     std::vector<char> enc_ragged_key; // ... and the descriptor bytes now resident there
     DevBuf deflate_tab; // lrf_deflate_columns_i8: the matrix table (DeflateMat) of the call in flight, filled stream-ordered from ...

@@ -97,6 +97,19 @@ struct CropEntry {
     int out;           // which [3][h][w] of the output it fills: its place in the caller's list
 };
 
+// ---- the decode at 1/2, 1/4, 1/8 scale (lrf_qmf_decode_scaled_rgb_u8, lrf_qmf_decode_scaled_crops_rgb_u8; kernels:
+// lrf_decode_scaled_kernel.hip) ----
+// One window of one scaled image, as the kernels read it (a uniform load per workgroup); a whole image is the window
+// (0, 0, ceil(H / f), ceil(W / f)).  image: an index into RaggedDesc
+struct ScaledItem {
+    int image, f;      // the scale: 2, 4 or 8
+    int y0, x0, h, w;  // the window inside the scaled image
+    int place;         // its place in the caller's list
+    int pad;
+    long out_off;      // bytes from rgb to its [3][h][w]
+    long pool_off;     // tiled body: int16 elements from the pooled-table workspace to the tables of (image, f)
+};
+
 // ---- the ragged encode (lrf_qmf_encode_ragged_rgb_u8; kernels: lrf_planes_ragged_kernel.hip) ----
 // One image of the call, as the planes kernels read it (uniform loads, like RaggedDesc; the workgroup table is RaggedBlock's:
 // image, unit = strip * per_strip + column group)

@@ -1492,6 +1492,16 @@ __device__ __forceinline__ float recon_at(const int8_t* __restrict__ Uc, const i
     return acc;
 }
 
+// The colour chain of k_decode (k-ordered fmas from 0) without the steps that cannot change a bit for finite values:
+// fma(1, c0, 0) = c0, fma(0, c, acc) = acc.  c0 = Y, c1 = Cb + -128.f, c2 = Cr + -128.f -> R, G, B before the clamp.  The fast
+// decoders and the scaled decoders (lrf_decode_scaled_kernel.hip) share it.
+__device__ __forceinline__ void decode_colour(float c0, float c1, float c2, float (&ch)[3])
+{
+    ch[0] = fmaf(1.402f, c2, c0);
+    ch[1] = fmaf(-0.714136f, c2, fmaf(-0.344136f, c1, c0));
+    ch[2] = fmaf(1.772f, c1, c0);
+}
+
 // Fast path for ranks <= 8 (the default sweeps): the three V tables of the image sit in LDS as floats (zero padded
 // to 8 columns), a thread keeps the u row of the patch it is in and reloads it only when the patch changes (four
 // horizontally adjacent pixels touch at most two luma and two chroma patches), and the four output bytes of a
@@ -1543,9 +1553,8 @@ __device__ __forceinline__ void decode8_quad(const int8_t* (&Uc)[3], const int (
             c1 = recon(1, yyc, sx + g.p[1].left_crop) + -128.f;
             c2 = recon(2, yyc, sx + g.p[2].left_crop) + -128.f;
         }
-        // the colour chain of k_decode (k-ordered fmas from 0) without the steps that cannot change a bit for finite values:
-        // fma(1, c0, 0) = c0, fma(0, c, acc) = acc; clamp + truncation as one v_med3 + conversion
-        const float chv[3] = {fmaf(1.402f, c2, c0), fmaf(-0.714136f, c2, fmaf(-0.344136f, c1, c0)), fmaf(1.772f, c1, c0)};
+        float chv[3]; // clamp + truncation as one v_med3 + conversion
+        decode_colour(c0, c1, c2, chv);
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) packed[ch] |= (uint32_t)__builtin_amdgcn_fmed3f(chv[ch], 0.f, 255.f) << (8 * i);
     }
@@ -1673,11 +1682,12 @@ __device__ __forceinline__ void decode_row8(const float (&ul)[RL], const float* 
     for (int h = 0; h < 2; h++) {
         float ch[3][4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) { // the k-ordered chains without their no-op steps
-            const float c0 = y[4 * h + i], c1 = cb[2 * h + (i >> 1)], c2 = cr[2 * h + (i >> 1)];
-            ch[0][i] = fmaf(1.402f, c2, c0);
-            ch[1][i] = fmaf(-0.714136f, c2, fmaf(-0.344136f, c1, c0));
-            ch[2][i] = fmaf(1.772f, c1, c0);
+        for (int i = 0; i < 4; i++) {
+            float t[3];
+            decode_colour(y[4 * h + i], cb[2 * h + (i >> 1)], cr[2 * h + (i >> 1)], t);
+            ch[0][i] = t[0];
+            ch[1][i] = t[1];
+            ch[2][i] = t[2];
         }
 #pragma unroll
         for (int k = 0; k < 3; k++) {

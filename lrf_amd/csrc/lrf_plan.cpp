@@ -325,6 +325,65 @@ CropPlan plan_decode_crops(const std::vector<RaggedWork>& images, const std::vec
     return p;
 }
 
+// ---- the launches of a decode at 1/2, 1/4, 1/8 scale ----------------------------------------------------------------------------
+// The table is a stable sort of the call's items by (path, f, class): the tiled body is instantiated per scale and rank-bound
+// class, the general body reads the scale from the item and takes one launch per scale (the items of a scale are of a similar
+// size, and a launch's grid is its largest item's).  The tiled items of one (image, f) share one set of pooled tables.
+ScaledPlan plan_decode_scaled(const std::vector<ScaledImage>& images, const std::vector<ScaledItem>& items)
+{
+    ScaledPlan p;
+    const int nslots = LRF_SCALED_MAX_LAUNCHES;
+    auto fi = [](int f) { return f == 2 ? 0 : (f == 4 ? 1 : 2); };
+    auto slot_of = [&](const ScaledItem& e) {
+        const ScaledImage& im = images[(size_t)e.image];
+        return im.tiled ? fi(e.f) * LRF_DEC_CLASSES + im.cls : 3 * LRF_DEC_CLASSES + fi(e.f);
+    };
+    auto wgs_of = [&](const ScaledItem& e) { return images[(size_t)e.image].tiled ? scaled_tiled_wgs(e.f, e.y0, e.x0, e.h, e.w) : scaled_any_wgs(e.h, e.w); };
+    std::vector<long> count((size_t)nslots, 0), wgs((size_t)nslots, 0);
+    for (const ScaledItem& e : items) {
+        const int s = slot_of(e);
+        const long g = wgs_of(e);
+        count[(size_t)s]++;
+        if (g > wgs[(size_t)s]) wgs[(size_t)s] = g;
+    }
+    for (int s = 0; s < nslots; s++)
+        if (count[(size_t)s] && (wgs[(size_t)s] >= (1L << 31) || count[(size_t)s] * wgs[(size_t)s] >= (1L << 31))) {
+            p.too_many = wgs[(size_t)s] >= (1L << 31) ? wgs[(size_t)s] : count[(size_t)s] * wgs[(size_t)s];
+            return p;
+        }
+    std::vector<long> pool_of(images.size() * 3, -1); // (image, f) -> its tables
+    p.table.reserve(items.size());
+    for (int s = 0; s < nslots; s++) {
+        if (!count[(size_t)s]) continue;
+        ScaledLaunch l;
+        l.tiled = s < 3 * LRF_DEC_CLASSES;
+        l.f = 2 << (l.tiled ? s / LRF_DEC_CLASSES : s - 3 * LRF_DEC_CLASSES);
+        l.cls = l.tiled ? s % LRF_DEC_CLASSES : 0;
+        l.item0 = (long)p.table.size();
+        l.nitems = count[(size_t)s];
+        l.wgs = wgs[(size_t)s];
+        for (size_t j = 0; j < items.size(); j++) {
+            if (slot_of(items[j]) != s) continue;
+            ScaledItem e = items[j];
+            e.place = (int)j;
+            e.pad = 0;
+            e.pool_off = 0;
+            if (l.tiled) {
+                long& at = pool_of[(size_t)e.image * 3 + (size_t)fi(e.f)];
+                if (at < 0) {
+                    at = p.pool_elems;
+                    p.jobs.push_back(ScaledPoolJob{e.image, e.f, at});
+                    p.pool_elems += scaled_pool_elems(images[(size_t)e.image].R, e.f);
+                }
+                e.pool_off = at;
+            }
+            p.table.push_back(e);
+        }
+        p.launches.push_back(l);
+    }
+    return p;
+}
+
 // ---- geometry -----------------------------------------------------------------------------------------------------------------
 void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M)
 {

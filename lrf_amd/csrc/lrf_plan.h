@@ -4,6 +4,7 @@
 // (lrf_bcd_persist.hip).  No device, no context, no HIP: the host compiler alone builds it (tests/test_bcd_plan.py does).
 #ifndef LRF_PLAN_H
 #define LRF_PLAN_H
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -179,6 +180,95 @@ struct CropPlan {
 };
 // images: (kind, cls) per image as decode_plan classified it (units unused); crops: (image, y0, x0) in call order, validated
 CropPlan plan_decode_crops(const std::vector<RaggedWork>& images, const std::vector<CropEntry>& crops, int h, int w);
+
+// ---- decode at 1/2, 1/4, 1/8 scale: the footprint of an output pixel, the thread maps and the launches of -----------------------
+// lrf_qmf_decode_scaled_rgb_u8 / lrf_qmf_decode_scaled_crops_rgb_u8 (kernels: lrf_decode_scaled_kernel.hip) ---------------------
+// Output pixel (i, j) of an H x W image at scale f is the mean of image rows scaled_lo(i, f) .. scaled_hi(i, f, H) - 1 and the
+// columns likewise: blocks are aligned to the IMAGE, the partial ones at the bottom and right edge hold the pixels that exist.
+// The kernels and tests/test_decode_scaled_plan.py call the same functions.
+LRF_HD inline bool scaled_f_ok(int f) { return f == 2 || f == 4 || f == 8; }
+LRF_HD inline long scaled_dim(long n, int f) { return (n + f - 1) / f; }
+LRF_HD inline int scaled_lo(int i, int f) { return i * f; } // (i < ceil(n / f) <= 2^30: no wrap)
+LRF_HD inline int scaled_hi(int i, int f, int n) { return (long)i * f + f < n ? i * f + f : n; }
+// the nearest-neighbour chroma row (column) under image row (column) y of n, the chroma plane having nc: ATen's rule in fp32, as
+// every decoder of lrf_kernels.hip computes it
+LRF_HD inline int scaled_chroma_index(int y, int n, int nc)
+{
+    const float s = (float)nc / (float)n;
+    const int q = (int)floorf((float)y * s);
+    return q > nc - 1 ? nc - 1 : q;
+}
+// the chroma row under image row y and how many of the rows y .. yhi - 1 share it (the index is monotone: they are consecutive)
+LRF_HD inline int scaled_chroma_run(int y, int yhi, int n, int nc, int* q)
+{
+    *q = scaled_chroma_index(y, n, nc);
+    int m = 1;
+    while (y + m < yhi && scaled_chroma_index(y + m, n, nc) == *q) m++;
+    return m;
+}
+// Tiled body (sides multiples of 16): the unit is the chroma patch, 16 x 16 image pixels = (16 / f)^2 output pixels, a thread one
+// patch, the patches of a window row by row, 256 to a workgroup.  y0, x0, h, w: the window in scaled coordinates.
+struct ScaledTile {
+    int pr, pc;  // the chroma patch (row, column): threads past the window's last patch hold that patch and keep nothing
+    CropSpan px; // the output pixels it keeps: rows y .. y + ny - 1, columns x .. x + nx - 1 of the scaled image; ny == 0: none
+};
+LRF_HD inline long scaled_tiled_wgs(int f, int y0, int x0, int h, int w)
+{
+    const int nc = 16 / f;
+    const long npr = (y0 + h - 1) / nc - y0 / nc + 1, npc = (x0 + w - 1) / nc - x0 / nc + 1;
+    return (npr * npc + 255) / 256;
+}
+LRF_HD inline ScaledTile scaled_tile_of(int f, int y0, int x0, int h, int w, long wg, int tid)
+{
+    const int nc = 16 / f, pr0 = y0 / nc, pc0 = x0 / nc;
+    const long npr = (y0 + h - 1) / nc - pr0 + 1, npc = (x0 + w - 1) / nc - pc0 + 1;
+    long o = wg * 256 + tid;
+    const bool live = o < npr * npc;
+    if (!live) o = npr * npc - 1;
+    ScaledTile t;
+    t.pr = pr0 + (int)(o / npc);
+    t.pc = pc0 + (int)(o % npc);
+    const int ya = t.pr * nc > y0 ? t.pr * nc : y0, yb = (long)t.pr * nc + nc < (long)y0 + h ? t.pr * nc + nc : y0 + h;
+    const int xa = t.pc * nc > x0 ? t.pc * nc : x0, xb = (long)t.pc * nc + nc < (long)x0 + w ? t.pc * nc + nc : x0 + w;
+    t.px.y = ya; t.px.x = xa;
+    t.px.ny = live ? yb - ya : 0;
+    t.px.nx = live ? xb - xa : 0;
+    return t;
+}
+// General body: a thread one output pixel, the window's pixels row by row, 256 to a workgroup
+LRF_HD inline long scaled_any_wgs(int h, int w) { return ((long)h * w + 255) / 256; }
+LRF_HD inline CropSpan scaled_pixel_of(int y0, int x0, int h, int w, long wg, int tid)
+{
+    const long o = wg * 256 + tid;
+    CropSpan q = {y0, x0, 0, 0};
+    if (o >= (long)h * w) return q;
+    q.y = y0 + (int)(o / w);
+    q.x = x0 + (int)(o % w);
+    q.ny = q.nx = 1;
+    return q;
+}
+// One image as the entry points classified it: tiled = both sides multiples of 16 and ranks inside the tiled decoders' bounds
+// (decode_plan's DEC_TILE16), cls its rank-bound class there; R: its ranks (they size its pooled tables)
+struct ScaledImage { int tiled, cls, R[3]; };
+// int16 elements of the pooled tables of one image at scale f: luma [R_Y][(8/f)^2], then Cb and Cr [R_c][(16/f)^2]
+inline long scaled_pool_elems(const int R[3], int f) { return (long)R[0] * (8 / f) * (8 / f) + (long)(R[1] + R[2]) * (16 / f) * (16 / f); }
+// One launch: items item0 .. item0 + nitems - 1 of the sorted table, wgs workgroups each (grid.x = nitems * wgs; wgs: the most
+// an item of the launch needs, the workgroups an item does not need exit)
+struct ScaledLaunch {
+    int tiled, f, cls; // cls: tiled launches, else 0
+    long item0, nitems, wgs;
+};
+struct ScaledPoolJob { int image, f; long pool_off; }; // k_pool_v: one workgroup per (image, scale) of the tiled items
+struct ScaledPlan {
+    std::vector<ScaledLaunch> launches; // order: tiled by (f, class), then general by f; at most LRF_SCALED_MAX_LAUNCHES
+    std::vector<ScaledItem> table;      // the items grouped by launch, call order inside a group; place = the place in the call
+    std::vector<ScaledPoolJob> jobs;    // in order of first use by the table
+    long pool_elems = 0;                // int16 elements of the pooled-table workspace
+    long too_many = 0;                  // != 0: a launch would have this many (>= 2^31) workgroups; no table is built
+};
+#define LRF_SCALED_MAX_LAUNCHES (3 * LRF_DEC_CLASSES + 3)
+// items: validated, in call order (place and pool_off are set here)
+ScaledPlan plan_decode_scaled(const std::vector<ScaledImage>& images, const std::vector<ScaledItem>& items);
 
 // ---- inflate of factor columns: which lane decodes which column (lrf_inflate_columns_i8; tests/test_inflate_plan.py) ----------
 // One lane per stream, 64 consecutive slots to a wave.  The slots are the matrices' columns, matrix after matrix, a matrix's
