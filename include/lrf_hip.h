@@ -330,6 +330,34 @@ int lrf_qmf_decode_scaled_crops_rgb_u8(lrf_ctx* ctx, int64_t n_images, const lrf
                                        int64_t h, int64_t w, uint8_t* rgb /* [n_crops][3][h][w] */, int64_t rgb_len);
 
 /*
+ * Resized crops: n_crops boxes of any size and position, out of images that differ in size and ranks, resampled to one output
+ * size (oh, ow) in one call — what a random-resized-crop loader asks for at every step.  A box reads the patches it touches
+ * and nothing full-size is written.  Box j = rows y0 .. y0 + h - 1, columns x0 .. x0 + w - 1 of image `image` in
+ * full-resolution pixels; its output is written as [3][oh][ow] at 3 oh ow j.  Exact integers:
+ *   level   f = the largest of 8, 4, 2 with f oh <= h and f ow <= w, else 1.  L = what lrf_qmf_decode_rgb_u8 writes for the
+ *           image (f = 1) or lrf_qmf_decode_scaled_rgb_u8 at scale f, Hs x Ws = ceil(H / f) x ceil(W / f).  A box more than 16
+ *           times the output on its shorter ratio is sampled from level 8 without further prefiltering.
+ *   taps    per axis, (r, n_out, b0, nb, n_lvl) = (row, oh, y0, h, Hs) or the column values, in int64:
+ *           N = (2 r + 1) nb + 2 n_out b0 - n_out f, D = 2 n_out f, q = clamp(floor(256 N / D), 0, 256 (n_lvl - 1)),
+ *           i0 = q >> 8, i1 = min(i0 + 1, n_lvl - 1), t = q & 255
+ *   pixel   per channel ((256 - ty)(256 - tx) L[iy0][ix0] + (256 - ty) tx L[iy0][ix1] + ty (256 - tx) L[iy1][ix0]
+ *           + ty tx L[iy1][ix1] + 32768) >> 16; with flip != 0 output column c holds the value defined for column ow - 1 - c.
+ * So a box of the output's size is the crop of lrf_qmf_decode_crops_rgb_u8 byte for byte, a box with y0, x0 multiples of f,
+ * h = f oh and w = f ow the crop of lrf_qmf_decode_scaled_crops_rgb_u8 at scale f and (y0 / f, x0 / f), and every result lies
+ * within 2.5 levels of the real-valued bilinear interpolation of L at the same centres.  These are not torchvision's bytes.
+ * A box's bytes depend on nothing else in the call.  Launches: one per (path, level, rank class) present, at most sixteen.
+ * As lrf_qmf_decode_crops_rgb_u8 otherwise: images (rgb_off ignored), the resident descriptors, the staging slots, no stream
+ * wait for a fresh list, LRF_K_DECODE, the validation before any launch.  LRF_EINVAL in addition to that entry's list: oh or
+ * ow outside [1,16384], a box side below 1.
+ */
+typedef struct {
+    int32_t image, y0, x0, h, w, flip;
+} lrf_resized_crop;
+int lrf_qmf_decode_resized_crops_rgb_u8(lrf_ctx* ctx, int64_t n_images, const lrf_ragged_image* images /* host; rgb_off ignored */, const int8_t* U,
+                                        int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops, const lrf_resized_crop* crops /* host */,
+                                        int64_t oh, int64_t ow, uint8_t* rgb /* [n_crops][3][oh][ow] */, int64_t rgb_len);
+
+/*
  * The fused encode (lrf/compression/qmf.py:227-262) for a list of n images that differ in size and in ranks, in one call: what a
  * dataset of mixed sizes or a per-image quality choice hands to an encoder.
  *   images  [n] descriptors in host memory

@@ -48,6 +48,12 @@ class ScaledCrop(ctypes.Structure):
     _fields_ = [("image", ctypes.c_int32), ("scale", ctypes.c_int32), ("y0", ctypes.c_int32), ("x0", ctypes.c_int32)]
 
 
+class ResizedCrop(ctypes.Structure):
+    """lrf_resized_crop (include/lrf_hip.h)"""
+    _fields_ = [("image", ctypes.c_int32), ("y0", ctypes.c_int32), ("x0", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("flip", ctypes.c_int32)]
+
+
 class RaggedEncodeImage(ctypes.Structure):
     """lrf_ragged_encode_image (include/lrf_hip.h)"""
     _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int * 3), ("rgb_off", c_i64), ("u_off", c_i64), ("v_off", c_i64), ("sign_off", c_i64)]
@@ -105,6 +111,8 @@ def load():
         lib.lrf_qmf_decode_scaled_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_decode_scaled_crops_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_i64,
                                                            ctypes.POINTER(ScaledCrop), c_i64, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_decode_resized_crops_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_i64,
+                                                            ctypes.POINTER(ResizedCrop), c_i64, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_encode_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedEncodeImage), c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64,
                                                      c_void_p, c_i64, c_void_p, c_i64]
         lib.lrf_deflate_bound.restype = c_i64
@@ -157,7 +165,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -405,6 +413,55 @@ def check_scaled_args(U, V, images, scale=None, crops=None, size=None):
         j = bad[0]
         raise ValueError(f"crop {j}: {h}x{w} at ({boxes[j, 2]}, {boxes[j, 3]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]} at scale 1/{f[j]}")
     return ims, np.ascontiguousarray(boxes, dtype=np.int32), (h, w)
+
+
+RESIZED_MAX_SIDE = 16384  # lrf_qmf_decode_resized_crops_rgb_u8: the largest output side
+
+
+def check_resized_args(U, V, images, crops, size):
+    """The argument checks of lrf_qmf_decode_resized_crops_rgb_u8, before any device is touched.  U, V, images: as
+    check_ragged_args takes them; crops: an integer array-like [n, 6] of (image, y0, x0, h, w, flip) on the host, 1 <= n <= 2^20,
+    h and w >= 1, every box inside its image; size: (oh, ow), both in [1, 16384].  TypeError for factors that are not int8
+    tensors and for boxes or sizes that are not integers, ValueError for everything else.
+    -> (images as check_ragged_args returns them, crops as an int32 array [n, 6] with flip 0 or 1, (oh, ow))."""
+    import numpy as np
+    ims = check_ragged_args(U, V, images)
+    try:
+        oh, ow = size
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (oh, ow), got {size!r}") from None
+    if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in (oh, ow)):
+        raise TypeError(f"size must hold two integers, got {size!r}")
+    oh, ow = int(oh), int(ow)
+    if oh < 1 or ow < 1 or oh > RESIZED_MAX_SIDE or ow > RESIZED_MAX_SIDE:
+        raise ValueError(f"output size {oh}x{ow}: both sides must be in [1, {RESIZED_MAX_SIDE}]")
+    if hasattr(crops, "detach"):  # a torch tensor
+        if crops.is_cuda:
+            raise ValueError("crops live on the host: the call validates every box before it launches")
+        crops = crops.detach().numpy()
+    boxes = np.asarray(crops)
+    if boxes.size == 0:
+        raise ValueError("decode_resized_crops needs 1 to 2^20 crops")
+    if boxes.dtype.kind not in "iu":
+        raise TypeError(f"crops must be integers (image, y0, x0, h, w, flip), got {boxes.dtype}")
+    if boxes.ndim != 2 or boxes.shape[1] != 6:
+        raise ValueError(f"crops must be [n, 6] (image, y0, x0, h, w, flip), got shape {tuple(boxes.shape)}")
+    if boxes.shape[0] > 2 ** 20:
+        raise ValueError("decode_resized_crops needs 1 to 2^20 crops")
+    boxes = boxes.astype(np.int64)
+    bad = np.flatnonzero((boxes[:, 0] < 0) | (boxes[:, 0] >= len(ims)))
+    if bad.size:
+        raise ValueError(f"crop {bad[0]}: image {boxes[bad[0], 0]} out of range [0, {len(ims)})")
+    bad = np.flatnonzero((boxes[:, 3] < 1) | (boxes[:, 4] < 1))
+    if bad.size:
+        raise ValueError(f"crop {bad[0]}: box of {boxes[bad[0], 3]}x{boxes[bad[0], 4]}: both sides must be >= 1")
+    Hs, Ws = np.array([im[0] for im in ims], dtype=np.int64)[boxes[:, 0]], np.array([im[1] for im in ims], dtype=np.int64)[boxes[:, 0]]
+    bad = np.flatnonzero((boxes[:, 1] < 0) | (boxes[:, 2] < 0) | (boxes[:, 1] + boxes[:, 3] > Hs) | (boxes[:, 2] + boxes[:, 4] > Ws))
+    if bad.size:
+        j = bad[0]
+        raise ValueError(f"crop {j}: {boxes[j, 3]}x{boxes[j, 4]} at ({boxes[j, 1]}, {boxes[j, 2]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]}")
+    boxes[:, 5] = boxes[:, 5] != 0
+    return ims, np.ascontiguousarray(boxes, dtype=np.int32), (oh, ow)
 
 
 def check_encode_ragged_args(rgb, images, sign=None):
@@ -796,6 +853,27 @@ class Context:
         self.use_torch_stream()
         check(self._lib.lrf_qmf_decode_scaled_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
                                                            boxes.ctypes.data_as(ctypes.POINTER(ScaledCrop)), h, w, _dptr(rgb), rgb.numel()))
+        return rgb
+
+    def decode_resized_crops(self, U, V, images, crops, size):
+        """Boxes of any size resampled to one output size straight from the factors (lrf_qmf_decode_resized_crops_rgb_u8).  U, V,
+        images: as decode_ragged takes them; crops: an integer array-like [n, 6] of (image, y0, x0, h, w, flip) on the host, the
+        box in full-resolution pixels; size: (oh, ow) -> a uint8 CUDA tensor [n, 3, oh, ow].  Crop j is the fixed-point bilinear
+        resampling include/lrf_hip.h defines, from the level (1, 1/2, 1/4, 1/8) nearest above the output's size: not torchvision's
+        bytes.  Asynchronous on torch's current stream; a new crop list costs no stream wait."""
+        import torch
+        ims, boxes, (oh, ow) = check_resized_args(U, V, images, crops, size)
+        if not (U.is_cuda and U.device.index == self.device):
+            raise ValueError(f"decode_resized_crops needs its tensors on cuda:{self.device}, got {U.device}")
+        desc = (RaggedImage * len(ims))()
+        for d, (H, W, ranks, u_off, v_off) in zip(desc, ims):
+            d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, 0
+            d.R[0], d.R[1], d.R[2] = ranks
+        n = boxes.shape[0]
+        rgb = torch.empty((n, 3, oh, ow), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_decode_resized_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
+                                                            boxes.ctypes.data_as(ctypes.POINTER(ResizedCrop)), oh, ow, _dptr(rgb), rgb.numel()))
         return rgb
 
     def encode_ragged(self, rgb, images, K, lo, hi, sign=None):

@@ -1655,6 +1655,40 @@ class ResidentFactors:
             return self._ctx.decode_crops(self.U, self.V, self.images, crops, size)
         return _decode_crops_at_scales(self._ctx, self.U, self.V, self.images, crops, size, scale)
 
+    def decode_resized_crops(self, boxes, size, flip=None) -> torch.Tensor:
+        """boxes: integers [n, 5] of (image, y0, x0, h, w) on the host, full-resolution pixels; size: (oh, ow); flip: None, one
+        bool, or one bool per box (mirror the output's columns) -> uint8 CUDA [n, 3, oh, ow]: qmf_decode_resized_crops"""
+        return self._ctx.decode_resized_crops(self.U, self.V, self.images, _resized_boxes(boxes, flip), size)
+
+
+def _resized_boxes(boxes, flip):
+    """boxes: integers [n, 5] of (image, y0, x0, h, w) on the host; flip: None, one bool, or one bool per box -> an int64 array
+    [n, 6] of (image, y0, x0, h, w, flip), the rows Context.decode_resized_crops takes (which validates the boxes themselves)"""
+    if hasattr(boxes, "detach"):
+        if boxes.is_cuda:
+            raise ValueError("boxes live on the host: the call validates every box before it launches")
+        boxes = boxes.detach().numpy()
+    b = np.asarray(boxes)
+    if b.size == 0:
+        raise ValueError("decode_resized_crops needs 1 to 2^20 crops")
+    if b.dtype.kind not in "iu":
+        raise TypeError(f"boxes must be integers (image, y0, x0, h, w), got {b.dtype}")
+    if b.ndim != 2 or b.shape[1] != 5:
+        raise ValueError(f"boxes must be [n, 5] (image, y0, x0, h, w), got shape {tuple(b.shape)}")
+    n = b.shape[0]
+    if flip is None:
+        fl = np.zeros(n, dtype=np.int64)
+    else:
+        fl = np.asarray(flip.detach().cpu().numpy() if hasattr(flip, "detach") else flip)
+        if fl.dtype != np.bool_:
+            raise TypeError(f"flip must be None, a bool or one bool per box, got {flip!r}")
+        if fl.ndim == 0:
+            fl = np.full(n, bool(fl))
+        if fl.ndim != 1 or fl.shape[0] != n:
+            raise ValueError(f"flip must be one value or one per box ({n}), got shape {tuple(fl.shape)}")
+        fl = fl.astype(np.int64)
+    return np.concatenate([b.astype(np.int64), fl[:, None]], axis=1)
+
 
 def _resident(images, Uh, Vh, device) -> ResidentFactors:
     ctx = _lib.context(device)
@@ -1689,6 +1723,31 @@ def qmf_decode_crops(source, crops, size, device=None, inflate: str = "host", sc
             _split_crops_by_scale(torch.from_numpy(Uh), torch.from_numpy(Vh), images, crops, size, scale)
         source = _resident(images, Uh, Vh, device)
     return source.decode_crops(crops, size, scale)
+
+
+def qmf_decode_resized_crops(source, boxes, size, flip=None, device=None, inflate: str = "host") -> torch.Tensor:
+    """RandomResizedCrop straight from the factors: n boxes of any size and position, out of images of any sizes and ranks,
+    resampled to one output size in one call.  source: a list of streams or the ResidentFactors of qmf_load_factors; boxes:
+    integers [n, 5] of (image, y0, x0, h, w) on the host, each inside its image with h, w >= 1; size: (oh, ow), sides in
+    [1, 16384]; flip: None, one bool, or one bool per box (output column c then holds column ow - 1 - c) -> uint8 CUDA
+    [n, 3, oh, ow].  Each box is sampled bilinearly, in fixed point (weights in 1/256, one rounding), from the level of its image
+    nearest above the output's size: the image itself, or qmf_decode_scaled at the largest scale f of 8, 4, 2 with f oh <= h and
+    f ow <= w; a box more than 16 times the output is sampled from level 8 without further prefiltering.  A box of the output's
+    size is qmf_decode_crops' crop byte for byte, a box aligned to f and f times the output the crop at scale f; otherwise
+    within 2.5 levels of real-valued bilinear interpolation of the level.  These are NOT torchvision's bytes: torchvision
+    interpolates the full-resolution pixels in floating point (and antialiases differently).  Exact definition:
+    include/lrf_hip.h, lrf_qmf_decode_resized_crops_rgb_u8.  The default branch only, as qmf_decode_crops: a stream of another
+    branch raises NotImplementedError naming it.  inflate="device" (a list of streams only): their columns are inflated on the GPU."""
+    on_device = _check_inflate(inflate)
+    rows = _resized_boxes(boxes, flip)
+    if on_device and not isinstance(source, ResidentFactors):
+        ctx, images, U, V = _factors_ragged_device(source, device)
+        source = ResidentFactors(ctx, U, V, images)
+    if not isinstance(source, ResidentFactors):
+        images, Uh, Vh = _factors_ragged(source)
+        _lib.check_resized_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, rows, size)  # refused before a GPU is asked for
+        source = _resident(images, Uh, Vh, device)
+    return source._ctx.decode_resized_crops(source.U, source.V, source.images, rows, size)
 
 
 def qmf_decode_scaled(source, scale, device=None, inflate: str = "host") -> list:

@@ -17,7 +17,7 @@
 //                                  entries of V each), Cb and Cr [R_c][(16/f)^2] (f/2 x f/2 entries each: V itself at f = 2)
 //   k_decode_scaled_tiled<F, CLS>  images whose sides are multiples of 16 (no padding, chroma row = y >> 1, a block never
 //                                  straddles a patch), one instantiation per scale and rank-bound class of the tiled decoders
-//   k_decode_scaled_any            every geometry and rank: a thread one output pixel
+//   k_decode_scaled_any            every geometry and rank: a thread one output pixel (scaled_pixel_rgb)
 
 __global__ __launch_bounds__(256) void k_pool_v(const int8_t* __restrict__ V, int16_t* __restrict__ pool, const RaggedDesc* __restrict__ descs,
                                                 const ScaledPoolJob* __restrict__ jobs)
@@ -152,15 +152,11 @@ __global__ __launch_bounds__(256) void k_decode_scaled_tiled(const int8_t* __res
 // Every geometry and rank, the definition as it stands: the block's luma integers summed patch by patch (u . the sum of the V
 // rows the block holds of that patch), its chroma integers through the nearest-neighbour rows and columns with the number of
 // block pixels over each (scaled_chroma_run), the true division by the block's pixel count.
-__global__ __launch_bounds__(256) void k_decode_scaled_any(const int8_t* __restrict__ U, const int8_t* __restrict__ V, uint8_t* __restrict__ rgb,
-                                                           const RaggedDesc* __restrict__ descs, const ScaledItem* __restrict__ items, int wgs)
+// scaled_pixel_rgb: pixel (oy, ox) of image d at scale f as its three bytes, R | G << 8 | B << 16 (k_decode_scaled_any stores them;
+// the resized crops of lrf_decode_resized_kernel.hip interpolate between them).
+__device__ __forceinline__ unsigned scaled_pixel_rgb(const int8_t* __restrict__ U, const int8_t* __restrict__ V, const RaggedDesc& d, int f, int oy, int ox)
 {
-    const int ii = (int)(blockIdx.x / (unsigned)wgs), wg = (int)(blockIdx.x - (unsigned)ii * (unsigned)wgs);
-    const ScaledItem it = items[ii];
-    const CropSpan o = scaled_pixel_of(it.y0, it.x0, it.h, it.w, wg, (int)threadIdx.x);
-    if (o.ny == 0) return;
-    const RaggedDesc& d = descs[it.image];
-    const int ya = scaled_lo(o.y, it.f), yb = scaled_hi(o.y, it.f, d.H), xa = scaled_lo(o.x, it.f), xb = scaled_hi(o.x, it.f, d.W);
+    const int ya = scaled_lo(oy, f), yb = scaled_hi(oy, f, d.H), xa = scaled_lo(ox, f), xb = scaled_hi(ox, f, d.W);
     const int8_t *Ui = U + d.u_off, *Vi = V + d.v_off;
     const int8_t* Uc[3] = {Ui, Ui + (long)d.g.p[0].M * d.R0, Ui + (long)d.g.p[0].M * d.R0 + (long)d.g.p[1].M * d.R1};
     const int8_t* Vc[3] = {Vi, Vi + 64 * d.R0, Vi + 64 * d.R0 + 64 * d.R1};
@@ -204,8 +200,22 @@ __global__ __launch_bounds__(256) void k_decode_scaled_any(const int8_t* __restr
     const float n = (float)((yb - ya) * (xb - xa));
     float ch[3];
     decode_colour(__fdiv_rn((float)S[0], n), __fdiv_rn((float)S[1], n) + -128.f, __fdiv_rn((float)S[2], n) + -128.f, ch);
+    unsigned px = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) px |= (unsigned)(uint8_t)__builtin_amdgcn_fmed3f(ch[k], 0.f, 255.f) << (8 * k);
+    return px;
+}
+
+__global__ __launch_bounds__(256) void k_decode_scaled_any(const int8_t* __restrict__ U, const int8_t* __restrict__ V, uint8_t* __restrict__ rgb,
+                                                           const RaggedDesc* __restrict__ descs, const ScaledItem* __restrict__ items, int wgs)
+{
+    const int ii = (int)(blockIdx.x / (unsigned)wgs), wg = (int)(blockIdx.x - (unsigned)ii * (unsigned)wgs);
+    const ScaledItem it = items[ii];
+    const CropSpan o = scaled_pixel_of(it.y0, it.x0, it.h, it.w, wg, (int)threadIdx.x);
+    if (o.ny == 0) return;
+    const unsigned px = scaled_pixel_rgb(U, V, descs[it.image], it.f, o.y, o.x);
     uint8_t* dst = rgb + it.out_off + (long)(o.y - it.y0) * it.w + (o.x - it.x0);
     const long hw = (long)it.h * it.w;
 #pragma unroll
-    for (int k = 0; k < 3; k++) dst[k * hw] = (uint8_t)__builtin_amdgcn_fmed3f(ch[k], 0.f, 255.f);
+    for (int k = 0; k < 3; k++) dst[k * hw] = (uint8_t)(px >> (8 * k));
 }

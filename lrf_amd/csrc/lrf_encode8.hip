@@ -10,6 +10,7 @@
 #include "lrf_decode_ragged_kernel.hip"
 #include "lrf_decode_crops_kernel.hip"
 #include "lrf_decode_scaled_kernel.hip"
+#include "lrf_decode_resized_kernel.hip"
 #include "lrf_planes_ragged_kernel.hip"
 
 // gram_exp: the fixed-point grid exponent of the exact Gram matrix (max|x| < 2^gram_exp) when the caller knows it — 8 for the
@@ -1007,3 +1008,4 @@ int lrf_debug_read_gram_stamps(lrf_ctx* c, unsigned long long* out_host, int n)
 } // extern "C"
 
 #include "lrf_decode_scaled_host.inc"
+#include "lrf_decode_resized_host.inc"

@@ -110,6 +110,15 @@ struct ScaledItem {
     long pool_off;     // tiled body: int16 elements from the pooled-table workspace to the tables of (image, f)
 };
 
+// ---- resized crops (lrf_qmf_decode_resized_crops_rgb_u8; kernels: lrf_decode_resized_kernel.hip) ----
+// One box of the call, as the kernels read it (a uniform load per workgroup).  image: an index into RaggedDesc
+struct ResizedItem {
+    int image, f;       // the level the box is sampled from: 1, 2, 4 or 8 (resized_level)
+    int y0, x0, hb, wb; // the box in full-resolution image pixels
+    int flip;           // != 0: output column c holds the value of column ow - 1 - c
+    int place;          // its place in the caller's list: its output is [3][oh][ow] at 3 oh ow place
+};
+
 // ---- the ragged encode (lrf_qmf_encode_ragged_rgb_u8; kernels: lrf_planes_ragged_kernel.hip) ----
 // One image of the call, as the planes kernels read it (uniform loads, like RaggedDesc; the workgroup table is RaggedBlock's:
 // image, unit = strip * per_strip + column group)

@@ -384,6 +384,52 @@ ScaledPlan plan_decode_scaled(const std::vector<ScaledImage>& images, const std:
     return p;
 }
 
+// The table is a stable sort of the call's boxes by (path, level, rank class): one launch per group that occurs, so at most
+// LRF_RESIZED_MAX_LAUNCHES.  Every box of a call has the same output size, so the workgroups per box depend on the path alone.
+ResizedPlan plan_decode_resized(const std::vector<int>& r8, const std::vector<ResizedItem>& crops, int oh, int ow)
+{
+    ResizedPlan p;
+    const int nslots = LRF_RESIZED_MAX_LAUNCHES;
+    auto fi = [](int f) { return f == 1 ? 0 : (f == 2 ? 1 : (f == 4 ? 2 : 3)); };
+    auto slot_of = [&](const ResizedItem& e, int f) { return (resized_staged(e.hb, e.wb, oh, ow, f) ? 0 : 8) + fi(f) * 2 + (r8[(size_t)e.image] ? 0 : 1); };
+    std::vector<int> level(crops.size()), slot(crops.size());
+    std::vector<long> count((size_t)nslots, 0);
+    for (size_t j = 0; j < crops.size(); j++) {
+        level[j] = resized_level(crops[j].hb, crops[j].wb, oh, ow);
+        slot[j] = slot_of(crops[j], level[j]);
+        count[(size_t)slot[j]]++;
+    }
+    const long wgs[2] = {resized_staged_wgs(oh, ow), resized_direct_wgs(oh, ow)};
+    for (int s = 0; s < nslots; s++) {
+        const long g = wgs[s >> 3];
+        if (count[(size_t)s] && (g >= (1L << 31) || count[(size_t)s] * g >= (1L << 31))) {
+            p.too_many = g >= (1L << 31) ? g : count[(size_t)s] * g;
+            return p;
+        }
+    }
+    p.table.reserve(crops.size());
+    for (int s = 0; s < nslots; s++) {
+        if (!count[(size_t)s]) continue;
+        ResizedLaunch l;
+        l.direct = s >> 3;
+        l.f = 1 << ((s >> 1) & 3);
+        l.r8 = !(s & 1);
+        l.item0 = (long)p.table.size();
+        l.nitems = count[(size_t)s];
+        l.wgs = wgs[l.direct];
+        for (size_t j = 0; j < crops.size(); j++) {
+            if (slot[j] != s) continue;
+            ResizedItem e = crops[j];
+            e.f = level[j];
+            e.place = (int)j;
+            e.flip = e.flip != 0;
+            p.table.push_back(e);
+        }
+        p.launches.push_back(l);
+    }
+    return p;
+}
+
 // ---- geometry -----------------------------------------------------------------------------------------------------------------
 void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M)
 {

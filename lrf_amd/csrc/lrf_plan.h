@@ -270,6 +270,97 @@ struct ScaledPlan {
 // items: validated, in call order (place and pool_off are set here)
 ScaledPlan plan_decode_scaled(const std::vector<ScaledImage>& images, const std::vector<ScaledItem>& items);
 
+// ---- resized crops: boxes of any size resampled to one output size (lrf_qmf_decode_resized_crops_rgb_u8; kernels: -------------
+// lrf_decode_resized_kernel.hip).  The kernels and tests/test_decode_resized_plan.py call the same functions. -------------------
+// The level a box is sampled from: the largest f of 8, 4, 2 whose f x output still fits inside the box, else 1 (the full image)
+LRF_HD inline int resized_level(int hb, int wb, int oh, int ow)
+{
+    for (int f = 8; f >= 2; f >>= 1)
+        if ((long)f * oh <= hb && (long)f * ow <= wb) return f;
+    return 1;
+}
+// The two level rows (columns) output row (column) r of n_out reads and the weight of the second in 1/256: the centre of
+// output sample r lies at ((r + 1/2) nb / n_out + b0) / f - 1/2 of the level, floored to 1/256 and clamped into the level
+struct ResizedTap { int i0, i1, t; };
+LRF_HD inline ResizedTap resized_tap(int r, int n_out, int b0, int nb, int f, int n_lvl)
+{
+    const long long N = (2LL * r + 1) * nb + 2LL * n_out * b0 - (long long)n_out * f, D = 2LL * n_out * f; // |N| < 2^47
+    const long long a = 256 * N;
+    long long q = a / D;
+    if (a % D != 0 && a < 0) q--; // floor, not truncation (D > 0)
+    const long long top = 256LL * (n_lvl - 1);
+    q = q < 0 ? 0 : (q > top ? top : q);
+    ResizedTap t;
+    t.i0 = (int)(q >> 8);
+    t.i1 = t.i0 + 1 < n_lvl ? t.i0 + 1 : n_lvl - 1;
+    t.t = (int)(q & 255);
+    return t;
+}
+// The level rows (columns) lo .. lo + n - 1 that output rows (columns) ra .. rb read: the taps are monotone in r
+struct ResizedSpan { int lo, n; };
+LRF_HD inline ResizedSpan resized_span(int ra, int rb, int n_out, int b0, int nb, int f, int n_lvl)
+{
+    const int lo = resized_tap(ra, n_out, b0, nb, f, n_lvl).i0, hi = resized_tap(rb, n_out, b0, nb, f, n_lvl).i1;
+    return ResizedSpan{lo, hi - lo + 1};
+}
+// Staged path: a workgroup owns LRF_RS_TH x LRF_RS_TW output pixels, a thread four adjacent pixels of a row, and decodes the
+// level pixels its tile reads — at most LRF_RS_FH x LRF_RS_FW of them — into LDS first.  t consecutive outputs advance the tap
+// by (t - 1) nb / (n_out f) level pixels, the floor adds less than one, and i1 one more: resized_span_bound >= every span.
+#define LRF_RS_TH 16
+#define LRF_RS_TW 64
+#define LRF_RS_FH 44
+#define LRF_RS_FW 192
+LRF_HD inline long resized_span_bound(int tile, int n_out, int nb, int f)
+{
+    const int t = tile < n_out ? tile : n_out;
+    return (long)(t - 1) * nb / ((long)n_out * f) + 3;
+}
+// whether the footprint of every tile of the box fits the LDS tile: else the direct path takes it (extreme aspect ratios, and
+// boxes many times the output, which level 8 leaves more than twice the output's size)
+LRF_HD inline bool resized_staged(int hb, int wb, int oh, int ow, int f)
+{
+    return resized_span_bound(LRF_RS_TH, oh, hb, f) <= LRF_RS_FH && resized_span_bound(LRF_RS_TW, ow, wb, f) <= LRF_RS_FW;
+}
+LRF_HD inline long resized_staged_wgs(int oh, int ow) { return (long)((oh + LRF_RS_TH - 1) / LRF_RS_TH) * ((ow + LRF_RS_TW - 1) / LRF_RS_TW); }
+// output rows r0 .. r0 + nr - 1 and columns c0 .. c0 + nc - 1 of tile wg (before the flip: the columns the taps are defined for)
+struct ResizedTile { int r0, nr, c0, nc; };
+LRF_HD inline ResizedTile resized_tile_of(int oh, int ow, int wg)
+{
+    const int ntx = (ow + LRF_RS_TW - 1) / LRF_RS_TW, ty = wg / ntx, tx = wg - ty * ntx;
+    ResizedTile t;
+    t.r0 = ty * LRF_RS_TH;
+    t.c0 = tx * LRF_RS_TW;
+    t.nr = oh - t.r0 < LRF_RS_TH ? oh - t.r0 : LRF_RS_TH;
+    t.nc = ow - t.c0 < LRF_RS_TW ? ow - t.c0 : LRF_RS_TW;
+    return t;
+}
+// thread tid of the tile: row r, columns c .. c + n - 1 (n = 0: none); column s is written at resized_out_col(s, ow, flip)
+struct ResizedPx { int r, c, n; };
+LRF_HD inline ResizedPx resized_thread_of(const ResizedTile& t, int tid)
+{
+    const int tr = tid / (LRF_RS_TW / 4), tc = (tid - tr * (LRF_RS_TW / 4)) * 4;
+    ResizedPx p = {t.r0 + tr, t.c0 + tc, 0};
+    if (tr < t.nr && tc < t.nc) p.n = t.nc - tc < 4 ? t.nc - tc : 4;
+    return p;
+}
+LRF_HD inline int resized_out_col(int s, int ow, int flip) { return flip ? ow - 1 - s : s; }
+// Direct path: a thread one output pixel, row by row, 256 to a workgroup (scaled_pixel_of over (0, 0, oh, ow))
+LRF_HD inline long resized_direct_wgs(int oh, int ow) { return scaled_any_wgs(oh, ow); }
+// One launch: items item0 .. item0 + nitems - 1 of the sorted table, wgs workgroups each (grid.x = nitems * wgs)
+struct ResizedLaunch {
+    int direct, f, r8; // the path, the level, and whether every rank of the launch's images is <= 8 (the decode8 fill)
+    long item0, nitems, wgs;
+};
+struct ResizedPlan {
+    std::vector<ResizedLaunch> launches; // order: (path, level, rank class), staged first; at most LRF_RESIZED_MAX_LAUNCHES
+    std::vector<ResizedItem> table;      // the boxes grouped by launch, call order inside a group; place = the place in the call
+    long too_many = 0;                   // != 0: a launch would have this many (>= 2^31) workgroups; no table is built
+};
+#define LRF_RESIZED_MAX_LAUNCHES 16 // 2 paths x 4 levels x 2 rank classes
+// r8: per image, whether its three ranks are all <= 8; crops: (image, y0, x0, hb, wb, flip) in call order, validated (f and
+// place are set here)
+ResizedPlan plan_decode_resized(const std::vector<int>& r8, const std::vector<ResizedItem>& crops, int oh, int ow);
+
 // ---- inflate of factor columns: which lane decodes which column (lrf_inflate_columns_i8; tests/test_inflate_plan.py) ----------
 // One lane per stream, 64 consecutive slots to a wave.  The slots are the matrices' columns, matrix after matrix, a matrix's
 // columns ascending — so a wave's lanes hold adjacent columns of one matrix (adjacent bytes of every row) until the matrix
