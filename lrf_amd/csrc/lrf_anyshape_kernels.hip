@@ -2138,6 +2138,96 @@ __global__ __launch_bounds__(256) void k_any_eig(double* __restrict__ G, int n, 
     }
 
     // ---- orthonormalisation: classical Gram-Schmidt, twice, against the vectors already fixed
+    // x <- x minus its components along Z[0..r), twice (all threads; x: the thread's elements tid + 256 c)
+    auto orth = [&](double (&x)[NCT], int r) __attribute__((always_inline)) {
+        for (int pass = 0; pass < 2 && r > 0; pass++) {
+#pragma unroll
+            for (int c = 0; c < NCT; c++) {
+                const int i = tid + 256 * c;
+                if (i < n) Lv[i] = x[c];
+            }
+            __syncthreads();
+            // the earlier vectors live in global memory (L2): their loads are issued in batches (all 4 NCT pieces of a
+            // dot product at once, eight vectors per step of the update) instead of one per loop trip; same chains
+            // (DB earlier vectors per trip and wave, their loads in flight together and their reduction trees interleaved: one at
+            // a time a trip waited for its own L2 round trip — the stage was 4.1 of k_any_eig<2>'s 9.2 ms at rank 102, side
+            // 512; each dot product's arithmetic is what it was)
+            constexpr int DB = NCT <= 2 ? 4 : 2;
+            for (int pr0 = wave; pr0 < r; pr0 += 4 * DB) {
+                double zv[DB][4 * NCT];
+#pragma unroll
+                for (int d = 0; d < DB; d++) {
+                    const int pr = pr0 + 4 * d;
+                    const double* Zp = Z + (long)(pr < r ? pr : r - 1) * n;
+#pragma unroll
+                    for (int e = 0; e < 4 * NCT; e++) {
+                        const int i = lane + 64 * e;
+                        zv[d][e] = Zp[i < n ? i : n - 1];
+                    }
+                }
+                double dsum[DB];
+#pragma unroll
+                for (int d = 0; d < DB; d++) {
+                    dsum[d] = 0.0;
+#pragma unroll
+                    for (int e = 0; e < 4 * NCT; e++) {
+                        const int i = lane + 64 * e;
+                        if (i < n) dsum[d] = fma(zv[d][e], Lv[i], dsum[d]);
+                    }
+                }
+#pragma unroll
+                for (int d = 0; d < DB; d++) dsum[d] = wave_sum(dsum[d]);
+#pragma unroll
+                for (int d = 0; d < DB; d++)
+                    if (lane == 0 && pr0 + 4 * d < r) Lw[pr0 + 4 * d] = dsum[d];
+            }
+            __syncthreads();
+            // (two batches of eight earlier vectors in flight: the loads of batch b + 1 are issued before batch b's fmas —
+            // a batch at a time waited out one L2 round trip per eight vectors)
+            auto load_batch = [&](int p0, double (&zv)[8][NCT]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const double* Zp = Z + (long)(p0 + u < r ? p0 + u : r - 1) * n;
+#pragma unroll
+                    for (int c = 0; c < NCT; c++) {
+                        const int i = tid + 256 * c;
+                        const double zz = Zp[i < n ? i : n - 1];
+                        // entries past the side must stay zero: they are part of the norm below (until round 3 the clamped
+                        // load went into x there: harmless while the coefficients are ~1e-16, but the vectors of a cluster
+                        // — rank-deficient matrices — came out with norms below one; found by the oracle's restatement)
+                        zv[u][c] = (i < n) ? zz : 0.0;
+                    }
+                }
+            };
+            auto apply_batch = [&](int p0, const double (&zv)[8][NCT]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    if (p0 + u < r) {
+                        const double cf = Lw[p0 + u];
+#pragma unroll
+                        for (int c = 0; c < NCT; c++) x[c] = fma(-cf, zv[u][c], x[c]);
+                    }
+                }
+            };
+            if constexpr (NCT <= 2) {
+                double za[8][NCT], zb[8][NCT];
+                load_batch(0, za);
+                for (int p0 = 0; p0 < r; p0 += 16) {
+                    if (p0 + 8 < r) load_batch(p0 + 8, zb);
+                    apply_batch(p0, za);
+                    if (p0 + 16 < r) load_batch(p0 + 16, za);
+                    if (p0 + 8 < r) apply_batch(p0 + 8, zb);
+                }
+            } else { // (sides above 512: the second batch does not fit the registers)
+                for (int p0 = 0; p0 < r; p0 += 8) {
+                    double za[8][NCT];
+                    load_batch(p0, za);
+                    apply_batch(p0, za);
+                }
+            }
+            __syncthreads();
+        }
+    };
     for (int r = 0; r < Rc; r++) {
         double* Zr = Z + (long)r * n;
         double x[NCT];
@@ -2148,7 +2238,7 @@ __global__ __launch_bounds__(256) void k_any_eig(double* __restrict__ G, int n, 
             x[c] = (i < n) ? Zr[i] : 0.0;
             fin = fin && isfinite(x[c]);
         }
-        bool use_twisted = __syncthreads_and(fin) != 0;
+        bool use_twisted = __syncthreads_and(fin) != 0, failed = false;
         int uidx = 0;
         for (;;) {
             if (use_twisted) {
@@ -2159,98 +2249,12 @@ __global__ __launch_bounds__(256) void k_any_eig(double* __restrict__ G, int n, 
 #pragma unroll
                 for (int c = 0; c < NCT; c++) x[c] = x[c] / n0;
             } else {
-                if (uidx >= n) break;
+                if (uidx >= n) { failed = true; break; }
 #pragma unroll
                 for (int c = 0; c < NCT; c++) x[c] = (tid + 256 * c == uidx) ? 1.0 : 0.0;
                 uidx++;
             }
-            for (int pass = 0; pass < 2 && r > 0; pass++) {
-#pragma unroll
-                for (int c = 0; c < NCT; c++) {
-                    const int i = tid + 256 * c;
-                    if (i < n) Lv[i] = x[c];
-                }
-                __syncthreads();
-                // the earlier vectors live in global memory (L2): their loads are issued in batches (all 4 NCT pieces of a
-                // dot product at once, eight vectors per step of the update) instead of one per loop trip; same chains
-                // (DB earlier vectors per trip and wave, their loads in flight together and their reduction trees interleaved: one at
-                // a time a trip waited for its own L2 round trip — the stage was 4.1 of k_any_eig<2>'s 9.2 ms at rank 102, side
-                // 512; each dot product's arithmetic is what it was)
-                constexpr int DB = NCT <= 2 ? 4 : 2;
-                for (int pr0 = wave; pr0 < r; pr0 += 4 * DB) {
-                    double zv[DB][4 * NCT];
-#pragma unroll
-                    for (int d = 0; d < DB; d++) {
-                        const int pr = pr0 + 4 * d;
-                        const double* Zp = Z + (long)(pr < r ? pr : r - 1) * n;
-#pragma unroll
-                        for (int e = 0; e < 4 * NCT; e++) {
-                            const int i = lane + 64 * e;
-                            zv[d][e] = Zp[i < n ? i : n - 1];
-                        }
-                    }
-                    double dsum[DB];
-#pragma unroll
-                    for (int d = 0; d < DB; d++) {
-                        dsum[d] = 0.0;
-#pragma unroll
-                        for (int e = 0; e < 4 * NCT; e++) {
-                            const int i = lane + 64 * e;
-                            if (i < n) dsum[d] = fma(zv[d][e], Lv[i], dsum[d]);
-                        }
-                    }
-#pragma unroll
-                    for (int d = 0; d < DB; d++) dsum[d] = wave_sum(dsum[d]);
-#pragma unroll
-                    for (int d = 0; d < DB; d++)
-                        if (lane == 0 && pr0 + 4 * d < r) Lw[pr0 + 4 * d] = dsum[d];
-                }
-                __syncthreads();
-                // (two batches of eight earlier vectors in flight: the loads of batch b + 1 are issued before batch b's fmas —
-                // a batch at a time waited out one L2 round trip per eight vectors)
-                auto load_batch = [&](int p0, double (&zv)[8][NCT]) __attribute__((always_inline)) {
-#pragma unroll
-                    for (int u = 0; u < 8; u++) {
-                        const double* Zp = Z + (long)(p0 + u < r ? p0 + u : r - 1) * n;
-#pragma unroll
-                        for (int c = 0; c < NCT; c++) {
-                            const int i = tid + 256 * c;
-                            const double zz = Zp[i < n ? i : n - 1];
-                            // entries past the side must stay zero: they are part of the norm below (until round 3 the clamped
-                            // load went into x there: harmless while the coefficients are ~1e-16, but the vectors of a cluster
-                            // — rank-deficient matrices — came out with norms below one; found by the oracle's restatement)
-                            zv[u][c] = (i < n) ? zz : 0.0;
-                        }
-                    }
-                };
-                auto apply_batch = [&](int p0, const double (&zv)[8][NCT]) __attribute__((always_inline)) {
-#pragma unroll
-                    for (int u = 0; u < 8; u++) {
-                        if (p0 + u < r) {
-                            const double cf = Lw[p0 + u];
-#pragma unroll
-                            for (int c = 0; c < NCT; c++) x[c] = fma(-cf, zv[u][c], x[c]);
-                        }
-                    }
-                };
-                if constexpr (NCT <= 2) {
-                    double za[8][NCT], zb[8][NCT];
-                    load_batch(0, za);
-                    for (int p0 = 0; p0 < r; p0 += 16) {
-                        if (p0 + 8 < r) load_batch(p0 + 8, zb);
-                        apply_batch(p0, za);
-                        if (p0 + 16 < r) load_batch(p0 + 16, za);
-                        if (p0 + 8 < r) apply_batch(p0 + 8, zb);
-                    }
-                } else { // (sides above 512: the second batch does not fit the registers)
-                    for (int p0 = 0; p0 < r; p0 += 8) {
-                        double za[8][NCT];
-                        load_batch(p0, za);
-                        apply_batch(p0, za);
-                    }
-                }
-                __syncthreads();
-            }
+            orth(x, r);
             double s = 0.0;
 #pragma unroll
             for (int c = 0; c < NCT; c++) s = fma(x[c], x[c], s);
@@ -2262,6 +2266,81 @@ __global__ __launch_bounds__(256) void k_any_eig(double* __restrict__ G, int n, 
                 break;
             }
             use_twisted = false;
+        }
+        // A replacement (a later copy of a repeated eigenvalue: the twisted factorisation returns the first copy's vector
+        // again) is exchanged for a vector of the eigenvalue's eigenspace — oracle: inverse_step, k_init: init_refine.
+        // LRF_ANY_REFINE steps of inverse iteration, T - lambda = L D+ L^T with the pivots the twisted factorisation left in
+        // Dp, from a fixed dense start vector; the start vector and every iterate are orthonormalised as a twisted vector is
+        // above (normalisation, Gram-Schmidt, loss test); the two substitutions are sequential (thread 0, in place in Lv).  A
+        // step that gives no usable vector (overflow behind a pivot at the guard: zero and diagonal matrices; an iterate inside
+        // the span of the vectors already fixed) leaves the replacement as it is.  Only eigenvalues above LRF_ANY_REFINE_FLOOR
+        // lambda_0 come here: below it the cluster is a null space, whose vectors carry no energy and stay the unit-vector
+        // replacements they always were.  Cold: block-uniform branch.
+        constexpr double LRF_ANY_REFINE_FLOOR = 1e-12;
+        if (!use_twisted && !failed && Llam[r] > LRF_ANY_REFINE_FLOOR * Llam[0]) {
+            constexpr int LRF_ANY_REFINE = 3;
+            double y[NCT];
+#pragma unroll
+            for (int c = 0; c < NCT; c++) {
+                const int i = tid + 256 * c;
+                y[c] = (i < n) ? 1.0 + (double)((i * 29) & 63) * 0.015625 : 0.0;
+            }
+            auto solve = [&]() __attribute__((always_inline)) { // y <- (T - lambda)^-1 y
+#pragma unroll
+                for (int c = 0; c < NCT; c++) {
+                    const int i = tid + 256 * c;
+                    if (i < n) Lv[i] = y[c];
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    auto pivot = [&](int j) {
+                        const double q = Dp[(long)j * Rc + r];
+                        return fabs(q) < pivmin ? -pivmin : q;
+                    };
+                    double q = pivot(0), z = Lv[0];
+                    Lv[0] = z / q;
+                    for (int j = 1; j < n; j++) { // z_j = y_j - (e_{j-1} / D+_{j-1}) z_{j-1};  w_j = z_j / D+_j
+                        z = fma(-(Le[j - 1] / q), z, Lv[j]);
+                        q = pivot(j);
+                        Lv[j] = z / q;
+                    }
+                    double yn = Lv[n - 1];
+                    for (int j = n - 2; j >= 0; j--) { // y_j = w_j - (e_j / D+_j) y_{j+1}
+                        yn = fma(-(Le[j] / pivot(j)), yn, Lv[j]);
+                        Lv[j] = yn;
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int c = 0; c < NCT; c++) {
+                    const int i = tid + 256 * c;
+                    y[c] = (i < n) ? Lv[i] : 0.0;
+                }
+                __syncthreads();
+            };
+            bool ok = true;
+            for (int it = 0; it <= LRF_ANY_REFINE && ok; it++) { // (it = 0: the start vector itself)
+                if (it > 0) solve();
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < NCT; c++) s = fma(y[c], y[c], s);
+                const double n0 = sqrt(block_sum(s, Lpart, tid));
+#pragma unroll
+                for (int c = 0; c < NCT; c++) y[c] = y[c] / n0;
+                orth(y, r);
+                s = 0.0;
+#pragma unroll
+                for (int c = 0; c < NCT; c++) s = fma(y[c], y[c], s);
+                const double n2 = block_sum(s, Lpart, tid);
+                ok = n2 > 1e-6 && n2 < 1e300;
+                const double nr = sqrt(n2);
+#pragma unroll
+                for (int c = 0; c < NCT; c++) y[c] = y[c] / nr;
+            }
+            if (ok) {
+#pragma unroll
+                for (int c = 0; c < NCT; c++) x[c] = y[c];
+            }
         }
 #pragma unroll
         for (int c = 0; c < NCT; c++) {

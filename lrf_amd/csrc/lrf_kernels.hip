@@ -551,6 +551,64 @@ struct InitLds {
 static_assert(LRF_INIT_VPACK + 3 * 64 * 8 <= 64 * 64, "ZR = 8: packed v_k + D1 + D2 + Z inside A");
 static_assert(LRF_INIT_VPACK % 2 == 0 && LRF_INIT_VPACK >= 63 * 62 / 2 + 62 && LRF_INIT_VPACK + 2 * 64 * 16 <= 64 * 64, "packed v_k + D1 + D2 inside A");
 
+// The fallback of the orthonormalisation stage (oracle: inverse_step and the block behind the loss test of
+// lrf_oracle_top_eig_f64): a twisted vector that Gram-Schmidt rejected — a later copy of a repeated eigenvalue, where the
+// factorisation returns the vector of the first copy again — has been replaced by an orthogonalised unit vector x; that
+// replacement is exchanged for a vector of the eigenvalue's eigenspace: LRF_INIT_REFINE steps of inverse iteration
+// (T - lambda = L D+ L^T with the pivots D+ the twisted factorisation left in LDS) from a fixed dense start vector; the start
+// vector and every iterate are orthonormalised as a twisted vector is (normalisation, Gram-Schmidt, loss test).  One wave,
+// lane = element; the two substitutions are sequential: every lane runs the chain (uniform operands) and keeps its own
+// element.  A step that gives no usable vector (overflow behind a pivot at the guard: zero and diagonal matrices; an iterate
+// inside the span of the vectors already fixed) leaves x as it is.  Only eigenvalues above LRF_INIT_REFINE_FLOOR lambda_0
+// come here: below it the cluster is a null space (rank-deficient, constant, zero matrices), whose vectors carry no energy
+// and stay the unit-vector replacements they always were.
+#define LRF_INIT_REFINE 3
+#define LRF_INIT_REFINE_FLOOR 1e-12
+template <int ZR>
+static __device__ __forceinline__ double init_refine(InitLds<ZR>& L, const double* Zs, int r, int lane, double x)
+{
+    const double pivmin = L.scal[1];
+    const double* Dp = L.D1() + r;
+    auto pivot = [&](int j) {
+        const double q = Dp[j * ZR];
+        return fabs(q) < pivmin ? -pivmin : q;
+    };
+    auto bcast = [&](double v, int j) {
+        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
+    };
+    double y = 1.0 + (double)((lane * 29) & 63) * 0.015625;
+    bool ok = true;
+    for (int it = 0; it <= LRF_INIT_REFINE && ok; it++) { // (it = 0: the start vector itself)
+        if (it > 0) {
+            double z = bcast(y, 0), w = 0.0, q = pivot(0);
+            if (lane == 0) w = z / q;
+#pragma unroll 1
+            for (int j = 1; j < 64; j++) { // z_j = y_j - (e_{j-1} / D+_{j-1}) z_{j-1};  w_j = z_j / D+_j
+                z = fma(-(L.e[j - 1] / q), z, bcast(y, j));
+                q = pivot(j);
+                if (lane == j) w = z / q;
+            }
+            double yn = bcast(w, 63);
+            y = yn; // (lane 63's element; the other lanes' are set below)
+#pragma unroll 1
+            for (int j = 62; j >= 0; j--) { // y_j = w_j - (e_j / D+_j) y_{j+1}
+                yn = fma(-(L.e[j] / pivot(j)), yn, bcast(w, j));
+                if (lane == j) y = yn;
+            }
+        }
+        y = y / sqrt(wave_tree64(y * y));
+        for (int pr = 0; pr < r; pr++) {
+            const double pv = Zs[pr * 64 + lane];
+            const double c = wave_tree64(pv * y);
+            y = fma(-c, pv, y);
+        }
+        const double n2 = wave_tree64(y * y);
+        ok = n2 > 1e-6 && n2 < 1e300;
+        y = y / sqrt(n2);
+    }
+    return ok ? y : x;
+}
+
 // NW waves per workgroup: 4 hold the matrix during the tridiagonalisation; with NW = 8 (ranks above 8: ZR = 16 / 64, where LDS
 // leaves a CU two workgroups or one and its SIMDs mostly idle) waves 4..7 wait at the barriers of that stage and then take
 // their share of what scales with the rank — sixteen eigenvalue searches and sixteen back-transformations per round instead of
@@ -955,6 +1013,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
                 }
                 use_twisted = false;
             }
+            // (wave-uniform; cold: the later copies of a repeated eigenvalue above the floor — a null space keeps its unit vectors)
+            if (!use_twisted && L.lam[r] > LRF_INIT_REFINE_FLOOR * L.lam[0]) x = init_refine<ZR>(L, Zs, r, i, x);
             Zs[r * 64 + i] = x;
         }
     }

@@ -710,6 +710,34 @@ static void twisted_vector(const double* d, const double* e, double lam, double 
     }
 }
 
+/* One step of inverse iteration, x <- (T - lam)^-1 x (T of side n), through the factorisation L D+ L^T that the twisted
+ * vector's forward recurrence computes (the same pivots, the same guard; qg[n]: scratch):
+ *   z_i = x_i - l_{i-1} z_{i-1},  w_i = z_i / D+_i,  y_i = w_i - l_i y_{i+1},   l_i = e_i / D+_i,  each update one fma.
+ * Only the fallback of the orthonormalisation stage comes here — the copies of a repeated eigenvalue after the first, whose
+ * twisted vector repeats an earlier one: LRF_INIT_REFINE steps from a fixed dense start vector, each followed by the
+ * stage's normalisation, Gram-Schmidt and loss test, give a vector of the eigenvalue's eigenspace.
+ * Only eigenvalues above LRF_INIT_REFINE_FLOOR lam[0] are repaired.  Below it the cluster is a null space (rank-deficient,
+ * constant and zero matrices: their eigenvalues come out below 1e-14 lam[0]), any orthonormal vectors serve, and the
+ * unit-vector replacements stay what they always were; a copy of a genuine eigenvalue that small, left unrepaired, adds at
+ * most 1e-12 |X|_F^2 to the residual. */
+#define LRF_INIT_REFINE 3
+#define LRF_INIT_REFINE_FLOOR 1e-12
+#define LRF_INIT_START(i) (1.0 + (double)(((i) * 29) & 63) * 0.015625)
+static void inverse_step(const double* d, const double* e, int n, double lam, double pivmin, double* x, double* qg)
+{
+    double q = d[0] - lam;
+    if (fabs(q) < pivmin) q = -pivmin;
+    qg[0] = q;
+    for (int i = 1; i < n; i++) {
+        q = (d[i] - lam) - (e[i - 1] * e[i - 1]) / q;
+        if (fabs(q) < pivmin) q = -pivmin;
+        qg[i] = q;
+    }
+    for (int i = 1; i < n; i++) x[i] = fma(-(e[i - 1] / qg[i - 1]), x[i - 1], x[i]);
+    for (int i = 0; i < n; i++) x[i] = x[i] / qg[i];
+    for (int i = n - 2; i >= 0; i--) x[i] = fma(-(e[i] / qg[i]), x[i + 1], x[i]);
+}
+
 /* G (EN x EN symmetric, destroyed) -> lam[R] (descending) and orthonormal eigenvectors Ev[r*EN + j]. */
 int lrf_oracle_top_eig_f64(double* G, int R, double* lam, double* Ev)
 {
@@ -747,6 +775,35 @@ int lrf_oracle_top_eig_f64(double* G, int R, double* lam, double* Ev)
                 break;
             }
             use_twisted = 0;
+        }
+        /* a replacement is exchanged for a vector of lam[r]'s eigenspace: inverse iteration from a fixed dense start vector
+         * (a unit vector has no component in the other blocks of a reducible T), the start vector and every iterate
+         * orthonormalised as a twisted vector is above, loss test included.  A step that gives no usable vector (overflow
+         * behind a pivot at the guard: zero and diagonal matrices; an iterate inside the span of the vectors already
+         * fixed) leaves the replacement as it is.  (Above the floor only: a null space keeps its unit vectors.) */
+        if (!use_twisted && lam[r] > LRF_INIT_REFINE_FLOOR * lam[0]) {
+            double y[EN], qg[EN];
+            int ok = 1;
+            for (int i = 0; i < EN; i++) y[i] = LRF_INIT_START(i);
+            for (int it = 0; it <= LRF_INIT_REFINE && ok; it++) {
+                if (it > 0) inverse_step(d, e, EN, lam[r], pivmin, y, qg);
+                for (int i = 0; i < EN; i++) s[i] = y[i] * y[i];
+                double n0 = sqrt(tree64(s));
+                for (int i = 0; i < EN; i++) y[i] = y[i] / n0;
+                for (int pr = 0; pr < r; pr++) {
+                    const double* pv = Z + pr * EN;
+                    for (int i = 0; i < EN; i++) s[i] = pv[i] * y[i];
+                    double c = tree64(s);
+                    for (int i = 0; i < EN; i++) y[i] = fma(-c, pv[i], y[i]);
+                }
+                for (int i = 0; i < EN; i++) s[i] = y[i] * y[i];
+                double n2 = tree64(s);
+                ok = n2 > 1e-6 && n2 < 1e300;
+                double nr = sqrt(n2);
+                for (int i = 0; i < EN; i++) y[i] = y[i] / nr;
+            }
+            if (ok)
+                for (int i = 0; i < EN; i++) x[i] = y[i];
         }
     }
     for (int r = 0; r < R; r++) { /* back-transform: x <- H_0 H_1 ... H_{n-3} x */

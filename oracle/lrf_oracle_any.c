@@ -626,6 +626,38 @@ static int any_sturm_count(const double* ds, const double* e2s, int n, double x)
     return cnt;
 }
 
+/* the orthonormalisation stage's two pieces (k_any_eig): classical Gram-Schmidt, twice, of x against Z[0..r), and |x|^2 */
+static void any_cgs2(const double* Z, int n, int r, int NCT, double* x, double* cf)
+{
+    double lanes[64];
+    for (int pass = 0; pass < 2 && r > 0; pass++) {
+        for (int pr = 0; pr < r; pr++) { /* lane l owns i = l, l + 64, ... (4 NCT of them) */
+            const double* Zp = Z + (long)pr * n;
+            for (int l = 0; l < 64; l++) {
+                double ds_ = 0.0;
+                for (int ee = 0; ee < 4 * NCT; ee++) { const int i = l + 64 * ee; if (i < n) ds_ = fma(Zp[i], x[i], ds_); }
+                lanes[l] = ds_;
+            }
+            cf[pr] = tree64c(lanes);
+        }
+        for (int pr = 0; pr < r; pr++) {
+            const double* Zp = Z + (long)pr * n;
+            for (int i = 0; i < n; i++) x[i] = fma(-cf[pr], Zp[i], x[i]);
+        }
+    }
+}
+
+static double any_norm2(const double* x, int n, int NCT)
+{
+    double tv[256];
+    for (int t = 0; t < 256; t++) {
+        double s = 0.0;
+        for (int c = 0; c < NCT; c++) { const int i = t + 256 * c; if (i < n) s = fma(x[i], x[i], s); }
+        tv[t] = s;
+    }
+    return block_sum256(tv);
+}
+
 /* Top-R eigen-pairs of the n x n Gram matrix G (destroyed) -> E1 = e sqrt(sigma), E2 = e / sqrt(sigma), fp32 [n][R]:
  * the tridiagonalisation the host code picks for this n, then k_any_eig's stages.  rcap: rank of the matrix at most this. */
 int lrf_oracle_any_eig(double* G, int n, int R, int rcap, const int8_t* sign, float* E1, float* E2)
@@ -637,7 +669,7 @@ int lrf_oracle_any_eig(double* G, int n, int R, int rcap, const int8_t* sign, fl
            *lam = (double*)malloc(sizeof(double) * (Rc > 0 ? Rc : 1)), *Z = (double*)calloc((size_t)(Rc > 0 ? Rc : 1) * n, sizeof(double)),
            *Dp = (double*)malloc(sizeof(double) * n), *Dm = (double*)malloc(sizeof(double) * n), *x = (double*)malloc(sizeof(double) * n),
            *cf = (double*)malloc(sizeof(double) * (Rc > 0 ? Rc : 1));
-    double tv[256], lanes[64];
+    double lanes[64];
     const char* tdv = getenv("LRF_ORACLE_ANY_TRIDIAG"); /* developer aid: "unblocked" = the round-2 variants above n = 192 */
     if (n > 64 && n <= 192) any_tridiag_reg(G, n, n <= 128 ? 2 : 3, d, e, tau);
     else if (n <= 64) any_tridiag_plain(G, n, d, e, tau);
@@ -744,45 +776,22 @@ int lrf_oracle_any_eig(double* G, int n, int R, int rcap, const int8_t* sign, fl
     }
     /* orthonormalisation: classical Gram-Schmidt, twice, against the vectors already fixed */
     int failed = 0;
+    double* y = (double*)malloc(sizeof(double) * n);
     for (int r = 0; r < Rc && !failed; r++) {
         double* Zr = Z + (long)r * n;
         int use_twisted = 1, uidx = 0;
         for (int i = 0; i < n; i++) { x[i] = Zr[i]; use_twisted &= isfinite(x[i]) != 0; }
         for (;;) {
             if (use_twisted) {
-                for (int t = 0; t < 256; t++) {
-                    double s = 0.0;
-                    for (int c = 0; c < NCT; c++) { const int i = t + 256 * c; if (i < n) s = fma(x[i], x[i], s); }
-                    tv[t] = s;
-                }
-                const double n0 = sqrt(block_sum256(tv));
+                const double n0 = sqrt(any_norm2(x, n, NCT));
                 for (int i = 0; i < n; i++) x[i] = x[i] / n0;
             } else {
                 if (uidx >= n) { failed = 1; break; }
                 for (int i = 0; i < n; i++) x[i] = (i == uidx) ? 1.0 : 0.0;
                 uidx++;
             }
-            for (int pass = 0; pass < 2 && r > 0; pass++) {
-                for (int pr = 0; pr < r; pr++) { /* lane l owns i = l, l + 64, ... (4 NCT of them) */
-                    const double* Zp = Z + (long)pr * n;
-                    for (int l = 0; l < 64; l++) {
-                        double ds_ = 0.0;
-                        for (int ee = 0; ee < 4 * NCT; ee++) { const int i = l + 64 * ee; if (i < n) ds_ = fma(Zp[i], x[i], ds_); }
-                        lanes[l] = ds_;
-                    }
-                    cf[pr] = tree64c(lanes);
-                }
-                for (int pr = 0; pr < r; pr++) {
-                    const double* Zp = Z + (long)pr * n;
-                    for (int i = 0; i < n; i++) x[i] = fma(-cf[pr], Zp[i], x[i]);
-                }
-            }
-            for (int t = 0; t < 256; t++) {
-                double s = 0.0;
-                for (int c = 0; c < NCT; c++) { const int i = t + 256 * c; if (i < n) s = fma(x[i], x[i], s); }
-                tv[t] = s;
-            }
-            const double n2 = block_sum256(tv);
+            any_cgs2(Z, n, r, NCT, x, cf);
+            const double n2 = any_norm2(x, n, NCT);
             if (n2 > 1e-6 && n2 < 1e300) {
                 const double nr = sqrt(n2);
                 for (int i = 0; i < n; i++) x[i] = x[i] / nr;
@@ -790,8 +799,28 @@ int lrf_oracle_any_eig(double* G, int n, int R, int rcap, const int8_t* sign, fl
             }
             use_twisted = 0;
         }
+        /* a replacement is exchanged for a vector of lam[r]'s eigenspace (lrf_oracle_top_eig_f64: inverse iteration from the
+         * fixed dense start vector; the start vector and every iterate orthonormalised as a twisted vector is above; above
+         * the floor only: a null space keeps its unit vectors) */
+        if (!use_twisted && !failed && lam[r] > LRF_INIT_REFINE_FLOOR * lam[0]) {
+            int ok = 1;
+            for (int i = 0; i < n; i++) y[i] = LRF_INIT_START(i);
+            for (int it = 0; it <= LRF_INIT_REFINE && ok; it++) {
+                if (it > 0) inverse_step(d, e, n, lam[r], pivmin, y, Dp);
+                const double n0 = sqrt(any_norm2(y, n, NCT));
+                for (int i = 0; i < n; i++) y[i] = y[i] / n0;
+                any_cgs2(Z, n, r, NCT, y, cf);
+                const double n2 = any_norm2(y, n, NCT);
+                ok = n2 > 1e-6 && n2 < 1e300;
+                const double nr = sqrt(n2);
+                for (int i = 0; i < n; i++) y[i] = y[i] / nr;
+            }
+            if (ok)
+                for (int i = 0; i < n; i++) x[i] = y[i];
+        }
         for (int i = 0; i < n; i++) Zr[i] = x[i];
     }
+    free(y);
     if (getenv("LRF_ORACLE_ANY_STAGE") && atoi(getenv("LRF_ORACLE_ANY_STAGE")) / 100 == 14) { /* developer aid */
         double* dbg = (double*)E1;
         const int r0 = atoi(getenv("LRF_ORACLE_ANY_STAGE")) % 100;
