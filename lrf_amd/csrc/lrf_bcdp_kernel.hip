@@ -389,8 +389,64 @@ __device__ __forceinline__ void bcdp_vupdate32(const PlaneDesc& pd, int pli, con
     }
 }
 
-// ---- ranks <= 8: one (matrix, 384-row block) on one wave — k_bcd_w<0> (lrf_bcdw_kernel.hip) operation for operation, with the
-// V table, the b table, the old int8 rows and the partial tables reached through sc1 accesses.  Xs: the wave's LDS share
+// ---- ranks <= 8: both products of the block body on 4x4x1 MFMA blocks, by rank QUAD (ranks 4 q .. 4 q + 3; one quad at R <= 4,
+// two at R = 5..8).  v_mfma_f32_4x4x1_16b_f32 is sixteen 4x4 outer products (block = lane >> 2; A: 4x1, i = lane & 3; B: 1x4,
+// j = lane & 3; D: register v of lane l = D_block[v][l & 3]); with cbsz:4 abid:T every block takes its A from block T, so
+// register v of lane l accumulates A[lane 4 T + v] * B[lane l]: the rank sits on the 4-side, the 64 lanes are 64 rows (x V) or
+// 64 columns (X^T u), and every element stays ONE chain of single fmas in ascending k — the order of row_times_v and of the
+// 16x16x4 tiles of k_bcd_w, without their padding of the rank to 16 or the 64 R DPP fmas.
+template <int T>
+__device__ __forceinline__ f32x4 mfma_quad(float a, float b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, acc, 4, T, 0); }
+// a quad operand of a [64][pitch] table held as four registers: op[s], lane l = tab[16 s + (l >> 2)][4 q + (l & 3)]
+// acc[c][v] = fma(op[c][k >> 4] (lane 4 (k & 15) + v), x[lane][k], acc[c][v]) for k = 0..63 in order; the NC chains are
+// interleaved step by step (two or more: no wait state between dependent MFMAs).  x: the lane's own row of the LDS tile.
+template <int NC>
+__device__ __forceinline__ void row_times_quads(const float* xrow_lds, int g16, const float (&op)[4][4], f32x4 (&acc)[4])
+{
+    // the sixteen reads go out together, ahead of the MFMAs (left to itself the compiler issues one, waits, and uses it)
+    f32x4 xv[16];
+    static_for<16>([&](auto Jc) {
+        constexpr int J = Jc;
+        xv[J] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(xrow_lds) + ((16 * J) ^ g16));
+    });
+    __builtin_amdgcn_sched_barrier(0);
+    static_for<64>([&](auto kc) {
+        constexpr int k = kc;
+#pragma unroll
+        for (int c = 0; c < NC; c++) acc[c] = mfma_quad<(k & 15)>(op[c][k >> 4], xv[k >> 2][k & 3], acc[c]);
+    });
+}
+// accP[q][v] (lane = column n) += u[m][4 q + v] * X[m][n] for the sub-tile's rows m = 0..63 in order.  us: the fp32 u tile
+// [64][8]; X[m][n]: one ds_read_b32 at dword 64 m + 4 ((n >> 2) ^ xsw(m)) + (n & 3), a permutation of the row's 64 banks; the
+// reads go out sixteen rows ahead of the MFMAs that use them.
+template <int Q>
+__device__ __forceinline__ void xt_u_quads(const float* Xs, const float* us, int lane, f32x4 (&accP)[2])
+{
+    float uq[Q][4];
+#pragma unroll
+    for (int q = 0; q < Q; q++)
+#pragma unroll
+        for (int s = 0; s < 4; s++) uq[q][s] = us[(16 * s + (lane >> 2)) * 8 + 4 * q + (lane & 3)];
+    const char* xb = reinterpret_cast<const char*>(Xs);
+    const int l4 = 4 * lane;
+    static_for<4>([&](auto sc) {
+        constexpr int s = sc;
+        float xc[16];
+        static_for<16>([&](auto cc) {
+            constexpr int c = cc;
+            xc[c] = *reinterpret_cast<const float*>(xb + 256 * (16 * s + c) + (l4 ^ (16 * c)));
+        });
+        static_for<16>([&](auto cc) {
+            constexpr int c = cc;
+#pragma unroll
+            for (int q = 0; q < Q; q++) accP[q] = mfma_quad<c>(uq[q][s], xc[c], accP[q]);
+        });
+    });
+}
+
+// ---- ranks <= 8: one (matrix, 384-row block) on one wave — k_bcd_w<0> (lrf_bcdw_kernel.hip) element for element in the same
+// order of operations, a = x V and a' += X^T u on 4x4x1 MFMA blocks (above) instead of the VALU chain and the 16-wide tiles, with
+// the V table, the b table, the old int8 rows and the partial tables reached through sc1 accesses.  Xs: the wave's LDS share
 // (X tile 16 KB, then the fp32 u tile 2 KB, then the U-span staging area, LRF_BCDP_USTAGE bytes).
 // MODE 1 (round 5, k_bcd_p<.., .., true>): the call's FIRST iteration, k_bcd_w<1> — the old U is X @ W0 (the initialisation's
 // table Wf, written before the launch), no int8 rows are read.
@@ -402,10 +458,6 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
     constexpr int RMAX = 8;
     const int li = lane & 15, lq = lane >> 4;
     float* us = Xs + 64 * 64;
-    const float* xp[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++) xp[e] = &Xs[lq * 64 + 4 * (li ^ (4 * e + lq))];
-    const float* ub = &us[lq * RMAX + (li & 7)];
     const float* uq = &us[(lq + 4 * (li >> 3)) * RMAX + (li & 7)];
     const float* xrow = &Xs[lane * 64];
     const int g16 = 16 * xsw(lane);
@@ -419,22 +471,33 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
     const int nsub = (nrows + 63) >> 6;
     const bool native = pd.native_t2_u != 0;
 
-    // the V table: row 16 kb + li, columns 0..7 = two 16-B chunks; the b table: entry tn < 7 of row tr, or its reciprocal
-    // denominator (tn = 7), picked out of the 16-B chunk that holds it; the denominator from the chunk at LRF_GT_RDEN
-    float vreg[8][4], wreg[MODE == 1 ? 8 : 1][4];
+    // the V table (MODE 1: and W0) as quad operands (row_times_quads): vq[q][s], lane l = V[16 s + (l >> 2)][4 q + (l & 3)], one
+    // word per lane out of the 16-B chunk q of that row.  Ranks at or past R are ZERO operands (the tables hold whatever an
+    // earlier call of a higher rank left there); the second quad exists at R > 4 only (wave-uniform).
+    // The b table: entry tn < 7 of row tr, or its reciprocal denominator (tn = 7), picked out of the 16-B chunk that holds it;
+    // the denominator from the chunk at LRF_GT_RDEN
+    const bool quads2 = R > 4;
+    float vq[2][4], wq[2][4]; // (wq: MODE 1 only)
+    {
+        const int lr = lane & 3, lrow = lane >> 2;
 #pragma unroll
-    for (int kb = 0; kb < 4; kb++)
+        for (int q = 0; q < 2; q++)
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const f32x4 v4 = ld_sc1_x4(Vp, ((16 * kb + li) * LRF_RP + 4 * h) * 4);
-#pragma unroll
-            for (int c = 0; c < 4; c++) vreg[4 * h + c][kb] = v4[c];
-        }
-    if constexpr (MODE == 1) {
-#pragma unroll
-        for (int r = 0; r < 8; r++)
-#pragma unroll
-            for (int kb = 0; kb < 4; kb++) wreg[r][kb] = Wf[((long)bd.plane * 64 + 16 * kb + li) * LRF_RP + r];
+            for (int s = 0; s < 4; s++) {
+                vq[q][s] = 0.f;
+                if (q == 0 || quads2) {
+                    const f32x4 v4 = ld_sc1_x4(Vp, ((16 * s + lrow) * LRF_RP + 4 * q) * 4);
+                    const float v = lr == 0 ? v4[0] : lr == 1 ? v4[1] : lr == 2 ? v4[2] : v4[3];
+                    vq[q][s] = 4 * q + lr < R ? v : 0.f;
+                }
+                wq[q][s] = 0.f;
+                if constexpr (MODE == 1) {
+                    if (q == 0 || quads2) {
+                        const float w = Wf[((long)bd.plane * 64 + 16 * s + lrow) * LRF_RP + 4 * q + lr];
+                        wq[q][s] = 4 * q + lr < R ? w : 0.f;
+                    }
+                }
+            }
     }
     static_assert(LRF_GT_LD % 4 == 0 && LRF_GT_RDEN % 4 == 0 && LRF_GT_DEN == LRF_GT_RDEN + 1, "b-table chunks");
     float tab[5];
@@ -498,9 +561,9 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
         hi = __builtin_amdgcn_alignbyte(w2, w1, (unsigned)(o & 3));
     };
 
-    f32x4 accP[4], accQ = (f32x4){0.f, 0.f, 0.f, 0.f};
+    f32x4 accP[2], accQ = (f32x4){0.f, 0.f, 0.f, 0.f}; // accP[q][v], lane n = P[column n][rank 4 q + v]
 #pragma unroll
-    for (int c = 0; c < 4; c++) accP[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < 2; q++) accP[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     if constexpr (MODE == 0) issue_u(0);
     issue_x(0, 0, 4, true);
@@ -540,14 +603,42 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
             }
         }
         __builtin_amdgcn_sched_barrier(0);
+        // a = x V (MODE 1: and u = x W0) of the lane's row: one chain per quad, the chains of a sub-tile interleaved
         float a[RMAX];
+        {
+            f32x4 acc[4];
 #pragma unroll
-        for (int r = 0; r < RMAX; r++) a[r] = 0.f;
-        row_times_v_dispatch(R, xrow, g16, vreg, a);
-        if constexpr (MODE == 1) {
+            for (int c = 0; c < 4; c++) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            float op[4][4];
 #pragma unroll
-            for (int r = 0; r < RMAX; r++) u[r] = 0.f;
-            row_times_v_dispatch(R, xrow, g16, wreg, u);
+            for (int s = 0; s < 4; s++) {
+                op[0][s] = vq[0][s];
+                op[1][s] = vq[1][s];
+                op[2][s] = wq[0][s];
+                op[3][s] = wq[1][s];
+            }
+            if constexpr (MODE == 0) {
+                if (quads2) row_times_quads<2>(xrow, g16, op, acc);
+                else row_times_quads<1>(xrow, g16, op, acc);
+            } else {
+                if (quads2) row_times_quads<4>(xrow, g16, op, acc);
+                else {
+#pragma unroll
+                    for (int s = 0; s < 4; s++) op[1][s] = wq[0][s];
+                    row_times_quads<2>(xrow, g16, op, acc);
+                    acc[2] = acc[1];
+                    acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+            }
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                a[v] = acc[0][v];
+                a[4 + v] = acc[1][v];
+                if constexpr (MODE == 1) {
+                    u[v] = acc[2][v];
+                    u[4 + v] = acc[3][v];
+                }
+            }
         }
         issue_x(tn, 2, 3, more);
         __builtin_amdgcn_sched_barrier(0);
@@ -601,37 +692,28 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        float pu[16], qu[8];
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-            float v = ub[4 * s * RMAX];
-            pu[s] = (li < RMAX) ? v : 0.f;
-        }
+        // b' += u^T u on its eight 16x16x4 tiles (small integers: exact in any order), a' += X^T u by rank quad
+        float qu[8];
 #pragma unroll
         for (int h = 0; h < 8; h++) qu[h] = uq[8 * h * RMAX];
-        f32x4 px[16];
 #pragma unroll
-        for (int s = 0; s < 16; s++) px[s] = *reinterpret_cast<const f32x4*>(xp[s & 3] + 256 * s);
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-#pragma unroll
-            for (int c = 0; c < 4; c++) accP[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(px[s][c], pu[s], accP[c], 0, 0, 0);
-            if (s & 1) accQ = __builtin_amdgcn_mfma_f32_16x16x4f32(qu[s >> 1], qu[s >> 1], accQ, 0, 0, 0);
-        }
+        for (int h = 0; h < 8; h++) accQ = __builtin_amdgcn_mfma_f32_16x16x4f32(qu[h], qu[h], accQ, 0, 0, 0);
+        if (quads2) xt_u_quads<2>(Xs, us, lane, accP);
+        else xt_u_quads<1>(Xs, us, lane, accP);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
-    // the dense slot (bcdp_dense_chunks) through the X tile's LDS, which the loop's closing barrier has freed: lane (li, lq)
-    // holds P[16 lq + 4 reg + c][li] in accP[c][reg], i.e. the 16 B of P^T row li at column 16 lq + 4 reg; b' entry
-    // (4 lq + reg, li) = mine + other.  Then whole 16-B chunks out, consecutive lanes on consecutive chunks.
+    // the dense slot (bcdp_dense_chunks) through the X tile's LDS, which the loop's closing barrier has freed: lane n holds
+    // column n of P^T row 4 q + v in accP[q][v]; b' entry (4 lq + reg, li) = mine + other.  Then whole 16-B chunks out,
+    // consecutive lanes on consecutive chunks.
     float* ps = Xs;
-    if (li < R) {
 #pragma unroll
-        for (int reg = 0; reg < 4; reg++)
-            *reinterpret_cast<f32x4*>(&ps[li * 64 + 16 * lq + 4 * reg]) = (f32x4){accP[0][reg], accP[1][reg], accP[2][reg], accP[3][reg]};
-    }
+    for (int q = 0; q < 2; q++)
+#pragma unroll
+        for (int v = 0; v < 4; v++)
+            if (4 * q + v < R) ps[(4 * q + v) * 64 + lane] = accP[q][v];
 #pragma unroll
     for (int reg = 0; reg < 4; reg++) {
         const int i = 4 * lq + reg;
