@@ -389,6 +389,43 @@ int lrf_qmf_encode_ragged_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_encod
                                  int K, int lo, int hi, const int8_t* sign /* optional, flat */, int64_t sign_len, int8_t* U, int64_t u_len,
                                  int8_t* V, int64_t v_len);
 
+/*
+ * A ragged sweep: n images of differing sizes, each at a list of candidate rank triples of its own, m candidates in all, in one
+ * call — lrf_qmf_encode_sweep_rgb_u8 and lrf_qmf_encode_ragged_rgb_u8 married (rate control over a list of mixed sizes).
+ *   images  n descriptors in host memory: size, where the image's [3][H][W] bytes start in rgb, and where its signs start
+ *           in sign (-1, or a NULL sign: the default signs).  The signs of an image are [Rmax_Y + Rmax_Cb + Rmax_Cr], the largest
+ *           rank of each channel over the image's candidates; every candidate uses the leading signs of its ranks (the uniform
+ *           sweep's convention)
+ *   cands   m descriptors in host memory: the image a candidate belongs to, its ranks (1..32) and where its factors are
+ *           written in U / V, in lrf_qmf_encode_rgb_u8's layout of ONE image.  The candidates of an image may lie anywhere in
+ *           the list; every image needs at least one
+ * Candidate j's U / V bytes are exactly those lrf_qmf_encode_ragged_rgb_u8 writes for (image, R) alone with the same K, lo, hi
+ * and signs, which in turn are lrf_qmf_encode_rgb_u8's at B = 1.
+ * Shared per image: the planes stage (the ragged planes kernels, plan_encode_ragged's launches), the X workspace (the sum over
+ * images, not candidates), the exact Gram matrix and the SVD initialisation, once per (image, channel) at the image's largest
+ * rank for the channel; the other candidates take its leading columns.  The BCD of all m candidates is one table in the uniform
+ * sweep's order, its kernels chosen by the same plan.  Asynchronous on the context's stream, except that a new list uploads its
+ * tables and waits for the stream.
+ * Everything is validated on the host before any launch or write.  LRF_EINVAL: a NULL pointer, n outside [1,65535], m outside
+ * [n,2^20], a candidate naming no image, an image without a candidate, a size or rank or bounds lrf_qmf_encode_rgb_u8 refuses
+ * with it, a negative offset, pixels, signs or factors that leave their buffer, factor ranges of two candidates that overlap.
+ * LRF_ENOTSUP: a rank above 32, an image of 2^31 / 3 pixels or more, 2^31 or more blocks in the call.
+ */
+typedef struct {
+    int64_t H, W;      /* image size */
+    int64_t rgb_off;   /* bytes from rgb to this image's [3][H][W] input */
+    int64_t sign_off;  /* int8 elements from sign to this image's signs; -1: default signs */
+} lrf_ragged_sweep_image;
+typedef struct {
+    int32_t image;        /* index into images */
+    int R[3];             /* ranks Y, Cb, Cr, each 1..32 */
+    int64_t u_off, v_off; /* int8 elements from U / V to this candidate's factors */
+} lrf_ragged_sweep_candidate;
+int lrf_qmf_encode_ragged_sweep_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_sweep_image* images /* host */, int64_t m,
+                                       const lrf_ragged_sweep_candidate* cands /* host */, const uint8_t* rgb, int64_t rgb_len, int K, int lo,
+                                       int hi, const int8_t* sign /* optional, flat */, int64_t sign_len, int8_t* U, int64_t u_len, int8_t* V,
+                                       int64_t v_len);
+
 /* ---- scoring (the third stage of the reference's experiment loop) ----------------------------- */
 
 /*
@@ -429,6 +466,22 @@ int lrf_image_metrics_u8(lrf_ctx* ctx, const uint8_t* a, const uint8_t* b, int B
  */
 int lrf_qmf_sweep_sse_rgb_u8(lrf_ctx* ctx, const uint8_t* rgb /* [B,3,H,W] */, const int8_t* U, const int8_t* V, int64_t B, int64_t H,
                              int64_t W, int Q, const int* R /* [Q][3] */, uint64_t* sse /* [Q][B] */);
+
+/*
+ * The same for a list of items that differ in size and ranks: sse[i] = sum over the 3 H_i W_i samples of
+ * (source_i - decode(U_i, V_i))^2, an exact integer, where decode is byte for byte the image lrf_qmf_decode_ragged_rgb_u8 writes
+ * for the same descriptor and source_i is the [3][H_i][W_i] at rgb + items[i].rgb_off.  Several items may read one source (the
+ * candidates of an image do) and the items may come in any order; the value depends on neither.
+ *   items  n descriptors in host memory, lrf_qmf_decode_ragged_rgb_u8's, with rgb_off naming where the SOURCE is read
+ *   sse    [n] uint64 (device memory); zeroed by the call on its stream
+ * The kernels are the ragged decode kernels with the uniform scorer's sink: integer sums (uint32 per lane and wave, uint64 per
+ * workgroup, one 64-bit integer atomic per workgroup).  At most eight launches (plan_decode_ragged), timed under LRF_K_DECODE.
+ * The table travels stream-ordered through pinned slots and is not kept: the call does not wait for the stream.
+ * LRF_EINVAL: what lrf_qmf_decode_ragged_rgb_u8 refuses (a NULL pointer, n outside [1,65535], a rank outside [1,64], a negative
+ * offset, factors or a source that leave their buffer); source ranges may overlap.
+ */
+int lrf_qmf_sse_ragged_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_image* items /* host */, const int8_t* U, int64_t u_len, const int8_t* V,
+                              int64_t v_len, const uint8_t* rgb, int64_t rgb_len, uint64_t* sse /* [n] */);
 
 /* ---- the SVD baseline ------------------------------------------------- */
 

@@ -1,6 +1,7 @@
 """ctypes binding of liblrf_hip.so (include/lrf_hip.h).  There is no CPU fallback: if the HIP
 library is missing or no GPU is visible, the calls raise."""
 import ctypes
+import functools
 import os
 import threading
 
@@ -59,6 +60,16 @@ class RaggedEncodeImage(ctypes.Structure):
     _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int * 3), ("rgb_off", c_i64), ("u_off", c_i64), ("v_off", c_i64), ("sign_off", c_i64)]
 
 
+class RaggedSweepImage(ctypes.Structure):
+    """lrf_ragged_sweep_image (include/lrf_hip.h)"""
+    _fields_ = [("H", c_i64), ("W", c_i64), ("rgb_off", c_i64), ("sign_off", c_i64)]
+
+
+class RaggedSweepCandidate(ctypes.Structure):
+    """lrf_ragged_sweep_candidate (include/lrf_hip.h)"""
+    _fields_ = [("image", ctypes.c_int32), ("R", c_int * 3), ("u_off", c_i64), ("v_off", c_i64)]
+
+
 def load():
     """Loads liblrf_hip.so; raises ImportError when it has not been built (see __graft_entry__.build)."""
     global _lib
@@ -115,6 +126,9 @@ def load():
                                                             ctypes.POINTER(ResizedCrop), c_i64, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_encode_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedEncodeImage), c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64,
                                                      c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_encode_ragged_sweep_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedSweepImage), c_i64, ctypes.POINTER(RaggedSweepCandidate),
+                                                           c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_sse_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]
         lib.lrf_deflate_bound.restype = c_i64
         lib.lrf_deflate_bound.argtypes = [c_i64]
         lib.lrf_deflate_columns_i8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64]
@@ -165,7 +179,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_qmf_encode_ragged_sweep_rgb_u8", "lrf_qmf_sse_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -188,14 +202,33 @@ def check(rc):
     raise LrfError(msg)
 
 
-def plane_dims(H, W):
-    """[(h, w, hp, wp, M)] of the Y, Cb, Cr planes of an H x W image (host-only arithmetic)."""
+@functools.lru_cache(maxsize=8192)
+def _plane_dims_of(H, W):
     out = []
     for c in range(3):
         v = [c_i64() for _ in range(5)]
         check(load().lrf_plane_dims(H, W, c, *[ctypes.byref(x) for x in v]))
         out.append(tuple(int(x.value) for x in v))
-    return out
+    return tuple(out)
+
+
+def plane_dims(H, W):
+    """[(h, w, hp, wp, M)] of the Y, Cb, Cr planes of an H x W image (host-only arithmetic; remembered per size: lists of many
+    images ask for few distinct sizes)."""
+    return list(_plane_dims_of(int(H), int(W)))
+
+
+def plane_patches(H, W):
+    """int64 array [n, 3]: the patch counts M of the Y, Cb, Cr planes for arrays H, W of n sizes, plane_dims asked once per distinct size"""
+    H, W = np.asarray(H, dtype=np.int64).reshape(-1), np.asarray(W, dtype=np.int64).reshape(-1)
+    sizes, inverse = np.unique(np.stack([H, W], axis=1), axis=0, return_inverse=True)
+    Ms = np.array([[d[4] for d in plane_dims(int(h), int(w))] for h, w in sizes], dtype=np.int64).reshape(-1, 3)
+    return Ms[inverse.reshape(-1)]
+
+
+# the C structures as numpy records (same layout: checked against ctypes.sizeof where they are used)
+_RAGGED_IMAGE_DT = np.dtype([("H", "<i8"), ("W", "<i8"), ("R", "<i4", (3,)), ("u_off", "<i8"), ("v_off", "<i8"), ("rgb_off", "<i8")], align=True)
+_SWEEP_CAND_DT = np.dtype([("image", "<i4"), ("R", "<i4", (3,)), ("u_off", "<i8"), ("v_off", "<i8")], align=True)
 
 
 def plane_dims_any(H, W, patch_size, chroma=None):
@@ -496,6 +529,142 @@ def check_encode_ragged_args(rgb, images, sign=None):
             raise ValueError(f"image {i}: its {sum(ranks)} signs at {sign_off} leave the sign buffer")
         out.append((H, W, ranks, rgb_off, sign_off))
     return out
+
+
+def _check_encode_ragged_sweep(rgb, images, cands, sign=None):
+    """The argument checks of lrf_qmf_encode_ragged_sweep_rgb_u8 on its tensors, before any device is touched.  rgb: a flat uint8
+    tensor; images: 1 to 65535 tuples (H, W, rgb_off[, sign_off]) with every image's bytes inside rgb; cands: up to 2^20 tuples
+    (image, ranks), every rank in 1..32, at least one per image, in any order; sign: None or a flat int8 tensor on rgb's device,
+    an image's sign_off (-1 or absent: the default signs) naming where its signs start — one per channel's largest rank over the
+    image's candidates.  TypeError for tensors of another type, ValueError for everything else.
+    -> ([(H, W, rgb_off, sign_off)], int64 array [m, 4] of (image, R_Y, R_Cb, R_Cr)); the candidates may be given as such an array."""
+    import torch
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8:
+        raise TypeError("encode_ragged_sweep takes its pixels as a uint8 tensor")
+    if sign is not None and (not isinstance(sign, torch.Tensor) or sign.dtype != torch.int8):
+        raise TypeError("encode_ragged_sweep takes its signs as an int8 tensor")
+    if rgb.dim() != 1 or not rgb.is_contiguous() or (sign is not None and (sign.dim() != 1 or not sign.is_contiguous() or sign.device != rgb.device)):
+        raise ValueError("rgb (and sign) must be flat contiguous tensors on one device")
+    if images is None or len(images) < 1 or len(images) > 65535:
+        raise ValueError("encode_ragged_sweep needs 1 to 65535 images")
+    if cands is None or len(cands) < len(images) or len(cands) > 2 ** 20:
+        raise ValueError(f"encode_ragged_sweep needs a candidate per image at least and 2^20 at most, got {0 if cands is None else len(cands)} for {len(images)} images")
+    ims = []
+    for i, im in enumerate(images):
+        if len(im) not in (3, 4):
+            raise ValueError(f"image {i}: (H, W, rgb_off[, sign_off]) expected")
+        H, W, rgb_off = im[:3]
+        sign_off = im[3] if len(im) == 4 and im[3] is not None else -1
+        if any(int(x) != x for x in (H, W, rgb_off, sign_off)):
+            raise ValueError(f"image {i}: integers expected")
+        H, W, rgb_off, sign_off = int(H), int(W), int(rgb_off), int(sign_off)
+        if H < 1 or W < 1 or 3 * H * W >= 2 ** 31:
+            raise ValueError(f"image {i}: size {H}x{W} out of range (fewer than 2^31 / 3 pixels)")
+        if rgb_off < 0 or rgb_off + 3 * H * W > rgb.numel():
+            raise ValueError(f"image {i}: its {3 * H * W} bytes at {rgb_off} leave the buffer of {rgb.numel()} bytes")
+        ims.append((H, W, rgb_off, sign_off))
+    ims_a = np.array(ims, dtype=np.int64).reshape(-1, 4)
+    cds = _sweep_candidates_array(cands, len(ims))
+    rmax = np.zeros((len(ims), 3), dtype=np.int64)
+    np.maximum.at(rmax, cds[:, 0], cds[:, 1:4])
+    none = np.nonzero(rmax[:, 0] == 0)[0]
+    if none.size:
+        raise ValueError(f"image {int(none[0])} has no candidate")
+    bad = (ims_a[:, 3] < -1) | ((ims_a[:, 3] >= 0) & ((sign is None) | (ims_a[:, 3] + rmax.sum(axis=1) > (0 if sign is None else sign.numel()))))
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"image {i}: its {int(rmax[i].sum())} signs at {int(ims_a[i, 3])} leave the sign buffer")
+    return ims, cds
+
+
+def check_encode_ragged_sweep_args(rgb, images, cands, sign=None):
+    """_check_encode_ragged_sweep with the candidates as a list: ([(H, W, rgb_off, sign_off)], [(image, [R_Y, R_Cb, R_Cr])])"""
+    ims, cds = _check_encode_ragged_sweep(rgb, images, cands, sign)
+    return ims, [(c[0], c[1:]) for c in cds.tolist()]
+
+
+def _sweep_candidates_array(cands, n_images):
+    """[(image, (R_Y, R_Cb, R_Cr))] -> int64 array [m, 4], checked as a whole (ValueError names the first offender)"""
+    if isinstance(cands, np.ndarray) and cands.ndim == 2 and cands.shape[1] == 4:  # (image, R_Y, R_Cb, R_Cr) per row
+        raw = cands
+    else:
+        try:
+            flat = [(cd[0], cd[1][0], cd[1][1], cd[1][2]) for cd in cands if len(cd) == 2 and len(cd[1]) == 3]
+        except TypeError:
+            flat = []
+        if len(flat) != len(cands):
+            j = next(j for j, cd in enumerate(cands) if not (hasattr(cd, "__len__") and len(cd) == 2 and hasattr(cd[1], "__len__") and len(cd[1]) == 3))
+            raise ValueError(f"candidate {j}: (image, (R_Y, R_Cb, R_Cr)) expected")
+        raw = np.array(flat)
+    if raw.dtype.kind not in "iu":
+        if raw.dtype.kind != "f" or not np.array_equal(raw, np.floor(raw)):
+            raise ValueError("candidates: integers expected")
+    cds = raw.astype(np.int64).reshape(-1, 4)
+    bad = (cds[:, 0] < 0) | (cds[:, 0] >= n_images)
+    if bad.any():
+        j = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"candidate {j}: image {int(cds[j, 0])} out of range [0,{n_images})")
+    bad = (cds[:, 1:].min(axis=1) < 1) | (cds[:, 1:].max(axis=1) > 32)
+    if bad.any():
+        j = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"candidate {j}: ranks {cds[j, 1:].tolist()} out of range (1..32)")
+    return cds
+
+
+def _sse_items_array(rgb, items, U, V):
+    """check_sse_ragged_args on the whole list at once -> int64 array [n, 8] of (H, W, R_Y, R_Cb, R_Cr, u_off, v_off, rgb_off)"""
+    import torch
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8:
+        raise TypeError("sse_ragged takes its sources as a uint8 tensor")
+    if not isinstance(U, torch.Tensor) or not isinstance(V, torch.Tensor) or U.dtype != torch.int8 or V.dtype != torch.int8:
+        raise TypeError("factors must be int8 tensors")
+    if rgb.dim() != 1 or not rgb.is_contiguous():
+        raise ValueError("sse_ragged takes its sources as a flat contiguous tensor")
+    if U.dim() != 1 or V.dim() != 1 or U.device != V.device or not U.is_contiguous() or not V.is_contiguous():
+        raise ValueError(f"U and V must be flat contiguous tensors on one device, got {tuple(U.shape)} on {U.device} and {tuple(V.shape)} on {V.device}")
+    if U.device != rgb.device:
+        raise ValueError(f"sse_ragged needs its tensors on one device, got {rgb.device} and {U.device}")
+    if isinstance(items, np.ndarray) and items.ndim == 2 and items.shape[1] == 8 and items.dtype.kind in "iu":
+        a = items.astype(np.int64, copy=False)
+    else:
+        if items is None or len(items) < 1:
+            raise ValueError("sse_ragged needs at least one item")
+        try:
+            flat = [(it[0], it[1], it[2][0], it[2][1], it[2][2], it[3], it[4], it[5]) for it in items if len(it) == 6 and len(it[2]) == 3]
+        except TypeError:
+            flat = []
+        if len(flat) != len(items):
+            i = next(i for i, it in enumerate(items) if not (hasattr(it, "__len__") and len(it) == 6 and hasattr(it[2], "__len__") and len(it[2]) == 3))
+            raise ValueError(f"item {i}: (H, W, (R_Y, R_Cb, R_Cr), u_off, v_off, rgb_off) expected")
+        raw = np.array(flat)
+        if raw.dtype.kind not in "iu" and (raw.dtype.kind != "f" or not np.array_equal(raw, np.floor(raw))):
+            raise ValueError("items: integers expected")
+        a = raw.astype(np.int64).reshape(-1, 8)
+    if a.shape[0] < 1:
+        raise ValueError("sse_ragged needs at least one item")
+
+    def first(bad, what):
+        if bad.any():
+            i = int(np.nonzero(bad)[0][0])
+            raise ValueError(f"item {i}: {what(i)}")
+    first((a[:, 0] < 1) | (a[:, 1] < 1) | (a[:, 0] >= 2 ** 31) | (a[:, 1] >= 2 ** 31) | (a[:, 2:5].min(axis=1) < 1) | (a[:, 2:5].max(axis=1) > 64),
+          lambda i: f"size {a[i, 0]}x{a[i, 1]} or ranks {a[i, 2:5].tolist()} out of range (ranks 1..64)")
+    Ms = plane_patches(a[:, 0], a[:, 1])
+    nu, nv, px = (Ms * a[:, 2:5]).sum(axis=1), 64 * a[:, 2:5].sum(axis=1), 3 * a[:, 0] * a[:, 1]
+    first((a[:, 5] < 0) | (a[:, 6] < 0) | (a[:, 5] > U.numel() - nu) | (a[:, 6] > V.numel() - nv),
+          lambda i: f"its factors (U {nu[i]} elements at {a[i, 5]}, V {nv[i]} at {a[i, 6]}) leave the buffers of {U.numel()} and {V.numel()} elements")
+    first((a[:, 7] < 0) | (a[:, 7] > rgb.numel() - px), lambda i: f"its source of {px[i]} bytes at {a[i, 7]} leaves the buffer of {rgb.numel()} bytes")
+    return a
+
+
+def check_sse_ragged_args(rgb, items, U, V):
+    """The argument checks of lrf_qmf_sse_ragged_rgb_u8 on its tensors, before any device is touched.  rgb: a flat uint8 tensor
+    holding the sources; U, V: flat int8 tensors on its device; items: at least one tuple (H, W, ranks, u_off, v_off, rgb_off) — or
+    an integer array [n, 8] of (H, W, R_Y, R_Cb, R_Cr, u_off, v_off, rgb_off) — every rank in 1..64, the factors inside U and V and
+    the [3,H,W] source inside rgb (sources may be shared).  The list is checked as a whole, the geometry asked once per distinct
+    size.  TypeError for tensors of another type, ValueError for everything else.
+    -> [(H, W, [R_Y, R_Cb, R_Cr], u_off, v_off, rgb_off)] as integers."""
+    return [(r[0], r[1], r[2:5], r[5], r[6], r[7]) for r in _sse_items_array(rgb, items, U, V).tolist()]
 
 
 def deflate_bound(length):
@@ -900,6 +1069,56 @@ class Context:
         check(self._lib.lrf_qmf_encode_ragged_rgb_u8(self._h, len(ims), desc, _dptr(rgb), rgb.numel(), int(K), int(lo), int(hi), _dptr(sign),
                                                      0 if sign is None else sign.numel(), _dptr(U), uo, _dptr(V), vo))
         return U, V, u_off, v_off
+
+    def encode_ragged_sweep(self, rgb, images, cands, K, lo, hi, sign=None):
+        """Images that differ in size, each at candidate rank triples of its own, in one encode
+        (lrf_qmf_encode_ragged_sweep_rgb_u8).  rgb: a flat uint8 CUDA tensor; images: [(H, W, rgb_off[, sign_off])]; cands:
+        [(image, ranks)] in any order, at least one per image; sign: None or a flat int8 CUDA tensor holding, per image with a
+        sign_off, the signs of its largest rank per channel -> (U, V, u_off, v_off): two flat int8 CUDA tensors and, per
+        candidate, where its factors start in them, each in encode_rgb's layout of one image, back to back in list order."""
+        import torch
+        ims, cd = _check_encode_ragged_sweep(rgb, images, cands, sign)
+        if not (rgb.is_cuda and rgb.device.index == self.device):
+            raise ValueError(f"encode_ragged_sweep needs its tensors on cuda:{self.device}, got {rgb.device}")
+        idesc = (RaggedSweepImage * len(ims))()
+        for d, (H, W, rgb_off, sign_off) in zip(idesc, ims):
+            d.H, d.W, d.rgb_off, d.sign_off = H, W, rgb_off, sign_off
+        ims_a = np.array(ims, dtype=np.int64).reshape(-1, 4)
+        Ms = plane_patches(ims_a[:, 0], ims_a[:, 1])[cd[:, 0]]
+        nu, nv = (Ms * cd[:, 1:]).sum(axis=1), 64 * cd[:, 1:].sum(axis=1)
+        assert _SWEEP_CAND_DT.itemsize == ctypes.sizeof(RaggedSweepCandidate)
+        rec = np.zeros((cd.shape[0],), dtype=_SWEEP_CAND_DT)
+        rec["image"], rec["R"], rec["u_off"], rec["v_off"] = cd[:, 0], cd[:, 1:], np.cumsum(nu) - nu, np.cumsum(nv) - nv
+        cdesc = rec.ctypes.data_as(ctypes.POINTER(RaggedSweepCandidate))
+        u_off, v_off, uo, vo = rec["u_off"].tolist(), rec["v_off"].tolist(), int(nu.sum()), int(nv.sum())
+        U = torch.empty((uo,), dtype=torch.int8, device=rgb.device)
+        V = torch.empty((vo,), dtype=torch.int8, device=rgb.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_encode_ragged_sweep_rgb_u8(self._h, len(ims), idesc, int(cd.shape[0]), cdesc, _dptr(rgb), rgb.numel(), int(K), int(lo), int(hi),
+                                                           _dptr(sign), 0 if sign is None else sign.numel(), _dptr(U), uo, _dptr(V), vo))
+        return U, V, u_off, v_off
+
+    def sse_ragged(self, rgb, items, U, V):
+        """The squared error of items that differ in size and ranks straight from their factors (lrf_qmf_sse_ragged_rgb_u8).  rgb:
+        a flat uint8 CUDA tensor holding the sources; items: [(H, W, ranks, u_off, v_off, rgb_off)] (or an integer array [n, 8] with
+        the ranks spread out), item i's factors at
+        U[u_off:], V[v_off:] and its source [3,H,W] at rgb[rgb_off:] (several items may share a source) -> int64 CUDA tensor
+        [len(items)], sse[i] = ((decode_ragged's image of item i).long() - source.long()) ** 2 summed, without the decoded
+        images.  Lists above 65535 items take one call per 65535.  Asynchronous on torch's current stream."""
+        import torch
+        its = _sse_items_array(rgb, items, U, V)
+        if not (rgb.is_cuda and rgb.device.index == self.device):
+            raise ValueError(f"sse_ragged needs its tensors on cuda:{self.device}, got {rgb.device}")
+        assert _RAGGED_IMAGE_DT.itemsize == ctypes.sizeof(RaggedImage)
+        rec = np.zeros((its.shape[0],), dtype=_RAGGED_IMAGE_DT)
+        rec["H"], rec["W"], rec["R"], rec["u_off"], rec["v_off"], rec["rgb_off"] = its[:, 0], its[:, 1], its[:, 2:5], its[:, 5], its[:, 6], its[:, 7]
+        sse = torch.empty((its.shape[0],), dtype=torch.int64, device=rgb.device)
+        self.use_torch_stream()
+        for k in range(0, its.shape[0], 65535):
+            part = rec[k:k + 65535]
+            check(self._lib.lrf_qmf_sse_ragged_rgb_u8(self._h, part.shape[0], part.ctypes.data_as(ctypes.POINTER(RaggedImage)), _dptr(U), U.numel(), _dptr(V),
+                                                      V.numel(), _dptr(rgb), rgb.numel(), c_void_p(sse[k:].data_ptr())))
+        return sse
 
     def deflate_columns_into(self, src, table, slots, lens):
         """lrf_deflate_columns_i8 with every offset named by the caller: src a flat int8 CUDA tensor, table an int64 array [n, 5]

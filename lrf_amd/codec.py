@@ -1,6 +1,7 @@
 """qmf_encode / qmf_decode with the reference's signatures (lrf/compression/qmf.py:116-353), running the
 arithmetic on the MI355X.  Python keeps the byte container (JSON metadata + per-column zlib), exactly
 as the reference does on the host."""
+import functools
 import math
 from typing import Iterable, Optional, Sequence
 
@@ -130,9 +131,9 @@ def target_candidates(image_hw, qualities):
     return triples, lowest
 
 
-def select_target(sse: torch.Tensor, n: int, target: torch.Tensor):
+def select_target(sse: torch.Tensor, n, target: torch.Tensor):
     """The choice qmf_encode_target makes, from exact squared errors: sse int64 [Q,B] (candidate q in ascending quality, image b),
-    n samples per image, target float64 [B] in dB -> (table float64 [Q,B] of PSNR, index int64 [B], reached bool [B]).
+    n samples per image (an integer, or one integer per image as a tensor [B]: a list of mixed sizes), target float64 [B] in dB -> (table float64 [Q,B] of PSNR, index int64 [B], reached bool [B]).
     index[b] is the FIRST candidate whose PSNR >= target[b] — every candidate is looked at, nothing assumes that PSNR grows with
     quality — and, where none reaches it, the first candidate of the highest PSNR (reached False).  sse = 0 is PSNR inf, which
     reaches every target.  Evaluated on the device `sse` lives on, by the expression image_metrics_batch uses."""
@@ -193,8 +194,8 @@ def _sweep_candidates(images, qualities, bounds, num_iters):
     return ctx, dev, triples, lowest, factors, sse
 
 
-def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
-                      pack_workers: Optional[int] = None, deflate: str = "host") -> dict:
+def qmf_encode_target(images, psnr, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
+                      pack_workers: Optional[int] = None, deflate: str = "host", x_workspace_bytes: int = 1 << 30) -> dict:
     """Per image of a batch [B,3,H,W], the smallest-quality stream that reaches `psnr` dB (one number, or one per image).
 
     Default branch only (YCbCr, 8x8 patches, uint8, num_iters >= 1).  Every distinct rank triple of `qualities` is factorised on
@@ -209,8 +210,18 @@ def qmf_encode_target(images: torch.Tensor, psnr, qualities=range(1, 33), bounds
     (quality of `qualities`, image) pair}.  The tensors are host tensors.
 
     deflate="device": the winners' columns are deflated on the GPU (as in qmf_encode_batch) and only their streams' bytes come
-    to the host; the streams then hold the same factors as the default call's but are not byte-identical to them."""
+    to the host; the streams then hold the same factors as the default call's but are not byte-identical to them.
+
+    `images` may also be a list or tuple of uint8 [3,H_i,W_i] tensors of differing sizes, all on the host or all on one device
+    (_rate_control_list): `psnr` is then one number or one per image, the candidates of image i are
+    target_candidates((H_i, W_i), qualities), and the dict has the same keys — "table" [len(qualities), B] with image i's column
+    computed over its own 3 H_i W_i samples.  A quality whose triple has a rank above 32 on some image is refused
+    (NotImplementedError naming the image and the quality; the default grid never gives one).  x_workspace_bytes bounds the fp32
+    patch matrices of one GPU call: a longer list is processed in chunks of consecutive images, which changes no byte.  A batch
+    of equal sizes is best given as a tensor."""
     on_device = _deflate_on_device(deflate)
+    if isinstance(images, (list, tuple)):
+        return _rate_control_list(images, "qmf_encode_target", dict(psnr=psnr), qualities, bounds, num_iters, pack_workers, on_device, x_workspace_bytes)
     qualities, target = _check_target_args(images, psnr, qualities, num_iters)
     H, W = images.shape[-2:]
     B = images.shape[0]
@@ -245,6 +256,11 @@ def _device_streams_of_rows(ctx, pair, sel, image_hw, triple, bounds, pack_worke
                                        np.arange(k, dtype=np.int64) * Vs.shape[1], bounds, _pack_threads(pack_workers))
 
 
+@functools.lru_cache(maxsize=256)
+def _factor_header_len(r):
+    return len(dict_to_bytes({"num_fibers": r, "mode": "col", "dtype": "int8"}))
+
+
 def container_bytes(meta_len, ranks, column_lengths):
     """len() of the container lrf_pack_qmf_streams_deflated folds from an image's deflated columns, by host arithmetic: the
     metadata JSON of meta_len bytes, then six factors (u_Y, v_Y, u_Cb, v_Cb, u_Cr, v_Cr), each one JSON header {"num_fibers",
@@ -258,7 +274,7 @@ def container_bytes(meta_len, ranks, column_lengths):
         raise ValueError(f"container_bytes: three ranks >= 1 and 2 sum(ranks) column lengths expected, got {ranks} and {tuple(lens.shape)}")
     const = 4 + int(meta_len) + 4 * 5  # the metadata's prefix; five of the six factors carry one
     for r in ranks:  # per factor: the header and its prefix, a prefix for every column but the last
-        const += 2 * (4 + len(dict_to_bytes({"num_fibers": r, "mode": "col", "dtype": "int8"})) + 4 * (r - 1))
+        const += 2 * (4 + _factor_header_len(r) + 4 * (r - 1))
     total = lens.sum(dim=-1, dtype=torch.int64) if isinstance(lens, torch.Tensor) else lens.sum(axis=-1, dtype=np.int64)
     return total + const
 
@@ -346,8 +362,8 @@ def _check_budget_args(images, bpp, nbytes, qualities, num_iters):
     return qualities, budget.expand(B).contiguous()
 
 
-def qmf_encode_budget(images: torch.Tensor, bpp=None, nbytes=None, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
-                      pack_workers: Optional[int] = None) -> dict:
+def qmf_encode_budget(images, bpp=None, nbytes=None, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
+                      pack_workers: Optional[int] = None, x_workspace_bytes: int = 1 << 30) -> dict:
     """Per image of a batch [B,3,H,W], the best stream that fits a byte budget: `nbytes` bytes, or `bpp` bits per pixel (=
     floor(bpp H W / 8) bytes); one number, or one per image.
 
@@ -362,8 +378,15 @@ def qmf_encode_budget(images: torch.Tensor, bpp=None, nbytes=None, qualities=ran
     deflate="device")[0]; "quality": the chosen quality per image (the lowest of those that share its rank triple); "nbytes":
     int64 [B], their lengths; "bpp": float64 [B], bits_per_pixel((H, W), stream); "psnr": float64 [B]; "reached": bool [B], False
     where no candidate fits (the smallest stream is returned then); "size_table": int64 [len(qualities), B]; "table": float64
-    [len(qualities), B], the PSNR of every (quality, image) pair}.  The tensors are host tensors."""
+    [len(qualities), B], the PSNR of every (quality, image) pair}.  The tensors are host tensors.
+
+    `images` may also be a list or tuple of uint8 [3,H_i,W_i] tensors of differing sizes, all on the host or all on one device
+    (_rate_control_list): `bpp` / `nbytes` are then one number or one per image, `bpp` converted with each image's own H_i W_i;
+    same keys, same meanings.  Refusals and x_workspace_bytes: as in qmf_encode_target."""
     from .metrics import bits_per_pixel, psnr_from_sse
+    if isinstance(images, (list, tuple)):
+        return _rate_control_list(images, "qmf_encode_budget", dict(bpp=bpp, nbytes=nbytes), qualities, bounds, num_iters, pack_workers, True,
+                                  x_workspace_bytes)
     qualities, budget = _check_budget_args(images, bpp, nbytes, qualities, num_iters)
     H, W = images.shape[-2:]
     B = images.shape[0]
@@ -395,6 +418,228 @@ def qmf_encode_budget(images: torch.Tensor, bpp=None, nbytes=None, qualities=ran
     return {"streams": streams, "quality": [lowest[i] for i in index.tolist()], "nbytes": counted,
             "bpp": torch.tensor([bits_per_pixel((H, W), s) for s in streams], dtype=torch.float64), "psnr": chosen_psnr,
             "reached": reached, "size_table": size[row_of], "table": table[row_of]}
+
+
+def _check_rate_list_args(images, qualities, num_iters, name):
+    """what the list forms of qmf_encode_target and qmf_encode_budget refuse about images, qualities and num_iters, before a GPU
+    is asked for -> (qualities as a list, [(H, W)], per image (triples, lowest, rows): what target_candidates gives for its size and,
+    per quality in ascending order, which of the triples it has — worked out once per distinct size)"""
+    if len(images) < 1:
+        raise ValueError(f"{name} takes a non-empty list of images")
+    for i, im in enumerate(images):
+        if not isinstance(im, torch.Tensor):
+            raise TypeError(f"{name}: image {i} is {type(im).__name__}, not a tensor")
+        if im.dim() == 4:  # a batch wrapped in a list is the wrong kind of argument, as before lists were taken: the batch itself is the tensor form
+            raise TypeError(f"{name}: entry {i} of the list is a batch {tuple(im.shape)}; a list holds [3,H,W] images, a batch is passed as a tensor")
+        if im.dtype != torch.uint8:
+            raise NotImplementedError(f"{name}: image {i} is {im.dtype}; the HIP path takes uint8 images")
+        if im.dim() != 3 or im.shape[0] != 3 or im.shape[1] < 1 or im.shape[2] < 1:
+            raise ValueError(f"{name}: image {i} must be [3,H,W], got {tuple(im.shape)}")
+    if len({im.device for im in images}) != 1:
+        raise ValueError(f"{name}: the images of a list must all be on the host or all on one device, got {sorted({str(im.device) for im in images})}")
+    if num_iters < 1:
+        raise NotImplementedError(f"{name}: num_iters = 0 (the truncated initialisation) is outside the fused sweep")
+    qualities = list(qualities)
+    if not qualities or any(not (0 <= q <= 100) for q in qualities):
+        raise ValueError(f"{name}: 'qualities' must be a non-empty sequence of numbers between 0 and 100")
+    sizes = [(int(im.shape[1]), int(im.shape[2])) for im in images]
+    per_size = {}
+    for i, hw in enumerate(sizes):
+        if hw in per_size:
+            continue
+        if 3 * hw[0] * hw[1] >= 2 ** 31:
+            raise NotImplementedError(f"{name}: image {i} of {hw[0]}x{hw[1]} has 2^31 / 3 pixels or more")
+        for q in sorted(qualities):
+            t = qmf_ranks(hw, None, q)
+            if max(t) > 32:
+                raise NotImplementedError(f"{name}: image {i} ({hw[0]}x{hw[1]}) at quality {q} has ranks {tuple(t)}: a list takes ranks up to 32 "
+                                          f"(encode such images one by one through the tensor form)")
+        triples, lowest = target_candidates(hw, qualities)
+        per_size[hw] = (triples, lowest, [triples.index(tuple(qmf_ranks(hw, None, q))) for q in sorted(qualities)])
+    return qualities, sizes, [per_size[hw] for hw in sizes]
+
+
+def _per_image_numbers(value, n, name, what):
+    """`value` (one number or one per image) as a float64 tensor [n] on the host; ValueError for another count or a NaN"""
+    v = torch.as_tensor(value).detach().cpu()
+    if v.dtype == torch.bool or v.is_complex():
+        raise TypeError(f"{name}: '{what}' must hold numbers, got {v.dtype}")
+    v = v.to(torch.float64).reshape(-1)
+    if v.numel() not in (1, n) or bool(torch.isnan(v).any()):
+        raise ValueError(f"{name}: '{what}' must be one number or one per image ({n}), got {v.numel()} values")
+    return v.expand(n).contiguous()
+
+
+def budget_bytes_per_image(sizes, bpp=None, nbytes=None) -> torch.Tensor:
+    """The byte budget of every image of a list, int64 [B]: `nbytes` as it is, or `bpp` bits per pixel converted with each image's
+    own size, floor(bpp H_i W_i / 8) — in float64 once, integers from there on (what qmf_encode_budget does for a tensor)."""
+    name = "qmf_encode_budget"
+    if (bpp is None) == (nbytes is None):
+        raise ValueError(f"{name}: give exactly one of 'bpp' and 'nbytes'")
+    v = _per_image_numbers(bpp if bpp is not None else nbytes, len(sizes), name, "bpp" if bpp is not None else "nbytes")
+    if bool((v < 0).any()):
+        raise ValueError(f"{name}: '{'bpp' if bpp is not None else 'nbytes'}' must be >= 0")
+    if bpp is not None:
+        v = v * torch.tensor([h * w for h, w in sizes], dtype=torch.float64) / 8
+    return torch.floor(v).clamp(max=2.0 ** 62).to(torch.int64)
+
+
+def qmf_stream_sizes_ragged(U, V, sizes, triples, u_off, v_off, bounds=(-16, 15)) -> torch.Tensor:
+    """The exact length of the deflate="device" stream of every candidate of a ragged sweep, counted on the GPU without producing
+    one.  U, V: flat int8 CUDA tensors holding m candidates of sizes[j] = (H, W) and ranks triples[j] at u_off[j] / v_off[j]
+    (Context.encode_ragged_sweep's layout, or encode_ragged's) -> int64 CUDA tensor [m], out[j] = len() of the stream
+    streams_from_device_factors produces for candidate j.  One lrf_deflate_sizes_i8 count over all U matrices and one over all V
+    matrices; the column lengths are summed per candidate on the device and container_bytes adds the constant of the candidate's
+    own metadata length and ranks."""
+    m = len(sizes)
+    if m < 1 or not (len(triples) == len(u_off) == len(v_off) == m):
+        raise ValueError("qmf_stream_sizes_ragged needs one size, rank triple, u_off and v_off per candidate")
+    if not (isinstance(U, torch.Tensor) and isinstance(V, torch.Tensor) and U.dtype == torch.int8 and V.dtype == torch.int8):
+        raise TypeError("factors must be int8 tensors")
+    key = np.concatenate([np.asarray(sizes, dtype=np.int64).reshape(m, 2), np.asarray(triples, dtype=np.int64).reshape(m, 3)], axis=1)
+    Rs = key[:, 2:]
+    if Rs.min() < 1:
+        raise ValueError("qmf_stream_sizes_ragged: ranks must be >= 1")
+    Ms = _lib.plane_patches(key[:, 0], key[:, 1])
+    # the container constant once per distinct (size, triple): container_bytes of all-zero column lengths
+    distinct, inverse = np.unique(key, axis=0, return_inverse=True)
+    const = np.array([int(container_bytes(len(_stream_metadata((int(k[0]), int(k[1])), [int(r) for r in k[2:]], bounds)), [int(r) for r in k[2:]],
+                                          np.zeros(2 * int(k[2:].sum()), dtype=np.int64))) for k in distinct], dtype=np.int64)[inverse.reshape(-1)]
+    u_mats = np.empty((m, 3, 3), dtype=np.int64)  # (src_off, rows, cols): candidate after candidate, plane after plane
+    u_mats[:, :, 0] = np.asarray(u_off, dtype=np.int64).reshape(m, 1) + np.cumsum(Ms * Rs, axis=1) - Ms * Rs
+    u_mats[:, :, 1] = Ms
+    u_mats[:, :, 2] = Rs
+    v_mats = u_mats.copy()
+    v_mats[:, :, 0] = np.asarray(v_off, dtype=np.int64).reshape(m, 1) + 64 * (np.cumsum(Rs, axis=1) - Rs)
+    v_mats[:, :, 1] = 64
+    ctx = _lib.context(U.device.index)
+    out = torch.from_numpy(const).to(U.device)
+    per = Rs.sum(axis=1)
+    step = (1 << 20) // 3  # (lrf_deflate_sizes_i8 takes 2^20 matrices a call)
+    for k in range(0, m, step):
+        owner = torch.from_numpy(np.repeat(np.arange(k, min(k + step, m), dtype=np.int64), per[k:k + step])).to(U.device)
+        for flat, mats in ((U, u_mats), (V, v_mats)):
+            lens = ctx.deflate_sizes(flat.reshape(-1), mats[k:k + step].reshape(-1, 3))
+            out.index_add_(0, owner, lens.to(torch.int64))
+    return out
+
+
+def _rate_control_list(images, name, goal, qualities, bounds, num_iters, pack_workers, on_device, x_workspace_bytes) -> dict:
+    """qmf_encode_target / qmf_encode_budget for a list of images of differing sizes.  Per chunk of consecutive images (as many as
+    keep the fp32 patch matrices within x_workspace_bytes; one image at least): ONE ragged sweep encode of every (image, candidate
+    triple), ONE ragged squared error straight from the factors, for the budget ONE ragged size count, the choice on the device
+    (select_target / select_budget on [len(qualities), B] tables gathered from the per-candidate vectors), and only the winners
+    packed.  Nothing depends on the other images of a call, so a chunk boundary changes no byte."""
+    from .metrics import bits_per_pixel, psnr_from_sse
+    budget_mode = name == "qmf_encode_budget"
+    qualities, sizes, cand_of = _check_rate_list_args(images, qualities, num_iters, name)
+    B = len(images)
+    if budget_mode:
+        goal_t = budget_bytes_per_image(sizes, goal["bpp"], goal["nbytes"])
+    else:
+        goal_t = _per_image_numbers(goal["psnr"], B, name, "psnr")
+    if int(x_workspace_bytes) < 1:
+        raise ValueError(f"{name}: x_workspace_bytes must be >= 1")
+    sorted_q = sorted(qualities)
+    x_bytes = [4 * 64 * sum(d[4] for d in _lib.plane_dims(*hw)) for hw in sizes]
+    chunks, at = [], 0
+    while at < B:
+        end, tot, ncand = at, 0, 0
+        while end < B and (end == at or (tot + x_bytes[end] <= x_workspace_bytes and end - at < 65535 and ncand + len(cand_of[end][0]) <= 2 ** 20)):
+            tot += x_bytes[end]
+            ncand += len(cand_of[end][0])
+            end += 1
+        chunks.append(range(at, end))
+        at = end
+    ctx = _lib.context(images[0].device.index if images[0].is_cuda else None)
+    dev = torch.device("cuda", ctx.device)
+    lo, hi = math.ceil(bounds[0]), math.floor(bounds[1])
+    streams, quality = [None] * B, [None] * B
+    tables, size_tables, chosen, reached_all, counted_all = [], [], [], [], []
+    for chunk in chunks:
+        n = len(chunk)
+        offs, off = [], 0
+        for i in chunk:
+            offs.append(off)
+            off = (off + 3 * sizes[i][0] * sizes[i][1] + 15) // 16 * 16
+        if images[0].is_cuda:
+            flat = torch.empty((off,), dtype=torch.uint8, device=dev)
+            for i, o in zip(chunk, offs):
+                flat[o:o + images[i].numel()].view(images[i].shape).copy_(images[i])
+        else:
+            stage = torch.empty((off,), dtype=torch.uint8).pin_memory()
+            for i, o in zip(chunk, offs):
+                stage[o:o + images[i].numel()].view(images[i].shape).copy_(images[i])
+            flat = stage.to(dev, non_blocking=True)
+        # the candidates, image after image in ascending quality, and row[q][k]: the candidate of (sorted quality q, image k)
+        counts = np.array([len(cand_of[i][0]) for i in chunk], dtype=np.int64)
+        first = np.cumsum(counts) - counts
+        owner = np.repeat(np.arange(n, dtype=np.int64), counts)               # the image (within the chunk) of every candidate
+        ranks = np.array([t for i in chunk for t in cand_of[i][0]], dtype=np.int64).reshape(-1, 3)
+        row = first.reshape(1, n) + np.array([cand_of[i][2] for i in chunk], dtype=np.int64).T
+        cands = np.concatenate([owner.reshape(-1, 1), ranks], axis=1)
+        hw = np.array([sizes[i] for i in chunk], dtype=np.int64).reshape(n, 2)
+        U, V, u_off, v_off = ctx.encode_ragged_sweep(flat, [(sizes[i][0], sizes[i][1], o) for i, o in zip(chunk, offs)], cands, num_iters, lo, hi, None)
+        u_off, v_off = np.asarray(u_off, dtype=np.int64), np.asarray(v_off, dtype=np.int64)
+        c_hw = hw[owner]
+        items = np.concatenate([c_hw, ranks, u_off.reshape(-1, 1), v_off.reshape(-1, 1), np.asarray(offs, dtype=np.int64)[owner].reshape(-1, 1)], axis=1)
+        sse_vec = ctx.sse_ragged(flat, items, U, V)
+        row_d = torch.from_numpy(row).to(dev)
+        sse = sse_vec[row_d]
+        samples = torch.tensor([3 * sizes[i][0] * sizes[i][1] for i in chunk], dtype=torch.int64)  # (on the host: psnr_from_sse groups the columns by count)
+        goal_c = goal_t[chunk.start:chunk.stop]
+        if budget_mode:
+            size = qmf_stream_sizes_ragged(U, V, c_hw, ranks, u_off, v_off, bounds)[row_d]
+            index, reached = select_budget(size, sse, goal_c)
+            table = psnr_from_sse(sse, samples)[1]
+            counted_all.append(size.gather(0, index.reshape(1, -1))[0].cpu())
+            size_tables.append(size.cpu())
+        else:
+            table, index, reached = select_target(sse, samples, goal_c)
+        chosen.append(table.gather(0, index.reshape(1, -1))[0].cpu())
+        tables.append(table.cpu())
+        reached_all.append(reached.cpu())
+        index = index.cpu().tolist()
+        win = [int(row[index[k], k]) for k in range(n)]
+        w_sizes, w_triples = [sizes[i] for i in chunk], [ranks[j].tolist() for j in win]
+        u_off, v_off = u_off.tolist(), v_off.tolist()
+        if on_device:
+            packed = streams_from_device_factors(ctx, U, V, w_sizes, w_triples, [u_off[j] for j in win], [v_off[j] for j in win], bounds,
+                                                 _pack_threads(pack_workers))
+        else:  # only the winners' factors come to the host: gathered back to back on the device first
+            nus = [sum(d[4] * r for d, r in zip(_lib.plane_dims(*hw), t)) for hw, t in zip(w_sizes, w_triples)]
+            nvs = [64 * sum(t) for t in w_triples]
+            Uw = torch.cat([U[u_off[j]:u_off[j] + nu] for j, nu in zip(win, nus)])
+            Vw = torch.cat([V[v_off[j]:v_off[j] + nv] for j, nv in zip(win, nvs)])
+            Uh, Vh = (x.numpy() for x in ctx.to_host(Uw, Vw))  # waits for the stream, then raises if a launch of this call gave up
+            wu, wv = np.cumsum([0] + nus[:-1]).tolist(), np.cumsum([0] + nvs[:-1]).tolist()
+            packed = None
+            if pack_workers != "python" and not (isinstance(pack_workers, int) and pack_workers < 0):
+                try:
+                    packed, rc = pack_streams_ragged_native(Uh, Vh, w_sizes, w_triples, wu, wv, bounds, threads=pack_workers or default_pack_threads())
+                    if rc:
+                        raise RuntimeError(f"lrf_pack_qmf_streams_ragged failed ({rc})")
+                except OSError:  # liblrf_pack.so missing or linked against another zlib: the Python container code, same bytes
+                    packed = None
+            if packed is None:
+                packed = [pack_image(split_factors(Uh[a:a + nu], Vh[b:b + nv], hw, t), hw, t, bounds, (8, 8), "uint8")
+                          for a, b, nu, nv, hw, t in zip(wu, wv, nus, nvs, w_sizes, w_triples)]
+        for k, i in enumerate(chunk):
+            streams[i] = packed[k]
+            quality[i] = sorted_q[index[k]]
+    if budget_mode:
+        counted = torch.cat(counted_all)
+        for b, s in enumerate(streams):
+            if len(s) != int(counted[b]):
+                raise RuntimeError(f"qmf_encode_budget: image {b} at quality {quality[b]}: the stream has {len(s)} bytes, {int(counted[b])} were counted")
+    row_of = [sorted_q.index(q) for q in qualities]
+    out = {"streams": streams, "quality": quality, "psnr": torch.cat(chosen), "reached": torch.cat(reached_all),
+           "table": torch.cat(tables, dim=1)[row_of]}
+    if budget_mode:
+        out["nbytes"] = counted
+        out["bpp"] = torch.tensor([bits_per_pixel(hw, s) for hw, s in zip(sizes, streams)], dtype=torch.float64)
+        out["size_table"] = torch.cat(size_tables, dim=1)[row_of]
+    return out
 
 
 def qmf_factorize_host(images: torch.Tensor, ranks: Sequence[int], num_iters: int = 10, bounds=(-16, 15), init_sign=None,

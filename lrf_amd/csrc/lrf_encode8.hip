@@ -8,6 +8,7 @@
 #include "lrf_bcdw16_kernel.hip"
 #include "lrf_sweep_sse_kernel.hip"
 #include "lrf_decode_ragged_kernel.hip"
+#include "lrf_sse_ragged_kernel.hip"
 #include "lrf_decode_crops_kernel.hip"
 #include "lrf_decode_scaled_kernel.hip"
 #include "lrf_decode_resized_kernel.hip"
@@ -518,6 +519,47 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64
     return init_then_bcd(c, X, t, plan, sign, LRF_PLANES_GRAM_EXP, U, V);
 }
 
+} // extern "C"
+
+// the planes stage of a ragged call: its table on the device (resident while calls repeat the list), then the launches of the plan
+static int run_planes_ragged(lrf_ctx* c, const std::vector<EncRaggedDesc>& descs, const std::vector<RaggedBlock>& blocks,
+                             const std::vector<EncRaggedLaunch>& launches, const uint8_t* rgb, float* X)
+{
+    int rc;
+    // the planes table: descriptors, then workgroups (a function of the descriptors: they alone are the key)
+    const size_t db = descs.size() * sizeof(EncRaggedDesc), bb = blocks.size() * sizeof(RaggedBlock);
+    if (c->enc_ragged_key.size() != db || memcmp(c->enc_ragged_key.data(), descs.data(), db) != 0 || !c->enc_ragged_tab.p) {
+        c->enc_ragged_key.clear();
+        std::vector<char> tab(db + bb);
+        memcpy(tab.data(), descs.data(), db);
+        memcpy(tab.data() + db, blocks.data(), bb);
+        if ((rc = upload(c, c->enc_ragged_tab, tab.data(), tab.size()))) return rc;
+        c->enc_ragged_key.assign((const char*)descs.data(), (const char*)descs.data() + db);
+    }
+    const EncRaggedDesc* d_desc = (const EncRaggedDesc*)c->enc_ragged_tab.p;
+    const RaggedBlock* d_blk = (const RaggedBlock*)((const char*)c->enc_ragged_tab.p + db);
+    {
+        Prof p(c, LRF_K_PLANES);
+        for (const EncRaggedLaunch& l : launches) {
+            const RaggedBlock* bl = d_blk + l.block0;
+#define LRF_RAGGED_STRIP(KH, KW) \
+    hipLaunchKernelGGL((k_planes_strip_ragged<KH, KW>), dim3((unsigned)(8 * l.xcd_chunk)), dim3(256), 0, c->stream, rgb, X, d_desc, bl, (int)l.nblocks, l.xcd_chunk)
+            switch (l.body) {
+            case ENC_TILE16: hipLaunchKernelGGL(k_planes16_ragged, dim3((unsigned)l.nblocks), dim3(256), 0, c->stream, rgb, X, d_desc, bl); break;
+            case ENC_STRIP22: LRF_RAGGED_STRIP(2, 2); break;
+            case ENC_STRIP23: LRF_RAGGED_STRIP(2, 3); break;
+            case ENC_STRIP32: LRF_RAGGED_STRIP(3, 2); break;
+            default: LRF_RAGGED_STRIP(3, 3); break;
+            }
+#undef LRF_RAGGED_STRIP
+            LAUNCH_CHECK();
+        }
+    }
+    return LRF_OK;
+}
+
+extern "C" {
+
 // A list of images that differ in size and ranks in one encode (planes kernels: lrf_planes_ragged_kernel.hip; the tables:
 // plan_encode_ragged).  Behind the planes stage the call is its plane table: Gram pass, initialisation and iterations read
 // PlaneDesc / BlockDesc as in every other call, chosen by the same plan_bcd.  Everything the kernels index with is checked here,
@@ -580,36 +622,96 @@ int lrf_qmf_encode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_encode_
     if (rc) return rc;
     const BcdPlan bcd = plan_bcd(plan.t.planes, K, lo, hi, PLAN_FIRST_W0, settings);
     if ((rc = upload_tables(c, plan.t, bcd))) return rc;
-    // the planes table: descriptors, then workgroups (a function of the descriptors: they alone are the key)
-    const size_t db = plan.descs.size() * sizeof(EncRaggedDesc), bb = plan.blocks.size() * sizeof(RaggedBlock);
-    if (c->enc_ragged_key.size() != db || memcmp(c->enc_ragged_key.data(), plan.descs.data(), db) != 0 || !c->enc_ragged_tab.p) {
-        c->enc_ragged_key.clear();
-        std::vector<char> tab(db + bb);
-        memcpy(tab.data(), plan.descs.data(), db);
-        memcpy(tab.data() + db, plan.blocks.data(), bb);
-        if ((rc = upload(c, c->enc_ragged_tab, tab.data(), tab.size()))) return rc;
-        c->enc_ragged_key.assign((const char*)plan.descs.data(), (const char*)plan.descs.data() + db);
-    }
-    const EncRaggedDesc* d_desc = (const EncRaggedDesc*)c->enc_ragged_tab.p;
-    const RaggedBlock* d_blk = (const RaggedBlock*)((const char*)c->enc_ragged_tab.p + db);
     float* X = (float*)c->x.p;
-    {
-        Prof p(c, LRF_K_PLANES);
-        for (const EncRaggedLaunch& l : plan.launches) {
-            const RaggedBlock* bl = d_blk + l.block0;
-#define LRF_RAGGED_STRIP(KH, KW) \
-    hipLaunchKernelGGL((k_planes_strip_ragged<KH, KW>), dim3((unsigned)(8 * l.xcd_chunk)), dim3(256), 0, c->stream, rgb, X, d_desc, bl, (int)l.nblocks, l.xcd_chunk)
-            switch (l.body) {
-            case ENC_TILE16: hipLaunchKernelGGL(k_planes16_ragged, dim3((unsigned)l.nblocks), dim3(256), 0, c->stream, rgb, X, d_desc, bl); break;
-            case ENC_STRIP22: LRF_RAGGED_STRIP(2, 2); break;
-            case ENC_STRIP23: LRF_RAGGED_STRIP(2, 3); break;
-            case ENC_STRIP32: LRF_RAGGED_STRIP(3, 2); break;
-            default: LRF_RAGGED_STRIP(3, 3); break;
-            }
-#undef LRF_RAGGED_STRIP
-            LAUNCH_CHECK();
-        }
+    if ((rc = run_planes_ragged(c, plan.descs, plan.blocks, plan.launches, rgb, X))) return rc;
+    if (c->planes_done) HIP_TRY(hipEventRecord(c->planes_done, c->stream)); // the RGB bytes are not read again
+    return init_then_bcd(c, X, plan.t, bcd, sign, LRF_PLANES_GRAM_EXP, U, V);
+}
+
+// The two entries above married: n images that differ in size, each at a list of candidate rank triples of its own, m candidates
+// in all (the tables: plan_encode_ragged_sweep).  The planes stage runs once per image, the Gram pass and the initialisation
+// once per (image, channel) at the image's largest rank for that channel; the other candidates take its leading columns
+// (k_init_share), and the BCD of all m candidates runs as one table that shares X.  Everything the kernels index with is checked
+// here, before anything is launched or written.
+int lrf_qmf_encode_ragged_sweep_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_sweep_image* images, int64_t m, const lrf_ragged_sweep_candidate* cands,
+                                       const uint8_t* rgb, int64_t rgb_len, int K, int lo, int hi, const int8_t* sign, int64_t sign_len, int8_t* U,
+                                       int64_t u_len, int8_t* V, int64_t v_len)
+{
+    if (!c || !images || !cands || !rgb || !U || !V) return set_err(LRF_EINVAL, "NULL argument");
+    if (n < 1 || n > 65535) return set_err(LRF_EINVAL, "n=%ld out of range [1,65535]", (long)n);
+    if (m < n || m > (1 << 20)) return set_err(LRF_EINVAL, "m=%ld out of range [n,2^20] (every image needs a candidate)", (long)m);
+    if (rgb_len < 1 || u_len < 1 || v_len < 1 || (sign && sign_len < 1)) return set_err(LRF_EINVAL, "a buffer length below 1");
+    if (sign && sign_len > INT32_MAX) return set_err(LRF_ENOTSUP, "sign_len=%ld: sign offsets are 32-bit", (long)sign_len);
+    std::vector<EncSweepImage> ims((size_t)n);
+    std::vector<ImageGeom> geoms((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_ragged_sweep_image& im = images[i];
+        if (im.H < 1 || im.W < 1 || im.H > INT32_MAX || im.W > INT32_MAX) return set_err(LRF_EINVAL, "image %ld: size %ldx%ld out of range", (long)i, (long)im.H, (long)im.W);
+        int rc = make_geom(im.H, im.W, &geoms[(size_t)i]);
+        if (rc) return rc;
+        if (im.rgb_off < 0 || im.sign_off < -1) return set_err(LRF_EINVAL, "image %ld: negative offset", (long)i);
+        if (im.H * im.W * 3 >= (1L << 31)) return set_err(LRF_ENOTSUP, "image %ld: too large for 32-bit pixel indexing", (long)i);
+        const long bytes = 3 * im.H * im.W;
+        if (bytes > rgb_len || im.rgb_off > rgb_len - bytes) return set_err(LRF_EINVAL, "image %ld: its pixels leave the buffer of %ld bytes", (long)i, (long)rgb_len);
+        EncSweepImage& e = ims[(size_t)i];
+        e.H = im.H; e.W = im.W;
+        e.rgb_off = im.rgb_off;
+        e.sign_off = sign && im.sign_off >= 0 ? im.sign_off : -1;
+        e.aligned8 = ((reinterpret_cast<uintptr_t>(rgb) + (uintptr_t)im.rgb_off) & 7) == 0;
     }
+    std::vector<EncSweepCand> cs((size_t)m);
+    std::vector<long> s_img((size_t)n * 3, 0); // the largest rank per (image, channel)
+    struct Range { long off, len; };
+    std::vector<Range> ur((size_t)m), vr((size_t)m);
+    for (int64_t j = 0; j < m; j++) {
+        const lrf_ragged_sweep_candidate& cd = cands[j];
+        if (cd.image < 0 || cd.image >= n) return set_err(LRF_EINVAL, "candidate %ld: image %d out of range [0,%ld)", (long)j, cd.image, (long)n);
+        const ImageGeom& g = geoms[(size_t)cd.image];
+        int rc;
+        for (int ch = 0; ch < 3; ch++)
+            if ((rc = check_params(g.p[ch].M, 64, cd.R[ch], K, lo, hi))) return rc;
+        for (int ch = 0; ch < 3; ch++)
+            if (cd.R[ch] > LRF_BIG_TO_ANY_RANK)
+                return set_err(LRF_ENOTSUP, "candidate %ld: rank %d > %d (ranks above it iterate on the any-shape kernels: lrf_qmf_encode_rgb_u8 per image)", (long)j, cd.R[ch], LRF_BIG_TO_ANY_RANK);
+        if (cd.u_off < 0 || cd.v_off < 0) return set_err(LRF_EINVAL, "candidate %ld: negative offset", (long)j);
+        // (every term is checked against the length before it is added to an offset: no sum can wrap)
+        long u_img = 0, v_img = 0;
+        for (int ch = 0; ch < 3; ch++) {
+            u_img += (long)g.p[ch].M * cd.R[ch];
+            v_img += 64L * cd.R[ch];
+            long& s = s_img[(size_t)cd.image * 3 + ch];
+            s = cd.R[ch] > s ? cd.R[ch] : s;
+        }
+        if (u_img > u_len || cd.u_off > u_len - u_img) return set_err(LRF_EINVAL, "candidate %ld: its U factors leave the buffer of %ld elements", (long)j, (long)u_len);
+        if (v_img > v_len || cd.v_off > v_len - v_img) return set_err(LRF_EINVAL, "candidate %ld: its V factors leave the buffer of %ld elements", (long)j, (long)v_len);
+        EncSweepCand& e = cs[(size_t)j];
+        e.image = cd.image;
+        for (int ch = 0; ch < 3; ch++) e.R[ch] = cd.R[ch];
+        e.u_off = cd.u_off; e.v_off = cd.v_off;
+        ur[(size_t)j] = Range{cd.u_off, u_img};
+        vr[(size_t)j] = Range{cd.v_off, v_img};
+    }
+    for (int64_t i = 0; i < n; i++) {
+        const long s = s_img[(size_t)i * 3] + s_img[(size_t)i * 3 + 1] + s_img[(size_t)i * 3 + 2];
+        if (s_img[(size_t)i * 3] == 0) return set_err(LRF_EINVAL, "image %ld has no candidate", (long)i);
+        if (ims[(size_t)i].sign_off >= 0 && (s > sign_len || ims[(size_t)i].sign_off > sign_len - s))
+            return set_err(LRF_EINVAL, "image %ld: its %ld signs leave the buffer of %ld elements", (long)i, s, (long)sign_len);
+    }
+    for (std::vector<Range>* r : {&ur, &vr}) { // no two candidates may share output bytes
+        std::sort(r->begin(), r->end(), [](const Range& a, const Range& b) { return a.off < b.off; });
+        for (size_t i = 1; i < r->size(); i++)
+            if ((*r)[i].off - (*r)[i - 1].off < (*r)[i - 1].len) return set_err(LRF_EINVAL, "the %s ranges of two candidates overlap (at element %ld)", r == &ur ? "U" : "V", (*r)[i].off);
+    }
+    const PlanSettings settings = plan_settings(c);
+    EncRaggedSweepPlan plan = plan_encode_ragged_sweep(ims, cs, settings);
+    if (plan.too_many) return set_err(LRF_ENOTSUP, "%ld blocks in one call: split the list", plan.too_many);
+    LRF_ON_DEVICE(c);
+    int rc = ensure(c, c->x, (size_t)plan.x_floats * sizeof(float));
+    if (rc) return rc;
+    const BcdPlan bcd = plan_bcd(plan.t.planes, K, lo, hi, PLAN_FIRST_W0, settings, true);
+    if ((rc = upload_tables(c, plan.t, bcd))) return rc;
+    float* X = (float*)c->x.p;
+    if ((rc = run_planes_ragged(c, plan.descs, plan.blocks, plan.launches, rgb, X))) return rc;
     if (c->planes_done) HIP_TRY(hipEventRecord(c->planes_done, c->stream)); // the RGB bytes are not read again
     return init_then_bcd(c, X, plan.t, bcd, sign, LRF_PLANES_GRAM_EXP, U, V);
 }
@@ -981,6 +1083,90 @@ int lrf_qmf_sweep_sse_rgb_u8(lrf_ctx* c, const uint8_t* rgb, const int8_t* U, co
     if (int nq = (int)items[2].size()) {
         hipLaunchKernelGGL(k_sse_any, dim3((unsigned)(groups[2] * nq), (unsigned)B), dim3(256), 0, c->stream, rgb, U, V, (int)H, (int)W, g,
                            d_tab + items[0].size() + items[1].size(), nq, (int)B, d_sse);
+        LAUNCH_CHECK();
+    }
+    return LRF_OK;
+}
+
+
+// The squared error of n (factors, source) items that differ in size and ranks, without the decoded images (kernels:
+// lrf_sse_ragged_kernel.hip; classification: decode_plan; the launches: plan_decode_ragged).  Validation is
+// lrf_qmf_decode_ragged_rgb_u8's with rgb read-only: the source ranges of items may overlap.  Candidate lists change from call
+// to call, so the table (descriptors, then blocks) is not kept: it travels stream-ordered through the pinned slots of the crop
+// table, and the call does not wait for the stream.
+int lrf_qmf_sse_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* items, const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len,
+                              const uint8_t* rgb, int64_t rgb_len, uint64_t* sse)
+{
+    if (!c || !items || !U || !V || !rgb || !sse) return set_err(LRF_EINVAL, "NULL argument");
+    if (n < 1 || n > 65535) return set_err(LRF_EINVAL, "n=%ld out of range [1,65535]", (long)n);
+    std::vector<RaggedDesc> descs((size_t)n);
+    std::vector<RaggedWork> work((size_t)n);
+    memset((void*)descs.data(), 0, descs.size() * sizeof(RaggedDesc));
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_ragged_image& im = items[i];
+        RaggedDesc& d = descs[(size_t)i];
+        if (im.H < 1 || im.W < 1 || im.H > INT32_MAX || im.W > INT32_MAX) return set_err(LRF_EINVAL, "item %ld: size %ldx%ld out of range", (long)i, (long)im.H, (long)im.W);
+        int rc = make_geom(im.H, im.W, &d.g);
+        if (rc) return rc;
+        for (int ch = 0; ch < 3; ch++)
+            if (im.R[ch] < 1 || im.R[ch] > 64) return set_err(LRF_EINVAL, "item %ld: rank %d out of range", (long)i, im.R[ch]);
+        if (im.u_off < 0 || im.v_off < 0 || im.rgb_off < 0) return set_err(LRF_EINVAL, "item %ld: negative offset", (long)i);
+        long u_img = 0, v_img = 0;
+        for (int ch = 0; ch < 3; ch++) {
+            u_img += (long)d.g.p[ch].M * im.R[ch];
+            v_img += 64L * im.R[ch];
+        }
+        // (every term is checked against the length before it is added to an offset: no sum can wrap)
+        if (u_img > u_len || im.u_off > u_len - u_img) return set_err(LRF_EINVAL, "item %ld: its U factors leave the buffer of %ld elements", (long)i, (long)u_len);
+        if (v_img > v_len || im.v_off > v_len - v_img) return set_err(LRF_EINVAL, "item %ld: its V factors leave the buffer of %ld elements", (long)i, (long)v_len);
+        if (rgb_len < 3 || im.H * im.W > rgb_len / 3 || im.rgb_off > rgb_len - 3 * im.H * im.W)
+            return set_err(LRF_EINVAL, "item %ld: its source leaves the buffer of %ld bytes", (long)i, (long)rgb_len);
+        // (the sink's loads need no alignment: a 16-aligned item keeps the 16-aligned body wherever its source starts)
+        const DecodePlan plan = decode_plan(d.g, im.H, im.W, im.R, true);
+        d.u_off = im.u_off; d.v_off = im.v_off; d.rgb_off = im.rgb_off;
+        d.H = (int)im.H; d.W = (int)im.W;
+        d.R0 = im.R[0]; d.R1 = im.R[1]; d.R2 = im.R[2];
+        d.kind = plan.kind; d.cls = plan.cls;
+        d.per_strip = (d.g.p[0].nw + 31) / 32;
+        RaggedWork& w = work[(size_t)i];
+        w.kind = plan.kind; w.cls = plan.cls;
+        if (plan.kind == DEC_TILE16) w.units = (long)(im.H / 16) * d.per_strip;
+        else if (plan.kind == DEC_STRIP) w.units = (long)((d.g.p[0].nh + 1) / 2) * d.per_strip;
+        else w.units = (long)im.H * ((im.W + 3) / 4);
+    }
+    const RaggedPlan plan = plan_decode_ragged(work);
+    if (plan.too_many) return set_err(LRF_EINVAL, "%ld work items in one launch: split the list", plan.too_many);
+    LRF_ON_DEVICE(c);
+    const size_t db = descs.size() * sizeof(RaggedDesc), bb = plan.blocks.size() * sizeof(RaggedBlock);
+    std::vector<char> tab(db + bb);
+    memcpy(tab.data(), descs.data(), db);
+    memcpy(tab.data() + db, plan.blocks.data(), bb);
+    Prof p(c, LRF_K_DECODE);
+    int rc = stage_crop_bytes(c, tab.data(), tab.size());
+    if (rc) return rc;
+    const RaggedDesc* d_desc = (const RaggedDesc*)c->crop_tab.p;
+    const RaggedBlock* d_blk = (const RaggedBlock*)((const char*)c->crop_tab.p + db);
+    unsigned long long* d_sse = reinterpret_cast<unsigned long long*>(sse);
+    HIP_TRY(hipMemsetAsync(sse, 0, (size_t)n * sizeof(uint64_t), c->stream));
+    for (const RaggedLaunch& l : plan.launches) {
+        const dim3 grid((unsigned)l.nblocks);
+        const RaggedBlock* bl = d_blk + l.block0;
+        if (l.kind == DEC_TILE16)
+            hipLaunchKernelGGL((k_sse_ragged_tiled<false, -1>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, d_sse);
+        else if (l.kind == DEC_STRIP) {
+#define LRF_SSE_RAGGED_STRIP(CLS) hipLaunchKernelGGL((k_sse_ragged_tiled<true, CLS>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, d_sse)
+            switch (l.cls) {
+            case 0: LRF_SSE_RAGGED_STRIP(0); break;
+            case 1: LRF_SSE_RAGGED_STRIP(1); break;
+            case 2: LRF_SSE_RAGGED_STRIP(2); break;
+            case 3: LRF_SSE_RAGGED_STRIP(3); break;
+            default: LRF_SSE_RAGGED_STRIP(4); break;
+            }
+#undef LRF_SSE_RAGGED_STRIP
+        } else if (l.kind == DEC_R8)
+            hipLaunchKernelGGL(k_sse8_ragged, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, l.reps, d_sse);
+        else
+            hipLaunchKernelGGL(k_sse_ragged_any, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, d_sse);
         LAUNCH_CHECK();
     }
     return LRF_OK;

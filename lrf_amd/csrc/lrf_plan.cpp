@@ -473,59 +473,78 @@ int geom_of(int64_t H, int64_t W, ImageGeom* g, int64_t* bad_h, int64_t* bad_w)
 // ---- the tables of a ragged encode ----------------------------------------------------------------------------------------------
 // The planes stage: all ENC_TILE16 images share one launch, the others one launch per window size present.  A workgroup finds
 // its work through blocks[i].  Behind it the call is the table of its planes: everything from the Gram pass on reads PlaneDesc.
-EncRaggedPlan plan_encode_ragged(const std::vector<EncRaggedImage>& images, const PlanSettings& s)
+// the descriptors of the planes stage (geometry, body, units, the X workspace as a running sum) -> its workgroups in all
+struct PlanesStage {
+    std::vector<EncRaggedDesc> descs;
+    std::vector<long> units;
+    long count[LRF_ENC_BODIES] = {0, 0, 0, 0, 0}, total = 0, x_floats = 0;
+};
+static PlanesStage planes_stage_descs(const std::vector<EncRaggedImage>& images)
 {
-    EncRaggedPlan p;
+    PlanesStage st;
     const size_t n = images.size();
-    p.descs.resize(n);
-    memset((void*)p.descs.data(), 0, n * sizeof(EncRaggedDesc)); // (the bytes are the device table's key: padding included)
-    long count[LRF_ENC_BODIES] = {0, 0, 0, 0, 0}, bcd_blocks = 0;
-    std::vector<long> units(n);
-    int rmax_t = 1;
+    st.descs.resize(n);
+    memset((void*)st.descs.data(), 0, n * sizeof(EncRaggedDesc)); // (the bytes are the device table's key: padding included)
+    st.units.resize(n);
     for (size_t i = 0; i < n; i++) {
         const EncRaggedImage& im = images[i];
-        EncRaggedDesc& d = p.descs[i];
+        EncRaggedDesc& d = st.descs[i];
         int64_t bh, bw;
         (void)geom_of(im.H, im.W, &d.g, &bh, &bw); // (validated by the caller)
         const ImageGeom& g = d.g;
         d.rgb_off = im.rgb_off;
-        d.x_off = p.x_floats;
-        p.x_floats += g.img_floats;
+        d.x_off = st.x_floats;
+        st.x_floats += g.img_floats;
         d.H = (int)im.H; d.W = (int)im.W;
         if (im.H % 16 == 0 && im.W % 16 == 0 && im.aligned8) {
             d.body = ENC_TILE16;
             d.per_strip = (g.p[0].nw + 31) / 32;
-            units[i] = (im.H / 16) * d.per_strip;
+            st.units[i] = (im.H / 16) * d.per_strip;
         } else { // k_planes16's tiling laid over the padded planes (lrf_qmf_planes_from_rgb_u8)
             d.body = ENC_STRIP22 + 2 * (int)(im.H & 1) + (int)(im.W & 1);
             const int ncols = g.p[0].nw > 2 * g.p[1].nw ? g.p[0].nw : 2 * g.p[1].nw;
             const int nstrips = (g.p[0].nh + 1) / 2 > g.p[1].nh ? (g.p[0].nh + 1) / 2 : g.p[1].nh;
             d.per_strip = (ncols + 31) / 32;
-            units[i] = (long)nstrips * d.per_strip;
+            st.units[i] = (long)nstrips * d.per_strip;
         }
-        count[d.body] += units[i];
-        for (int ch = 0; ch < 3; ch++) {
-            bcd_blocks += (g.p[ch].M + LRF_KC - 1) / LRF_KC;
-            rmax_t = im.R[ch] > rmax_t ? im.R[ch] : rmax_t;
+        st.count[d.body] += st.units[i];
+    }
+    for (int b = 0; b < LRF_ENC_BODIES; b++) st.total += st.count[b];
+    return st;
+}
+// its launches and workgroup table: by body, inside a launch the images in call order, an image's units ascending
+static void planes_stage_launches(const PlanesStage& st, std::vector<EncRaggedLaunch>& launches, std::vector<RaggedBlock>& blocks)
+{
+    blocks.reserve((size_t)st.total);
+    for (int b = 0; b < LRF_ENC_BODIES; b++) {
+        if (!st.count[b]) continue;
+        launches.push_back(EncRaggedLaunch{b, (long)blocks.size(), st.count[b], b == ENC_TILE16 ? 0 : (int)((st.count[b] + 7) / 8)});
+        for (size_t i = 0; i < st.descs.size(); i++) {
+            if (st.descs[i].body != b) continue;
+            for (long u = 0; u < st.units[i]; u++) blocks.push_back(RaggedBlock{(int)i, (int)u});
         }
     }
-    long total = 0;
-    for (int b = 0; b < LRF_ENC_BODIES; b++) total += count[b];
-    if (bcd_blocks >= (1L << 31) || total >= (1L << 31)) {
-        p.too_many = bcd_blocks > total ? bcd_blocks : total;
-        p.descs.clear();
-        p.x_floats = 0;
+}
+
+EncRaggedPlan plan_encode_ragged(const std::vector<EncRaggedImage>& images, const PlanSettings& s)
+{
+    EncRaggedPlan p;
+    const size_t n = images.size();
+    PlanesStage st = planes_stage_descs(images);
+    long bcd_blocks = 0;
+    int rmax_t = 1;
+    for (size_t i = 0; i < n; i++)
+        for (int ch = 0; ch < 3; ch++) {
+            bcd_blocks += (st.descs[i].g.p[ch].M + LRF_KC - 1) / LRF_KC;
+            rmax_t = images[i].R[ch] > rmax_t ? images[i].R[ch] : rmax_t;
+        }
+    if (bcd_blocks >= (1L << 31) || st.total >= (1L << 31)) {
+        p.too_many = bcd_blocks > st.total ? bcd_blocks : st.total;
         return p;
     }
-    p.blocks.reserve((size_t)total);
-    for (int b = 0; b < LRF_ENC_BODIES; b++) {
-        if (!count[b]) continue;
-        p.launches.push_back(EncRaggedLaunch{b, (long)p.blocks.size(), count[b], b == ENC_TILE16 ? 0 : (int)((count[b] + 7) / 8)});
-        for (size_t i = 0; i < n; i++) {
-            if (p.descs[i].body != b) continue;
-            for (long u = 0; u < units[i]; u++) p.blocks.push_back(RaggedBlock{(int)i, (int)u});
-        }
-    }
+    planes_stage_launches(st, p.launches, p.blocks);
+    p.descs.swap(st.descs);
+    p.x_floats = st.x_floats;
     p.split = plan_splits(bcd_blocks, rmax_t, s);
     p.order.reserve(3 * n);
     for (int fam = 0; fam < (p.split ? 3 : 1); fam++)
@@ -543,6 +562,71 @@ EncRaggedPlan plan_encode_ragged(const std::vector<EncRaggedImage>& images, cons
         }
         add_plane(p.t, p.descs[(size_t)o.image].x_off + g.p[o.ch].xoff, uo, vo, 0, 0, g.p[o.ch].M, im.R[o.ch], im.sign_off < 0 ? -1 : (int)so);
     }
+    return p;
+}
+
+// ---- the tables of a ragged sweep -------------------------------------------------------------------------------------------------
+// The planes stage is plan_encode_ragged's for the list of images (its kernels do not look at ranks).  Behind it the call is a
+// table of 3 m planes on 3 n matrices: per (image, channel) the first candidate of the largest rank computes the initialisation
+// (and alone owns Gram chunks: finish_gram_chunks), the others name it in init_src and take its leading columns (k_init_share).
+EncRaggedSweepPlan plan_encode_ragged_sweep(const std::vector<EncSweepImage>& images, const std::vector<EncSweepCand>& cands, const PlanSettings& s)
+{
+    EncRaggedSweepPlan p;
+    const size_t n = images.size(), m = cands.size();
+    p.rmax.assign(3 * n, 0);
+    std::vector<int> base(3 * n, -1); // the candidate that initialises (image, channel)
+    int rmax_t = 1;
+    for (size_t j = 0; j < m; j++)
+        for (int ch = 0; ch < 3; ch++) {
+            const size_t k = 3 * (size_t)cands[j].image + ch;
+            if (cands[j].R[ch] > p.rmax[k]) { p.rmax[k] = cands[j].R[ch]; base[k] = (int)j; }
+            rmax_t = cands[j].R[ch] > rmax_t ? cands[j].R[ch] : rmax_t;
+        }
+    std::vector<EncRaggedImage> ims(n);
+    for (size_t i = 0; i < n; i++) {
+        EncRaggedImage& e = ims[i];
+        e.H = images[i].H; e.W = images[i].W;
+        for (int ch = 0; ch < 3; ch++) e.R[ch] = p.rmax[3 * i + ch];
+        e.rgb_off = images[i].rgb_off; e.u_off = e.v_off = 0; e.sign_off = images[i].sign_off;
+        e.aligned8 = images[i].aligned8;
+    }
+    PlanesStage st = planes_stage_descs(ims);
+    long bcd_blocks = 0; // of the candidates' table: the only plane table this call has
+    for (size_t j = 0; j < m; j++)
+        for (int ch = 0; ch < 3; ch++) bcd_blocks += (st.descs[(size_t)cands[j].image].g.p[ch].M + LRF_KC - 1) / LRF_KC;
+    if (bcd_blocks >= (1L << 31) || st.total >= (1L << 31)) {
+        p.too_many = bcd_blocks > st.total ? bcd_blocks : st.total;
+        return p;
+    }
+    planes_stage_launches(st, p.launches, p.blocks);
+    p.descs.swap(st.descs);
+    p.x_floats = st.x_floats;
+    p.split = plan_splits(bcd_blocks, rmax_t, s);
+    p.order.reserve(3 * m);
+    for (int fam = 0; fam < (p.split ? 3 : 1); fam++)
+        for (int self = 1; self >= 0; self--)
+            for (int ch = 0; ch < 3; ch++)
+                for (size_t j = 0; j < m; j++) {
+                    if (p.split && fam_of_rank(cands[j].R[ch]) != fam) continue;
+                    if ((base[3 * (size_t)cands[j].image + ch] == (int)j) != (self == 1)) continue;
+                    p.order.push_back(EncSweepPlane{(int)j, ch});
+                }
+    std::vector<int> base_plane(3 * n, -1);
+    for (const EncSweepPlane& o : p.order) {
+        const EncSweepCand& cd = cands[(size_t)o.cand];
+        const size_t i = (size_t)cd.image;
+        const ImageGeom& g = p.descs[i].g;
+        long uo = cd.u_off, vo = cd.v_off, so = images[i].sign_off;
+        for (int c2 = 0; c2 < o.ch; c2++) {
+            uo += (long)g.p[c2].M * cd.R[c2];
+            vo += 64L * cd.R[c2];
+            so += p.rmax[3 * i + c2];
+        }
+        if (base[3 * i + o.ch] == o.cand) base_plane[3 * i + o.ch] = (int)p.t.planes.size();
+        add_plane(p.t, p.descs[i].x_off + g.p[o.ch].xoff, uo, vo, 0, 0, g.p[o.ch].M, cd.R[o.ch], images[i].sign_off < 0 ? -1 : (int)so);
+    }
+    for (size_t pi = 0; pi < p.t.planes.size(); pi++)
+        p.t.planes[pi].init_src = base_plane[3 * (size_t)cands[(size_t)p.order[pi].cand].image + p.order[pi].ch];
     return p;
 }
 

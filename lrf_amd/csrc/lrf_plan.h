@@ -409,6 +409,36 @@ struct EncRaggedPlan {
 // initialisation, so each run's leading planes are its self-initialising ones, as plan_bcd assumes.
 EncRaggedPlan plan_encode_ragged(const std::vector<EncRaggedImage>& images, const PlanSettings& s);
 
+// ---- encode: the tables of a ragged sweep (lrf_qmf_encode_ragged_sweep_rgb_u8): images of differing sizes, each at a list of
+// candidate rank triples of its own.  One image as the entry point hands it over, every field validated there
+struct EncSweepImage {
+    long H, W;
+    long rgb_off, sign_off; // sign_off: -1 = the default signs, else where its [Rmax_Y + Rmax_Cb + Rmax_Cr] signs start
+    bool aligned8;          // rgb + rgb_off is a multiple of 8
+};
+struct EncSweepCand {
+    int image;
+    int R[3];
+    long u_off, v_off;
+};
+struct EncSweepPlane { int cand, ch; };
+struct EncRaggedSweepPlan {
+    std::vector<EncRaggedDesc> descs;      // per image, launches and blocks of the planes stage: plan_encode_ragged's for the list
+    std::vector<EncRaggedLaunch> launches;
+    std::vector<RaggedBlock> blocks;
+    Tables t;                              // one plane per (candidate, channel); init_src: the plane of the same image and channel
+                                           // with the image's largest rank for that channel (the first of equal ranks)
+    std::vector<EncSweepPlane> order;      // which (candidate, channel) plane i of the table is
+    std::vector<int> rmax;                 // [3 n]: the largest rank per (image, channel) over the image's candidates
+    bool split = false;                    // plan_splits of the whole call
+    long x_floats = 0;                     // the X workspace: the sum over IMAGES
+    long too_many = 0;                     // != 0: this many (>= 2^31) BCD blocks or planes workgroups; nothing is built
+};
+// Plane order, the uniform sweep's: by kernel family when the call splits, inside a family the self-initialising planes first,
+// then luma before Cb before Cr, candidates in call order.  With one candidate per image, in image order, the table is
+// plan_encode_ragged's.  Every image must have a candidate (the entry point checks).
+EncRaggedSweepPlan plan_encode_ragged_sweep(const std::vector<EncSweepImage>& images, const std::vector<EncSweepCand>& cands, const PlanSettings& s);
+
 // ---- the any-shape path (lrf_anyshape_host.inc executes these; tests/test_any_plan.py reads them on the CPU) ----------------
 #define LRF_ANY_GS_MAX_LDS (160 * 1024) // dynamic LDS of k_any_gs<float, .>
 #define LRF_ANY_NATIVE_BELOW 400        // products of fewer multiply-adds take ATen's small-product order

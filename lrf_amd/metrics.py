@@ -75,10 +75,22 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
     return torch.tensor(np.mean(per_channel))
 
 
-def psnr_from_sse(sse: torch.Tensor, n: int, max_value: int = 255):
+def psnr_from_sse(sse: torch.Tensor, n, max_value: int = 255):
     """(mse, psnr) in float64 from exact integer squared errors over n samples each: mse = sse / n, psnr = 20 log10(max_value /
-    sqrt(mse)), inf where sse is 0.  The ONE expression behind image_metrics_batch and qmf_encode_target, evaluated where `sse` lives."""
-    m = sse.double() / n
+    sqrt(mse)), inf where sse is 0.  The ONE expression behind image_metrics_batch and qmf_encode_target, evaluated where `sse` lives.
+    n: an integer, or an integer tensor [B] with one count per column of sse [..., B] (images of differing sizes).  The columns of
+    each distinct count go through the integer form's own expression, so a column equals what the integer form gives for that
+    count by construction, on any device (a list has few distinct sizes)."""
+    if isinstance(n, torch.Tensor):
+        counts = n.reshape(-1).cpu()
+        if counts.numel() != sse.shape[-1]:
+            raise ValueError(f"psnr_from_sse: {counts.numel()} counts for {sse.shape[-1]} columns")
+        m = torch.empty(sse.shape, dtype=torch.float64, device=sse.device)
+        for v in torch.unique(counts).tolist():
+            cols = torch.nonzero(counts == v).reshape(-1).to(sse.device)
+            m[..., cols] = sse[..., cols].double() / int(v)
+    else:
+        m = sse.double() / n
     return m, 20 * torch.log10(max_value / torch.sqrt(m))
 
 
