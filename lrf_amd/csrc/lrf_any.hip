@@ -387,6 +387,7 @@ int lrf_qmf_planes_any_hw_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64_t 
     if (rc) return rc;
     LRF_ON_DEVICE(c);
     const long elems = g.M * g.N;
+    if ((elems + 255) / 256 > INT32_MAX) return set_err(LRF_ENOTSUP, "matrix of %ld elements: more than 2^31 - 1 workgroups in one launch", elems);
     Prof pr(c, LRF_K_PLANES);
     hipLaunchKernelGGL(k_any_planes, dim3((unsigned)((elems + 255) / 256), (unsigned)B), dim3(256), 0, c->stream, rgb, (int)H, (int)W, ch,
                        g.h, g.w, p, q, g.top, g.left, g.nw, elems, X);
@@ -424,6 +425,7 @@ int lrf_qmf_decode_any_hw_u8(lrf_ctx* c, const int8_t* U0, const int8_t* V0, con
         d[ch].h = g.h; d[ch].w = g.w; d[ch].p = p; d[ch].q = q; d[ch].top = g.top; d[ch].left = g.left; d[ch].nw = g.nw;
         d[ch].R = R[ch];
     }
+    if (((long)H * W + 255) / 256 > INT32_MAX) return set_err(LRF_ENOTSUP, "image of %ld pixels: more than 2^31 - 1 workgroups in one launch", (long)H * W);
     LRF_ON_DEVICE(c);
     Prof pr(c, LRF_K_DECODE);
     hipLaunchKernelGGL(k_any_decode, dim3((unsigned)(((long)H * W + 255) / 256), (unsigned)B), dim3(256), 0, c->stream, d[0], d[1], d[2],

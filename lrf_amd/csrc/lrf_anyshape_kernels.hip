@@ -2500,7 +2500,7 @@ __global__ __launch_bounds__(256) void k_any_planes(const uint8_t* __restrict__ 
         x = (int)(e - (long)y * w);
     }
     const uint8_t* img = rgb + (long)blockIdx.y * 3 * H * W;
-    const int hw = H * W;
+    const long hw = (long)H * W;
     float out;
     if (c == 0) {
         const uint8_t* p0 = img + (long)y * W + x;
