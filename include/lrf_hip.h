@@ -67,6 +67,11 @@ int lrf_ctx_synchronize(lrf_ctx* ctx);
  * call on this context up to the check are invalid; the context itself stays usable (the next call clears the state).
  * Replaces nothing in the reference (its calls are synchronous Python): this is the error half of the async boundary. */
 int lrf_ctx_check(lrf_ctx* ctx);
+/* Where the persistent kernel of the context's last lrf_qmf_encode_rgb_u8 read the luma matrices from: 0 = the fp32 workspace X,
+ * 1 = the caller's image bytes (large calls on sides that are multiples of 16; LRF_LUMA_BYTES=0 turns it off); -1: no such call
+ * yet, or ctx is NULL.
+ * The factors are the same bit for bit; tests use it to see that a call took the path they mean to test. */
+int lrf_ctx_last_luma_source(const lrf_ctx* ctx);
 /* bytes of scratch the context currently holds.  The scratch grows to the largest call seen (2.4 KB per input pixel of the
  * default branch: a 512 x 1365x2048 batch holds ~9 GB) and is kept for reuse; lrf_ctx_trim waits for the stream and gives
  * all of it back (the next call allocates again). */

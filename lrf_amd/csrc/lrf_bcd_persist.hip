@@ -11,7 +11,8 @@
 
 template <bool F16, int NP32, bool FIRST = false>
 static int bcdp_launch_t(lrf_ctx* c, int attr_bit, int wgs, int wave_lds, const float* X, const PlaneDesc* pl, const BlockDesc* bl, int nblocks,
-                         int nplanes, int plane0, const BcdpTabs& t16, const BcdpTabs& t64, int8_t* U, int8_t* V, GsParams gp, int niter)
+                         int nplanes, int plane0, const BcdpTabs& t16, const BcdpTabs& t64, int8_t* U, int8_t* V, GsParams gp, int niter,
+                         const LumaSrc& ls = LumaSrc{nullptr, 0, 0, 0, 0})
 {
     if (!(c->attr_persist & (1u << attr_bit))) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_bcd_p<F16, NP32, FIRST>, hipFuncAttributeMaxDynamicSharedMemorySize, LRF_BCDW_WAVES * wave_lds));
@@ -19,7 +20,7 @@ static int bcdp_launch_t(lrf_ctx* c, int attr_bit, int wgs, int wave_lds, const 
     }
     Prof p(c, LRF_K_BCD_PERSIST);
     hipLaunchKernelGGL((k_bcd_p<F16, NP32, FIRST>), dim3((unsigned)wgs), dim3(64 * LRF_BCDW_WAVES), (size_t)LRF_BCDW_WAVES * wave_lds, c->stream, X, pl, bl, t16,
-                       t64, U, V, gp, nblocks, niter, nplanes, plane0, (BcdpSync*)c->psync.p, c->h_perr, 2 * nplanes, ++c->pseq, wave_lds);
+                       t64, U, V, gp, nblocks, niter, nplanes, plane0, (BcdpSync*)c->psync.p, c->h_perr, 2 * nplanes, ++c->pseq, wave_lds, ls);
     LAUNCH_CHECK();
     return LRF_OK;
 }
@@ -30,6 +31,7 @@ int bcdp_launch(lrf_ctx* c, const BcdPlan& plan, const float* X, const PlaneDesc
     const bool first = plan.persist_first; // item iteration 0 is the call's first iteration
     const int niter = first ? plan.K : plan.K - 1;
     if (!plan.persist || (first && plan.persist_np32 != 0)) return set_err(LRF_EINVAL, "internal: no instantiation of k_bcd_p for this plan");
+    if (plan.luma_bytes && !first) return set_err(LRF_EINVAL, "internal: luma from the image bytes needs every iteration inside k_bcd_p");
     if (!c->h_perr) {
         HIP_TRY(hipHostMalloc((void**)&c->h_perr, sizeof(int), hipHostMallocDefault));
         *c->h_perr = 0;
@@ -56,7 +58,12 @@ int bcdp_launch(lrf_ctx* c, const BcdPlan& plan, const float* X, const PlaneDesc
     return bcdp_launch_t<F16, NP>(c, BIT, (int)wgs, NP ? (LRF_BCDW32_WAVE_LDS(NP) > wave_lds ? LRF_BCDW32_WAVE_LDS(NP) : wave_lds) : wave_lds, X, pl, bl, \
                                   nblocks, nplanes, plane0, t16, t64, U, V, gp, niter)
     if (first) {
-        if (!plan.persist_f16) return bcdp_launch_t<false, 0, true>(c, 10, (int)wgs, wave_lds, X, pl, bl, nblocks, nplanes, plane0, t16, t64, U, V, gp, niter);
+        // (the only instantiation with the luma-from-bytes body: plan_luma_bytes asks for this branch; plane 0 of the table is
+        // image 0's luma plane there)
+        const LumaSrc ls = plan.luma_bytes && plane0 == 0 ? plan.luma : LumaSrc{nullptr, 0, 0, 0, 0};
+        if (plan.luma_bytes && ls.nluma == 0) return set_err(LRF_EINVAL, "internal: luma from the image bytes without its source");
+        if (!plan.persist_f16) return bcdp_launch_t<false, 0, true>(c, 10, (int)wgs, wave_lds, X, pl, bl, nblocks, nplanes, plane0, t16, t64, U, V, gp, niter, ls);
+        if (plan.luma_bytes) return set_err(LRF_EINVAL, "internal: no luma-from-bytes body in this instantiation of k_bcd_p");
         return bcdp_launch_t<true, 0, true>(c, 11, (int)wgs, wave_lds, X, pl, bl, nblocks, nplanes, plane0, t16, t64, U, V, gp, niter);
     }
     if (!plan.persist_f16) LRF_P(false, 0, 0);

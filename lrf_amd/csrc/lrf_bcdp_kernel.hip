@@ -400,6 +400,16 @@ __device__ __forceinline__ f32x4 mfma_quad(float a, float b, f32x4 acc) { return
 // a quad operand of a [64][pitch] table held as four registers: op[s], lane l = tab[16 s + (l >> 2)][4 q + (l & 3)]
 // acc[c][v] = fma(op[c][k >> 4] (lane 4 (k & 15) + v), x[lane][k], acc[c][v]) for k = 0..63 in order; the NC chains are
 // interleaved step by step (two or more: no wait state between dependent MFMAs).  x: the lane's own row of the LDS tile.
+// xv: the lane's own row, sixteen 16-B chunks in column order
+template <int NC>
+__device__ __forceinline__ void regs_times_quads(const f32x4 (&xv)[16], const float (&op)[4][4], f32x4 (&acc)[4])
+{
+    static_for<64>([&](auto kc) {
+        constexpr int k = kc;
+#pragma unroll
+        for (int c = 0; c < NC; c++) acc[c] = mfma_quad<(k & 15)>(op[c][k >> 4], xv[k >> 2][k & 3], acc[c]);
+    });
+}
 template <int NC>
 __device__ __forceinline__ void row_times_quads(const float* xrow_lds, int g16, const float (&op)[4][4], f32x4 (&acc)[4])
 {
@@ -410,11 +420,7 @@ __device__ __forceinline__ void row_times_quads(const float* xrow_lds, int g16, 
         xv[J] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(xrow_lds) + ((16 * J) ^ g16));
     });
     __builtin_amdgcn_sched_barrier(0);
-    static_for<64>([&](auto kc) {
-        constexpr int k = kc;
-#pragma unroll
-        for (int c = 0; c < NC; c++) acc[c] = mfma_quad<(k & 15)>(op[c][k >> 4], xv[k >> 2][k & 3], acc[c]);
-    });
+    regs_times_quads<NC>(xv, op, acc);
 }
 // accP[q][v] (lane = column n) += u[m][4 q + v] * X[m][n] for the sub-tile's rows m = 0..63 in order.  us: the fp32 u tile
 // [64][8]; X[m][n]: one ds_read_b32 at dword 64 m + 4 ((n >> 2) ^ xsw(m)) + (n & 3), a permutation of the row's 64 banks; the
@@ -450,10 +456,17 @@ __device__ __forceinline__ void xt_u_quads(const float* Xs, const float* us, int
 // (X tile 16 KB, then the fp32 u tile 2 KB, then the U-span staging area, LRF_BCDP_USTAGE bytes).
 // MODE 1 (round 5, k_bcd_p<.., .., true>): the call's FIRST iteration, k_bcd_w<1> — the old U is X @ W0 (the initialisation's
 // table Wf, written before the launch), no int8 rows are read.
-template <int MODE>
-__device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const PlaneDesc& pd, const BlockDesc& bd, const float* __restrict__ Vf,
-                                             const float* __restrict__ Wf, const float* __restrict__ Bf, int8_t* __restrict__ U, float* __restrict__ Ppart,
-                                             const GsParams& gp, float* Xs, const int lane)
+// BYTES (a luma block of a call that plan_luma_bytes accepted): the sub-tile comes from the caller's image bytes, three bytes an
+// element instead of the four of X.  Lane m takes patch m of the sub-tile (luma_patch_byte0, lrf_plan.h): per pixel row and
+// channel one 8-byte load, contiguous across the lanes of a patch row, 24 loads a sub-tile (48 registers against xq's 64), in
+// flight one sub-tile ahead as xq is.  luma_of on them is k_planes16's arithmetic bit for bit, so the lane holds ROW m of the
+// sub-tile in registers: the operand of the x V chain as it stands (no LDS read), and written to the tile's own-row slots —
+// the addresses row_times_quads reads, conflict-free for the same reason — for xt_u_quads.  Everything behind the operand is
+// the fp32 body's.
+template <int MODE, bool BYTES>
+__device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const LumaSrc& ls, const PlaneDesc& pd, const BlockDesc& bd,
+                                             const float* __restrict__ Vf, const float* __restrict__ Wf, const float* __restrict__ Bf,
+                                             int8_t* __restrict__ U, float* __restrict__ Ppart, const GsParams& gp, float* Xs, const int lane)
 {
     constexpr int RMAX = 8;
     const int li = lane & 15, lq = lane >> 4;
@@ -526,6 +539,27 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
             }
         }
     };
+    // BYTES: by[ch][j] = the eight bytes of pixel row j of the lane's patch in channel ch.  One buffer resource per image
+    // (wave-uniform: the plane index is the image), the patch's first byte as the lane's offset, channel and pixel row as the
+    // scalar offset: no address arithmetic per load.  The resource ends with the image: 3 hw records.
+    u32x2 by[3][8];
+    __amdgpu_buffer_rsrc_t irs;
+    if constexpr (BYTES)
+        irs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(ls.img + (long)bd.plane * 3 * ls.hw), (short)0, 3 * ls.hw, 0x00020000);
+    auto patch0_of = [&](int t) { // rows at or past nrows clamp to the block's last row, as issue_x's
+        int row = t * 64 + lane;
+        row = row < nrows ? row : nrows - 1;
+        return luma_patch_byte0(bd.row0 + row, ls.W, ls.nwl);
+    };
+    auto issue_b = [&](int p0, int j0, int j1) {
+        if constexpr (BYTES) {
+#pragma unroll
+            for (int j = j0; j < j1; j++)
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++)
+                    by[ch][j] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(irs, p0, ch * ls.hw + j * ls.W, 0));
+        }
+    };
     // int8 U rows as whole spans: the 64 rows of sub-tile t are ONE contiguous span of the wave's own, bytes [a, a + len) with
     // a = Ub + 64 R t.  It passes through the wave's LDS staging area `ust` at the address's phase (span byte i at a % 16 + i),
     // so that 16-B slot k of the staging area is the naturally aligned 16 bytes at (a & ~15) + 16 k; lane k < nslots moves slot k.
@@ -565,18 +599,42 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
 #pragma unroll
     for (int q = 0; q < 2; q++) accP[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
+#ifdef LRF_BCDP_PROBE_3Q // timing experiment only (wrong results): planes below this index request three quarters of every sub-tile
+    const bool probe3q = bd.plane < (LRF_BCDP_PROBE_3Q);
+#else
+    constexpr bool probe3q = false;
+#endif
     if constexpr (MODE == 0) issue_u(0);
-    issue_x(0, 0, 4, true);
+    if constexpr (BYTES) {
+        issue_b(patch0_of(0), 0, 8);
+    } else {
+        issue_x(0, 0, 3, true);
+        if (!probe3q) issue_x(0, 3, 4, true);
+    }
     for (int t = 0; t < nsub; t++) {
         const int r0 = t * 64;
         __builtin_amdgcn_sched_barrier(0);
+        f32x4 xv[16]; // BYTES: the lane's row, chunk J = pixels 4 (J & 1) .. + 3 of pixel row J >> 1
+        if constexpr (BYTES) {
 #pragma unroll
-        for (int T = 0; T < 4; T++)
+            for (int J = 0; J < 16; J++) {
+                const unsigned r = by[0][J >> 1][J & 1], g = by[1][J >> 1][J & 1], b = by[2][J >> 1][J & 1];
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int m = 16 * T + 4 * q + lq;
-                *reinterpret_cast<f32x4*>(&Xs[m * 64 + 4 * (li ^ (4 * q + lq))]) = xq[T][q];
+                for (int i = 0; i < 4; i++)
+                    xv[J][i] = luma_of((float)((r >> (8 * i)) & 255u), (float)((g >> (8 * i)) & 255u), (float)((b >> (8 * i)) & 255u));
             }
+#pragma unroll
+            for (int J = 0; J < 16; J++)
+                *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(const_cast<float*>(xrow)) + ((16 * J) ^ g16)) = xv[J];
+        } else {
+#pragma unroll
+            for (int T = 0; T < 4; T++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int m = 16 * T + 4 * q + lq;
+                    *reinterpret_cast<f32x4*>(&Xs[m * 64 + 4 * (li ^ (4 * q + lq))]) = xq[probe3q && T == 3 ? 2 : T][q]; // (probe: a loaded quarter again)
+                }
+        }
         float u[RMAX];
         const int row = r0 + lane;
         int cph = 0;
@@ -589,7 +647,14 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
         if constexpr (MODE == 0) {
             if (more) issue_u(tn);
         }
-        issue_x(tn, 0, 2, more);
+        int p0n = 0; // BYTES: the lane's patch of the next sub-tile
+        if constexpr (BYTES) {
+            if (more) {
+                p0n = patch0_of(tn);
+                issue_b(p0n, 0, 4);
+            }
+        } else
+            issue_x(tn, 0, 2, more);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -617,15 +682,20 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
                 op[2][s] = wq[0][s];
                 op[3][s] = wq[1][s];
             }
+            auto rtq = [&](auto ncc) { // BYTES: the row is in registers already
+                constexpr int NC = ncc;
+                if constexpr (BYTES) regs_times_quads<NC>(xv, op, acc);
+                else row_times_quads<NC>(xrow, g16, op, acc);
+            };
             if constexpr (MODE == 0) {
-                if (quads2) row_times_quads<2>(xrow, g16, op, acc);
-                else row_times_quads<1>(xrow, g16, op, acc);
+                if (quads2) rtq(std::integral_constant<int, 2>{});
+                else rtq(std::integral_constant<int, 1>{});
             } else {
-                if (quads2) row_times_quads<4>(xrow, g16, op, acc);
+                if (quads2) rtq(std::integral_constant<int, 4>{});
                 else {
 #pragma unroll
                     for (int s = 0; s < 4; s++) op[1][s] = wq[0][s];
-                    row_times_quads<2>(xrow, g16, op, acc);
+                    rtq(std::integral_constant<int, 2>{});
                     acc[2] = acc[1];
                     acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 }
@@ -640,14 +710,20 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
                 }
             }
         }
-        issue_x(tn, 2, 3, more);
+        if constexpr (BYTES) {
+            if (more) issue_b(p0n, 4, 6);
+        } else
+            issue_x(tn, 2, 3, more);
         __builtin_amdgcn_sched_barrier(0);
         gs_regs_dispatch<RMAX>(R, a, u, tab, native, gp);
         if (row >= nrows) {
 #pragma unroll
             for (int r = 0; r < RMAX; r++) u[r] = 0.f;
         }
-        issue_x(tn, 3, 4, more);
+        if constexpr (BYTES) {
+            if (more) issue_b(p0n, 6, 8);
+        } else if (!probe3q)
+            issue_x(tn, 3, 4, more);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int r = 0; r < RMAX; r += 4) *reinterpret_cast<f32x4*>(&us[lane * RMAX + r]) = (f32x4){u[r], u[r + 1], u[r + 2], u[r + 3]};
@@ -739,7 +815,7 @@ template <bool F16, int NP32, bool FIRST = false>
 __global__ __launch_bounds__(64 * LRF_BCDW_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_bcd_p(
     const float* __restrict__ X, const PlaneDesc* __restrict__ planes, const BlockDesc* __restrict__ blocks, const BcdpTabs t16,
     const BcdpTabs t64, int8_t* __restrict__ U, int8_t* __restrict__ V8, GsParams gp, int nblocks, int niter, int nplanes, int plane0,
-    BcdpSync* sync, int* err_host, int ncells, int seq, int wave_lds)
+    BcdpSync* sync, int* err_host, int ncells, int seq, int wave_lds, const LumaSrc ls)
 {
     extern __shared__ __attribute__((aligned(16))) float bcdp_lds[]; // LRF_BCDW_WAVES x wave_lds bytes
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -816,10 +892,24 @@ __global__ __launch_bounds__(64 * LRF_BCDW_WAVES) __attribute__((amdgpu_waves_pe
         static_assert(!FIRST || NP32 == 0, "the first iteration of ranks 17..32 stays a launch of its own (k_bcd_w32f)");
         const bool first = FIRST && it == 0; // wave-uniform
         if (fam == 0) {
+            // a luma block of a call that reads luma from the image bytes (wave-uniform; only <false, 0, true> carries that body:
+            // plan_luma_bytes)
+            constexpr bool kBytes = FIRST && !F16 && NP32 == 0;
+            bool bytes = false;
+            if constexpr (kBytes) bytes = bd.plane < ls.nluma;
             if (first) {
-                if constexpr (FIRST) bcdp_w_block<1>(X, pd, bd, t16.vf, t16.wf, t16.bf, U, t16.pp, gp, Xs, ln);
-            } else
-                bcdp_w_block<0>(X, pd, bd, t16.vf, nullptr, t16.bf, U, t16.pp, gp, Xs, ln);
+                if constexpr (FIRST) {
+                    if constexpr (kBytes) {
+                        if (bytes) bcdp_w_block<1, true>(X, ls, pd, bd, t16.vf, t16.wf, t16.bf, U, t16.pp, gp, Xs, ln);
+                    }
+                    if (!bytes) bcdp_w_block<1, false>(X, ls, pd, bd, t16.vf, t16.wf, t16.bf, U, t16.pp, gp, Xs, ln);
+                }
+            } else {
+                if constexpr (kBytes) {
+                    if (bytes) bcdp_w_block<0, true>(X, ls, pd, bd, t16.vf, nullptr, t16.bf, U, t16.pp, gp, Xs, ln);
+                }
+                if (!bytes) bcdp_w_block<0, false>(X, ls, pd, bd, t16.vf, nullptr, t16.bf, U, t16.pp, gp, Xs, ln);
+            }
         }
         if constexpr (F16) {
             if (fam == 1) {

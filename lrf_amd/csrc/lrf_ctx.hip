@@ -360,6 +360,8 @@ int lrf_ctx_check(lrf_ctx* c)
     return ctx_check(c);
 }
 
+int lrf_ctx_last_luma_source(const lrf_ctx* c) { return c ? c->last_luma_source : -1; }
+
 size_t lrf_ctx_workspace_bytes(const lrf_ctx* c)
 {
     if (!c) return 0;

@@ -68,6 +68,15 @@ __device__ __forceinline__ float ycc_of(float r, float g, float b, int c)
     return (c ? 128.f : 0.f) + acc;
 }
 
+// luma of one pixel: ycc_of(.., 0) without its `0.f + acc` (acc >= +0: the same bits).  The strip kernels of lrf_kernels.hip and
+// the luma-from-bytes body of k_bcd_p (lrf_bcdp_kernel.hip)
+__device__ __forceinline__ float luma_of(float r, float g, float b)
+{
+    float acc = 0.299f * r; // = fmaf(0.299f, r, 0.f)
+    acc = fmaf(0.587f, g, acc);
+    return fmaf(0.114f, b, acc);
+}
+
 // tree64 of the oracle: lane i ends with s[i] + s[i+off] for off = 32..1; lane 0 holds the result,
 // which is broadcast.  (Lanes >= off compute unused values.)
 // The partner fetches of the tree without the LDS crossbar: lane i needs lane i + off.

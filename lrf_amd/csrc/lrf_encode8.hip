@@ -426,7 +426,12 @@ int lrf_qmf_encode_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64_t H, 
     const long u_img = ep.u_img, v_img = ep.v_img;
     const long *uoff = ep.uoff, *voff = ep.voff, *u0c = ep.u0c, *v0c = ep.v0c;
     float* X = (float*)c->x.p;
-    if ((rc = fuse ? planes_gram_from_rgb(c, rgb, H, W, g, t, X) : lrf_qmf_planes_from_rgb_u8(c, rgb, B, H, W, X))) return rc;
+    // luma from the image bytes (plan_luma_bytes, lrf_plan.h): the luma blocks of k_bcd_p read `rgb`, and the fused planes kernel
+    // leaves the luma rows of X unwritten (a pipe, which hands the bytes back at planes_done, keeps the X path)
+    ep.bcd.luma_bytes = plan_luma_bytes(ep.bcd, t.planes, (int)B, H, W, reinterpret_cast<uintptr_t>(rgb), c->planes_done != nullptr, plan_settings(c));
+    if (ep.bcd.luma_bytes) ep.bcd.luma = LumaSrc{rgb, (int)(H * W), (int)W, (int)(W / 8), (int)B};
+    c->last_luma_source = ep.bcd.luma_bytes ? 1 : 0;
+    if ((rc = fuse ? planes_gram_from_rgb(c, rgb, H, W, g, t, X, !ep.bcd.luma_bytes) : lrf_qmf_planes_from_rgb_u8(c, rgb, B, H, W, X))) return rc;
     if (c->planes_done) HIP_TRY(hipEventRecord(c->planes_done, c->stream)); // the RGB bytes are not read again
     if (ep.bcd.rmax > LRF_BIG_TO_ANY_RANK) {
         float *U0, *V0;

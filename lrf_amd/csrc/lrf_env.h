@@ -6,7 +6,9 @@
 //   LRF_PERSIST              0: never k_bcd_p; 1: k_bcd_p from LRF_BCDW_MIN_BLOCKS blocks on
 //   LRF_FAMILY_SPLIT_BLOCKS  blocks from which a call's rank families run on kernels of their own  (plan_splits)
 //   LRF_BCDW16_MIN_BLOCKS / LRF_BCDW32_MIN_BLOCKS  blocks from which the wave kernels of ranks 9..16 / 17..32 run
-//   LRF_DEBUG_INIT_SWEEPS    stops k_init after a stage / forces the Sturm replacement loop       (tests/test_hip_parity.py)
+//   LRF_LUMA_BYTES           0: k_bcd_p always reads luma from X; else (the default) from the image bytes in every eligible
+//                            call (plan_luma_bytes, lrf_plan.h); lrf_ctx_last_luma_source says which a call took
+//   LRF_DEBUG_INIT_SWEEPS   stops k_init after a stage / forces the Sturm replacement loop       (tests/test_hip_parity.py)
 //   LRF_PIPE_BULK / LRF_PIPE_TAIL  the pipe's piece sizes                                          (tests/test_pipeline.py)
 //   LRF_FUSED_GRAM_MIN_CHUNKS  from how many luma Gram chunks on k_planes16_gram forms the patch matrices (tests/test_fused_gram.py)
 //

@@ -67,6 +67,15 @@ struct BlockDesc {
     int blk;           // block number inside the plane
     int pad;
 };
+// Where k_bcd_p's rank <= 8 body finds the luma matrices of a call that reads them from the caller's image bytes instead of X
+// (plan_luma_bytes, lrf_plan.h): plane i < nluma of the table is the luma plane of image i, whose [3][H][W] bytes start at
+// img + 3 hw i.  nluma == 0: every block reads X.  Passed to the kernel by value.
+struct LumaSrc {
+    const uint8_t* img;
+    int hw, W;         // H W, W
+    int nwl;           // luma patches per patch row (W / 8)
+    int nluma;
+};
 struct GramChunk {
     int plane; // index into the PlaneDesc table
     int row0;  // first row of the chunk

@@ -238,13 +238,7 @@ __device__ __forceinline__ float div_win(float x) { return K == 2 ? x * 0.5f : d
 // byte j (0..7) of an 8-byte word held as two dwords -> float
 template <int J>
 __device__ __forceinline__ float byte_f(uint32_t lo, uint32_t hi) { return (float)(((J < 4 ? lo : hi) >> (8 * (J & 3))) & 255u); }
-// luma of one pixel: ycc_of(.., 0) without its `0.f + acc` (acc >= +0: the same bits)
-__device__ __forceinline__ float luma_of(float r, float g, float b)
-{
-    float acc = 0.299f * r; // = fmaf(0.299f, r, 0.f)
-    acc = fmaf(0.587f, g, acc);
-    return fmaf(0.114f, b, acc);
-}
+// (luma_of: lrf_device.h)
 
 // sixteen luma samples of a 2 x 8 pixel block (channel words lo / hi = bytes 0..3 / 4..7 of each row) into the staging tile
 __device__ __forceinline__ void strip_luma(const uint32_t (&lo)[2][3], const uint32_t (&hi)[2][3], float* Lp, int rp)

@@ -31,8 +31,21 @@ const PlanSettings& plan_settings_env()
     static const PlanSettings s{(int)env_long("LRF_PERSIST", -1), env_long("LRF_FAMILY_SPLIT_BLOCKS", -1),
                                 env_long("LRF_BCDW16_MIN_BLOCKS", LRF_BCDW16_MIN_BLOCKS), env_long("LRF_BCDW32_MIN_BLOCKS", LRF_BCDW32_MIN_BLOCKS),
                                 dev_flag("LRF_BCD_WG"), dev_flag("LRF_NO_FAMILY_SPLIT"), dev_flag("LRF_NO_FAMILY_STREAMS"), dev_flag("LRF_NO_BCDW32"),
-                                dev_flag("LRF_GENERIC_GS"), dev_flag("LRF_NO_PERSIST_FIRST"), dev_flag("LRF_NO_INIT_FORK"), false};
+                                dev_flag("LRF_GENERIC_GS"), dev_flag("LRF_NO_PERSIST_FIRST"), dev_flag("LRF_NO_INIT_FORK"), false,
+                                (int)env_long("LRF_LUMA_BYTES", -1)};
     return s;
+}
+
+bool plan_luma_bytes(const BcdPlan& p, const std::vector<PlaneDesc>& planes, int nluma, int64_t H, int64_t W, uintptr_t rgb_addr, bool rgb_released,
+                     const PlanSettings& s)
+{
+    if (s.luma_bytes == 0 || rgb_released) return false;
+    if (H < 16 || W < 16 || H % 16 != 0 || W % 16 != 0 || (rgb_addr & 7) != 0 || (long)H * W * 3 >= (1L << 31)) return false;
+    if (!p.persist || !p.persist_first || p.persist_f16 || p.persist_np32 != 0) return false;
+    if (nluma < 1 || nluma > (int)planes.size()) return false;
+    for (int i = 0; i < nluma; i++)
+        if (fam_of_rank(planes[i].R) != 0 || planes[i].M != (H / 8) * (W / 8)) return false;
+    return true;
 }
 
 // A small call takes ONE family, the one its largest rank needs: its launches are latency chains per block and a second launch

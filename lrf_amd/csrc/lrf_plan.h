@@ -38,6 +38,7 @@ struct PlanSettings {
     // LRF_NO_FAMILY_STREAMS, LRF_NO_BCDW32 (k_bcd_mid instead), LRF_GENERIC_GS (never the exact-integer Gauss-Seidel), LRF_NO_PERSIST_FIRST, LRF_NO_INIT_FORK
     bool bcd_wg = false, no_family_split = false, no_family_streams = false, no_bcdw32 = false, generic_gs = false, no_persist_first = false, no_init_fork = false;
     bool persist_arch = false; // the device is the part the in-launch hand-offs of k_bcd_p were validated on (gfx950)
+    int luma_bytes = -1;       // LRF_LUMA_BYTES (lrf_env.h): 0 = no call reads luma from the image bytes; else every eligible one
 };
 const PlanSettings& plan_settings_env(); // the environment's part (persist_arch false)
 
@@ -72,11 +73,28 @@ struct BcdPlan {
     bool persist_f16 = false;   // planes of ranks 9..16 occur (the instantiations with ranks 17..32 carry that body too: their chroma planes)
     int persist_np32 = 0;       // pairs of rank columns of the planes of ranks 17..32 (0: none)
     FamStreams streams = FAM_STREAMS_NONE;
+    // the luma blocks of k_bcd_p read the caller's image bytes, not X (plan_luma_bytes; set by lrf_qmf_encode_rgb_u8 alone)
+    bool luma_bytes = false;
+    LumaSrc luma = {nullptr, 0, 0, 0, 0};
 };
 // whether a call of that size gives every plane the kernel family of its own rank (the sweep entry point orders its planes by it)
 bool plan_splits(long nblocks, int rmax_t, const PlanSettings& s);
 // reads R, nblk, native_t2_u and init_src of the planes.  sweep: lrf_qmf_encode_sweep_rgb_u8's table
 BcdPlan plan_bcd(const std::vector<PlaneDesc>& planes, int K, int lo, int hi, int first_mode, const PlanSettings& s, bool sweep = false);
+
+// ---- luma from the image bytes: a luma element of X is ycc_of(r, g, b, 0), a pure function of three bytes that k_bcd_p would
+// read as four from X, K times a call.  Whether the fused encode (lrf_qmf_encode_rgb_u8, nobody else) lets the rank <= 8 body of
+// k_bcd_p<false, 0, true> take the luma matrices from the caller's [3][H][W] bytes:
+//   * k_planes16's geometry (planes_gram_eligible's, without its batch size): H and W multiples of 16, the bytes 8-byte aligned,
+//     3 H W < 2^31;
+//   * the plan runs ALL iterations in that instantiation (persist && persist_first, no plane above rank 8 — so every luma plane
+//     is of rank family 0), for nobody else reads luma X after the planes kernel;
+//   * the bytes stay the caller's to the end of the call: not under a pipe, which frees its upload slot behind the planes
+//     kernel (`rgb_released`: lrf_ctx::planes_done is set);
+//   * LRF_LUMA_BYTES is not 0.
+// nluma: the leading planes of the table that are the images' luma planes, image i at plane i (encode_rgb_prepare's order).
+bool plan_luma_bytes(const BcdPlan& p, const std::vector<PlaneDesc>& planes, int nluma, int64_t H, int64_t W, uintptr_t rgb_addr, bool rgb_released,
+                     const PlanSettings& s);
 
 // ---- decode: which body serves an image, and the launches of a ragged call (lrf_qmf_decode_ragged_rgb_u8) ------------------
 enum { DEC_TILE16 = 0, DEC_STRIP = 1, DEC_R8 = 2, DEC_ANY = 3 }; // decode_plan (lrf_encode8.hip) decides
@@ -117,6 +135,17 @@ RaggedPlan plan_decode_ragged(const std::vector<RaggedWork>& images);
 #else
 #define LRF_HD
 #endif
+// Luma from the image bytes (LumaSrc; k_bcd_p's body and tests/test_luma_bytes_plan.py call the same functions): row m of a luma
+// matrix is patch (m / nwl, m % nwl), column n is pixel (n >> 3, n & 7) of that patch; sides multiples of 16, so no padding.
+// luma_patch_byte0: the byte offset of the patch's first pixel inside a channel; luma_byte_off: of the byte of channel ch under
+// element (m, n), from the image's first byte (3 H W < 2^31: int)
+LRF_HD inline int luma_patch_byte0(int m, int W, int nwl)
+{
+    const int pr = m / nwl, pc = m - pr * nwl;
+    return 8 * pr * W + 8 * pc;
+}
+LRF_HD inline int luma_byte_off(int m, int n, int ch, int hw, int W, int nwl) { return ch * hw + luma_patch_byte0(m, W, nwl) + (n >> 3) * W + (n & 7); }
+
 struct CropSpan { int y, x, ny, nx; }; // image rows y .. y + ny - 1, columns x .. x + nx - 1; ny == 0 or nx == 0: none
 // Tiled body: the tiles of decode_strip_tile (16 padded luma rows x 32 luma patches, a thread two rows of one patch), laid from
 // the strip and the patch column that hold the window's origin.  h rows touch at most floor((h + 14) / 16) + 1 strips, w

@@ -23,13 +23,18 @@ bool planes_gram_eligible(const uint8_t* rgb, int64_t B, int64_t H, int64_t W)
     if (off || H % 16 != 0 || W % 16 != 0 || (reinterpret_cast<uintptr_t>(rgb) & 7) != 0 || (long)H * W * 3 >= (1L << 31)) return false;
     return min_chunks <= 1 || B * (H / 8) * (W / 8) >= min_chunks * LRF_GRAM_ROWS_FUSED; // (luma rows of the call)
 }
-int planes_gram_from_rgb(lrf_ctx* c, const uint8_t* rgb, int64_t H, int64_t W, const ImageGeom& g, const Tables& t, float* X)
+int planes_gram_from_rgb(lrf_ctx* c, const uint8_t* rgb, int64_t H, int64_t W, const ImageGeom& g, const Tables& t, float* X, bool luma_out)
 {
     const int nfused = (int)t.gchunks.size() - t.ngram_rest;
     if (nfused < 1) return set_err(LRF_EINVAL, "internal: no plane is marked for k_planes16_gram");
     Prof p(c, LRF_K_PLANES_GRAM);
-    hipLaunchKernelGGL(k_planes16_gram, dim3((unsigned)nfused), dim3(256), 0, c->stream, rgb, (int)H, (int)W, g, X, (const PlaneDesc*)c->planes.p,
-                       (const GramChunk*)c->gchunks.p + t.ngram_rest, (ulonglong2*)c->gpart.p);
+    // luma_out false: the call's k_bcd_p reads luma from `rgb` (plan_luma_bytes): the luma rows of X are not written
+    if (luma_out)
+        hipLaunchKernelGGL(k_planes16_gram<true>, dim3((unsigned)nfused), dim3(256), 0, c->stream, rgb, (int)H, (int)W, g, X, (const PlaneDesc*)c->planes.p,
+                           (const GramChunk*)c->gchunks.p + t.ngram_rest, (ulonglong2*)c->gpart.p);
+    else
+        hipLaunchKernelGGL(k_planes16_gram<false>, dim3((unsigned)nfused), dim3(256), 0, c->stream, rgb, (int)H, (int)W, g, X, (const PlaneDesc*)c->planes.p,
+                           (const GramChunk*)c->gchunks.p + t.ngram_rest, (ulonglong2*)c->gpart.p);
     LAUNCH_CHECK();
     return LRF_OK;
 }

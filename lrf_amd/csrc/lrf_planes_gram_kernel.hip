@@ -15,6 +15,9 @@
 #include "lrf_device.h"
 #include "lrf_internal.h"
 
+// LUMA_OUT false: a call whose k_bcd_p reads luma from the image bytes (plan_luma_bytes, lrf_plan.h): nobody reads luma X, the
+// "luma rows out" phase is left out (the staging, the Gram digits and the chroma rows are the same).
+template <bool LUMA_OUT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_planes16_gram(
     const uint8_t* __restrict__ rgb, int H, int W, ImageGeom g, float* __restrict__ X, const PlaneDesc* __restrict__ planes,
     const GramChunk* __restrict__ chunks, ulonglong2* __restrict__ Gpart)
@@ -138,14 +141,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int a = 0; a < 5; a++) lb[(wave * 5 + a) * 64 + lane] = make_uint4(pk[a][0], pk[a][1], pk[a][2], pk[a][3]);
         // ---- luma rows out, lane-contiguous (k_planes16's second phase)
-        const int npw = nwl - ww0 < 32 ? nwl - ww0 : 32;
+        if constexpr (LUMA_OUT) {
+            const int npw = nwl - ww0 < 32 ? nwl - ww0 : 32;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int f = k * 256 + tid, h = f >> 9, rem = f & 511, pw = rem >> 4, q = rem & 15;
-            if (pw < npw) {
-                const int sw = (h << 1) | (q >> 3);
-                const f32x4 v = *reinterpret_cast<const f32x4*>(Ls + (h * 32 + pw) * 64 + 4 * (q ^ sw));
-                *reinterpret_cast<f32x4*>(Xi + g.p[0].xoff + ((long)(2 * strip + h) * nwl + ww0) * 64 + rem * 4) = v;
+            for (int k = 0; k < 4; k++) {
+                const int f = k * 256 + tid, h = f >> 9, rem = f & 511, pw = rem >> 4, q = rem & 15;
+                if (pw < npw) {
+                    const int sw = (h << 1) | (q >> 3);
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(Ls + (h * 32 + pw) * 64 + 4 * (q ^ sw));
+                    *reinterpret_cast<f32x4*>(Xi + g.p[0].xoff + ((long)(2 * strip + h) * nwl + ww0) * 64 + rem * 4) = v;
+                }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
