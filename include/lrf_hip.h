@@ -162,10 +162,13 @@ int lrf_qmf_bcd_f32(lrf_ctx* ctx, const float* X, int64_t B, int64_t M, int64_t 
  *                       updates then see safe_divide(x - w0, w1) (:104-105, utils.py:18-33) and update_w (:141-147) refits
  *                       (w0, w1) after them.  The reference solves that least-squares problem with torch.linalg.lstsq
  *                       (LAPACK); this library with the 2 x 2 normal equations in fp64: everything downstream of an updated
- *                       w is parity by tolerance (loss to 2e-4), everything else is the reference's bit for bit.
+ *                       w is parity by tolerance (loss to 2e-4), everything else is the reference's bit for bit.  For a constant
+ *                       z = u v^T = c != 0 the determinant is exactly zero and this library returns (mean x, 0), where the
+ *                       reference's lstsq returns an ill-conditioned pair whose reconstruction w0 + w1 c only nears the mean.
  *   U0 [B,M,R], V0 [B,N,R] fp32, both or neither: initial factors; NULL = this library's SVD initialisation (sign as in
  *                       lrf_qmf_decompose_f32).
- *   U [B,M,R], V [B,N,R], W [B,2] = (w0, w1) fp32, device memory.  eps is the class default 1e-16.  K = 0 returns the
+ *   U [B,M,R], V [B,N,R], W [B,2] = (w0, w1) fp32, device memory.  eps (opts, default 1e-16) is also the eps of that safe_divide
+ *   (qmf.py:105): a pair with |w1| < eps divides by eps * sign(w1) — the default pair (0, 1) included, when eps > 1.  K = 0 returns the
  *   initial factors.  Runs on the any-shape kernels for every shape (R <= LRF_ANY_MAX_RANK).
  */
 typedef struct lrf_qmf_opts {

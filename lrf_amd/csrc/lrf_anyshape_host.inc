@@ -143,10 +143,12 @@ static int any_run_bcd(lrf_ctx* c, const float* X, int B, int M, int N, int R, i
 // QMF.decompose in its general form (lrf/factorization/qmf.py:74-214; include/lrf_hip.h lrf_qmf_decompose_ex_f32): fp32
 // factors in any_uf / any_vf on entry (the initialisation) and on return.  Wd [B][2] device, initial pair on entry.
 // affine_always: the pair is not [0; 1] on entry (SVDInit(num_levels=...), qmf.py:56-68): the u / v updates see
-// safe_divide(x - w0, w1) also when w itself is not updated.
+// safe_divide(x - w0, w1) also when w itself is not updated.  The same holds for [0; 1] itself when eps > 1: safe_divide takes
+// CoordinateDescent's eps (qmf.py:105) and |w1| = 1 < eps divides x by eps.
 static int any_run_bcd_general(lrf_ctx* c, const float* X, int B, int M, int N, int R, int K, float lo, float hi, float l1_u, float l2_u,
                                float l1_v, float l2_v, int factors, float* Wd, float eps = LRF_EPS, bool affine_always = false)
 {
+    affine_always = affine_always || eps > 1.f;
     float* Uf = (float*)c->any_uf.p;
     float* Vf = (float*)c->any_vf.p;
     const long per = (long)M * N;
@@ -161,7 +163,8 @@ static int any_run_bcd_general(lrf_ctx* c, const float* X, int B, int M, int N, 
     for (int it = 0; it < K; it++) {
         Prof p(c, LRF_K_BCD);
         if ((factors & 4) || (affine_always && it == 0)) { // (a pair that is never updated: once)
-            hipLaunchKernelGGL(k_any_affine, dim3((unsigned)((per + 255) / 256), (unsigned)B), dim3(256), 0, c->stream, X, (const float*)Wd, Xp, per);
+            hipLaunchKernelGGL(k_any_affine, dim3((unsigned)((per + 255) / 256), (unsigned)B), dim3(256), 0, c->stream, X, (const float*)Wd, Xp, per,
+                               eps);
             LAUNCH_CHECK();
             Xuse = Xp;
         }

@@ -491,14 +491,16 @@ __global__ __launch_bounds__(64) void k_any_gs(const float* __restrict__ a, cons
 }
 
 // ---- the affine pair w of the general QMF class (x ~ w0 + w1 u v^T; qmf.py:104-105, 141-147) ---------------------------
-// Xp = safe_divide(X - w0, w1) (factorization/utils.py:18-33: |w1| < eps -> eps * sign(w1)); W [B][2]
-__global__ __launch_bounds__(256) void k_any_affine(const float* __restrict__ X, const float* __restrict__ W, float* __restrict__ Xp, long per)
+// Xp = safe_divide(X - w0, w1, eps) (factorization/utils.py:18-33: |w1| < eps -> eps * sign(w1)); eps: CoordinateDescent's own
+// (qmf.py:105); W [B][2]
+__global__ __launch_bounds__(256) void k_any_affine(const float* __restrict__ X, const float* __restrict__ W, float* __restrict__ Xp, long per,
+                                                    float eps)
 {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= per) return;
     const float w0 = W[2 * blockIdx.y], w1 = W[2 * blockIdx.y + 1];
     float den = w1;
-    if (fabsf(w1) < LRF_EPS) den = LRF_EPS * ((w1 > 0.f) ? 1.f : (w1 < 0.f ? -1.f : 0.f));
+    if (fabsf(w1) < eps) den = eps * ((w1 > 0.f) ? 1.f : (w1 < 0.f ? -1.f : 0.f));
     Xp[(long)blockIdx.y * per + e] = (X[(long)blockIdx.y * per + e] - w0) / den;
 }
 

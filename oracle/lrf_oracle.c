@@ -287,8 +287,8 @@ int lrf_oracle_bcd_ex(const float* X, long M, long N, int R, int num_iters, int 
 {
     return lrf_oracle_bcd_ex_eps(X, M, N, R, num_iters, bounded, lo, hi, l2u, l2v, l1_ratio, factors, U, V, W, 1e-16);
 }
-/* eps_d: CoordinateDescent's eps (qmf.py:82, 90, 117-118), a Python float that meets fp32 tensors: rounded to fp32.  The eps of
- * safe_divide (utils.py:18) is that function's own default and stays 1e-16. */
+/* eps_d: CoordinateDescent's eps (qmf.py:82, 90, 117-118), a Python float that meets fp32 tensors: rounded to fp32.  update_u
+ * hands the same eps to safe_divide (qmf.py:105): a pair with |w1| < eps divides by eps * sign(w1). */
 int lrf_oracle_bcd_ex_eps(const float* X, long M, long N, int R, int num_iters, int bounded, float lo, float hi,
                           double l2u, double l2v, double l1_ratio, int factors, float* U, float* V, float* W, double eps_d)
 {
@@ -306,7 +306,7 @@ int lrf_oracle_bcd_ex_eps(const float* X, long M, long N, int R, int num_iters, 
         /* x <- safe_divide(x - w0, w1): utils.py:18-33 (|w1| < eps -> eps * sign(w1)) */
         const float w0 = W[0], w1 = W[1];
         float den = w1;
-        if (fabsf(w1) < LRF_EPS) den = LRF_EPS * ((w1 > 0.f) ? 1.f : (w1 < 0.f ? -1.f : 0.f));
+        if (fabsf(w1) < eps) den = eps * ((w1 > 0.f) ? 1.f : (w1 < 0.f ? -1.f : 0.f));
         for (long e = 0; e < M * N; e++) Xp[e] = (X[e] - w0) / den;
         if (factors & 1) update_factor_ex(Xp, N, 1, M, N, R, U, V, bounded, lo, hi, l1_u, l2_u, a_ws, b_ws, eps);
         if (factors & 2) update_factor_ex(Xp, 1, N, N, M, R, V, U, bounded, lo, hi, l1_v, l2_v, a_ws, b_ws, eps);
