@@ -72,6 +72,13 @@ int lrf_ctx_check(lrf_ctx* ctx);
  * yet, or ctx is NULL.
  * The factors are the same bit for bit; tests use it to see that a call took the path they mean to test. */
 int lrf_ctx_last_luma_source(const lrf_ctx* ctx);
+/* What the last lrf_qmf_encode_rgb_u8 of this context kept in the Infinity Cache: the number of chroma planes whose fp32 patch
+ * matrices the persistent kernel loads on the default cache policy, their bytes in *kept_bytes (may be NULL); every other
+ * matrix of such a call streams with non-temporal loads.  0 and 0 bytes: the policy did not apply (a call below the persistent
+ * kernel's threshold or whose matrices all fit the budget, ranks above 8, under a pipe, LRF_X_KEEP_MB=0) and every load was
+ * plain; -1: no such call yet, or ctx is NULL.
+ * A cache policy changes no result; tests use it to see that a call took the path they mean to test. */
+int lrf_ctx_last_x_residency(const lrf_ctx* ctx, int64_t* kept_bytes);
 /* bytes of scratch the context currently holds.  The scratch grows to the largest call seen (2.4 KB per input pixel of the
  * default branch: a 512 x 1365x2048 batch holds ~9 GB) and is kept for reuse; lrf_ctx_trim waits for the stream and gives
  * all of it back (the next call allocates again). */

@@ -91,6 +91,7 @@ def load():
         lib.lrf_ctx_synchronize.argtypes = [c_void_p]
         lib.lrf_ctx_check.argtypes = [c_void_p]
         lib.lrf_ctx_last_luma_source.argtypes = [c_void_p]
+        lib.lrf_ctx_last_x_residency.argtypes = [c_void_p, ctypes.POINTER(c_i64)]
         lib.lrf_ctx_trim.argtypes = [c_void_p]
         lib.lrf_ctx_profile.argtypes = [c_void_p, c_int]
         lib.lrf_ctx_profile_reset.argtypes = [c_void_p]
@@ -177,7 +178,7 @@ def load():
 
 
 EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create", "lrf_ctx_destroy", "lrf_ctx_set_stream", "lrf_ctx_use_own_stream",
-           "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_last_luma_source", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
+           "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_last_luma_source", "lrf_ctx_last_x_residency", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
            "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_qmf_encode_ragged_sweep_rgb_u8", "lrf_qmf_sse_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
@@ -773,6 +774,15 @@ class Context:
         "x" when from the fp32 workspace, None before the first such call (lrf_ctx_last_luma_source; the factors are the same
         bit for bit)"""
         return {0: "x", 1: "bytes"}.get(int(self._lib.lrf_ctx_last_luma_source(self._h)))
+
+    def last_x_residency(self):
+        """(kept planes, kept bytes) of this context's last encode_rgb: the chroma planes whose X the persistent kernel loads on
+        the default cache policy, so that they stay in the Infinity Cache from one iteration to the next, while the rest of the
+        call streams non-temporal; (0, 0) when the policy did not apply, None before the first such call
+        (lrf_ctx_last_x_residency; the factors are the same bit for bit)"""
+        nbytes = c_i64(-1)
+        planes = int(self._lib.lrf_ctx_last_x_residency(self._h, ctypes.byref(nbytes)))
+        return None if planes < 0 else (planes, int(nbytes.value))
 
     def to_host(self, *tensors):
         """the tensors on the host (torch's copy waits for the stream the kernels ran on), then `check`: the one way results

@@ -525,8 +525,13 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
         tab[4] = t4[4][1];
     }
 
+    // The block's X source by cache policy (plan_x_residency, lrf_plan.h; wave-uniform): a streamed block loads non-temporal, so
+    // that what it reads once a pass does not push the kept planes' X out of the Infinity Cache; a kept block, and every block
+    // of a call without the policy, loads plain.  The policy bit is an immediate of the load: two load sequences, one branch.
+    const bool x_nt = bd.x_nt != 0;
     f32x4 xq[4][4];
-    auto issue_x = [&](int t, int T0, int T1, bool live) {
+    auto issue_x_as = [&](auto ntc, int t, int T0, int T1, bool live) {
+        constexpr bool NT = ntc;
         const int r0 = t * 64;
 #pragma unroll
         for (int T = T0; T < T1; T++) {
@@ -534,10 +539,15 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
             for (int q = 0; q < 4; q++) {
                 int row = r0 + 16 * T + 4 * q + lq;
                 row = row < nrows ? row : nrows - 1;
-                if (live) xq[T][q] = *reinterpret_cast<const f32x4*>(Xp + (long)row * 64 + 4 * li);
+                const f32x4* src = reinterpret_cast<const f32x4*>(Xp + (long)row * 64 + 4 * li);
+                if (live) xq[T][q] = NT ? __builtin_nontemporal_load(src) : *src;
                 else xq[T][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
         }
+    };
+    auto issue_x = [&](int t, int T0, int T1, bool live) {
+        if (x_nt) issue_x_as(std::true_type{}, t, T0, T1, live);
+        else issue_x_as(std::false_type{}, t, T0, T1, live);
     };
     // BYTES: by[ch][j] = the eight bytes of pixel row j of the lane's patch in channel ch.  One buffer resource per image
     // (wave-uniform: the plane index is the image), the patch's first byte as the lane's offset, channel and pixel row as the
@@ -551,13 +561,18 @@ __device__ __forceinline__ void bcdp_w_block(const float* __restrict__ X, const 
         row = row < nrows ? row : nrows - 1;
         return luma_patch_byte0(bd.row0 + row, ls.W, ls.nwl);
     };
+    auto issue_b_as = [&](auto ntc, int p0, int j0, int j1) {
+        constexpr int AUX = decltype(ntc)::value ? 2 : 0; // (2: nt)
+#pragma unroll
+        for (int j = j0; j < j1; j++)
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++)
+                by[ch][j] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(irs, p0, ch * ls.hw + j * ls.W, AUX));
+    };
     auto issue_b = [&](int p0, int j0, int j1) {
         if constexpr (BYTES) {
-#pragma unroll
-            for (int j = j0; j < j1; j++)
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                    by[ch][j] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(irs, p0, ch * ls.hw + j * ls.W, 0));
+            if (x_nt) issue_b_as(std::true_type{}, p0, j0, j1);
+            else issue_b_as(std::false_type{}, p0, j0, j1);
         }
     };
     // int8 U rows as whole spans: the 64 rows of sub-tile t are ONE contiguous span of the wave's own, bytes [a, a + len) with
@@ -854,7 +869,9 @@ __global__ __launch_bounds__(64 * LRF_BCDW_WAVES) __attribute__((amdgpu_waves_pe
         // interleaved within an iteration — luma blocks beside chroma blocks on a SIMD: within noise —, and chunks of ~86 images
         // (2064 blocks, 200 MB of X) running all their iterations before the next chunk, so that X stays in the 256 MB Infinity
         // Cache: 139 -> 164 us per iteration at (7,3,3), 246 -> 353 at (26,13,13): a chunk is barely one round of the resident
-        // waves, so blocks poll for V tables that are still being computed — and the kernel is not bound by HBM bandwidth)
+        // waves, so blocks poll for V tables that are still being computed.  That experiment moved all of X and added the
+        // polling, so it says nothing about the cache by itself; what the kernel does follow is how its X loads land: the
+        // streamed sources loaded non-temporal took 7 % off the launch in this order — plan_x_residency)
         const int it = idx / nblocks, blk = idx - it * nblocks;
 #ifdef LRF_BCDP_DEBUG
         atomicAdd(&sync->cell[2 * nplanes + blk], 1 + 1000 * it); // every active lane

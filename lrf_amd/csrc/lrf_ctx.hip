@@ -362,6 +362,12 @@ int lrf_ctx_check(lrf_ctx* c)
 
 int lrf_ctx_last_luma_source(const lrf_ctx* c) { return c ? c->last_luma_source : -1; }
 
+int lrf_ctx_last_x_residency(const lrf_ctx* c, int64_t* kept_bytes)
+{
+    if (kept_bytes) *kept_bytes = c ? (int64_t)c->last_x_kept_bytes : -1;
+    return c ? c->last_x_kept_planes : -1;
+}
+
 size_t lrf_ctx_workspace_bytes(const lrf_ctx* c)
 {
     if (!c) return 0;

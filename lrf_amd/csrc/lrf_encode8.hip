@@ -377,7 +377,8 @@ int lrf_qmf_svd_init_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64
 } // extern "C"
 
 int encode_rgb_prepare(lrf_ctx* c, int64_t B, int64_t H, int64_t W, const int R[3], int K, int lo, int hi, bool with_sign,
-                       bool fuse_gram /* planes_gram_eligible(rgb, H, W): the luma planes' Gram partials come from k_planes16_gram */, EncodePlan& ep)
+                       bool fuse_gram /* planes_gram_eligible(rgb, H, W): the luma planes' Gram partials come from k_planes16_gram */, EncodePlan& ep,
+                       bool upload)
 {
     if (B < 1 || B > 65535) return set_err(LRF_EINVAL, "B=%ld out of range [1,65535]", (long)B);
     int rc = make_geom(H, W, &ep.g);
@@ -407,7 +408,7 @@ int encode_rgb_prepare(lrf_ctx* c, int64_t B, int64_t H, int64_t W, const int R[
             if (fuse_gram && ch == 0) ep.t.planes.back().gram_fused = 1;
         }
     ep.bcd = plan_bcd(ep.t.planes, K, lo, hi, PLAN_FIRST_W0, plan_settings(c));
-    return upload_tables(c, ep.t, ep.bcd);
+    return upload ? upload_tables(c, ep.t, ep.bcd) : LRF_OK;
 }
 
 extern "C" {
@@ -419,18 +420,24 @@ int lrf_qmf_encode_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64_t H, 
     LRF_ON_DEVICE(c);
     EncodePlan ep;
     const bool fuse = planes_gram_eligible(rgb, B, H, W);
-    int rc = encode_rgb_prepare(c, B, H, W, R, K, lo, hi, sign != nullptr, fuse, ep);
+    int rc = encode_rgb_prepare(c, B, H, W, R, K, lo, hi, sign != nullptr, fuse, ep, false);
     if (rc) return rc;
     const ImageGeom& g = ep.g;
     Tables& t = ep.t;
     const long u_img = ep.u_img, v_img = ep.v_img;
     const long *uoff = ep.uoff, *voff = ep.voff, *u0c = ep.u0c, *v0c = ep.v0c;
-    float* X = (float*)c->x.p;
     // luma from the image bytes (plan_luma_bytes, lrf_plan.h): the luma blocks of k_bcd_p read `rgb`, and the fused planes kernel
     // leaves the luma rows of X unwritten (a pipe, which hands the bytes back at planes_done, keeps the X path)
     ep.bcd.luma_bytes = plan_luma_bytes(ep.bcd, t.planes, (int)B, H, W, reinterpret_cast<uintptr_t>(rgb), c->planes_done != nullptr, plan_settings(c));
     if (ep.bcd.luma_bytes) ep.bcd.luma = LumaSrc{rgb, (int)(H * W), (int)W, (int)(W / 8), (int)B};
     c->last_luma_source = ep.bcd.luma_bytes ? 1 : 0;
+    // which X of the call k_bcd_p keeps in the Infinity Cache and which it streams past it (plan_x_residency marks the blocks:
+    // the tables go up behind it; under a pipe nothing is marked, and these are the tables its prepare call left resident)
+    const XResidency xr = plan_x_residency(ep.bcd, t, (int)B, ep.bcd.luma_bytes, c->planes_done != nullptr, plan_settings(c));
+    c->last_x_kept_planes = xr.kept_planes;
+    c->last_x_kept_bytes = xr.kept_bytes;
+    if ((rc = upload_tables(c, t, ep.bcd))) return rc;
+    float* X = (float*)c->x.p;
     if ((rc = fuse ? planes_gram_from_rgb(c, rgb, H, W, g, t, X, !ep.bcd.luma_bytes) : lrf_qmf_planes_from_rgb_u8(c, rgb, B, H, W, X))) return rc;
     if (c->planes_done) HIP_TRY(hipEventRecord(c->planes_done, c->stream)); // the RGB bytes are not read again
     if (ep.bcd.rmax > LRF_BIG_TO_ANY_RANK) {

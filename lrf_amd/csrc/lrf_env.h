@@ -8,6 +8,10 @@
 //   LRF_BCDW16_MIN_BLOCKS / LRF_BCDW32_MIN_BLOCKS  blocks from which the wave kernels of ranks 9..16 / 17..32 run
 //   LRF_LUMA_BYTES           0: k_bcd_p always reads luma from X; else (the default) from the image bytes in every eligible
 //                            call (plan_luma_bytes, lrf_plan.h); lrf_ctx_last_luma_source says which a call took
+//   LRF_X_KEEP_MB            10^6 bytes of chroma X that a k_bcd_p call of ranks <= 8 keeps on the default cache policy, the rest of its
+//                            X sources streaming non-temporal (plan_x_residency, lrf_plan.h; default LRF_X_KEEP_MB_DEFAULT);
+//                            a call that fits the budget as a whole is left alone; 0: no policy, every load plain;
+//                            lrf_ctx_last_x_residency says what a call kept
 //   LRF_DEBUG_INIT_SWEEPS   stops k_init after a stage / forces the Sturm replacement loop       (tests/test_hip_parity.py)
 //   LRF_PIPE_BULK / LRF_PIPE_TAIL  the pipe's piece sizes                                          (tests/test_pipeline.py)
 //   LRF_FUSED_GRAM_MIN_CHUNKS  from how many luma Gram chunks on k_planes16_gram forms the patch matrices (tests/test_fused_gram.py)

@@ -130,6 +130,8 @@ struct lrf_ctx {
     hipEvent_t fam_fork = nullptr, fam_join[2] = {nullptr, nullptr};
     bool fam_forked = false;     // run_init forked: run_bcd uses the same streams and joins
     int last_luma_source = -1;   // where the luma blocks of the last lrf_qmf_encode_rgb_u8 read X: 0 = the X workspace, 1 = the image bytes; -1: no such call yet
+    int last_x_kept_planes = -1; // the residency decision of the last lrf_qmf_encode_rgb_u8 (plan_x_residency): planes kept on the default cache
+    long last_x_kept_bytes = -1; // policy and their X bytes, 0 / 0 when the policy did not apply; -1: no such call yet
     hipEvent_t planes_done = nullptr; // set by a pipe: recorded after the planes kernel of lrf_qmf_encode_rgb_u8 (input buffer free)
     // the persistent iteration kernel (k_bcd_p, default for large rank <= 8 calls): its queue head, tickets and flags; its error
     // word is page-locked host memory the kernel writes directly — the sequence number of the first launch whose poll expired.
@@ -204,8 +206,9 @@ struct EncodePlan {
     BcdPlan bcd; // of the call that initialises and iterates (first_mode 1)
     long u_img = 0, v_img = 0, uoff[3], voff[3], u0c[4] = {0, 0, 0, 0}, v0c[4] = {0, 0, 0, 0};
 };
+// upload false: the caller uploads the tables itself (lrf_qmf_encode_rgb_u8, behind plan_x_residency, which marks blocks).
 int encode_rgb_prepare(lrf_ctx* c, int64_t B, int64_t H, int64_t W, const int R[3], int K, int lo, int hi, bool with_sign, bool fuse_gram,
-                       EncodePlan& ep);
+                       EncodePlan& ep, bool upload = true);
 bool planes_gram_eligible(const uint8_t* rgb, int64_t B, int64_t H, int64_t W); // lrf_planes_gram.hip
 int planes_gram_from_rgb(lrf_ctx* c, const uint8_t* rgb, int64_t H, int64_t W, const ImageGeom& g, const Tables& t, float* X, bool luma_out = true);
 

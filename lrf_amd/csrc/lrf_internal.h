@@ -65,7 +65,11 @@ struct BlockDesc {
     int plane;         // index into the PlaneDesc table
     int row0;          // first row of the block
     int blk;           // block number inside the plane
-    int pad;
+    union {
+        int x_nt;      // 1: the rank <= 8 body of k_bcd_p streams the block's X source (fp32 rows or image bytes) with non-temporal
+                       // loads (plan_x_residency, lrf_plan.h); 0: plain loads — every block of a call without the policy
+        int pad;       // (the word's name while it was unused: comparisons of whole tables still say so)
+    };
 };
 // Where k_bcd_p's rank <= 8 body finds the luma matrices of a call that reads them from the caller's image bytes instead of X
 // (plan_luma_bytes, lrf_plan.h): plane i < nluma of the table is the luma plane of image i, whose [3][H][W] bytes start at

@@ -19,6 +19,11 @@
 #define LRF_BCDW32_MIN_BLOCKS 128  // likewise for rank 17..32 runs and k_bcd_w32 / k_bcd_w32f (12 images: 1.06 -> 0.99 ms at (20,10,10))
 #define LRF_PERSIST_MIN_BLOCKS 3584 // a call of this many blocks runs its iterations in one launch (k_bcd_p) ...
 #define LRF_PERSIST_MIN_BLOCKS_ONE_FAMILY 2304 // ... of this many when all its planes are of one rank family
+// X bytes (10^6) of a k_bcd_p call that stay on the default cache policy (plan_x_residency): the 256 MiB (268 MB) Infinity Cache
+// less the hand-off lines of a pass (U rows, partials, tables: ~30 MB at 256 x 512x768) and a margin.  Measured on 512x768 images
+// at ranks (7,3,3), policy against plain loads: 104 / 112 images (204 / 220 MB a pass) lose 0.7 / 1.1 % under the policy — they
+// still fit —, 120 (236 MB) gain 0.5 %, 128 (252 MB) 2.2 %, 256 (503 MB, 201 MB of chroma X kept) 5.7 %
+#define LRF_X_KEEP_MB_DEFAULT 230
 
 // ---- descriptor tables ------------------------------------------------------------------------
 struct Tables {
@@ -39,6 +44,7 @@ struct PlanSettings {
     bool bcd_wg = false, no_family_split = false, no_family_streams = false, no_bcdw32 = false, generic_gs = false, no_persist_first = false, no_init_fork = false;
     bool persist_arch = false; // the device is the part the in-launch hand-offs of k_bcd_p were validated on (gfx950)
     int luma_bytes = -1;       // LRF_LUMA_BYTES (lrf_env.h): 0 = no call reads luma from the image bytes; else every eligible one
+    long x_keep_bytes = LRF_X_KEEP_MB_DEFAULT * 1000000L; // LRF_X_KEEP_MB x 10^6 (plan_x_residency): 0 = no residency policy
 };
 const PlanSettings& plan_settings_env(); // the environment's part (persist_arch false)
 
@@ -95,6 +101,25 @@ BcdPlan plan_bcd(const std::vector<PlaneDesc>& planes, int K, int lo, int hi, in
 // nluma: the leading planes of the table that are the images' luma planes, image i at plane i (encode_rgb_prepare's order).
 bool plan_luma_bytes(const BcdPlan& p, const std::vector<PlaneDesc>& planes, int nluma, int64_t H, int64_t W, uintptr_t rgb_addr, bool rgb_released,
                      const PlanSettings& s);
+
+// ---- which X stays in the Infinity Cache: k_bcd_p reads every X source of the call once per iteration, K times a call.  What
+// fits the cache between two passes is served on-die from the second pass on — but only if the sources that cannot fit do not
+// pass through the cache on their way (BlockDesc::x_nt: non-temporal loads, which also land sooner than plain ones).
+//   * A call whose sources all fit the budget — luma as it is read, three bytes an element from the image (`luma_from_bytes`) or
+//     four from X, plus the chroma planes' X — is left alone: nothing is marked, every load is plain, as without the policy.
+//   * Otherwise, in table order, the planes behind the `nluma` leading luma planes — the chroma planes, whose X is fp32 in
+//     every call — are KEPT (plain loads) while their X bytes, added up, stay within the budget; every other block of the call
+//     streams: luma, from the image bytes or from fp32 X (four times a chroma plane: in a call that does not fit, the part that
+//     cannot), and the planes from the first that passes the budget on.  Luma is never among the kept planes.
+// The policy applies to calls that k_bcd_p's rank <= 8 body alone iterates (plan.persist, no plane above rank 8) outside a pipe
+// (`piped`: two contexts' kernels share the cache); elsewhere, and with a budget of 0, no block is marked and every load is
+// plain.  Sets BlockDesc::x_nt of every block of the table; the plane table is not touched.
+struct XResidency {
+    int kept_planes = 0;  // planes whose X loads plain under the policy
+    long kept_bytes = 0;  // their X bytes
+    bool on = false;      // the policy applies: the other blocks are marked x_nt
+};
+XResidency plan_x_residency(const BcdPlan& p, Tables& t, int nluma, bool luma_from_bytes, bool piped, const PlanSettings& s);
 
 // ---- decode: which body serves an image, and the launches of a ragged call (lrf_qmf_decode_ragged_rgb_u8) ------------------
 enum { DEC_TILE16 = 0, DEC_STRIP = 1, DEC_R8 = 2, DEC_ANY = 3 }; // decode_plan (lrf_encode8.hip) decides
