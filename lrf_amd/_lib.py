@@ -340,6 +340,52 @@ def check_ragged_args(U, V, images):
     return out
 
 
+def _check_size(size, upper=None):
+    """The (h, w) of an entry's windows, both >= 1 — or, with `upper`, the (oh, ow) of its output, both in [1, upper] -> integers"""
+    import numpy as np
+    try:
+        h, w = size
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be ({'h, w' if upper is None else 'oh, ow'}), got {size!r}") from None
+    if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in (h, w)):
+        raise TypeError(f"size must hold two integers, got {size!r}")
+    h, w = int(h), int(w)
+    if upper is None and (h < 1 or w < 1):
+        raise ValueError(f"crop size {h}x{w}: both sides must be >= 1")
+    if upper is not None and (h < 1 or w < 1 or h > upper or w > upper):
+        raise ValueError(f"output size {h}x{w}: both sides must be in [1, {upper}]")
+    return h, w
+
+
+def _check_boxes(crops, columns, entry):
+    """The box list of `entry`: an integer array-like [n, len(columns)] on the host, 1 <= n <= 2^20; columns: their names, for
+    the messages -> an int64 array"""
+    import numpy as np
+    if hasattr(crops, "detach"):  # a torch tensor
+        if crops.is_cuda:
+            raise ValueError("crops live on the host: the call validates every box before it launches")
+        crops = crops.detach().numpy()
+    boxes = np.asarray(crops)
+    if boxes.size == 0:
+        raise ValueError(f"{entry} needs 1 to 2^20 crops")
+    if boxes.dtype.kind not in "iu":
+        raise TypeError(f"crops must be integers ({', '.join(columns)}), got {boxes.dtype}")
+    if boxes.ndim != 2 or boxes.shape[1] != len(columns):
+        raise ValueError(f"crops must be [n, {len(columns)}] ({', '.join(columns)}), got shape {tuple(boxes.shape)}")
+    if boxes.shape[0] > 2 ** 20:
+        raise ValueError(f"{entry} needs 1 to 2^20 crops")
+    return boxes.astype(np.int64)
+
+
+def _check_box_images(boxes, ims):
+    """column 0 of the boxes indexes the images -> (H, W) of every box's image"""
+    import numpy as np
+    bad = np.flatnonzero((boxes[:, 0] < 0) | (boxes[:, 0] >= len(ims)))
+    if bad.size:
+        raise ValueError(f"crop {bad[0]}: image {boxes[bad[0], 0]} out of range [0, {len(ims)})")
+    return np.array([im[0] for im in ims], dtype=np.int64)[boxes[:, 0]], np.array([im[1] for im in ims], dtype=np.int64)[boxes[:, 0]]
+
+
 def check_crop_args(U, V, images, crops, size):
     """The argument checks of lrf_qmf_decode_crops_rgb_u8, before any device is touched.  U, V, images: as check_ragged_args takes
     them; crops: an integer array-like [n, 3] of (image, y0, x0) on the host, 1 <= n <= 2^20; size: (h, w), both >= 1; every
@@ -347,33 +393,9 @@ def check_crop_args(U, V, images, crops, size):
     ValueError for everything else.  -> (images as check_ragged_args returns them, crops as an int32 array [n, 3], (h, w))."""
     import numpy as np
     ims = check_ragged_args(U, V, images)
-    try:
-        h, w = size
-    except (TypeError, ValueError):
-        raise ValueError(f"size must be (h, w), got {size!r}") from None
-    if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in (h, w)):
-        raise TypeError(f"size must hold two integers, got {size!r}")
-    h, w = int(h), int(w)
-    if h < 1 or w < 1:
-        raise ValueError(f"crop size {h}x{w}: both sides must be >= 1")
-    if hasattr(crops, "detach"):  # a torch tensor
-        if crops.is_cuda:
-            raise ValueError("crops live on the host: the call validates every box before it launches")
-        crops = crops.detach().numpy()
-    boxes = np.asarray(crops)
-    if boxes.size == 0:
-        raise ValueError("decode_crops needs 1 to 2^20 crops")
-    if boxes.dtype.kind not in "iu":
-        raise TypeError(f"crops must be integers (image, y0, x0), got {boxes.dtype}")
-    if boxes.ndim != 2 or boxes.shape[1] != 3:
-        raise ValueError(f"crops must be [n, 3] (image, y0, x0), got shape {tuple(boxes.shape)}")
-    if boxes.shape[0] > 2 ** 20:
-        raise ValueError("decode_crops needs 1 to 2^20 crops")
-    boxes = boxes.astype(np.int64)
-    bad = np.flatnonzero((boxes[:, 0] < 0) | (boxes[:, 0] >= len(ims)))
-    if bad.size:
-        raise ValueError(f"crop {bad[0]}: image {boxes[bad[0], 0]} out of range [0, {len(ims)})")
-    Hs, Ws = np.array([im[0] for im in ims], dtype=np.int64)[boxes[:, 0]], np.array([im[1] for im in ims], dtype=np.int64)[boxes[:, 0]]
+    h, w = _check_size(size)
+    boxes = _check_boxes(crops, ("image", "y0", "x0"), "decode_crops")
+    Hs, Ws = _check_box_images(boxes, ims)
     bad = np.flatnonzero((boxes[:, 1] < 0) | (boxes[:, 2] < 0) | (boxes[:, 1] + h > Hs) | (boxes[:, 2] + w > Ws))
     if bad.size:
         j = bad[0]
@@ -411,38 +433,14 @@ def check_scaled_args(U, V, images, scale=None, crops=None, size=None):
         return ims, int(scale)
     if scale is not None or crops is None or size is None:
         raise ValueError("give either a scale (whole images) or crops of (image, scale, y0, x0) and a size")
-    try:
-        h, w = size
-    except (TypeError, ValueError):
-        raise ValueError(f"size must be (h, w), got {size!r}") from None
-    if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in (h, w)):
-        raise TypeError(f"size must hold two integers, got {size!r}")
-    h, w = int(h), int(w)
-    if h < 1 or w < 1:
-        raise ValueError(f"crop size {h}x{w}: both sides must be >= 1")
-    if hasattr(crops, "detach"):  # a torch tensor
-        if crops.is_cuda:
-            raise ValueError("crops live on the host: the call validates every box before it launches")
-        crops = crops.detach().numpy()
-    boxes = np.asarray(crops)
-    if boxes.size == 0:
-        raise ValueError("decode_scaled_crops needs 1 to 2^20 crops")
-    if boxes.dtype.kind not in "iu":
-        raise TypeError(f"crops must be integers (image, scale, y0, x0), got {boxes.dtype}")
-    if boxes.ndim != 2 or boxes.shape[1] != 4:
-        raise ValueError(f"crops must be [n, 4] (image, scale, y0, x0), got shape {tuple(boxes.shape)}")
-    if boxes.shape[0] > 2 ** 20:
-        raise ValueError("decode_scaled_crops needs 1 to 2^20 crops")
-    boxes = boxes.astype(np.int64)
-    bad = np.flatnonzero((boxes[:, 0] < 0) | (boxes[:, 0] >= len(ims)))
-    if bad.size:
-        raise ValueError(f"crop {bad[0]}: image {boxes[bad[0], 0]} out of range [0, {len(ims)})")
+    h, w = _check_size(size)
+    boxes = _check_boxes(crops, ("image", "scale", "y0", "x0"), "decode_scaled_crops")
+    Hs, Ws = _check_box_images(boxes, ims)
     bad = np.flatnonzero(~np.isin(boxes[:, 1], SCALES))
     if bad.size:
         raise ValueError(f"crop {bad[0]}: scale {boxes[bad[0], 1]}: 2, 4 or 8 expected")
     f = boxes[:, 1]
-    Hs = -(-np.array([im[0] for im in ims], dtype=np.int64)[boxes[:, 0]] // f)
-    Ws = -(-np.array([im[1] for im in ims], dtype=np.int64)[boxes[:, 0]] // f)
+    Hs, Ws = -(-Hs // f), -(-Ws // f)
     bad = np.flatnonzero((boxes[:, 2] < 0) | (boxes[:, 3] < 0) | (boxes[:, 2] + h > Hs) | (boxes[:, 3] + w > Ws))
     if bad.size:
         j = bad[0]
@@ -461,36 +459,12 @@ def check_resized_args(U, V, images, crops, size):
     -> (images as check_ragged_args returns them, crops as an int32 array [n, 6] with flip 0 or 1, (oh, ow))."""
     import numpy as np
     ims = check_ragged_args(U, V, images)
-    try:
-        oh, ow = size
-    except (TypeError, ValueError):
-        raise ValueError(f"size must be (oh, ow), got {size!r}") from None
-    if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in (oh, ow)):
-        raise TypeError(f"size must hold two integers, got {size!r}")
-    oh, ow = int(oh), int(ow)
-    if oh < 1 or ow < 1 or oh > RESIZED_MAX_SIDE or ow > RESIZED_MAX_SIDE:
-        raise ValueError(f"output size {oh}x{ow}: both sides must be in [1, {RESIZED_MAX_SIDE}]")
-    if hasattr(crops, "detach"):  # a torch tensor
-        if crops.is_cuda:
-            raise ValueError("crops live on the host: the call validates every box before it launches")
-        crops = crops.detach().numpy()
-    boxes = np.asarray(crops)
-    if boxes.size == 0:
-        raise ValueError("decode_resized_crops needs 1 to 2^20 crops")
-    if boxes.dtype.kind not in "iu":
-        raise TypeError(f"crops must be integers (image, y0, x0, h, w, flip), got {boxes.dtype}")
-    if boxes.ndim != 2 or boxes.shape[1] != 6:
-        raise ValueError(f"crops must be [n, 6] (image, y0, x0, h, w, flip), got shape {tuple(boxes.shape)}")
-    if boxes.shape[0] > 2 ** 20:
-        raise ValueError("decode_resized_crops needs 1 to 2^20 crops")
-    boxes = boxes.astype(np.int64)
-    bad = np.flatnonzero((boxes[:, 0] < 0) | (boxes[:, 0] >= len(ims)))
-    if bad.size:
-        raise ValueError(f"crop {bad[0]}: image {boxes[bad[0], 0]} out of range [0, {len(ims)})")
+    oh, ow = _check_size(size, RESIZED_MAX_SIDE)
+    boxes = _check_boxes(crops, ("image", "y0", "x0", "h", "w", "flip"), "decode_resized_crops")
+    Hs, Ws = _check_box_images(boxes, ims)
     bad = np.flatnonzero((boxes[:, 3] < 1) | (boxes[:, 4] < 1))
     if bad.size:
         raise ValueError(f"crop {bad[0]}: box of {boxes[bad[0], 3]}x{boxes[bad[0], 4]}: both sides must be >= 1")
-    Hs, Ws = np.array([im[0] for im in ims], dtype=np.int64)[boxes[:, 0]], np.array([im[1] for im in ims], dtype=np.int64)[boxes[:, 0]]
     bad = np.flatnonzero((boxes[:, 1] < 0) | (boxes[:, 2] < 0) | (boxes[:, 1] + boxes[:, 3] > Hs) | (boxes[:, 2] + boxes[:, 4] > Ws))
     if bad.size:
         j = bad[0]
@@ -728,6 +702,24 @@ def flat_views(ts):
     return torch.as_strided(ts[0], (p - ts[0].data_ptr(),), (1,))
 
 
+def _ragged_images(ims, rgb_offs=None):
+    """the lrf_ragged_image array of a checked image list (check_ragged_args); rgb_offs: where each image's output starts, else 0"""
+    desc = (RaggedImage * len(ims))()
+    for i, (d, (H, W, ranks, u_off, v_off)) in enumerate(zip(desc, ims)):
+        d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, 0 if rgb_offs is None else rgb_offs[i]
+        d.R[0], d.R[1], d.R[2] = ranks
+    return desc
+
+
+def _packed_outputs(sizes):
+    """[3, h, w] outputs in one buffer, each starting at a multiple of 16 bytes -> (their offsets, the buffer's size)"""
+    offs, off = [], 0
+    for h, w in sizes:
+        offs.append(off)
+        off = (off + 3 * h * w + 15) // 16 * 16
+    return offs, off
+
+
 def _dptr(t):
     """device pointer of a torch CUDA tensor (must be contiguous) or None"""
     if t is None:
@@ -759,6 +751,10 @@ class Context:
     def use_torch_stream(self):
         import torch
         check(self._lib.lrf_ctx_set_stream(self._h, c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _need_here(self, entry, t):
+        if not (t.is_cuda and t.device.index == self.device):
+            raise ValueError(f"{entry} needs its tensors on cuda:{self.device}, got {t.device}")
 
     def synchronize(self):
         check(self._lib.lrf_ctx_synchronize(self._h))
@@ -967,15 +963,10 @@ class Context:
         sides are multiples of 16 keep the decoder made for them)."""
         import torch
         ims = check_ragged_args(U, V, images)
-        if not (U.is_cuda and U.device.index == self.device):
-            raise ValueError(f"decode_ragged needs its tensors on cuda:{self.device}, got {U.device}")
-        desc = (RaggedImage * len(ims))()
-        off = 0
-        for d, (H, W, ranks, u_off, v_off) in zip(desc, ims):
-            d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, off
-            d.R[0], d.R[1], d.R[2] = ranks
-            off = (off + 3 * H * W + 15) // 16 * 16
-        rgb = torch.empty((off,), dtype=torch.uint8, device=U.device)
+        self._need_here("decode_ragged", U)
+        offs, total = _packed_outputs([im[:2] for im in ims])
+        desc = _ragged_images(ims, offs)
+        rgb = torch.empty((total,), dtype=torch.uint8, device=U.device)
         self.use_torch_stream()
         check(self._lib.lrf_qmf_decode_ragged_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(rgb), rgb.numel()))
         return [rgb[d.rgb_off:d.rgb_off + 3 * d.H * d.W].view(3, d.H, d.W) for d in desc]
@@ -987,12 +978,8 @@ class Context:
         stream wait (a new image list does, once)."""
         import torch
         ims, boxes, (h, w) = check_crop_args(U, V, images, crops, size)
-        if not (U.is_cuda and U.device.index == self.device):
-            raise ValueError(f"decode_crops needs its tensors on cuda:{self.device}, got {U.device}")
-        desc = (RaggedImage * len(ims))()
-        for d, (H, W, ranks, u_off, v_off) in zip(desc, ims):
-            d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, 0
-            d.R[0], d.R[1], d.R[2] = ranks
+        self._need_here("decode_crops", U)
+        desc = _ragged_images(ims)
         n = boxes.shape[0]
         rgb = torch.empty((n, 3, h, w), dtype=torch.uint8, device=U.device)
         self.use_torch_stream()
@@ -1006,17 +993,11 @@ class Context:
         starting at a multiple of 16 bytes.  Asynchronous on torch's current stream."""
         import torch
         ims, scale = check_scaled_args(U, V, images, scale)
-        if not (U.is_cuda and U.device.index == self.device):
-            raise ValueError(f"decode_scaled needs its tensors on cuda:{self.device}, got {U.device}")
-        desc = (RaggedImage * len(ims))()
-        sizes, off = [], 0
-        for d, (H, W, ranks, u_off, v_off) in zip(desc, ims):
-            hs, ws = scaled_dims(H, W, scale)
-            d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, off
-            d.R[0], d.R[1], d.R[2] = ranks
-            sizes.append((hs, ws))
-            off = (off + 3 * hs * ws + 15) // 16 * 16
-        rgb = torch.empty((off,), dtype=torch.uint8, device=U.device)
+        self._need_here("decode_scaled", U)
+        sizes = [scaled_dims(H, W, scale) for H, W, *_ in ims]
+        offs, total = _packed_outputs(sizes)
+        desc = _ragged_images(ims, offs)
+        rgb = torch.empty((total,), dtype=torch.uint8, device=U.device)
         self.use_torch_stream()
         check(self._lib.lrf_qmf_decode_scaled_rgb_u8(self._h, len(ims), desc, scale, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(rgb), rgb.numel()))
         return [rgb[d.rgb_off:d.rgb_off + 3 * hs * ws].view(3, hs, ws) for d, (hs, ws) in zip(desc, sizes)]
@@ -1028,12 +1009,8 @@ class Context:
         image at its scale sliced [:, y0:y0+h, x0:x0+w].  Asynchronous on torch's current stream."""
         import torch
         ims, boxes, (h, w) = check_scaled_args(U, V, images, crops=crops, size=size)
-        if not (U.is_cuda and U.device.index == self.device):
-            raise ValueError(f"decode_scaled_crops needs its tensors on cuda:{self.device}, got {U.device}")
-        desc = (RaggedImage * len(ims))()
-        for d, (H, W, ranks, u_off, v_off) in zip(desc, ims):
-            d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, 0
-            d.R[0], d.R[1], d.R[2] = ranks
+        self._need_here("decode_scaled_crops", U)
+        desc = _ragged_images(ims)
         n = boxes.shape[0]
         rgb = torch.empty((n, 3, h, w), dtype=torch.uint8, device=U.device)
         self.use_torch_stream()
@@ -1049,12 +1026,8 @@ class Context:
         bytes.  Asynchronous on torch's current stream; a new crop list costs no stream wait."""
         import torch
         ims, boxes, (oh, ow) = check_resized_args(U, V, images, crops, size)
-        if not (U.is_cuda and U.device.index == self.device):
-            raise ValueError(f"decode_resized_crops needs its tensors on cuda:{self.device}, got {U.device}")
-        desc = (RaggedImage * len(ims))()
-        for d, (H, W, ranks, u_off, v_off) in zip(desc, ims):
-            d.H, d.W, d.u_off, d.v_off, d.rgb_off = H, W, u_off, v_off, 0
-            d.R[0], d.R[1], d.R[2] = ranks
+        self._need_here("decode_resized_crops", U)
+        desc = _ragged_images(ims)
         n = boxes.shape[0]
         rgb = torch.empty((n, 3, oh, ow), dtype=torch.uint8, device=U.device)
         self.use_torch_stream()
@@ -1069,8 +1042,7 @@ class Context:
         in encode_rgb's layout of one image, the images back to back in call order."""
         import torch
         ims = check_encode_ragged_args(rgb, images, sign)
-        if not (rgb.is_cuda and rgb.device.index == self.device):
-            raise ValueError(f"encode_ragged needs its tensors on cuda:{self.device}, got {rgb.device}")
+        self._need_here("encode_ragged", rgb)
         desc = (RaggedEncodeImage * len(ims))()
         u_off, v_off, uo, vo = [], [], 0, 0
         for d, (H, W, ranks, rgb_off, sign_off) in zip(desc, ims):
@@ -1095,8 +1067,7 @@ class Context:
         candidate, where its factors start in them, each in encode_rgb's layout of one image, back to back in list order."""
         import torch
         ims, cd = _check_encode_ragged_sweep(rgb, images, cands, sign)
-        if not (rgb.is_cuda and rgb.device.index == self.device):
-            raise ValueError(f"encode_ragged_sweep needs its tensors on cuda:{self.device}, got {rgb.device}")
+        self._need_here("encode_ragged_sweep", rgb)
         idesc = (RaggedSweepImage * len(ims))()
         for d, (H, W, rgb_off, sign_off) in zip(idesc, ims):
             d.H, d.W, d.rgb_off, d.sign_off = H, W, rgb_off, sign_off
@@ -1124,8 +1095,7 @@ class Context:
         images.  Lists above 65535 items take one call per 65535.  Asynchronous on torch's current stream."""
         import torch
         its = _sse_items_array(rgb, items, U, V)
-        if not (rgb.is_cuda and rgb.device.index == self.device):
-            raise ValueError(f"sse_ragged needs its tensors on cuda:{self.device}, got {rgb.device}")
+        self._need_here("sse_ragged", rgb)
         assert _RAGGED_IMAGE_DT.itemsize == ctypes.sizeof(RaggedImage)
         rec = np.zeros((its.shape[0],), dtype=_RAGGED_IMAGE_DT)
         rec["H"], rec["W"], rec["R"], rec["u_off"], rec["v_off"], rec["rgb_off"] = its[:, 0], its[:, 1], its[:, 2:5], its[:, 5], its[:, 6], its[:, 7]

@@ -1,7 +1,7 @@
 // lrf_decode_resized_host.inc — the host side of the resized crops (lrf_qmf_decode_resized_crops_rgb_u8; kernels:
 // lrf_decode_resized_kernel.hip; the launches: plan_decode_resized).  Included by lrf_encode8.hip after
-// lrf_decode_scaled_host.inc: the entry validates its images with scaled_images and shares the resident descriptor table and
-// the pinned staging slots of the decode of windows.
+// lrf_decode_scaled_host.inc: the entry describes its images as the decode of windows does (describe) and shares its resident
+// descriptor table and pinned staging slots.
 
 int lrf_qmf_decode_resized_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
                                         int64_t v_len, int64_t n_crops, const lrf_resized_crop* crops, int64_t oh, int64_t ow, uint8_t* rgb, int64_t rgb_len)
@@ -11,14 +11,13 @@ int lrf_qmf_decode_resized_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_
     if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
     if (oh < 1 || ow < 1 || oh > 16384 || ow > 16384) return set_err(LRF_EINVAL, "output size %ldx%ld out of range [1,16384]", (long)oh, (long)ow);
     std::vector<RaggedDesc> descs;
-    std::vector<ScaledImage> simg;
-    int rc = scaled_images(n_images, images, u_len, v_len, descs, simg);
+    int rc = describe(n_images, images, u_len, v_len, DescribeOptions{}, "image", "output", descs);
     if (rc) return rc;
     // (oh ow <= 2^28 and n_crops <= 2^20: 3 oh ow n_crops cannot wrap)
     if (rgb_len < 3 || n_crops > rgb_len / (3 * oh * ow))
         return set_err(LRF_EINVAL, "%ld crops of 3x%ldx%ld leave the output buffer of %ld bytes", (long)n_crops, (long)oh, (long)ow, (long)rgb_len);
-    std::vector<int> r8((size_t)n_images);
-    for (int64_t i = 0; i < n_images; i++) r8[(size_t)i] = images[i].R[0] <= 8 && images[i].R[1] <= 8 && images[i].R[2] <= 8;
+    std::vector<int> r8(descs.size());
+    std::transform(descs.begin(), descs.end(), r8.begin(), [](const RaggedDesc& d) { return d.R0 <= 8 && d.R1 <= 8 && d.R2 <= 8; });
     std::vector<ResizedItem> list((size_t)n_crops);
     for (int64_t j = 0; j < n_crops; j++) {
         const lrf_resized_crop& cr = crops[j];
@@ -33,17 +32,10 @@ int lrf_qmf_decode_resized_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_
     const ResizedPlan plan = plan_decode_resized(r8, list, (int)oh, (int)ow);
     if (plan.too_many) return set_err(LRF_EINVAL, "%ld workgroups in one launch: split the list", plan.too_many);
     LRF_ON_DEVICE(c);
-    const size_t db = descs.size() * sizeof(RaggedDesc);
-    if (c->crop_desc_key.size() != db || memcmp(c->crop_desc_key.data(), descs.data(), db) != 0 || !c->crop_desc.p) {
-        c->crop_desc_key.clear();
-        rc = upload(c, c->crop_desc, descs.data(), db);
-        if (rc) return rc;
-        c->crop_desc_key.assign((const char*)descs.data(), (const char*)descs.data() + db);
-    }
+    if ((rc = resident_crop_descs(c, descs))) return rc;
     const RaggedDesc* d_desc = (const RaggedDesc*)c->crop_desc.p;
     Prof p(c, LRF_K_DECODE);
-    rc = stage_crop_bytes(c, plan.table.data(), plan.table.size() * sizeof(ResizedItem));
-    if (rc) return rc;
+    if ((rc = stage_crop_bytes(c, plan.table.data(), plan.table.size() * sizeof(ResizedItem)))) return rc;
     const ResizedItem* d_item = (const ResizedItem*)c->crop_tab.p;
     for (const ResizedLaunch& l : plan.launches) {
         const dim3 grid((unsigned)(l.nitems * l.wgs));

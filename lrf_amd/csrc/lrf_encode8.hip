@@ -533,21 +533,34 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64
 
 } // extern "C"
 
+// A table that stays resident in `buf` under the bytes of its key: `tab`, and behind it `tail` — a function of the key that is
+// not part of it.  Calls that repeat the key skip the synchronising upload.  The key is cleared before the upload and assigned
+// only after it succeeded: a failed upload leaves no key that vouches for the buffer.
+static int keep_resident(lrf_ctx* c, DevBuf& buf, std::vector<char>& key, const void* tab, size_t tb, const void* tail = nullptr, size_t tail_bytes = 0)
+{
+    if (key.size() == tb && memcmp(key.data(), tab, tb) == 0 && buf.p) return LRF_OK;
+    key.clear();
+    int rc;
+    if (tail_bytes) {
+        std::vector<char> both(tb + tail_bytes);
+        memcpy(both.data(), tab, tb);
+        memcpy(both.data() + tb, tail, tail_bytes);
+        rc = upload(c, buf, both.data(), both.size());
+    } else
+        rc = upload(c, buf, tab, tb);
+    if (rc) return rc;
+    key.assign((const char*)tab, (const char*)tab + tb);
+    return LRF_OK;
+}
+
 // the planes stage of a ragged call: its table on the device (resident while calls repeat the list), then the launches of the plan
 static int run_planes_ragged(lrf_ctx* c, const std::vector<EncRaggedDesc>& descs, const std::vector<RaggedBlock>& blocks,
                              const std::vector<EncRaggedLaunch>& launches, const uint8_t* rgb, float* X)
 {
-    int rc;
     // the planes table: descriptors, then workgroups (a function of the descriptors: they alone are the key)
     const size_t db = descs.size() * sizeof(EncRaggedDesc), bb = blocks.size() * sizeof(RaggedBlock);
-    if (c->enc_ragged_key.size() != db || memcmp(c->enc_ragged_key.data(), descs.data(), db) != 0 || !c->enc_ragged_tab.p) {
-        c->enc_ragged_key.clear();
-        std::vector<char> tab(db + bb);
-        memcpy(tab.data(), descs.data(), db);
-        memcpy(tab.data() + db, blocks.data(), bb);
-        if ((rc = upload(c, c->enc_ragged_tab, tab.data(), tab.size()))) return rc;
-        c->enc_ragged_key.assign((const char*)descs.data(), (const char*)descs.data() + db);
-    }
+    int rc = keep_resident(c, c->enc_ragged_tab, c->enc_ragged_key, descs.data(), db, blocks.data(), bb);
+    if (rc) return rc;
     const EncRaggedDesc* d_desc = (const EncRaggedDesc*)c->enc_ragged_tab.p;
     const RaggedBlock* d_blk = (const RaggedBlock*)((const char*)c->enc_ragged_tab.p + db);
     {
@@ -728,32 +741,55 @@ int lrf_qmf_encode_ragged_sweep_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_s
     return init_then_bcd(c, X, plan.t, bcd, sign, LRF_PLANES_GRAM_EXP, U, V);
 }
 
-// which decode body serves a geometry and a rank triple (lrf_qmf_decode_rgb_u8, lrf_qmf_decode_ragged_rgb_u8 and
-// lrf_qmf_sweep_sse_rgb_u8 share it; the kinds DEC_*: lrf_plan.h)
-struct DecodePlan {
-    int kind;
-    int cls; // tiled kinds: index of the rank bounds (chroma, luma) = (4,8) (8,8) (8,16) (16,16) (16,32)
-};
-static DecodePlan decode_plan(const ImageGeom& g, int64_t H, int64_t W, const int R[3], bool aligned8)
+// ---- what the decode and SSE entries share (which body serves an image: decode_plan, lrf_plan.h) ---------------------------------
+static bool decode_no_tiled()
 {
     static const bool no_tiled = dev_flag("LRF_DECODE_NO_TILED");
-    // the tiled kernels (k_decode16: sides multiples of 16; k_decode_strip: any height, four-aligned chroma columns) are
-    // instantiated for the rank bounds (chroma, luma) = (4,8) (8,8) (8,16) (16,16) (16,32): the reference's quality sweep up to 40
-    const int rcm = R[1] > R[2] ? R[1] : R[2];
-    const int RCb = rcm <= 4 ? 4 : (rcm <= 8 ? 8 : 16), RLb = R[0] <= 8 ? 8 : (R[0] <= 16 ? 16 : 32);
-    const bool tiled_ranks = R[0] <= 32 && rcm <= 16 && !no_tiled;
-    const bool sides16 = H % 16 == 0 && W % 16 == 0 && aligned8;
-    const bool strip_ok = W % 2 == 0 && g.p[0].left_crop % 2 == 0 && (g.p[1].left_crop - g.p[0].left_crop / 2) % 4 == 0 && g.p[1].w == W / 2;
-    if (tiled_ranks && (sides16 || strip_ok)) {
-        int cls;
-        if (RLb == 8 && RCb == 4) cls = 0;
-        else if (RLb == 8 && RCb == 8) cls = 1;
-        else if (RLb == 16 && RCb <= 8) cls = 2;
-        else if (RLb <= 16) cls = 3;
-        else cls = 4;
-        return DecodePlan{sides16 ? DEC_TILE16 : DEC_STRIP, cls};
+    return no_tiled;
+}
+// A run-time rank-bound class 0 .. LRF_DEC_CLASSES - 1 as a template argument: LAUNCH(CLS) with CLS a constant; the bounds
+// (chroma, luma) of a class for the kernels that take the pair
+#define LRF_FOR_DEC_CLASS(cls, LAUNCH)  \
+    switch (cls) {                      \
+    case 0: LAUNCH(0); break;           \
+    case 1: LAUNCH(1); break;           \
+    case 2: LAUNCH(2); break;           \
+    case 3: LAUNCH(3); break;           \
+    default: LAUNCH(4); break;          \
     }
-    return DecodePlan{(R[0] <= 8 && R[1] <= 8 && R[2] <= 8) ? DEC_R8 : DEC_ANY, 0};
+constexpr int dec_class_rc(int cls) { return cls >= 3 ? 16 : (cls >= 1 ? 8 : 4); }
+constexpr int dec_class_rl(int cls) { return cls == 4 ? 32 : (cls >= 2 ? 16 : 8); }
+
+// The images of a list entry, described (describe_images) or refused in the entry's words: noun "image" or "item", buf what
+// rgb holds for the entry, "output" or "source".  Geometry refusals keep make_geom's wording.
+static int refuse_image(const DescribeRefusal& r, const char* noun, const char* buf)
+{
+    const long i = (long)r.image;
+    ImageGeom g;
+    switch (r.check) {
+    case DESC_SIZE: return set_err(LRF_EINVAL, "%s %ld: size %ldx%ld out of range", noun, i, (long)r.a, (long)r.b);
+    case DESC_GEOM: return make_geom(r.a, r.b, &g);
+    case DESC_RANK: return set_err(LRF_EINVAL, "%s %ld: rank %d out of range", noun, i, (int)r.a);
+    case DESC_NEGATIVE: return set_err(LRF_EINVAL, "%s %ld: negative offset", noun, i);
+    case DESC_U: return set_err(LRF_EINVAL, "%s %ld: its U factors leave the buffer of %ld elements", noun, i, (long)r.a);
+    case DESC_V: return set_err(LRF_EINVAL, "%s %ld: its V factors leave the buffer of %ld elements", noun, i, (long)r.a);
+    default: return set_err(LRF_EINVAL, "%s %ld: its %s leaves the buffer of %ld bytes", noun, i, buf, (long)r.a);
+    }
+}
+static int describe(int64_t n, const lrf_ragged_image* images, int64_t u_len, int64_t v_len, DescribeOptions o, const char* noun, const char* buf,
+                    std::vector<RaggedDesc>& descs, std::vector<RaggedWork>* work = nullptr)
+{
+    o.no_tiled = decode_no_tiled();
+    const DescribeRefusal r = describe_images(n, images, u_len, v_len, o, descs, work);
+    return r.check == DESC_OK ? LRF_OK : refuse_image(r, noun, buf);
+}
+// the options of an entry whose rgb holds the images at full size: rgb_off and the extents are checked
+static DescribeOptions full_size_rgb(int64_t rgb_len)
+{
+    DescribeOptions o;
+    o.check_rgb = true;
+    o.rgb_len = rgb_len;
+    return o;
 }
 // groups of four pixels per thread of k_decode8 / k_sse8: as many as leave the call ~2048 workgroups (small calls keep one group per thread)
 static long decode8_reps(long images, long n4) { return decode8_reps_of(images * ((n4 + 255) / 256)); }
@@ -776,24 +812,18 @@ int lrf_qmf_decode_rgb_u8(lrf_ctx* c, const int8_t* U, const int8_t* V, int64_t 
     }
     long n4 = (long)H * ((W + 3) / 4);
     Prof p(c, LRF_K_DECODE);
-    const DecodePlan plan = decode_plan(g, H, W, R, (reinterpret_cast<uintptr_t>(rgb) & 7) == 0);
+    const DecodePlan plan = decode_plan(g, H, W, R, (reinterpret_cast<uintptr_t>(rgb) & 7) == 0, decode_no_tiled());
     if (plan.kind == DEC_TILE16 || plan.kind == DEC_STRIP) {
         const int per_strip = (g.p[0].nw + 31) / 32;
         const dim3 grid16((unsigned)((H / 16) * per_strip), (unsigned)B), grids((unsigned)(((g.p[0].nh + 1) / 2) * per_strip), (unsigned)B);
-#define LRF_DECODE_TILED(RC, RL)                                                                                                  \
+#define LRF_DECODE_TILED(CLS)                                                                                                     \
     do {                                                                                                                         \
         if (plan.kind == DEC_TILE16)                                                                                             \
-            hipLaunchKernelGGL((k_decode16<RC, RL>), grid16, dim3(256), 0, c->stream, U, V, (int)H, (int)W, g, R[0], R[1], R[2], u_img, v_img, rgb); \
+            hipLaunchKernelGGL((k_decode16<dec_class_rc(CLS), dec_class_rl(CLS)>), grid16, dim3(256), 0, c->stream, U, V, (int)H, (int)W, g, R[0], R[1], R[2], u_img, v_img, rgb); \
         else                                                                                                                     \
-            hipLaunchKernelGGL((k_decode_strip<RC, RL>), grids, dim3(256), 0, c->stream, U, V, (int)H, (int)W, g, R[0], R[1], R[2], u_img, v_img, rgb, per_strip); \
+            hipLaunchKernelGGL((k_decode_strip<dec_class_rc(CLS), dec_class_rl(CLS)>), grids, dim3(256), 0, c->stream, U, V, (int)H, (int)W, g, R[0], R[1], R[2], u_img, v_img, rgb, per_strip); \
     } while (0)
-        switch (plan.cls) {
-        case 0: LRF_DECODE_TILED(4, 8); break;
-        case 1: LRF_DECODE_TILED(8, 8); break;
-        case 2: LRF_DECODE_TILED(8, 16); break;
-        case 3: LRF_DECODE_TILED(16, 16); break;
-        default: LRF_DECODE_TILED(16, 32); break;
-        }
+        LRF_FOR_DEC_CLASS(plan.cls, LRF_DECODE_TILED)
 #undef LRF_DECODE_TILED
     }
     else if (plan.kind == DEC_R8) {
@@ -815,54 +845,19 @@ int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* 
 {
     if (!c || !images || !U || !V || !rgb) return set_err(LRF_EINVAL, "NULL argument");
     if (n < 1 || n > 65535) return set_err(LRF_EINVAL, "n=%ld out of range [1,65535]", (long)n);
-    std::vector<RaggedDesc> descs((size_t)n);
-    std::vector<RaggedWork> work((size_t)n);
-    memset((void*)descs.data(), 0, descs.size() * sizeof(RaggedDesc)); // (the bytes are the table's key: padding included)
-    for (int64_t i = 0; i < n; i++) {
-        const lrf_ragged_image& im = images[i];
-        RaggedDesc& d = descs[(size_t)i];
-        if (im.H < 1 || im.W < 1 || im.H > INT32_MAX || im.W > INT32_MAX) return set_err(LRF_EINVAL, "image %ld: size %ldx%ld out of range", (long)i, (long)im.H, (long)im.W);
-        int rc = make_geom(im.H, im.W, &d.g);
-        if (rc) return rc;
-        for (int ch = 0; ch < 3; ch++)
-            if (im.R[ch] < 1 || im.R[ch] > 64) return set_err(LRF_EINVAL, "image %ld: rank %d out of range", (long)i, im.R[ch]);
-        if (im.u_off < 0 || im.v_off < 0 || im.rgb_off < 0) return set_err(LRF_EINVAL, "image %ld: negative offset", (long)i);
-        long u_img = 0, v_img = 0;
-        for (int ch = 0; ch < 3; ch++) {
-            u_img += (long)d.g.p[ch].M * im.R[ch];
-            v_img += 64L * im.R[ch];
-        }
-        // (every term is checked against the length before it is added to an offset: no sum can wrap)
-        if (u_img > u_len || im.u_off > u_len - u_img) return set_err(LRF_EINVAL, "image %ld: its U factors leave the buffer of %ld elements", (long)i, (long)u_len);
-        if (v_img > v_len || im.v_off > v_len - v_img) return set_err(LRF_EINVAL, "image %ld: its V factors leave the buffer of %ld elements", (long)i, (long)v_len);
-        if (rgb_len < 3 || im.H * im.W > rgb_len / 3 || im.rgb_off > rgb_len - 3 * im.H * im.W)
-            return set_err(LRF_EINVAL, "image %ld: its output leaves the buffer of %ld bytes", (long)i, (long)rgb_len);
-        const DecodePlan plan = decode_plan(d.g, im.H, im.W, im.R, ((reinterpret_cast<uintptr_t>(rgb) + (uintptr_t)im.rgb_off) & 7) == 0);
-        d.u_off = im.u_off; d.v_off = im.v_off; d.rgb_off = im.rgb_off;
-        d.H = (int)im.H; d.W = (int)im.W;
-        d.R0 = im.R[0]; d.R1 = im.R[1]; d.R2 = im.R[2];
-        d.kind = plan.kind; d.cls = plan.cls;
-        d.per_strip = (d.g.p[0].nw + 31) / 32;
-        RaggedWork& w = work[(size_t)i];
-        w.kind = plan.kind; w.cls = plan.cls;
-        if (plan.kind == DEC_TILE16) w.units = (long)(im.H / 16) * d.per_strip;
-        else if (plan.kind == DEC_STRIP) w.units = (long)((d.g.p[0].nh + 1) / 2) * d.per_strip;
-        else w.units = (long)im.H * ((im.W + 3) / 4);
-    }
+    std::vector<RaggedDesc> descs;
+    std::vector<RaggedWork> work;
+    DescribeOptions o = full_size_rgb(rgb_len);
+    o.aligned8 = false; // (k_decode16's 8-byte stores: per image, by where its output starts)
+    o.rgb_base = reinterpret_cast<uintptr_t>(rgb);
+    int rc = describe(n, images, u_len, v_len, o, "image", "output", descs, &work);
+    if (rc) return rc;
     const RaggedPlan plan = plan_decode_ragged(work);
     if (plan.too_many) return set_err(LRF_EINVAL, "%ld work items in one launch: split the list", plan.too_many);
     LRF_ON_DEVICE(c);
     // the table: descriptors, then blocks (a function of the descriptors: they alone are the key)
-    const size_t db = descs.size() * sizeof(RaggedDesc), bb = plan.blocks.size() * sizeof(RaggedBlock);
-    if (c->ragged_key.size() != db || memcmp(c->ragged_key.data(), descs.data(), db) != 0 || !c->ragged_tab.p) {
-        c->ragged_key.clear();
-        std::vector<char> tab(db + bb);
-        memcpy(tab.data(), descs.data(), db);
-        memcpy(tab.data() + db, plan.blocks.data(), bb);
-        int rc = upload(c, c->ragged_tab, tab.data(), tab.size());
-        if (rc) return rc;
-        c->ragged_key.assign((const char*)descs.data(), (const char*)descs.data() + db);
-    }
+    const size_t db = descs.size() * sizeof(RaggedDesc);
+    if ((rc = keep_resident(c, c->ragged_tab, c->ragged_key, descs.data(), db, plan.blocks.data(), plan.blocks.size() * sizeof(RaggedBlock)))) return rc;
     const RaggedDesc* d_desc = (const RaggedDesc*)c->ragged_tab.p;
     const RaggedBlock* d_blk = (const RaggedBlock*)((const char*)c->ragged_tab.p + db);
     Prof p(c, LRF_K_DECODE);
@@ -873,13 +868,7 @@ int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* 
             hipLaunchKernelGGL((k_decode_ragged_tiled<false, -1>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl);
         else if (l.kind == DEC_STRIP) {
 #define LRF_RAGGED_STRIP(CLS) hipLaunchKernelGGL((k_decode_ragged_tiled<true, CLS>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl)
-            switch (l.cls) {
-            case 0: LRF_RAGGED_STRIP(0); break;
-            case 1: LRF_RAGGED_STRIP(1); break;
-            case 2: LRF_RAGGED_STRIP(2); break;
-            case 3: LRF_RAGGED_STRIP(3); break;
-            default: LRF_RAGGED_STRIP(4); break;
-            }
+            LRF_FOR_DEC_CLASS(l.cls, LRF_RAGGED_STRIP)
 #undef LRF_RAGGED_STRIP
         } else if (l.kind == DEC_R8)
             hipLaunchKernelGGL(k_decode8_ragged, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, l.reps);
@@ -917,6 +906,11 @@ static int stage_crop_bytes(lrf_ctx* c, const void* table, size_t bytes)
     return LRF_OK;
 }
 static int stage_crop_table(lrf_ctx* c, const std::vector<CropEntry>& table) { return stage_crop_bytes(c, table.data(), table.size() * sizeof(CropEntry)); }
+// the image descriptors of the entries that decode windows (full-size, scaled, resized): one table, resident between their calls
+static int resident_crop_descs(lrf_ctx* c, const std::vector<RaggedDesc>& descs)
+{
+    return keep_resident(c, c->crop_desc, c->crop_desc_key, descs.data(), descs.size() * sizeof(RaggedDesc));
+}
 
 // n_crops windows of one size (h, w) out of a list of images that differ in size and ranks (kernels:
 // lrf_decode_crops_kernel.hip; the launches: plan_decode_crops).  Everything the kernels index with is checked here, before
@@ -928,33 +922,11 @@ int lrf_qmf_decode_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_i
     if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
     if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
     if (h < 1 || w < 1 || h > INT32_MAX || w > INT32_MAX) return set_err(LRF_EINVAL, "crop size %ldx%ld out of range", (long)h, (long)w);
-    std::vector<RaggedDesc> descs((size_t)n_images);
-    std::vector<RaggedWork> work((size_t)n_images);
-    memset((void*)descs.data(), 0, descs.size() * sizeof(RaggedDesc)); // (the bytes are the table's key: padding included)
-    for (int64_t i = 0; i < n_images; i++) {
-        const lrf_ragged_image& im = images[i];
-        RaggedDesc& d = descs[(size_t)i];
-        if (im.H < 1 || im.W < 1 || im.H > INT32_MAX || im.W > INT32_MAX) return set_err(LRF_EINVAL, "image %ld: size %ldx%ld out of range", (long)i, (long)im.H, (long)im.W);
-        int rc = make_geom(im.H, im.W, &d.g);
-        if (rc) return rc;
-        for (int ch = 0; ch < 3; ch++)
-            if (im.R[ch] < 1 || im.R[ch] > 64) return set_err(LRF_EINVAL, "image %ld: rank %d out of range", (long)i, im.R[ch]);
-        if (im.u_off < 0 || im.v_off < 0) return set_err(LRF_EINVAL, "image %ld: negative offset", (long)i);
-        long u_img = 0, v_img = 0;
-        for (int ch = 0; ch < 3; ch++) {
-            u_img += (long)d.g.p[ch].M * im.R[ch];
-            v_img += 64L * im.R[ch];
-        }
-        if (u_img > u_len || im.u_off > u_len - u_img) return set_err(LRF_EINVAL, "image %ld: its U factors leave the buffer of %ld elements", (long)i, (long)u_len);
-        if (v_img > v_len || im.v_off > v_len - v_img) return set_err(LRF_EINVAL, "image %ld: its V factors leave the buffer of %ld elements", (long)i, (long)v_len);
-        const DecodePlan plan = decode_plan(d.g, im.H, im.W, im.R, true); // (the windowed tiled body stores at any alignment)
-        d.u_off = im.u_off; d.v_off = im.v_off; // (rgb_off: 0, the output is the crops')
-        d.H = (int)im.H; d.W = (int)im.W;
-        d.R0 = im.R[0]; d.R1 = im.R[1]; d.R2 = im.R[2];
-        d.kind = plan.kind; d.cls = plan.cls;
-        d.per_strip = (d.g.p[0].nw + 31) / 32;
-        work[(size_t)i] = RaggedWork{plan.kind, plan.cls, 0};
-    }
+    std::vector<RaggedDesc> descs;
+    std::vector<RaggedWork> work;
+    // (the output is the crops', and the windowed tiled body stores at any alignment: the defaults)
+    int rc = describe(n_images, images, u_len, v_len, DescribeOptions{}, "image", "output", descs, &work);
+    if (rc) return rc;
     // (h * w <= rgb_len / 3 first: then 3 h w cannot wrap)
     if (rgb_len < 3 || h > rgb_len / 3 / w || n_crops > rgb_len / (3 * h * w))
         return set_err(LRF_EINVAL, "%ld crops of 3x%ldx%ld leave the output buffer of %ld bytes", (long)n_crops, (long)h, (long)w, (long)rgb_len);
@@ -971,30 +943,17 @@ int lrf_qmf_decode_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_i
     const CropPlan plan = plan_decode_crops(work, list, (int)h, (int)w);
     if (plan.too_many) return set_err(LRF_EINVAL, "%ld workgroups in one launch: split the list", plan.too_many);
     LRF_ON_DEVICE(c);
-    const size_t db = descs.size() * sizeof(RaggedDesc);
-    if (c->crop_desc_key.size() != db || memcmp(c->crop_desc_key.data(), descs.data(), db) != 0 || !c->crop_desc.p) {
-        c->crop_desc_key.clear();
-        int rc = upload(c, c->crop_desc, descs.data(), db);
-        if (rc) return rc;
-        c->crop_desc_key.assign((const char*)descs.data(), (const char*)descs.data() + db);
-    }
+    if ((rc = resident_crop_descs(c, descs))) return rc;
     const RaggedDesc* d_desc = (const RaggedDesc*)c->crop_desc.p;
     Prof p(c, LRF_K_DECODE);
-    int rc = stage_crop_table(c, plan.table);
-    if (rc) return rc;
+    if ((rc = stage_crop_table(c, plan.table))) return rc;
     const CropEntry* d_crop = (const CropEntry*)c->crop_tab.p;
     for (const CropLaunch& l : plan.launches) {
         const dim3 grid((unsigned)(l.ncrops * l.wgs));
         const CropEntry* ce = d_crop + l.crop0;
         if (l.kind == DEC_STRIP) {
 #define LRF_CROPS_TILED(CLS) hipLaunchKernelGGL((k_decode_crops_tiled<CLS>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs)
-            switch (l.cls) {
-            case 0: LRF_CROPS_TILED(0); break;
-            case 1: LRF_CROPS_TILED(1); break;
-            case 2: LRF_CROPS_TILED(2); break;
-            case 3: LRF_CROPS_TILED(3); break;
-            default: LRF_CROPS_TILED(4); break;
-            }
+            LRF_FOR_DEC_CLASS(l.cls, LRF_CROPS_TILED)
 #undef LRF_CROPS_TILED
         } else if (l.kind == DEC_R8)
             hipLaunchKernelGGL(k_decode8_crops, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs);
@@ -1034,7 +993,7 @@ int lrf_qmf_sweep_sse_rgb_u8(lrf_ctx* c, const uint8_t* rgb, const int8_t* U, co
         for (int ch = 0; ch < 3; ch++) { it.u_img += (long)g.p[ch].M * r[ch]; it.v_img += 64L * r[ch]; }
         it.R0 = r[0]; it.R1 = r[1]; it.R2 = r[2];
         it.q = q;
-        const DecodePlan plan = decode_plan(g, H, W, r, true);
+        const DecodePlan plan = decode_plan(g, H, W, r, true, decode_no_tiled());
         it.cls = plan.cls;
         if (plan.kind == DEC_TILE16) tiled_kind = DEC_TILE16; // (a property of the geometry: the same for every tiled triple)
         items[plan.kind <= DEC_STRIP ? 0 : plan.kind - 1].push_back(it);
@@ -1053,12 +1012,7 @@ int lrf_qmf_sweep_sse_rgb_u8(lrf_ctx* c, const uint8_t* rgb, const int8_t* U, co
         if (groups[k] * (long)items[k].size() >= (1L << 31)) return set_err(LRF_EINVAL, "%ld work items in one launch: split the sweep", groups[k] * (long)items[k].size());
         tab.insert(tab.end(), items[k].begin(), items[k].end());
     }
-    const size_t tb = tab.size() * sizeof(SseItem);
-    if (c->sse_key.size() != tb || memcmp(c->sse_key.data(), tab.data(), tb) != 0 || !c->sse_tab.p) {
-        c->sse_key.clear();
-        if ((rc = upload(c, c->sse_tab, tab.data(), tb))) return rc;
-        c->sse_key.assign((const char*)tab.data(), (const char*)tab.data() + tb);
-    }
+    if ((rc = keep_resident(c, c->sse_tab, c->sse_key, tab.data(), tab.size() * sizeof(SseItem)))) return rc;
     const SseItem* d_tab = (const SseItem*)c->sse_tab.p;
     unsigned long long* d_sse = reinterpret_cast<unsigned long long*>(sse);
     Prof p(c, LRF_K_METRICS); // the scoring stage: timed with lrf_image_metrics_u8
@@ -1075,13 +1029,7 @@ int lrf_qmf_sweep_sse_rgb_u8(lrf_ctx* c, const uint8_t* rgb, const int8_t* U, co
             const int nq = (int)(i1 - i0);
             const dim3 grid((unsigned)(tiles * nq), (unsigned)B);
 #define LRF_SSE_STRIP(CLS) hipLaunchKernelGGL((k_sse_tiled<true, CLS>), grid, dim3(256), 0, c->stream, rgb, U, V, (int)H, (int)W, g, d_tab + i0, nq, per_strip, (int)B, d_sse)
-            switch (items[0][i0].cls) {
-            case 0: LRF_SSE_STRIP(0); break;
-            case 1: LRF_SSE_STRIP(1); break;
-            case 2: LRF_SSE_STRIP(2); break;
-            case 3: LRF_SSE_STRIP(3); break;
-            default: LRF_SSE_STRIP(4); break;
-            }
+            LRF_FOR_DEC_CLASS(items[0][i0].cls, LRF_SSE_STRIP)
 #undef LRF_SSE_STRIP
             LAUNCH_CHECK();
             i0 = i1;
@@ -1111,41 +1059,11 @@ int lrf_qmf_sse_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* ite
 {
     if (!c || !items || !U || !V || !rgb || !sse) return set_err(LRF_EINVAL, "NULL argument");
     if (n < 1 || n > 65535) return set_err(LRF_EINVAL, "n=%ld out of range [1,65535]", (long)n);
-    std::vector<RaggedDesc> descs((size_t)n);
-    std::vector<RaggedWork> work((size_t)n);
-    memset((void*)descs.data(), 0, descs.size() * sizeof(RaggedDesc));
-    for (int64_t i = 0; i < n; i++) {
-        const lrf_ragged_image& im = items[i];
-        RaggedDesc& d = descs[(size_t)i];
-        if (im.H < 1 || im.W < 1 || im.H > INT32_MAX || im.W > INT32_MAX) return set_err(LRF_EINVAL, "item %ld: size %ldx%ld out of range", (long)i, (long)im.H, (long)im.W);
-        int rc = make_geom(im.H, im.W, &d.g);
-        if (rc) return rc;
-        for (int ch = 0; ch < 3; ch++)
-            if (im.R[ch] < 1 || im.R[ch] > 64) return set_err(LRF_EINVAL, "item %ld: rank %d out of range", (long)i, im.R[ch]);
-        if (im.u_off < 0 || im.v_off < 0 || im.rgb_off < 0) return set_err(LRF_EINVAL, "item %ld: negative offset", (long)i);
-        long u_img = 0, v_img = 0;
-        for (int ch = 0; ch < 3; ch++) {
-            u_img += (long)d.g.p[ch].M * im.R[ch];
-            v_img += 64L * im.R[ch];
-        }
-        // (every term is checked against the length before it is added to an offset: no sum can wrap)
-        if (u_img > u_len || im.u_off > u_len - u_img) return set_err(LRF_EINVAL, "item %ld: its U factors leave the buffer of %ld elements", (long)i, (long)u_len);
-        if (v_img > v_len || im.v_off > v_len - v_img) return set_err(LRF_EINVAL, "item %ld: its V factors leave the buffer of %ld elements", (long)i, (long)v_len);
-        if (rgb_len < 3 || im.H * im.W > rgb_len / 3 || im.rgb_off > rgb_len - 3 * im.H * im.W)
-            return set_err(LRF_EINVAL, "item %ld: its source leaves the buffer of %ld bytes", (long)i, (long)rgb_len);
-        // (the sink's loads need no alignment: a 16-aligned item keeps the 16-aligned body wherever its source starts)
-        const DecodePlan plan = decode_plan(d.g, im.H, im.W, im.R, true);
-        d.u_off = im.u_off; d.v_off = im.v_off; d.rgb_off = im.rgb_off;
-        d.H = (int)im.H; d.W = (int)im.W;
-        d.R0 = im.R[0]; d.R1 = im.R[1]; d.R2 = im.R[2];
-        d.kind = plan.kind; d.cls = plan.cls;
-        d.per_strip = (d.g.p[0].nw + 31) / 32;
-        RaggedWork& w = work[(size_t)i];
-        w.kind = plan.kind; w.cls = plan.cls;
-        if (plan.kind == DEC_TILE16) w.units = (long)(im.H / 16) * d.per_strip;
-        else if (plan.kind == DEC_STRIP) w.units = (long)((d.g.p[0].nh + 1) / 2) * d.per_strip;
-        else w.units = (long)im.H * ((im.W + 3) / 4);
-    }
+    std::vector<RaggedDesc> descs;
+    std::vector<RaggedWork> work;
+    // (the sink's loads need no alignment: a 16-aligned item keeps the 16-aligned body wherever its source starts)
+    int rc = describe(n, items, u_len, v_len, full_size_rgb(rgb_len), "item", "source", descs, &work);
+    if (rc) return rc;
     const RaggedPlan plan = plan_decode_ragged(work);
     if (plan.too_many) return set_err(LRF_EINVAL, "%ld work items in one launch: split the list", plan.too_many);
     LRF_ON_DEVICE(c);
@@ -1154,8 +1072,7 @@ int lrf_qmf_sse_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* ite
     memcpy(tab.data(), descs.data(), db);
     memcpy(tab.data() + db, plan.blocks.data(), bb);
     Prof p(c, LRF_K_DECODE);
-    int rc = stage_crop_bytes(c, tab.data(), tab.size());
-    if (rc) return rc;
+    if ((rc = stage_crop_bytes(c, tab.data(), tab.size()))) return rc;
     const RaggedDesc* d_desc = (const RaggedDesc*)c->crop_tab.p;
     const RaggedBlock* d_blk = (const RaggedBlock*)((const char*)c->crop_tab.p + db);
     unsigned long long* d_sse = reinterpret_cast<unsigned long long*>(sse);
@@ -1167,13 +1084,7 @@ int lrf_qmf_sse_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* ite
             hipLaunchKernelGGL((k_sse_ragged_tiled<false, -1>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, d_sse);
         else if (l.kind == DEC_STRIP) {
 #define LRF_SSE_RAGGED_STRIP(CLS) hipLaunchKernelGGL((k_sse_ragged_tiled<true, CLS>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, d_sse)
-            switch (l.cls) {
-            case 0: LRF_SSE_RAGGED_STRIP(0); break;
-            case 1: LRF_SSE_RAGGED_STRIP(1); break;
-            case 2: LRF_SSE_RAGGED_STRIP(2); break;
-            case 3: LRF_SSE_RAGGED_STRIP(3); break;
-            default: LRF_SSE_RAGGED_STRIP(4); break;
-            }
+            LRF_FOR_DEC_CLASS(l.cls, LRF_SSE_RAGGED_STRIP)
 #undef LRF_SSE_RAGGED_STRIP
         } else if (l.kind == DEC_R8)
             hipLaunchKernelGGL(k_sse8_ragged, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, l.reps, d_sse);

@@ -281,6 +281,70 @@ long plan_any_init_chunk(int n, int Rc, long B)
     return chunk > B ? B : chunk;
 }
 
+// ---- which decode body serves an image, and the image list of a decode or SSE entry ------------------------------------------
+DecodePlan decode_plan(const ImageGeom& g, int64_t H, int64_t W, const int R[3], bool aligned8, bool no_tiled)
+{
+    // the tiled kernels (k_decode16: sides multiples of 16; k_decode_strip: any height, four-aligned chroma columns) are
+    // instantiated for the rank bounds (chroma, luma) = (4,8) (8,8) (8,16) (16,16) (16,32): the reference's quality sweep up to 40
+    const int rcm = R[1] > R[2] ? R[1] : R[2];
+    const int RCb = rcm <= 4 ? 4 : (rcm <= 8 ? 8 : 16), RLb = R[0] <= 8 ? 8 : (R[0] <= 16 ? 16 : 32);
+    const bool tiled_ranks = R[0] <= 32 && rcm <= 16 && !no_tiled;
+    const bool sides16 = H % 16 == 0 && W % 16 == 0 && aligned8;
+    const bool strip_ok = W % 2 == 0 && g.p[0].left_crop % 2 == 0 && (g.p[1].left_crop - g.p[0].left_crop / 2) % 4 == 0 && g.p[1].w == W / 2;
+    if (tiled_ranks && (sides16 || strip_ok)) {
+        int cls;
+        if (RLb == 8 && RCb == 4) cls = 0;
+        else if (RLb == 8 && RCb == 8) cls = 1;
+        else if (RLb == 16 && RCb <= 8) cls = 2;
+        else if (RLb <= 16) cls = 3;
+        else cls = 4;
+        return DecodePlan{sides16 ? DEC_TILE16 : DEC_STRIP, cls};
+    }
+    return DecodePlan{(R[0] <= 8 && R[1] <= 8 && R[2] <= 8) ? DEC_R8 : DEC_ANY, 0};
+}
+
+DescribeRefusal describe_images(int64_t n, const lrf_ragged_image* images, int64_t u_len, int64_t v_len, const DescribeOptions& o,
+                                std::vector<RaggedDesc>& descs, std::vector<RaggedWork>* work)
+{
+    descs.resize((size_t)n);
+    memset((void*)descs.data(), 0, descs.size() * sizeof(RaggedDesc)); // (the bytes are the table's key: padding included)
+    if (work) work->resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_ragged_image& im = images[i];
+        RaggedDesc& d = descs[(size_t)i];
+        if (im.H < 1 || im.W < 1 || im.H > INT32_MAX || im.W > INT32_MAX) return DescribeRefusal{DESC_SIZE, i, im.H, im.W};
+        int64_t bh, bw;
+        if (geom_of(im.H, im.W, &d.g, &bh, &bw)) return DescribeRefusal{DESC_GEOM, i, im.H, im.W};
+        for (int ch = 0; ch < 3; ch++)
+            if (im.R[ch] < 1 || im.R[ch] > 64) return DescribeRefusal{DESC_RANK, i, im.R[ch], 0};
+        if (im.u_off < 0 || im.v_off < 0 || (o.check_rgb && im.rgb_off < 0)) return DescribeRefusal{DESC_NEGATIVE, i, 0, 0};
+        long u_img = 0, v_img = 0;
+        for (int ch = 0; ch < 3; ch++) {
+            u_img += (long)d.g.p[ch].M * im.R[ch];
+            v_img += 64L * im.R[ch];
+        }
+        if (u_img > u_len || im.u_off > u_len - u_img) return DescribeRefusal{DESC_U, i, u_len, 0};
+        if (v_img > v_len || im.v_off > v_len - v_img) return DescribeRefusal{DESC_V, i, v_len, 0};
+        if (o.check_rgb && (o.rgb_len < 3 || im.H * im.W > o.rgb_len / 3 || im.rgb_off > o.rgb_len - 3 * im.H * im.W))
+            return DescribeRefusal{DESC_RGB, i, o.rgb_len, 0};
+        const bool aligned8 = o.aligned8 || ((o.rgb_base + (uintptr_t)im.rgb_off) & 7) == 0;
+        const DecodePlan plan = decode_plan(d.g, im.H, im.W, im.R, aligned8, o.no_tiled);
+        d.u_off = im.u_off; d.v_off = im.v_off;
+        if (o.check_rgb) d.rgb_off = im.rgb_off;
+        d.H = (int)im.H; d.W = (int)im.W;
+        d.R0 = im.R[0]; d.R1 = im.R[1]; d.R2 = im.R[2];
+        d.kind = plan.kind; d.cls = plan.cls;
+        d.per_strip = (d.g.p[0].nw + 31) / 32;
+        if (!work) continue;
+        RaggedWork& w = (*work)[(size_t)i];
+        w.kind = plan.kind; w.cls = plan.cls;
+        if (plan.kind == DEC_TILE16) w.units = (long)(im.H / 16) * d.per_strip;
+        else if (plan.kind == DEC_STRIP) w.units = (long)((d.g.p[0].nh + 1) / 2) * d.per_strip;
+        else w.units = (long)im.H * ((im.W + 3) / 4);
+    }
+    return DescribeRefusal{};
+}
+
 // ---- the launches of a ragged decode -----------------------------------------------------------------------------------------
 // All DEC_TILE16 images share one launch (the 16-aligned body under a class switch keeps the registers of its largest class);
 // the strip body does not (204 registers under a switch), so DEC_STRIP images take one launch per class present; DEC_R8 and

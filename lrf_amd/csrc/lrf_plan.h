@@ -10,6 +10,7 @@
 
 #include <vector>
 
+#include "../../include/lrf_hip.h"
 #include "lrf_internal.h"
 
 // largest rank of the 64-column BCD kernels (k_bcd_w <= 8, k_bcd <= 16, k_bcd_mid <= 32); above it the any-shape kernels iterate
@@ -122,8 +123,16 @@ struct XResidency {
 XResidency plan_x_residency(const BcdPlan& p, Tables& t, int nluma, bool luma_from_bytes, bool piped, const PlanSettings& s);
 
 // ---- decode: which body serves an image, and the launches of a ragged call (lrf_qmf_decode_ragged_rgb_u8) ------------------
-enum { DEC_TILE16 = 0, DEC_STRIP = 1, DEC_R8 = 2, DEC_ANY = 3 }; // decode_plan (lrf_encode8.hip) decides
+enum { DEC_TILE16 = 0, DEC_STRIP = 1, DEC_R8 = 2, DEC_ANY = 3 }; // decode_plan decides
 #define LRF_DEC_CLASSES 5 // rank-bound classes of the tiled bodies
+// which decode body serves a geometry and a rank triple: every decode and SSE entry of lrf_encode8.hip rests on it
+struct DecodePlan {
+    int kind;
+    int cls; // tiled kinds: index of the rank bounds (chroma, luma) = (4,8) (8,8) (8,16) (16,16) (16,32)
+};
+// aligned8: the image's output bytes start at a multiple of 8 (DEC_TILE16 stores 8 bytes at a time; entries that only read the
+// bytes, or store through windows, pass true).  no_tiled: the developer switch LRF_DECODE_NO_TILED
+DecodePlan decode_plan(const ImageGeom& g, int64_t H, int64_t W, const int R[3], bool aligned8, bool no_tiled = false);
 // groups of four pixels per thread of k_decode8 / k_sse8 for a launch of `groups256` groups of 256 pixel quads: as many as leave
 // it ~2048 workgroups (small launches keep one group per thread)
 inline long decode8_reps_of(long groups256)
@@ -149,6 +158,31 @@ struct RaggedPlan {
     long too_many = 0;                  // != 0: a launch would have this many (>= 2^31) workgroups; no table is built
 };
 RaggedPlan plan_decode_ragged(const std::vector<RaggedWork>& images);
+
+// ---- the image list of a decode or SSE entry: checked, and described as the kernels read it -----------------------------------
+// Everything the kernels index the factors with comes from RaggedDesc alone, so this is the one place between a caller's numbers
+// and an out-of-bounds read.  Checks per image, in this order: the size, the geometry (geom_of), the ranks 1..64, negative
+// offsets, the U and the V extent against u_len / v_len (every term is checked against the length before it is added to an
+// offset: no sum can wrap), and — check_rgb — rgb_off and the image's [3][H][W] against rgb_len.
+enum { DESC_OK = 0, DESC_SIZE, DESC_GEOM, DESC_RANK, DESC_NEGATIVE, DESC_U, DESC_V, DESC_RGB };
+struct DescribeOptions {
+    bool check_rgb = false;   // the entry reads or writes full-size images at rgb_off: checked, and copied into the descriptor
+    int64_t rgb_len = 0;
+    bool aligned8 = true;     // every image counts as 8-byte aligned; false: image i is when (rgb_base + rgb_off) % 8 == 0
+    uintptr_t rgb_base = 0;
+    bool no_tiled = false;    // LRF_DECODE_NO_TILED (decode_plan)
+};
+// the first offender: which check, which image, and what its message needs (DESC_SIZE, DESC_GEOM: H, W; DESC_RANK: the rank;
+// DESC_U, DESC_V, DESC_RGB: the buffer's length)
+struct DescribeRefusal {
+    int check = DESC_OK;
+    int64_t image = 0, a = 0, b = 0;
+};
+// descs: n descriptors, zeroed first (their bytes are the device table's key: padding included); rgb_off stays 0 without
+// check_rgb.  work: if given, (kind, cls, units) per image for plan_decode_ragged / plan_decode_crops.  On a refusal both are
+// left unspecified.
+DescribeRefusal describe_images(int64_t n, const lrf_ragged_image* images, int64_t u_len, int64_t v_len, const DescribeOptions& o,
+                                std::vector<RaggedDesc>& descs, std::vector<RaggedWork>* work = nullptr);
 
 // ---- decode of windows: the launches of lrf_qmf_decode_crops_rgb_u8 and which pixels a thread answers for --------------------
 // The windows of a call share one size (h, w), so a launch's grid is uniform: (workgroups per window) x (its windows), the
@@ -304,6 +338,7 @@ LRF_HD inline CropSpan scaled_pixel_of(int y0, int x0, int h, int w, long wg, in
 // One image as the entry points classified it: tiled = both sides multiples of 16 and ranks inside the tiled decoders' bounds
 // (decode_plan's DEC_TILE16), cls its rank-bound class there; R: its ranks (they size its pooled tables)
 struct ScaledImage { int tiled, cls, R[3]; };
+inline ScaledImage scaled_image_of(const RaggedDesc& d) { return ScaledImage{d.kind == DEC_TILE16, d.cls, {d.R0, d.R1, d.R2}}; }
 // int16 elements of the pooled tables of one image at scale f: luma [R_Y][(8/f)^2], then Cb and Cr [R_c][(16/f)^2]
 inline long scaled_pool_elems(const int R[3], int f) { return (long)R[0] * (8 / f) * (8 / f) + (long)(R[1] + R[2]) * (16 / f) * (16 / f); }
 // One launch: items item0 .. item0 + nitems - 1 of the sorted table, wgs workgroups each (grid.x = nitems * wgs; wgs: the most

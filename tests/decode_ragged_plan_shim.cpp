@@ -27,3 +27,15 @@ extern "C" int lrf_test_plan_decode_ragged(int n, const int* kind, const int* cl
     }
     return (int)p.launches.size();
 }
+
+// decode_plan of an H x W image at ranks (r0, r1, r2): kind * 8 + cls, or -(what geom_of answers) when it refuses the size
+extern "C" int lrf_test_decode_plan(long H, long W, int r0, int r1, int r2, int aligned8, int no_tiled)
+{
+    ImageGeom g;
+    int64_t bh, bw;
+    const int bad = geom_of(H, W, &g, &bh, &bw);
+    if (bad) return -bad;
+    const int R[3] = {r0, r1, r2};
+    const DecodePlan p = decode_plan(g, H, W, R, aligned8 != 0, no_tiled != 0);
+    return p.kind * 8 + p.cls;
+}

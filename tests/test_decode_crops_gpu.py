@@ -240,3 +240,45 @@ def test_at_the_loaders_shape(n, ranks):
     whole = ctx.decode_rgb(U, V, H, W, list(ranks))
     want = torch.stack([whole[b, :, y:y + h, x:x + w] for b, y, x in boxes])
     assert torch.equal(got, want)
+
+
+def test_the_entries_that_share_the_resident_descriptor_table_take_turns():
+    """decode_crops, decode_scaled_crops, decode_resized_crops and decode_scaled keep their image descriptors in one device table
+    that stays resident under its bytes, decode_ragged in one of its own: two lists that differ in ranks alone, the entries in
+    turn on one context with nothing waited for in between (a new list's upload must not overtake the kernels still reading the
+    old one), a trim in the middle — every result byte-equal to the same call made alone on a fresh context"""
+    from lrf_amd import _lib
+    rng = np.random.default_rng(77)
+    lists = {}
+    for name, ranks in (("A", (7, 3, 3)), ("B", (26, 13, 13))):
+        items = [(24, 48, ranks), (45, 61, ranks)]
+        fac = [_random_factors(rng, *it) for it in items]
+        lists[name] = _table(items, [f[0] for f in fac], [f[1] for f in fac])
+    windows = [(0, 0, 0), (1, 36, 48), (0, 15, 35), (1, 7, 3)]
+    scaled = [(0, 2, 0, 0), (1, 2, 18, 26), (1, 4, 8, 12), (0, 4, 1, 7), (1, 8, 2, 4)]
+    boxes = [(0, 0, 0, 24, 48, 0), (1, 3, 5, 40, 50, 1), (1, 20, 20, 9, 9, 0), (0, 4, 8, 16, 32, 1)]
+    calls = [
+        lambda c: c.decode_crops(*lists["A"], windows, (9, 13)),
+        lambda c: c.decode_scaled_crops(*lists["A"], scaled, (4, 4)),
+        lambda c: c.decode_resized_crops(*lists["B"], boxes, (8, 8)),
+        lambda c: c.decode_crops(*lists["B"], windows, (9, 13)),
+        lambda c: c.decode_crops(*lists["A"], windows, (9, 13)),
+        lambda c: (c.trim(), None)[1],
+        lambda c: c.decode_scaled(*lists["A"], 2),
+        lambda c: c.decode_ragged(*lists["B"]),
+    ]
+    flat = lambda r: [] if r is None else [t.cpu() for t in (r if isinstance(r, list) else [r])]
+    ctx = _lib.Context(0)
+    try:
+        got = [call(ctx) for call in calls]  # (no synchronisation between the calls: the results are read after the last)
+        got = [flat(r) for r in got]
+    finally:
+        ctx.close()
+    for k, call in enumerate(calls):
+        fresh = _lib.Context(0)
+        try:
+            want = flat(call(fresh))
+        finally:
+            fresh.close()
+        assert len(got[k]) == len(want) and all(torch.equal(a, b) for a, b in zip(got[k], want)), f"call {k}"
+    assert sum(len(g) for g in got) == 5 + 2 + 2  # five [n, 3, h, w] tensors, two scaled images, two whole images

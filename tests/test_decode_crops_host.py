@@ -136,3 +136,36 @@ def test_streams_of_other_branches_raise_naming_the_branch(no_gpu):
             qmf_decode_crops([good, Case(name).encoded], [(0, 0, 0)], (4, 4))
         with pytest.raises(NotImplementedError, match=word):
             qmf_load_factors([Case(name).encoded, good])
+
+
+class OnDevice:
+    """stands for a CUDA tensor of boxes: the refusal must come before its values are asked for"""
+    is_cuda = True
+
+    def detach(self):
+        raise AssertionError("the boxes were read")
+
+
+# one bad input per check of check_crop_args, in the order of the checks, with the text it raises
+MESSAGES = [
+    ([(0, 0, 0)], 9, ValueError, 'size must be (h, w), got 9'),
+    ([(0, 0, 0)], (9.0, 13), TypeError, 'size must hold two integers, got (9.0, 13)'),
+    ([(0, 0, 0)], (0, 13), ValueError, 'crop size 0x13: both sides must be >= 1'),
+    (OnDevice(), (9, 13), ValueError, 'crops live on the host: the call validates every box before it launches'),
+    ([], (9, 13), ValueError, 'decode_crops needs 1 to 2^20 crops'),
+    ([(0.0, 0.0, 0.0)], (9, 13), TypeError, 'crops must be integers (image, y0, x0), got float64'),
+    ([(0, 0)], (9, 13), ValueError, 'crops must be [n, 3] (image, y0, x0), got shape (1, 2)'),
+    (np.zeros((2 ** 20 + 1, 3), dtype=np.int8), (9, 13), ValueError, 'decode_crops needs 1 to 2^20 crops'),
+    ([(0, 0, 0), (2, 0, 0)], (9, 13), ValueError, 'crop 1: image 2 out of range [0, 2)'),
+    ([(0, 0, 0), (1, 37, 0)], (9, 13), ValueError, 'crop 1: 9x13 at (37, 0) leaves image 1 of 45x61'),
+]
+
+
+@pytest.mark.parametrize("case", range(len(MESSAGES)))
+def test_check_crop_args_messages(case):
+    from lrf_amd._lib import check_crop_args
+    crops, size, kind, text = MESSAGES[case]
+    U, V, images = _two_images()
+    with pytest.raises(kind) as e:
+        check_crop_args(U, V, images, crops, size)
+    assert type(e.value) is kind and str(e.value) == text

@@ -24,7 +24,8 @@ TILE16, STRIP, R8, ANY = "tile16", "strip", "r8", "any"
 
 
 def group_of(H, W, ranks):
-    """the launch group of an image whose output is 8-byte aligned: the rule of decode_plan's comment for the sizes above (among
+    """the launch group of an image whose output is 8-byte aligned: the rule of decode_plan's comment (lrf_amd/csrc/lrf_plan.cpp;
+    tests/test_decode_ragged_plan.py compares the whole rule with the library on the CPU) for the sizes above (among
     them only the odd-width 45x61 and 173x264, whose chroma padding is not four-aligned, fall outside the tiled bodies)"""
     if (H, W) in ((45, 61), (173, 264)) or ranks[0] > 32 or max(ranks[1:]) > 16:
         return R8 if max(ranks) <= 8 else ANY

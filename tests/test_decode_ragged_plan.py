@@ -1,9 +1,10 @@
 """CPU suite: the launches of a ragged decode (plan_decode_ragged, lrf_amd/csrc/lrf_plan.cpp).  The plan source needs no device:
 it is built here with g++ together with tests/decode_ragged_plan_shim.cpp and called through ctypes.
 
-An image enters the planner as (kind, class, units), the way lrf_qmf_decode_ragged_rgb_u8 hands it over after decode_plan has
-classified it.  Here the classification is done by `classify` below, written from the rule in decode_plan's comment and the
-geometry of lrf/compression/qmf.py:230-242 — never by the library — and the expected groups follow from it:
+An image enters the planner as (kind, class, units), the way describe_images hands it over after decode_plan (both in
+lrf_plan.cpp) has classified it.  Here the classification is done by `classify` below, written from the rule in decode_plan's
+comment and the geometry of lrf/compression/qmf.py:230-242 — independently of the library, and compared with the library's
+decode_plan over a grid (test_classify_is_the_librarys_decode_plan) — and the expected groups follow from it:
   * every 16-aligned image within ranks (32,16,16) (DEC_TILE16), whatever its class      -> one launch
   * the other images the tiled body covers (DEC_STRIP)                                    -> one launch per class present
   * ranks <= 8 elsewhere (DEC_R8), everything else (DEC_ANY)                              -> one launch each
@@ -27,15 +28,16 @@ def lib(tmp_path_factory):
     return ctypes.CDLL(so)
 
 
-def classify(H, W, ranks, aligned8=True):
+def classify(H, W, ranks, aligned8=True, no_tiled=False):
     """(kind, cls, units) of an image: the rule of decode_plan's comment.  Planes: luma H x W, chroma floor(H/2) x floor(W/2),
-    reflect-padded to multiples of 8 with the smaller half of the padding on the left / top."""
+    reflect-padded to multiples of 8 with the smaller half of the padding on the left / top.  no_tiled: the developer switch
+    LRF_DECODE_NO_TILED (no image takes a tiled body)."""
     w = [W, W // 2]
     wp = [-(-x // 8) * 8 for x in w]
     left = [(p - x) // 2 for p, x in zip(wp, w)]
     nw, nh = wp[0] // 8, -(-H // 8)
     rcm = max(ranks[1], ranks[2])
-    tiled_ranks = ranks[0] <= 32 and rcm <= 16
+    tiled_ranks = ranks[0] <= 32 and rcm <= 16 and not no_tiled
     sides16 = H % 16 == 0 and W % 16 == 0 and aligned8
     strip_ok = W % 2 == 0 and left[0] % 2 == 0 and (left[1] - left[0] // 2) % 4 == 0
     per_strip = (nw + 31) // 32
@@ -110,6 +112,28 @@ def test_classes_are_what_the_triples_are_meant_to_hit():
     assert classify(173, 264, (12, 6, 6))[0] == ANY
     for r in ((33, 4, 4), (5, 17, 2), (64, 64, 64)):
         assert classify(64, 96, r)[0] == ANY and classify(40, 272, r)[0] == ANY
+
+
+GRID_SIDES = list(range(8, 41)) + [45, 61, 64, 96, 173, 264, 272]
+GRID_RANKS = [(1, 1, 1), (8, 4, 4), (8, 5, 4), (8, 8, 8), (9, 8, 8), (16, 8, 8), (16, 9, 8), (8, 16, 16), (17, 16, 16), (32, 16, 16), (33, 16, 16),
+              (32, 17, 1), (64, 64, 64)]
+
+
+def test_classify_is_the_librarys_decode_plan(lib):
+    """the rule restated above against decode_plan itself, at every point of the grid: every side is at least 8, which geom_of
+    accepts for both planes (asserted: the library answers a plan, never a refusal), so the restated rule covers all of it"""
+    points = 0
+    for no_tiled in (False, True):
+        for H in GRID_SIDES:
+            for W in GRID_SIDES:
+                for r in GRID_RANKS:
+                    for aligned8 in (True, False):
+                        got = lib.lrf_test_decode_plan(H, W, r[0], r[1], r[2], aligned8, no_tiled)
+                        assert got >= 0, (H, W, got)
+                        assert divmod(got, 8) == classify(H, W, r, aligned8, no_tiled)[:2], (H, W, r, aligned8, no_tiled)
+                        points += 1
+    assert points == 2 * len(GRID_SIDES) ** 2 * len(GRID_RANKS) * 2
+    assert not any(classify(H, 64, r, True, True)[0] in (TILE16, STRIP) for H in GRID_SIDES for r in GRID_RANKS)
 
 
 def test_aligned_images_of_all_five_classes_share_one_launch(lib):

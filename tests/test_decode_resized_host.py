@@ -187,3 +187,37 @@ def test_streams_of_other_branches_raise_naming_the_branch(no_gpu):
     for name, word in (("rgbsp_odd_q6", "RGB"), ("any_p16_q10", "patch size"), ("any_nopatch_q10", "patch=False")):
         with pytest.raises(NotImplementedError, match=word):
             qmf_decode_resized_crops([good, Case(name).encoded], [(0, 0, 0, 5, 5)], (5, 7))
+
+
+class OnDevice:
+    """stands for a CUDA tensor of boxes: the refusal must come before its values are asked for"""
+    is_cuda = True
+
+    def detach(self):
+        raise AssertionError("the boxes were read")
+
+
+# one bad input per check of check_resized_args, in the order of the checks, with the text it raises
+MESSAGES = [
+    ([(0, 0, 0, 8, 8, 0)], 9, ValueError, 'size must be (oh, ow), got 9'),
+    ([(0, 0, 0, 8, 8, 0)], (9, True), TypeError, 'size must hold two integers, got (9, True)'),
+    ([(0, 0, 0, 8, 8, 0)], (9, 16385), ValueError, 'output size 9x16385: both sides must be in [1, 16384]'),
+    (OnDevice(), (9, 13), ValueError, 'crops live on the host: the call validates every box before it launches'),
+    ([], (9, 13), ValueError, 'decode_resized_crops needs 1 to 2^20 crops'),
+    (np.zeros((1, 6), dtype=np.float32), (9, 13), TypeError, 'crops must be integers (image, y0, x0, h, w, flip), got float32'),
+    ([(0, 0, 0, 8, 8)], (9, 13), ValueError, 'crops must be [n, 6] (image, y0, x0, h, w, flip), got shape (1, 5)'),
+    (np.zeros((2 ** 20 + 1, 6), dtype=np.int8), (9, 13), ValueError, 'decode_resized_crops needs 1 to 2^20 crops'),
+    ([(0, 0, 0, 8, 8, 0), (2, 0, 0, 8, 8, 1)], (9, 13), ValueError, 'crop 1: image 2 out of range [0, 2)'),
+    ([(0, 0, 0, 8, 8, 0), (1, 0, 0, 0, 8, 1)], (9, 13), ValueError, 'crop 1: box of 0x8: both sides must be >= 1'),
+    ([(0, 0, 0, 8, 8, 0), (1, 40, 0, 6, 8, 1)], (9, 13), ValueError, 'crop 1: 6x8 at (40, 0) leaves image 1 of 32x48'),
+]
+
+
+@pytest.mark.parametrize("case", range(len(MESSAGES)))
+def test_check_resized_args_messages(case):
+    from lrf_amd._lib import check_resized_args
+    crops, size, kind, text = MESSAGES[case]
+    U, V, images = _two_images()
+    with pytest.raises(kind) as e:
+        check_resized_args(U, V, images, crops, size)
+    assert type(e.value) is kind and str(e.value) == text

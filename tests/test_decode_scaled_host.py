@@ -243,3 +243,40 @@ def test_streams_of_other_branches_raise_naming_the_branch(no_gpu):
     for name, word in (("rgbsp_odd_q6", "RGB"), ("any_p16_q10", "patch size"), ("any_nopatch_q10", "patch=False")):
         with pytest.raises(NotImplementedError, match=word):
             qmf_decode_scaled([good, Case(name).encoded], 2)
+
+
+class OnDevice:
+    """stands for a CUDA tensor of boxes: the refusal must come before its values are asked for"""
+    is_cuda = True
+
+    def detach(self):
+        raise AssertionError("the boxes were read")
+
+
+# one bad input per check of check_scaled_args, in the order of the checks, with the text it raises
+MESSAGES = [
+    (dict(scale=2.0), TypeError, 'scale must be an integer, got 2.0'),
+    (dict(scale=3), ValueError, 'scale 3: 2, 4 or 8 expected'),
+    (dict(scale=2, crops=[(0, 2, 0, 0)], size=(4, 4)), ValueError, 'give either a scale (whole images) or crops of (image, scale, y0, x0) and a size'),
+    (dict(crops=[(0, 2, 0, 0)], size=4), ValueError, 'size must be (h, w), got 4'),
+    (dict(crops=[(0, 2, 0, 0)], size=(4.0, 4)), TypeError, 'size must hold two integers, got (4.0, 4)'),
+    (dict(crops=[(0, 2, 0, 0)], size=(4, 0)), ValueError, 'crop size 4x0: both sides must be >= 1'),
+    (dict(crops=OnDevice(), size=(4, 4)), ValueError, 'crops live on the host: the call validates every box before it launches'),
+    (dict(crops=[], size=(4, 4)), ValueError, 'decode_scaled_crops needs 1 to 2^20 crops'),
+    (dict(crops=[(0.0, 2.0, 0.0, 0.0)], size=(4, 4)), TypeError, 'crops must be integers (image, scale, y0, x0), got float64'),
+    (dict(crops=[(0, 0, 0)], size=(4, 4)), ValueError, 'crops must be [n, 4] (image, scale, y0, x0), got shape (1, 3)'),
+    (dict(crops=np.zeros((2 ** 20 + 1, 4), dtype=np.int8), size=(4, 4)), ValueError, 'decode_scaled_crops needs 1 to 2^20 crops'),
+    (dict(crops=[(0, 2, 0, 0), (-1, 2, 0, 0)], size=(4, 4)), ValueError, 'crop 1: image -1 out of range [0, 2)'),
+    (dict(crops=[(0, 2, 0, 0), (1, 3, 0, 0)], size=(4, 4)), ValueError, 'crop 1: scale 3: 2, 4 or 8 expected'),
+    (dict(crops=[(0, 2, 0, 0), (1, 4, 9, 0)], size=(4, 4)), ValueError, 'crop 1: 4x4 at (9, 0) leaves image 1 of 12x16 at scale 1/4'),
+]
+
+
+@pytest.mark.parametrize("case", range(len(MESSAGES)))
+def test_check_scaled_args_messages(case):
+    from lrf_amd._lib import check_scaled_args
+    kw, kind, text = MESSAGES[case]
+    U, V, images = _two_images()
+    with pytest.raises(kind) as e:
+        check_scaled_args(U, V, images, **kw)
+    assert type(e.value) is kind and str(e.value) == text

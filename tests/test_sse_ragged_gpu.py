@@ -18,8 +18,8 @@ ITEMS = ([(64, 64, t) for t in ((8, 4, 4), (8, 8, 8), (16, 8, 8), (16, 16, 16), 
 
 
 def classify(H, W, ranks):
-    """(kind, cls) of an item: the rule of decode_plan's comment (lrf_amd/csrc/lrf_encode8.hip), restated as in
-    tests/test_decode_ragged_plan.py.  The scorer only loads its source, so a 16-aligned item keeps the 16-aligned body wherever
+    """(kind, cls) of an item: the rule of decode_plan's comment (lrf_amd/csrc/lrf_plan.cpp), restated as in
+    tests/test_decode_ragged_plan.py, which compares its restatement with the library's function on the CPU.  The scorer only loads its source, so a 16-aligned item keeps the 16-aligned body wherever
     the source starts.  Planes: luma H x W, chroma floor(H/2) x floor(W/2), reflect-padded to multiples of 8 with the smaller
     half of the padding on the left / top."""
     w = [W, W // 2]
