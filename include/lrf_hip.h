@@ -373,6 +373,46 @@ int lrf_qmf_decode_resized_crops_rgb_u8(lrf_ctx* ctx, int64_t n_images, const lr
                                         int64_t oh, int64_t ow, uint8_t* rgb /* [n_crops][3][oh][ow] */, int64_t rgb_len);
 
 /*
+ * Model-ready crops: the three entries above with the to-tensor and normalise steps of a training loader in their epilogue, so
+ * that no uint8 batch is written and read back.  A tensor format is (dtype, layout, scale[3], bias[3]):
+ *   dtype    LRF_T_F32, LRF_T_F16 (IEEE binary16) or LRF_T_BF16 (bfloat16)
+ *   layout   LRF_T_NCHW: crop j is [3][h][w] elements at 3 h w j; LRF_T_NHWC: [h][w][3] elements at 3 h w j (torch's
+ *            channels_last memory of a [n,3,h,w] tensor)
+ *   scale, bias   finite fp32 numbers per channel: 1 / (255 std_k) and -mean_k / std_k for torchvision's
+ *            ToDtype(scale=True) + Normalize(mean, std)
+ * For the byte b that the _rgb_u8 entry of the same name defines for (crop j, channel k, row y, column x) — flips included: the
+ * reversal is of pixels — the element is
+ *   t = fl32(float(b) * scale[k]);   v = fl32(t + bias[k]);   out = v rounded to nearest even into dtype
+ * two fp32 roundings and one conversion, NOT a fused multiply-add (for the ImageNet constants the fused form differs on 133,
+ * 132 and 124 of the 256 byte values of the three channels).  torch reproduces it bit for bit on the CPU: b.float().mul(s).add(o).to(dtype).  A float16
+ * result beyond 65504 is +-inf, as torch's conversion gives.
+ * Everything else is the _rgb_u8 entry's: the leading arguments, the resident descriptors, the pinned staging slots with no
+ * stream wait for a fresh list, the same launch plan (the format only selects the instantiation a launch names), LRF_K_DECODE,
+ * the validation of everything on the host before any launch, a refused call writing nothing.  LRF_EINVAL in addition to that
+ * entry's list: a NULL fmt, a dtype or layout outside the enums, a scale or bias that is not finite, an `out` that is not
+ * aligned to the element size, out_bytes below n_crops * 3 * h * w * sizeof(element).
+ */
+#define LRF_T_F32 0
+#define LRF_T_F16 1
+#define LRF_T_BF16 2
+#define LRF_T_NCHW 0
+#define LRF_T_NHWC 1
+typedef struct {
+    int32_t dtype;  /* LRF_T_F32, LRF_T_F16, LRF_T_BF16 */
+    int32_t layout; /* LRF_T_NCHW, LRF_T_NHWC */
+    float scale[3], bias[3];
+} lrf_tensor_format;
+int lrf_qmf_decode_crops_tensor(lrf_ctx* ctx, int64_t n_images, const lrf_ragged_image* images /* host; rgb_off ignored */, const int8_t* U,
+                                int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops, const lrf_crop* crops /* host */, int64_t h,
+                                int64_t w, const lrf_tensor_format* fmt /* host */, void* out, int64_t out_bytes);
+int lrf_qmf_decode_scaled_crops_tensor(lrf_ctx* ctx, int64_t n_images, const lrf_ragged_image* images /* host; rgb_off ignored */, const int8_t* U,
+                                       int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops, const lrf_scaled_crop* crops /* host */,
+                                       int64_t h, int64_t w, const lrf_tensor_format* fmt /* host */, void* out, int64_t out_bytes);
+int lrf_qmf_decode_resized_crops_tensor(lrf_ctx* ctx, int64_t n_images, const lrf_ragged_image* images /* host; rgb_off ignored */, const int8_t* U,
+                                        int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops, const lrf_resized_crop* crops /* host */,
+                                        int64_t oh, int64_t ow, const lrf_tensor_format* fmt /* host */, void* out, int64_t out_bytes);
+
+/*
  * The fused encode (lrf/compression/qmf.py:227-262) for a list of n images that differ in size and in ranks, in one call: what a
  * dataset of mixed sizes or a per-image quality choice hands to an encoder.
  *   images  [n] descriptors in host memory

@@ -55,6 +55,11 @@ class ResizedCrop(ctypes.Structure):
                 ("flip", ctypes.c_int32)]
 
 
+class TensorFormat(ctypes.Structure):
+    """lrf_tensor_format (include/lrf_hip.h)"""
+    _fields_ = [("dtype", ctypes.c_int32), ("layout", ctypes.c_int32), ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3)]
+
+
 class RaggedEncodeImage(ctypes.Structure):
     """lrf_ragged_encode_image (include/lrf_hip.h)"""
     _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int * 3), ("rgb_off", c_i64), ("u_off", c_i64), ("v_off", c_i64), ("sign_off", c_i64)]
@@ -126,6 +131,12 @@ def load():
                                                            ctypes.POINTER(ScaledCrop), c_i64, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_decode_resized_crops_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_i64,
                                                             ctypes.POINTER(ResizedCrop), c_i64, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_decode_crops_tensor.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_i64, ctypes.POINTER(Crop),
+                                                    c_i64, c_i64, ctypes.POINTER(TensorFormat), c_void_p, c_i64]
+        lib.lrf_qmf_decode_scaled_crops_tensor.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_i64,
+                                                           ctypes.POINTER(ScaledCrop), c_i64, c_i64, ctypes.POINTER(TensorFormat), c_void_p, c_i64]
+        lib.lrf_qmf_decode_resized_crops_tensor.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_i64,
+                                                            ctypes.POINTER(ResizedCrop), c_i64, c_i64, ctypes.POINTER(TensorFormat), c_void_p, c_i64]
         lib.lrf_qmf_encode_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedEncodeImage), c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64,
                                                      c_void_p, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_encode_ragged_sweep_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedSweepImage), c_i64, ctypes.POINTER(RaggedSweepCandidate),
@@ -181,7 +192,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_last_luma_source", "lrf_ctx_last_x_residency", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_encode_ragged_rgb_u8", "lrf_qmf_encode_ragged_sweep_rgb_u8", "lrf_qmf_sse_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_decode_crops_tensor", "lrf_qmf_decode_scaled_crops_tensor", "lrf_qmf_decode_resized_crops_tensor", "lrf_qmf_encode_ragged_rgb_u8", "lrf_qmf_encode_ragged_sweep_rgb_u8", "lrf_qmf_sse_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
@@ -471,6 +482,91 @@ def check_resized_args(U, V, images, crops, size):
         raise ValueError(f"crop {j}: {boxes[j, 3]}x{boxes[j, 4]} at ({boxes[j, 1]}, {boxes[j, 2]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]}")
     boxes[:, 5] = boxes[:, 5] != 0
     return ims, np.ascontiguousarray(boxes, dtype=np.int32), (oh, ow)
+
+
+T_F32, T_F16, T_BF16 = 0, 1, 2  # lrf_tensor_format.dtype
+T_NCHW, T_NHWC = 0, 1  # lrf_tensor_format.layout
+
+
+def _three_numbers(v, name):
+    """None, one number or three of them -> three Python floats, or None"""
+    import numpy as np
+    if v is None:
+        return None
+    number = lambda x: isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_))
+    if number(v):
+        return [float(v)] * 3
+    if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or not hasattr(v, "__getitem__"):
+        raise TypeError(f"{name} must be None, a number or three numbers, got {v!r}")
+    if hasattr(v, "tolist"):
+        v = v.tolist()
+    if not isinstance(v, (list, tuple)) or not all(number(x) for x in v):
+        raise TypeError(f"{name} must be None, a number or three numbers, got {v!r}")
+    if len(v) != 3:
+        raise ValueError(f"{name} must hold one value per channel (3), got {len(v)}")
+    return [float(x) for x in v]
+
+
+def check_tensor_format(dtype, mean=None, std=None, channels_last=False):
+    """The tensor format of the model-ready decode entries (lrf_tensor_format, include/lrf_hip.h), before any device is touched.
+    dtype: torch.float32, float16 or bfloat16; mean, std: None, one number or three, in [0, 1] units as torchvision's Normalize
+    after ToDtype(scale=True); channels_last: NHWC memory.  scale[k] = float32(1 / (255 std[k])), bias[k] = float32(-mean[k] /
+    std[k]), each computed in Python doubles and rounded once; without mean and std float32(1 / 255) and 0.  TypeError for
+    anything of the wrong type, ValueError for a std of 0, for values that are not finite (as float32 too) and for a wrong count.
+    -> TensorFormat"""
+    import math
+    import numpy as np
+    import torch
+    if not isinstance(dtype, torch.dtype):
+        raise TypeError(f"dtype must be a torch.dtype, got {dtype!r}")
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"dtype {dtype}: torch.float32, torch.float16 or torch.bfloat16 expected")
+    if not isinstance(channels_last, (bool, np.bool_)):
+        raise TypeError(f"channels_last must be a bool, got {channels_last!r}")
+    m, s = _three_numbers(mean, "mean"), _three_numbers(std, "std")
+    m, s = m if m is not None else [0.0] * 3, s if s is not None else [1.0] * 3
+    if not all(math.isfinite(x) for x in m + s):
+        raise ValueError(f"mean and std must be finite, got {mean!r} and {std!r}")
+    if any(x == 0.0 for x in s):
+        raise ValueError(f"std must not contain 0, got {std!r}")
+    fmt = TensorFormat()
+    fmt.dtype = {torch.float32: T_F32, torch.float16: T_F16, torch.bfloat16: T_BF16}[dtype]
+    fmt.layout = T_NHWC if channels_last else T_NCHW
+    for k in range(3):
+        with np.errstate(over="ignore"):
+            sc, bi = np.float32(1.0 / (255.0 * s[k])), np.float32(-m[k] / s[k])
+        if not (np.isfinite(sc) and np.isfinite(bi)):
+            raise ValueError(f"channel {k}: scale {sc} or bias {bi} is not a finite float32 (mean {m[k]}, std {s[k]})")
+        fmt.scale[k], fmt.bias[k] = float(sc), float(bi)
+    return fmt
+
+
+def _tensor_request(entry, dtype, mean, std, channels_last, out):
+    """The output arguments the decode entries share, checked before any device is touched -> None for the uint8 entry (the
+    defaults), else the TensorFormat"""
+    import torch
+    if dtype == torch.uint8:
+        if mean is not None or std is not None or channels_last or out is not None:
+            raise ValueError(f"{entry}: mean, std, channels_last and out= go with a float dtype (dtype=torch.uint8 is the byte entry, [n,3,h,w])")
+        return None
+    return check_tensor_format(dtype, mean, std, channels_last)
+
+
+def _tensor_output(entry, out, n, h, w, dtype, channels_last, device):
+    """the [n,3,h,w] result of a tensor entry: the caller's `out`, checked (a refusal launches nothing), or a new tensor"""
+    import torch
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    if out is None:
+        return torch.empty((n, 3, h, w), dtype=dtype, device=device, memory_format=fmt)
+    if not isinstance(out, torch.Tensor):
+        raise TypeError(f"{entry}: out must be a tensor, got {type(out).__name__}")
+    if out.dtype != dtype or tuple(out.shape) != (n, 3, h, w) or out.device != device:
+        raise ValueError(f"{entry}: out must be {dtype} {(n, 3, h, w)} on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    # (strides, not is_contiguous(memory_format=...): for h = w = 1 or n = 1 torch calls more than one layout contiguous)
+    want = (3 * h * w, 1, 3 * w, 3) if channels_last else (3 * h * w, h * w, w, 1)
+    if any(st != wt for st, wt, size in zip(out.stride(), want, out.shape) if size > 1):
+        raise ValueError(f"{entry}: out must be {'channels_last' if channels_last else 'contiguous'} memory (strides {want}), got strides {tuple(out.stride())}")
+    return out
 
 
 def check_encode_ragged_args(rgb, images, sign=None):
@@ -971,16 +1067,28 @@ class Context:
         check(self._lib.lrf_qmf_decode_ragged_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(rgb), rgb.numel()))
         return [rgb[d.rgb_off:d.rgb_off + 3 * d.H * d.W].view(3, d.H, d.W) for d in desc]
 
-    def decode_crops(self, U, V, images, crops, size):
+    def decode_crops(self, U, V, images, crops, size, dtype=None, mean=None, std=None, channels_last=False, out=None):
         """Windows straight from the factors (lrf_qmf_decode_crops_rgb_u8).  U, V, images: as decode_ragged takes them; crops: an
         integer array-like [n, 3] of (image, y0, x0) on the host; size: (h, w) -> a uint8 CUDA tensor [n, 3, h, w], crop j equal
         to the decode of its image sliced [:, y0:y0+h, x0:x0+w].  Asynchronous on torch's current stream; a new crop list costs no
-        stream wait (a new image list does, once)."""
+        stream wait (a new image list does, once).
+        dtype=torch.float32 / float16 / bfloat16 (default torch.uint8: the above): the model's tensor instead
+        (lrf_qmf_decode_crops_tensor), logical shape [n, 3, h, w], every byte b of the above as (b * scale_k) + bias_k in fp32 (two
+        roundings) rounded to dtype; mean, std: as check_tensor_format takes them; channels_last: torch.channels_last memory;
+        out: a tensor of that dtype, shape, device and memory format (a slice along n of a larger batch, say), written in place."""
         import torch
+        fmt = _tensor_request("decode_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
         ims, boxes, (h, w) = check_crop_args(U, V, images, crops, size)
         self._need_here("decode_crops", U)
         desc = _ragged_images(ims)
         n = boxes.shape[0]
+        if fmt is not None:
+            res = _tensor_output("decode_crops", out, n, h, w, dtype, channels_last, U.device)
+            self.use_torch_stream()
+            check(self._lib.lrf_qmf_decode_crops_tensor(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
+                                                        boxes.ctypes.data_as(ctypes.POINTER(Crop)), h, w, ctypes.byref(fmt), c_void_p(res.data_ptr()),
+                                                        res.numel() * res.element_size()))
+            return res
         rgb = torch.empty((n, 3, h, w), dtype=torch.uint8, device=U.device)
         self.use_torch_stream()
         check(self._lib.lrf_qmf_decode_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
@@ -1002,33 +1110,52 @@ class Context:
         check(self._lib.lrf_qmf_decode_scaled_rgb_u8(self._h, len(ims), desc, scale, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(rgb), rgb.numel()))
         return [rgb[d.rgb_off:d.rgb_off + 3 * hs * ws].view(3, hs, ws) for d, (hs, ws) in zip(desc, sizes)]
 
-    def decode_scaled_crops(self, U, V, images, crops, size):
+    def decode_scaled_crops(self, U, V, images, crops, size, dtype=None, mean=None, std=None, channels_last=False, out=None):
         """Windows of scaled images straight from the factors (lrf_qmf_decode_scaled_crops_rgb_u8).  U, V, images: as decode_ragged
         takes them; crops: an integer array-like [n, 4] of (image, scale, y0, x0) on the host, the scale per crop out of 2, 4, 8
         and y0, x0 in the scaled image; size: (h, w) -> a uint8 CUDA tensor [n, 3, h, w], crop j equal to decode_scaled of its
-        image at its scale sliced [:, y0:y0+h, x0:x0+w].  Asynchronous on torch's current stream."""
+        image at its scale sliced [:, y0:y0+h, x0:x0+w].  Asynchronous on torch's current stream.
+        dtype, mean, std, channels_last, out: as decode_crops takes them (lrf_qmf_decode_scaled_crops_tensor)."""
         import torch
+        fmt = _tensor_request("decode_scaled_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
         ims, boxes, (h, w) = check_scaled_args(U, V, images, crops=crops, size=size)
         self._need_here("decode_scaled_crops", U)
         desc = _ragged_images(ims)
         n = boxes.shape[0]
+        if fmt is not None:
+            res = _tensor_output("decode_scaled_crops", out, n, h, w, dtype, channels_last, U.device)
+            self.use_torch_stream()
+            check(self._lib.lrf_qmf_decode_scaled_crops_tensor(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
+                                                               boxes.ctypes.data_as(ctypes.POINTER(ScaledCrop)), h, w, ctypes.byref(fmt),
+                                                               c_void_p(res.data_ptr()), res.numel() * res.element_size()))
+            return res
         rgb = torch.empty((n, 3, h, w), dtype=torch.uint8, device=U.device)
         self.use_torch_stream()
         check(self._lib.lrf_qmf_decode_scaled_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
                                                            boxes.ctypes.data_as(ctypes.POINTER(ScaledCrop)), h, w, _dptr(rgb), rgb.numel()))
         return rgb
 
-    def decode_resized_crops(self, U, V, images, crops, size):
+    def decode_resized_crops(self, U, V, images, crops, size, dtype=None, mean=None, std=None, channels_last=False, out=None):
         """Boxes of any size resampled to one output size straight from the factors (lrf_qmf_decode_resized_crops_rgb_u8).  U, V,
         images: as decode_ragged takes them; crops: an integer array-like [n, 6] of (image, y0, x0, h, w, flip) on the host, the
         box in full-resolution pixels; size: (oh, ow) -> a uint8 CUDA tensor [n, 3, oh, ow].  Crop j is the fixed-point bilinear
         resampling include/lrf_hip.h defines, from the level (1, 1/2, 1/4, 1/8) nearest above the output's size: not torchvision's
-        bytes.  Asynchronous on torch's current stream; a new crop list costs no stream wait."""
+        bytes.  Asynchronous on torch's current stream; a new crop list costs no stream wait.
+        dtype, mean, std, channels_last, out: as decode_crops takes them (lrf_qmf_decode_resized_crops_tensor): resized crop, flip,
+        to-tensor and normalise in one call, no uint8 batch in between."""
         import torch
+        fmt = _tensor_request("decode_resized_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
         ims, boxes, (oh, ow) = check_resized_args(U, V, images, crops, size)
         self._need_here("decode_resized_crops", U)
         desc = _ragged_images(ims)
         n = boxes.shape[0]
+        if fmt is not None:
+            res = _tensor_output("decode_resized_crops", out, n, oh, ow, dtype, channels_last, U.device)
+            self.use_torch_stream()
+            check(self._lib.lrf_qmf_decode_resized_crops_tensor(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
+                                                                boxes.ctypes.data_as(ctypes.POINTER(ResizedCrop)), oh, ow, ctypes.byref(fmt),
+                                                                c_void_p(res.data_ptr()), res.numel() * res.element_size()))
+            return res
         rgb = torch.empty((n, 3, oh, ow), dtype=torch.uint8, device=U.device)
         self.use_torch_stream()
         check(self._lib.lrf_qmf_decode_resized_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,

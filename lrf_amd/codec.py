@@ -1857,15 +1857,22 @@ def _split_crops_by_scale(U, V, images, crops, size, scale):
     return full, b1, scaled, b2
 
 
-def _decode_crops_at_scales(ctx, U, V, images, crops, size, scale) -> torch.Tensor:
-    """entries at scale 1 take Context.decode_crops, the rest Context.decode_scaled_crops; merged in call order"""
+def _decode_crops_at_scales(ctx, U, V, images, crops, size, scale, **tensor) -> torch.Tensor:
+    """entries at scale 1 take Context.decode_crops, the rest Context.decode_scaled_crops; merged in call order.  tensor: the
+    dtype, mean, std, channels_last and out of those two (_tensor_kwargs: checked, empty for uint8), the result in that format (out=:
+    written in place)"""
     full, b1, scaled, b2 = _split_crops_by_scale(U, V, images, crops, size, scale)
     if not scaled.size:
-        return ctx.decode_crops(U, V, images, b1, size)
+        return ctx.decode_crops(U, V, images, b1, size, **tensor)
     if not full.size:
-        return ctx.decode_scaled_crops(U, V, images, b2, size)
-    a, b = ctx.decode_crops(U, V, images, b1, size), ctx.decode_scaled_crops(U, V, images, b2, size)
-    out = torch.empty((full.size + scaled.size,) + tuple(a.shape[1:]), dtype=torch.uint8, device=a.device)
+        return ctx.decode_scaled_crops(U, V, images, b2, size, **tensor)
+    out, parts = tensor.get("out"), {k: v for k, v in tensor.items() if k != "out"}
+    if out is not None:
+        _lib._tensor_output("decode_crops", out, full.size + scaled.size, int(size[0]), int(size[1]), tensor["dtype"], tensor.get("channels_last", False), U.device)
+    a, b = ctx.decode_crops(U, V, images, b1, size, **parts), ctx.decode_scaled_crops(U, V, images, b2, size, **parts)
+    if out is None:
+        fmt = torch.channels_last if tensor.get("channels_last", False) else torch.contiguous_format
+        out = torch.empty((full.size + scaled.size,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device, memory_format=fmt)
     out[torch.from_numpy(full).to(a.device)] = a
     out[torch.from_numpy(scaled).to(a.device)] = b
     return out
@@ -1893,17 +1900,29 @@ class ResidentFactors:
             return self._ctx.decode_ragged(self.U, self.V, self.images)
         return self._ctx.decode_scaled(self.U, self.V, self.images, scale)
 
-    def decode_crops(self, crops, size, scale=1) -> torch.Tensor:
+    def decode_crops(self, crops, size, scale=1, dtype=torch.uint8, mean=None, std=None, channels_last=False, out=None) -> torch.Tensor:
         """crops: integers [n, 3] of (image, y0, x0) on the host; size: (h, w) -> uint8 CUDA [n, 3, h, w].  scale: 1, 2, 4, 8 or
-        one of them per crop: crop j is the window (y0, x0) of its image decoded at 1/scale_j, y0 and x0 in that scaled image"""
+        one of them per crop: crop j is the window (y0, x0) of its image decoded at 1/scale_j, y0 and x0 in that scaled image.
+        dtype, mean, std, channels_last, out: the model's tensor instead of bytes, as qmf_decode_crops describes"""
+        tensor = _tensor_kwargs("decode_crops", dtype, mean, std, channels_last, out)
         if type(scale) is int and scale == 1:
-            return self._ctx.decode_crops(self.U, self.V, self.images, crops, size)
-        return _decode_crops_at_scales(self._ctx, self.U, self.V, self.images, crops, size, scale)
+            return self._ctx.decode_crops(self.U, self.V, self.images, crops, size, **tensor)
+        return _decode_crops_at_scales(self._ctx, self.U, self.V, self.images, crops, size, scale, **tensor)
 
-    def decode_resized_crops(self, boxes, size, flip=None) -> torch.Tensor:
+    def decode_resized_crops(self, boxes, size, flip=None, dtype=torch.uint8, mean=None, std=None, channels_last=False, out=None) -> torch.Tensor:
         """boxes: integers [n, 5] of (image, y0, x0, h, w) on the host, full-resolution pixels; size: (oh, ow); flip: None, one
-        bool, or one bool per box (mirror the output's columns) -> uint8 CUDA [n, 3, oh, ow]: qmf_decode_resized_crops"""
-        return self._ctx.decode_resized_crops(self.U, self.V, self.images, _resized_boxes(boxes, flip), size)
+        bool, or one bool per box (mirror the output's columns) -> uint8 CUDA [n, 3, oh, ow]: qmf_decode_resized_crops, which
+        also describes dtype, mean, std, channels_last and out"""
+        return self._ctx.decode_resized_crops(self.U, self.V, self.images, _resized_boxes(boxes, flip), size,
+                                              **_tensor_kwargs("decode_resized_crops", dtype, mean, std, channels_last, out))
+
+
+def _tensor_kwargs(entry, dtype, mean, std, channels_last, out) -> dict:
+    """the output arguments of the crop entries, checked (no device is touched), as the keywords Context's methods take: none for
+    the defaults, which are the uint8 calls as they always were"""
+    if _lib._tensor_request(entry, dtype, mean, std, channels_last, out) is None:
+        return {}
+    return dict(dtype=dtype, mean=mean, std=std, channels_last=channels_last, out=out)
 
 
 def _resized_boxes(boxes, flip):
@@ -1950,12 +1969,20 @@ def qmf_load_factors(streams: Sequence[bytes], device=None, inflate: str = "host
     return _resident(*_factors_ragged(streams), device)
 
 
-def qmf_decode_crops(source, crops, size, device=None, inflate: str = "host", scale=1) -> torch.Tensor:
+def qmf_decode_crops(source, crops, size, device=None, inflate: str = "host", scale=1, dtype=torch.uint8, mean=None, std=None, channels_last=False,
+                     out=None) -> torch.Tensor:
     """Windows of compressed images without decoding the images: source is a list of streams (parsed and uploaded for this call)
     or the ResidentFactors of qmf_load_factors (nothing but the crop list travels); crops: integers [n, 3] of (image, y0, x0) on
     the host; size: (h, w) -> uint8 CUDA [n, 3, h, w], crop j equal to qmf_decode(stream)[:, y0:y0+h, x0:x0+w].
     inflate="device" (a list of streams only): their columns are inflated on the GPU.
-    scale: 1, 2, 4, 8 or one of them per crop: crop j is then that window of qmf_decode_scaled(stream, scale_j)."""
+    scale: 1, 2, 4, 8 or one of them per crop: crop j is then that window of qmf_decode_scaled(stream, scale_j).
+    dtype: torch.float32, float16 or bfloat16 gives the tensor a model takes instead, in the same call and with no uint8 batch in
+    between: logical shape [n, 3, h, w], element = every byte b above as fl32(fl32(b * scale_k) + bias_k) rounded to dtype, with
+    scale_k = float32(1 / (255 std_k)) and bias_k = float32(-mean_k / std_k) — torchvision's ToDtype(scale=True) and
+    Normalize(mean, std) to within an fp32 rounding; mean, std: None, one number or three, in [0, 1] units; channels_last=True:
+    torch.channels_last memory; out: a tensor of that dtype, shape, device and memory format, written in place and returned.
+    With dtype=torch.uint8 (the default) the other four must be left alone: ValueError."""
+    tensor = _tensor_kwargs("qmf_decode_crops", dtype, mean, std, channels_last, out)  # refused before anything is parsed or uploaded
     on_device = _check_inflate(inflate)
     if on_device and not isinstance(source, ResidentFactors):
         ctx, images, U, V = _factors_ragged_device(source, device)
@@ -1967,10 +1994,11 @@ def qmf_decode_crops(source, crops, size, device=None, inflate: str = "host", sc
         else:
             _split_crops_by_scale(torch.from_numpy(Uh), torch.from_numpy(Vh), images, crops, size, scale)
         source = _resident(images, Uh, Vh, device)
-    return source.decode_crops(crops, size, scale)
+    return source.decode_crops(crops, size, scale, **tensor)
 
 
-def qmf_decode_resized_crops(source, boxes, size, flip=None, device=None, inflate: str = "host") -> torch.Tensor:
+def qmf_decode_resized_crops(source, boxes, size, flip=None, device=None, inflate: str = "host", dtype=torch.uint8, mean=None, std=None,
+                             channels_last=False, out=None) -> torch.Tensor:
     """RandomResizedCrop straight from the factors: n boxes of any size and position, out of images of any sizes and ranks,
     resampled to one output size in one call.  source: a list of streams or the ResidentFactors of qmf_load_factors; boxes:
     integers [n, 5] of (image, y0, x0, h, w) on the host, each inside its image with h, w >= 1; size: (oh, ow), sides in
@@ -1982,7 +2010,10 @@ def qmf_decode_resized_crops(source, boxes, size, flip=None, device=None, inflat
     within 2.5 levels of real-valued bilinear interpolation of the level.  These are NOT torchvision's bytes: torchvision
     interpolates the full-resolution pixels in floating point (and antialiases differently).  Exact definition:
     include/lrf_hip.h, lrf_qmf_decode_resized_crops_rgb_u8.  The default branch only, as qmf_decode_crops: a stream of another
-    branch raises NotImplementedError naming it.  inflate="device" (a list of streams only): their columns are inflated on the GPU."""
+    branch raises NotImplementedError naming it.  inflate="device" (a list of streams only): their columns are inflated on the GPU.
+    dtype, mean, std, channels_last, out: as qmf_decode_crops takes them — the resized crop, the flip, to-tensor and normalise in
+    one call; under flip the pixels are mirrored, whatever the element size or layout."""
+    tensor = _tensor_kwargs("qmf_decode_resized_crops", dtype, mean, std, channels_last, out)
     on_device = _check_inflate(inflate)
     rows = _resized_boxes(boxes, flip)
     if on_device and not isinstance(source, ResidentFactors):
@@ -1992,7 +2023,7 @@ def qmf_decode_resized_crops(source, boxes, size, flip=None, device=None, inflat
         images, Uh, Vh = _factors_ragged(source)
         _lib.check_resized_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, rows, size)  # refused before a GPU is asked for
         source = _resident(images, Uh, Vh, device)
-    return source._ctx.decode_resized_crops(source.U, source.V, source.images, rows, size)
+    return source._ctx.decode_resized_crops(source.U, source.V, source.images, rows, size, **tensor)
 
 
 def qmf_decode_scaled(source, scale, device=None, inflate: str = "host") -> list:

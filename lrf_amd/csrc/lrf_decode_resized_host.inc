@@ -3,9 +3,11 @@
 // lrf_decode_scaled_host.inc: the entry describes its images as the decode of windows does (describe) and shares its resident
 // descriptor table and pinned staging slots.
 
-int lrf_qmf_decode_resized_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
-                                        int64_t v_len, int64_t n_crops, const lrf_resized_crop* crops, int64_t oh, int64_t ow, uint8_t* rgb, int64_t rgb_len)
+static int decode_resized_to(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len,
+                             int64_t n_crops, const lrf_resized_crop* crops, int64_t oh, int64_t ow, const DecodeOut& o)
 {
+    void* const rgb = o.p;
+    const int64_t rgb_len = o.len;
     if (!c || !images || !U || !V || !crops || !rgb) return set_err(LRF_EINVAL, "NULL argument");
     if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
     if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
@@ -40,18 +42,38 @@ int lrf_qmf_decode_resized_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_
     for (const ResizedLaunch& l : plan.launches) {
         const dim3 grid((unsigned)(l.nitems * l.wgs));
         const ResizedItem* it = d_item + l.item0;
-#define LRF_RESIZED(K) hipLaunchKernelGGL((K), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, it, (int)oh, (int)ow, (int)l.wgs)
-        if (l.direct) {
-            if (l.f == 1) LRF_RESIZED(k_decode_resized_direct<true>);
-            else LRF_RESIZED(k_decode_resized_direct<false>);
-        } else if (l.f != 1)
-            LRF_RESIZED(k_decode_resized<2>);
-        else if (l.r8)
-            LRF_RESIZED(k_decode_resized<0>);
-        else
-            LRF_RESIZED(k_decode_resized<1>);
-#undef LRF_RESIZED
+#define LRF_RESIZED_ON(K, T)                                                                                                          \
+    do {                                                                                                                              \
+        if (l.direct) {                                                                                                               \
+            if (l.f == 1) K(k_decode_resized_direct, true, T);                                                                        \
+            else K(k_decode_resized_direct, false, T);                                                                                \
+        } else if (l.f != 1)                                                                                                          \
+            K(k_decode_resized, 2, T);                                                                                                \
+        else if (l.r8)                                                                                                                \
+            K(k_decode_resized, 0, T);                                                                                                \
+        else                                                                                                                          \
+            K(k_decode_resized, 1, T);                                                                                                \
+    } while (0)
+        if (o.dtype >= 0)
+            with_tensor_type(o, [&](auto* out) {
+                using T = std::remove_pointer_t<decltype(out)>;
+#define LRF_RESIZED_T(K, A, T) hipLaunchKernelGGL((K##_t<A, T>), grid, dim3(256), 0, c->stream, U, V, out, o.f, d_desc, it, (int)oh, (int)ow, (int)l.wgs)
+                LRF_RESIZED_ON(LRF_RESIZED_T, T);
+#undef LRF_RESIZED_T
+            });
+        else {
+#define LRF_RESIZED_U8(K, A, T) hipLaunchKernelGGL((K<A>), grid, dim3(256), 0, c->stream, U, V, (uint8_t*)rgb, d_desc, it, (int)oh, (int)ow, (int)l.wgs)
+            LRF_RESIZED_ON(LRF_RESIZED_U8, );
+#undef LRF_RESIZED_U8
+        }
+#undef LRF_RESIZED_ON
         LAUNCH_CHECK();
     }
     return LRF_OK;
+}
+
+int lrf_qmf_decode_resized_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
+                                        int64_t v_len, int64_t n_crops, const lrf_resized_crop* crops, int64_t oh, int64_t ow, uint8_t* rgb, int64_t rgb_len)
+{
+    return decode_resized_to(c, n_images, images, U, u_len, V, v_len, n_crops, crops, oh, ow, bytes_out(rgb, rgb_len));
 }

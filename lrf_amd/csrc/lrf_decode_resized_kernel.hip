@@ -18,6 +18,9 @@
 //                                  every rank (decode_quad); 2: f = 2, 4, 8 (scaled_pixel_rgb)
 //   k_decode_resized_direct<F1>    boxes whose tile footprint does not fit LDS (resized_staged): a thread one output pixel and its
 //                                  up to four distinct taps (decode_quad / scaled_pixel_rgb)
+// Both are thin kernels over a workgroup function (decode_resized_wg, decode_resized_direct_wg) that takes where the pixels go as a
+// type: DecodeU8Out for these, DecodeTensorOut<T> for k_decode_resized_t<MODE, T> and k_decode_resized_direct_t<F1, T>, which write
+// a model's tensor (lrf_qmf_decode_resized_crops_tensor; lrf_decode_tensor_kernel.hip) and are otherwise the same kernels.
 
 // The sink of the decode bodies aimed at the LDS tile: level pixel (y, x) lands at [ch][y - fy0][x - fx0], what lies outside
 // the footprint is dropped.
@@ -61,9 +64,11 @@ __device__ __forceinline__ int resized_blend(int ty, int tx, int a, int b, int c
     return ((256 - ty) * ((256 - tx) * a + tx * b) + ty * ((256 - tx) * c + tx * d) + 32768) >> 16;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void k_decode_resized(const int8_t* __restrict__ U, const int8_t* __restrict__ V, uint8_t* __restrict__ rgb,
-                                                        const RaggedDesc* __restrict__ descs, const ResizedItem* __restrict__ items, int oh, int ow, int wgs)
+// OUT: where the pixels go, DecodeU8Out or DecodeTensorOut<T> (lrf_decode_tensor_kernel.hip): box `place` is [3][oh][ow] (for a tensor in
+// NHWC [oh][ow][3]) at 3 oh ow place elements.
+template <int MODE, class OUT>
+__device__ __forceinline__ void decode_resized_wg(const int8_t* __restrict__ U, const int8_t* __restrict__ V, const OUT& out,
+                                                  const RaggedDesc* __restrict__ descs, const ResizedItem* __restrict__ items, int oh, int ow, int wgs)
 {
     __shared__ __attribute__((aligned(16))) uint8_t L[3 * LRF_RS_FH * LRF_RS_FW];
     __shared__ float Vs[3][MODE == 0 ? 64 * 8 : 1];
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(256) void k_decode_resized(const int8_t* __restrict
     const int ty = tapy[lr][2];
     const uint8_t* row0 = L + tapy[lr][0] * LRF_RS_FW;
     const uint8_t* row1 = L + tapy[lr][1] * LRF_RS_FW;
-    unsigned pk[3] = {0u, 0u, 0u}; // byte j: column p.c + j, or (flip) the mirrored order the output holds them in
+    unsigned pk[3][1] = {{0u}, {0u}, {0u}}; // byte j: column p.c + j, or (flip) the mirrored order the output holds them in
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         if (j >= p.n) break;
@@ -139,30 +144,40 @@ __global__ __launch_bounds__(256) void k_decode_resized(const int8_t* __restrict
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const int o = k * LRF_RS_FH * LRF_RS_FW;
-            pk[k] |= (unsigned)resized_blend(ty, tx, row0[o + x0], row0[o + x1], row1[o + x0], row1[o + x1]) << sh;
+            pk[k][0] |= (unsigned)resized_blend(ty, tx, row0[o + x0], row0[o + x1], row1[o + x0], row1[o + x1]) << sh;
         }
     }
-    const long hw = (long)oh * ow;
-    uint8_t* dst = rgb + (long)it.place * 3 * hw + (long)p.r * ow;
-    // four pixels of a channel leave as one dword, the tile's last columns byte by byte
-    if (p.n == 4) {
-        const int c = it.flip ? ow - 1 - (p.c + 3) : p.c;
-#pragma unroll
-        for (int k = 0; k < 3; k++) *reinterpret_cast<uint32_t __attribute__((aligned(1)))*>(dst + k * hw + c) = pk[k];
-    } else {
+    const long hw = (long)oh * ow, base = (long)it.place * 3 * hw;
+    // four pixels leave as one run (bytes: a dword per channel; a tensor: lrf_decode_tensor_kernel.hip), the tile's last columns one by one;
+    // the order under flip is the pixels', whatever an element's size
+    if (p.n == 4)
+        out.template run<4>(base, hw, ow, p.r, it.flip ? ow - 1 - (p.c + 3) : p.c, pk);
+    else {
         for (int j = 0; j < p.n; j++) {
             const int sh = 8 * (it.flip ? 3 - j : j);
-#pragma unroll
-            for (int k = 0; k < 3; k++) dst[k * hw + resized_out_col(p.c + j, ow, it.flip)] = (uint8_t)(pk[k] >> sh);
+            const unsigned v[3] = {(pk[0][0] >> sh) & 255u, (pk[1][0] >> sh) & 255u, (pk[2][0] >> sh) & 255u};
+            out.one(base, hw, ow, p.r, resized_out_col(p.c + j, ow, it.flip), v);
         }
     }
 }
 
+template <int MODE>
+__global__ __launch_bounds__(256) void k_decode_resized(const int8_t* __restrict__ U, const int8_t* __restrict__ V, uint8_t* __restrict__ rgb,
+                                                        const RaggedDesc* __restrict__ descs, const ResizedItem* __restrict__ items, int oh, int ow, int wgs)
+{
+    decode_resized_wg<MODE>(U, V, DecodeU8Out{rgb}, descs, items, oh, ow, wgs);
+}
+template <int MODE, class T>
+__global__ __launch_bounds__(256) void k_decode_resized_t(const int8_t* __restrict__ U, const int8_t* __restrict__ V, T* __restrict__ out, TensorFmt f,
+                                                          const RaggedDesc* __restrict__ descs, const ResizedItem* __restrict__ items, int oh, int ow, int wgs)
+{
+    decode_resized_wg<MODE>(U, V, DecodeTensorOut<T>{out, f}, descs, items, oh, ow, wgs);
+}
+
 // Correct rather than fast, like k_decode_crops_any: no sharing between threads.  F1: the launch's level is 1.
-template <bool F1>
-__global__ __launch_bounds__(256) void k_decode_resized_direct(const int8_t* __restrict__ U, const int8_t* __restrict__ V, uint8_t* __restrict__ rgb,
-                                                               const RaggedDesc* __restrict__ descs, const ResizedItem* __restrict__ items, int oh, int ow,
-                                                               int wgs)
+template <bool F1, class OUT>
+__device__ __forceinline__ void decode_resized_direct_wg(const int8_t* __restrict__ U, const int8_t* __restrict__ V, const OUT& out,
+                                                         const RaggedDesc* __restrict__ descs, const ResizedItem* __restrict__ items, int oh, int ow, int wgs)
 {
     const int ii = (int)(blockIdx.x / (unsigned)wgs), wg = (int)(blockIdx.x - (unsigned)ii * (unsigned)wgs);
     const ResizedItem it = items[ii];
@@ -188,8 +203,24 @@ __global__ __launch_bounds__(256) void k_decode_resized_direct(const int8_t* __r
         p11 = ax.i1 != ax.i0 ? level_px(ay.i1, ax.i1) : p10;
     }
     const long hw = (long)oh * ow;
-    uint8_t* dst = rgb + (long)it.place * 3 * hw + (long)o.y * ow + resized_out_col(o.x, ow, it.flip);
+    unsigned v[3];
 #pragma unroll
     for (int k = 0; k < 3; k++)
-        dst[k * hw] = (uint8_t)resized_blend(ay.t, ax.t, (p00 >> (8 * k)) & 255, (p01 >> (8 * k)) & 255, (p10 >> (8 * k)) & 255, (p11 >> (8 * k)) & 255);
+        v[k] = (unsigned)resized_blend(ay.t, ax.t, (p00 >> (8 * k)) & 255, (p01 >> (8 * k)) & 255, (p10 >> (8 * k)) & 255, (p11 >> (8 * k)) & 255);
+    out.one((long)it.place * 3 * hw, hw, ow, o.y, resized_out_col(o.x, ow, it.flip), v);
+}
+
+template <bool F1>
+__global__ __launch_bounds__(256) void k_decode_resized_direct(const int8_t* __restrict__ U, const int8_t* __restrict__ V, uint8_t* __restrict__ rgb,
+                                                               const RaggedDesc* __restrict__ descs, const ResizedItem* __restrict__ items, int oh, int ow,
+                                                               int wgs)
+{
+    decode_resized_direct_wg<F1>(U, V, DecodeU8Out{rgb}, descs, items, oh, ow, wgs);
+}
+template <bool F1, class T>
+__global__ __launch_bounds__(256) void k_decode_resized_direct_t(const int8_t* __restrict__ U, const int8_t* __restrict__ V, T* __restrict__ out, TensorFmt f,
+                                                                 const RaggedDesc* __restrict__ descs, const ResizedItem* __restrict__ items, int oh,
+                                                                 int ow, int wgs)
+{
+    decode_resized_direct_wg<F1>(U, V, DecodeTensorOut<T>{out, f}, descs, items, oh, ow, wgs);
 }

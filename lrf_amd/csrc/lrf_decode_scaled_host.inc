@@ -15,8 +15,9 @@ int lrf_scaled_dims(int64_t H, int64_t W, int scale, int64_t* Hs, int64_t* Ws)
 // descs: the images, described exactly as lrf_qmf_decode_crops_rgb_u8 describes them (the entries share the resident descriptor
 // table: a loader that mixes full-scale and scaled windows of one list uploads it once); items: validated.  The sorted items
 // and the pool jobs travel together through the pinned slots of the decode of windows, stream-ordered.
-static int run_scaled(lrf_ctx* c, const std::vector<RaggedDesc>& descs, const std::vector<ScaledItem>& items, const int8_t* U, const int8_t* V, uint8_t* rgb)
+static int run_scaled(lrf_ctx* c, const std::vector<RaggedDesc>& descs, const std::vector<ScaledItem>& items, const int8_t* U, const int8_t* V, const DecodeOut& o)
 {
+    uint8_t* const rgb = (uint8_t*)o.p;
     std::vector<ScaledImage> simg(descs.size());
     std::transform(descs.begin(), descs.end(), simg.begin(), scaled_image_of);
     const ScaledPlan plan = plan_decode_scaled(simg, items);
@@ -43,7 +44,27 @@ static int run_scaled(lrf_ctx* c, const std::vector<RaggedDesc>& descs, const st
     for (const ScaledLaunch& l : plan.launches) {
         const dim3 grid((unsigned)(l.nitems * l.wgs));
         const ScaledItem* it = d_item + l.item0;
-        if (!l.tiled)
+        if (o.dtype >= 0)
+            with_tensor_type(o, [&](auto* out) {
+                using T = std::remove_pointer_t<decltype(out)>;
+                if (!l.tiled)
+                    hipLaunchKernelGGL(k_decode_scaled_any_t<T>, grid, dim3(256), 0, c->stream, U, V, out, o.f, d_desc, it, (int)l.wgs);
+                else {
+#define LRF_SCALED_TILED(F, CLS) \
+    hipLaunchKernelGGL((k_decode_scaled_tiled_t<F, CLS, T>), grid, dim3(256), 0, c->stream, U, pool, out, o.f, d_desc, it, (int)l.wgs)
+#define LRF_SCALED_2(CLS) LRF_SCALED_TILED(2, CLS)
+#define LRF_SCALED_4(CLS) LRF_SCALED_TILED(4, CLS)
+#define LRF_SCALED_8(CLS) LRF_SCALED_TILED(8, CLS)
+                    if (l.f == 2) { LRF_FOR_DEC_CLASS(l.cls, LRF_SCALED_2) }
+                    else if (l.f == 4) { LRF_FOR_DEC_CLASS(l.cls, LRF_SCALED_4) }
+                    else { LRF_FOR_DEC_CLASS(l.cls, LRF_SCALED_8) }
+#undef LRF_SCALED_8
+#undef LRF_SCALED_4
+#undef LRF_SCALED_2
+#undef LRF_SCALED_TILED
+                }
+            });
+        else if (!l.tiled)
             hipLaunchKernelGGL(k_decode_scaled_any, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, it, (int)l.wgs);
         else {
 #define LRF_SCALED_TILED(F, CLS) hipLaunchKernelGGL((k_decode_scaled_tiled<F, CLS>), grid, dim3(256), 0, c->stream, U, pool, rgb, d_desc, it, (int)l.wgs)
@@ -81,12 +102,14 @@ int lrf_qmf_decode_scaled_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* 
             return set_err(LRF_EINVAL, "image %ld: its output of 3x%ldx%ld leaves the buffer of %ld bytes", (long)i, (long)hs, (long)ws, (long)rgb_len);
         items[(size_t)i] = ScaledItem{(int)i, scale, 0, 0, (int)hs, (int)ws, (int)i, 0, im.rgb_off, 0};
     }
-    return run_scaled(c, descs, items, U, V, rgb);
+    return run_scaled(c, descs, items, U, V, bytes_out(rgb, rgb_len));
 }
 
-int lrf_qmf_decode_scaled_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
-                                       int64_t v_len, int64_t n_crops, const lrf_scaled_crop* crops, int64_t h, int64_t w, uint8_t* rgb, int64_t rgb_len)
+static int decode_scaled_crops_to(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
+                                  int64_t v_len, int64_t n_crops, const lrf_scaled_crop* crops, int64_t h, int64_t w, const DecodeOut& o)
 {
+    void* const rgb = o.p;
+    const int64_t rgb_len = o.len;
     if (!c || !images || !U || !V || !crops || !rgb) return set_err(LRF_EINVAL, "NULL argument");
     if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
     if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
@@ -109,5 +132,11 @@ int lrf_qmf_decode_scaled_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_r
                            (long)hs, (long)ws, cr.scale);
         items[(size_t)j] = ScaledItem{cr.image, cr.scale, cr.y0, cr.x0, (int)h, (int)w, (int)j, 0, 3 * h * w * j, 0};
     }
-    return run_scaled(c, descs, items, U, V, rgb);
+    return run_scaled(c, descs, items, U, V, o);
+}
+
+int lrf_qmf_decode_scaled_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
+                                       int64_t v_len, int64_t n_crops, const lrf_scaled_crop* crops, int64_t h, int64_t w, uint8_t* rgb, int64_t rgb_len)
+{
+    return decode_scaled_crops_to(c, n_images, images, U, u_len, V, v_len, n_crops, crops, h, w, bytes_out(rgb, rgb_len));
 }

@@ -9,6 +9,7 @@
 #include "lrf_sweep_sse_kernel.hip"
 #include "lrf_decode_ragged_kernel.hip"
 #include "lrf_sse_ragged_kernel.hip"
+#include "lrf_decode_tensor_kernel.hip"
 #include "lrf_decode_crops_kernel.hip"
 #include "lrf_decode_scaled_kernel.hip"
 #include "lrf_decode_resized_kernel.hip"
@@ -915,9 +916,34 @@ static int resident_crop_descs(lrf_ctx* c, const std::vector<RaggedDesc>& descs)
 // n_crops windows of one size (h, w) out of a list of images that differ in size and ranks (kernels:
 // lrf_decode_crops_kernel.hip; the launches: plan_decode_crops).  Everything the kernels index with is checked here, before
 // any launch.  The image descriptors stay resident between calls (their bytes are the key); the crop list does not.
-int lrf_qmf_decode_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
-                                int64_t v_len, int64_t n_crops, const lrf_crop* crops, int64_t h, int64_t w, uint8_t* rgb, int64_t rgb_len)
+// DecodeOut: where the three entries that decode windows write — the bytes of the _rgb_u8 entries or the tensor of the _tensor
+// entries (lrf_decode_tensor_host.inc), `len` counted in its elements.  One body per entry serves both: the checks, the launch
+// plan and the staging do not depend on it, only which instantiation a launch names.
+struct DecodeOut {
+    void* p;
+    int64_t len;
+    int dtype; // LRF_T_*, or -1: uint8 [3][h][w]
+    TensorFmt f;
+};
+static DecodeOut bytes_out(uint8_t* rgb, int64_t rgb_len) { return DecodeOut{rgb, rgb_len, -1, TensorFmt{}}; }
+// fn(T* out) with T the element type of a tensor output
+extern "C++" {
+template <class F>
+static void with_tensor_type(const DecodeOut& o, F&& fn)
 {
+    switch (o.dtype) {
+    case LRF_T_F32: fn((float*)o.p); break;
+    case LRF_T_F16: fn((_Float16*)o.p); break;
+    default: fn((__bf16*)o.p); break;
+    }
+}
+}
+
+static int decode_crops_to(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len,
+                           int64_t n_crops, const lrf_crop* crops, int64_t h, int64_t w, const DecodeOut& o)
+{
+    void* const rgb = o.p;
+    const int64_t rgb_len = o.len;
     if (!c || !images || !U || !V || !crops || !rgb) return set_err(LRF_EINVAL, "NULL argument");
     if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
     if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
@@ -951,17 +977,36 @@ int lrf_qmf_decode_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_i
     for (const CropLaunch& l : plan.launches) {
         const dim3 grid((unsigned)(l.ncrops * l.wgs));
         const CropEntry* ce = d_crop + l.crop0;
-        if (l.kind == DEC_STRIP) {
-#define LRF_CROPS_TILED(CLS) hipLaunchKernelGGL((k_decode_crops_tiled<CLS>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs)
+        if (o.dtype >= 0)
+            with_tensor_type(o, [&](auto* out) {
+                using T = std::remove_pointer_t<decltype(out)>;
+                if (l.kind == DEC_STRIP) {
+#define LRF_CROPS_TILED(CLS) \
+    hipLaunchKernelGGL((k_decode_crops_tiled_t<CLS, T>), grid, dim3(256), 0, c->stream, U, V, out, o.f, d_desc, ce, (int)h, (int)w, (int)l.wgs)
+                    LRF_FOR_DEC_CLASS(l.cls, LRF_CROPS_TILED)
+#undef LRF_CROPS_TILED
+                } else if (l.kind == DEC_R8)
+                    hipLaunchKernelGGL(k_decode8_crops_t<T>, grid, dim3(256), 0, c->stream, U, V, out, o.f, d_desc, ce, (int)h, (int)w, (int)l.wgs);
+                else
+                    hipLaunchKernelGGL(k_decode_crops_any_t<T>, grid, dim3(256), 0, c->stream, U, V, out, o.f, d_desc, ce, (int)h, (int)w, (int)l.wgs);
+            });
+        else if (l.kind == DEC_STRIP) {
+#define LRF_CROPS_TILED(CLS) \
+    hipLaunchKernelGGL((k_decode_crops_tiled<CLS>), grid, dim3(256), 0, c->stream, U, V, (uint8_t*)rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs)
             LRF_FOR_DEC_CLASS(l.cls, LRF_CROPS_TILED)
 #undef LRF_CROPS_TILED
         } else if (l.kind == DEC_R8)
-            hipLaunchKernelGGL(k_decode8_crops, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs);
+            hipLaunchKernelGGL(k_decode8_crops, grid, dim3(256), 0, c->stream, U, V, (uint8_t*)rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs);
         else
-            hipLaunchKernelGGL(k_decode_crops_any, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs);
+            hipLaunchKernelGGL(k_decode_crops_any, grid, dim3(256), 0, c->stream, U, V, (uint8_t*)rgb, d_desc, ce, (int)h, (int)w, (int)l.wgs);
         LAUNCH_CHECK();
     }
     return LRF_OK;
+}
+int lrf_qmf_decode_crops_rgb_u8(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
+                                int64_t v_len, int64_t n_crops, const lrf_crop* crops, int64_t h, int64_t w, uint8_t* rgb, int64_t rgb_len)
+{
+    return decode_crops_to(c, n_images, images, U, u_len, V, v_len, n_crops, crops, h, w, bytes_out(rgb, rgb_len));
 }
 
 // The squared error of Q x B decodes against the B source images, without the decoded images (kernels and the choice of the
@@ -1118,3 +1163,4 @@ int lrf_debug_read_gram_stamps(lrf_ctx* c, unsigned long long* out_host, int n)
 
 #include "lrf_decode_scaled_host.inc"
 #include "lrf_decode_resized_host.inc"
+#include "lrf_decode_tensor_host.inc"
