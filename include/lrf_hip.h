@@ -602,6 +602,38 @@ int lrf_qmf_rgbspace_decode_any_u8(lrf_ctx* ctx, const int8_t* U, const int8_t* 
                                    uint8_t* rgb);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The same branch for images of another channel count: qmf_encode(image[C,H,W], color_space="RGB") takes any C, because
+ * patchify "c (h p) (w q) -> (h w) (c p q)" infers c (lrf/compression/qmf.py:43-56, :164-212) and qmf_decode infers it from
+ * the factor shapes (:309-323).  The three-channel entries above keep their code; these serve gray and n-channel images.
+ *
+ * lrf_chan_dims: the geometry (host only).  Reflect padding to multiples of (p, q) with top = pad / 2, left = pad / 2
+ *   (lrf/compression/utils.py:108-132), M = (hp / p)(wp / q), N = C p q; p = q = 0 (patch=False): hp, wp, M, N = H, W, H, W per
+ *   channel.  Refuses what lrf_rgbspace_dims_any refuses, C outside [1, 16], sides above 2^20 and patches above 1024. */
+int lrf_chan_dims(int64_t H, int64_t W, int64_t C, int p, int q, int64_t* hp, int64_t* wp, int64_t* M, int64_t* N);
+
+/* Gray images, 8x8 patches, K >= 1 (qmf.py:164-187 with c = 1): the image is ONE matrix X [M,64] of uint8-valued floats, the
+ * shape of the tuned 64-column kernels.  A planes kernel (uint8 -> float, reflect padding, patchify) writes X into the context's
+ * X workspace; the call then runs what lrf_qmf_decompose_f32 runs for N = 64 on that X (U0 / V0 NULL; sign optional [B,R]), or what
+ * lrf_qmf_bcd_f32 runs (U0 [B,M,R], V0 [B,64,R] fp32, both or neither), ranks above the tuned ones included.  The factors
+ * U [B,M,R], V [B,64,R] int8 are those entries' on the same X, bit for bit.  gray [B,H,W] uint8 (device). */
+int lrf_qmf_encode_gray_u8(lrf_ctx* ctx, const uint8_t* gray, int64_t B, int64_t H, int64_t W, int R, int K, int lo, int hi,
+                           const int8_t* sign, const float* U0, const float* V0, int8_t* U, int8_t* V);
+
+/* qmf_decode of those streams (qmf.py:311-323, :351 with c = 1): clamp(sum_r U[m,r] V[n,r], 0, 255), depatchify, centre crop.
+ * int32 sums of int8 products: exact for any int8 factors and any R <= LRF_MAX_RANK.  gray [B,H,W] uint8 (device). */
+int lrf_qmf_decode_gray_u8(lrf_ctx* ctx, const int8_t* U, const int8_t* V, int64_t B, int64_t H, int64_t W, int R, uint8_t* gray);
+
+/* The general route, 1 <= C <= 16, any patch size or none (qmf.py:164-212, decode :309-323): the host forms the matrices with
+ * lrf_qmf_chan_matrix_u8, factorises them with lrf_qmf_decompose_f32 / lrf_qmf_bcd_f32 / lrf_qmf_svd_init_f32 (any shape; their
+ * limits and errors apply) and decodes with lrf_qmf_chan_decode_u8.
+ *   p, q > 0: X [B, M, C p q], columns in (c, a, b) order; factors U [B,M,R], V [B,C p q,R];
+ *   p = q = 0: X [B, C, H, W], C matrices per image; factors U [B,C,H,R], V [B,C,W,R].  img / out [B,C,H,W] uint8 (device).
+ * For C = 1 with 8x8 patches the matrix entry runs the planes stage of lrf_qmf_encode_gray_u8: the same X, into the caller's buffer. */
+int lrf_qmf_chan_matrix_u8(lrf_ctx* ctx, const uint8_t* img, int64_t B, int64_t C, int64_t H, int64_t W, int p, int q, float* X);
+int lrf_qmf_chan_decode_u8(lrf_ctx* ctx, const int8_t* U, const int8_t* V, int64_t B, int64_t C, int64_t H, int64_t W, int p, int q, int R,
+                           uint8_t* out);
+
+/* ---------------------------------------------------------------------------------------------------
  * YCbCr branch with any patch size, or none: qmf_encode(color_space="YCbCr", patch_size=(p,q)) and patch=False
  * (lrf/compression/qmf.py:227-262 and :264-286; swept by experiments/ablation_patchsize/eval.py:49-55).
  * The host forms the matrices of one plane, factorises them with lrf_qmf_decompose_f32 (any M, N, R) and decodes with

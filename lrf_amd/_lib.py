@@ -159,6 +159,12 @@ def load():
         lib.lrf_rgbspace_dims_any.argtypes = [c_i64, c_i64, c_int, c_int] + [ctypes.POINTER(c_i64)] * 4
         lib.lrf_qmf_rgbspace_matrix_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_void_p]
         lib.lrf_qmf_rgbspace_decode_any_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_void_p]
+        lib.lrf_chan_dims.argtypes = [c_i64, c_i64, c_i64, c_int, c_int] + [ctypes.POINTER(c_i64)] * 4
+        lib.lrf_qmf_encode_gray_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]
+        lib.lrf_qmf_decode_gray_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p]
+        lib.lrf_qmf_chan_matrix_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_void_p]
+        lib.lrf_qmf_chan_decode_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_void_p]
         lib.lrf_plane_dims_any.argtypes = [c_i64, c_i64, c_int, c_int, c_int] + [ctypes.POINTER(c_i64)] * 6
         lib.lrf_plane_dims_any_hw.argtypes = [c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int] + [ctypes.POINTER(c_i64)] * 6
         lib.lrf_qmf_planes_any_hw_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_void_p]
@@ -195,6 +201,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_decode_crops_tensor", "lrf_qmf_decode_scaled_crops_tensor", "lrf_qmf_decode_resized_crops_tensor", "lrf_qmf_encode_ragged_rgb_u8", "lrf_qmf_encode_ragged_sweep_rgb_u8", "lrf_qmf_sse_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
+           "lrf_chan_dims", "lrf_qmf_encode_gray_u8", "lrf_qmf_decode_gray_u8", "lrf_qmf_chan_matrix_u8", "lrf_qmf_chan_decode_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
            "lrf_qmf_decode_any_hw_u8",
            "lrf_pipe_create", "lrf_pipe_destroy", "lrf_pipe_slots", "lrf_pipe_slot_ctx", "lrf_pipe_workspace_bytes",
@@ -272,6 +279,50 @@ def rgbspace_dims_any(H, W, patch_size):
     v = [c_i64() for _ in range(4)]
     check(load().lrf_rgbspace_dims_any(H, W, p, q, *[ctypes.byref(x) for x in v]))
     return tuple(int(x.value) for x in v)
+
+
+def chan_dims(H, W, C, patch_size):
+    """(Hp, Wp, M, N) of a [C,H,W] image in the RGB colour-space branch (lrf_chan_dims: host-only arithmetic): patches (p, q)
+    give one matrix [M, C p q]; patch_size None = patch=False, per channel the plane [H, W]"""
+    p, q = (0, 0) if patch_size is None else (int(patch_size[0]), int(patch_size[1]))
+    v = [c_i64() for _ in range(4)]
+    check(load().lrf_chan_dims(int(H), int(W), int(C), p, q, *[ctypes.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
+def chan_rank(M, N, rank=None, quality=None):
+    """the scalar rank of the RGB colour-space branch: R = max(round(min(M, N) * quality / 100), 1) (qmf.py:172-178, 196-202)"""
+    if rank is not None:
+        return int(rank)
+    assert quality >= 0 and quality <= 100, "'quality' must be between 0 and 100."
+    return max(round(min(M, N) * quality / 100), 1)
+
+
+def chan_stream_geometry(metadata, u_shape, v_shape):
+    """The header walk of a two-factor RGB colour-space stream, host only: -> (C, H, W, patch_size or None, R).  With patches
+    C = v.shape[0] / (p q), which must divide, and u, v and the padded size must be the geometry's; with patch=False C is
+    u.shape[0] and the image size the factors'.  ValueError for anything else: the kernels index the factors from these numbers."""
+    R = int(metadata["rank"])
+    if R < 1:
+        raise ValueError("stream metadata: 'rank' must be a positive integer")
+    u_shape, v_shape = tuple(int(x) for x in u_shape), tuple(int(x) for x in v_shape)
+    if metadata["patch"]:
+        p, q = (int(x) for x in metadata["patch size"])
+        H, W = (int(x) for x in metadata["original size"])
+        if p < 1 or q < 1 or len(u_shape) != 2 or len(v_shape) != 2:
+            raise ValueError("stream factors are not [M, R] / [C p q, R]")
+        if v_shape[0] % (p * q) or v_shape[0] == 0:
+            raise ValueError(f"stream factor v has {v_shape[0]} rows: not a multiple of the {p}x{q} patch")
+        C = v_shape[0] // (p * q)
+        Hp, Wp, M, N = chan_dims(H, W, C, (p, q))
+        if [int(x) for x in metadata["padded size"]] != [Hp, Wp] or u_shape != (M, R) or v_shape != (N, R):
+            raise ValueError("stream factors do not match the reflect-padded patch geometry its metadata describes")
+        return C, H, W, (p, q), R
+    if len(u_shape) != 3 or len(v_shape) != 3 or u_shape[0] != v_shape[0] or u_shape[2] != R or v_shape[2] != R:
+        raise ValueError("stream factors are not [C, H, R] / [C, W, R]")
+    C, H, W = u_shape[0], u_shape[1], v_shape[1]
+    chan_dims(H, W, C, None)
+    return C, H, W, None, R
 
 
 def check_metrics_args(a, b, want_ssim=True):
@@ -1492,6 +1543,73 @@ def _svd_methods():
                                               None if is_float else _dptr(qparams6), _dptr(rgb)))
         return rgb
 
+    def encode_gray(self, gray, R, num_iters=10, bounds=(-16, 15), sign=None, init=None):
+        """lrf_qmf_encode_gray_u8: gray uint8 [B,H,W] (CUDA) -> (U int8 [B,M,R], V int8 [B,64,R]); sign int8 [B,R];
+        init = (U0 [B,M,R], V0 [B,64,R]) fp32 overrides the SVD initialisation"""
+        import torch
+        gray = gray.contiguous()
+        B, H, W = gray.shape
+        assert gray.dtype == torch.uint8
+        _, _, M, N = chan_dims(H, W, 1, (8, 8))
+        U = torch.empty((B, M, R), dtype=torch.int8, device=gray.device)
+        V = torch.empty((B, N, R), dtype=torch.int8, device=gray.device)
+        u0 = v0 = None
+        if init is not None:
+            u0, v0 = (t.to(device=gray.device, dtype=torch.float32).contiguous() for t in init)
+            assert tuple(u0.shape) == (B, M, R) and tuple(v0.shape) == (B, N, R)
+        if sign is not None:
+            sign = sign.to(device=gray.device, dtype=torch.int8).contiguous()
+            assert tuple(sign.shape) == (B, R)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_encode_gray_u8(self._h, c_void_p(gray.data_ptr()), B, H, W, int(R), int(num_iters), int(bounds[0]), int(bounds[1]),
+                                              _dptr(sign), _dptr(u0), _dptr(v0), _dptr(U), _dptr(V)))
+        return U, V
+
+    def decode_gray(self, U, V, H, W):
+        """lrf_qmf_decode_gray_u8: int8 U [B,M,R], V [B,64,R] -> uint8 [B,H,W]"""
+        import torch
+        U, V = U.contiguous(), V.contiguous()
+        B, R = U.shape[0], U.shape[-1]
+        _, _, M, N = chan_dims(H, W, 1, (8, 8))
+        if tuple(U.shape) != (B, M, R) or tuple(V.shape) != (B, N, R) or U.dtype != torch.int8 or V.dtype != torch.int8:
+            raise ValueError(f"factor shapes {tuple(U.shape)} / {tuple(V.shape)} do not match the geometry {(B, M, R)} / {(B, N, R)}")
+        gray = torch.empty((B, H, W), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_decode_gray_u8(self._h, _dptr(U), _dptr(V), B, H, W, int(R), _dptr(gray)))
+        return gray
+
+    def chan_matrix(self, img, patch_size):
+        """img uint8 [B,C,H,W] (CUDA) -> X fp32: [B, M, C p q] for patches (p, q), [B, C, H, W] for patch_size None"""
+        import torch
+        img = img.contiguous()
+        B, C, H, W = img.shape
+        assert img.dtype == torch.uint8
+        p, q = (0, 0) if patch_size is None else (int(patch_size[0]), int(patch_size[1]))
+        _, _, M, N = chan_dims(H, W, C, patch_size)
+        X = torch.empty((B, C, H, W) if patch_size is None else (B, M, N), dtype=torch.float32, device=img.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_chan_matrix_u8(self._h, c_void_p(img.data_ptr()), B, C, H, W, p, q, _dptr(X)))
+        return X
+
+    def chan_decode(self, U, V, C, H, W, patch_size):
+        """int8 U [B,M,R] / V [B,C p q,R] (patches) or U [B,C,H,R] / V [B,C,W,R] (patch_size None) -> uint8 [B,C,H,W]"""
+        import torch
+        U, V = U.contiguous(), V.contiguous()
+        B, R = U.shape[0], U.shape[-1]
+        p, q = (0, 0) if patch_size is None else (int(patch_size[0]), int(patch_size[1]))
+        _, _, M, N = chan_dims(H, W, C, patch_size)
+        want_u, want_v = ((B, C, H, R), (B, C, W, R)) if patch_size is None else ((B, M, R), (B, N, R))
+        if tuple(U.shape) != want_u or tuple(V.shape) != want_v or U.dtype != torch.int8 or V.dtype != torch.int8:
+            raise ValueError(f"factor shapes {tuple(U.shape)} / {tuple(V.shape)} do not match the geometry {want_u} / {want_v}")
+        out = torch.empty((B, C, H, W), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_chan_decode_u8(self._h, _dptr(U), _dptr(V), B, C, H, W, p, q, int(R), _dptr(out)))
+        return out
+
+    Context.encode_gray = encode_gray
+    Context.decode_gray = decode_gray
+    Context.chan_matrix = chan_matrix
+    Context.chan_decode = chan_decode
     Context.quantize_u8 = quantize_u8
     Context.svd_decode_any = svd_decode_any
     Context.rgbspace_matrix_any = rgbspace_matrix_any

@@ -908,7 +908,8 @@ def streams_from_device_factors(ctx, U, V, sizes, triples, u_off, v_off, bounds,
 
 
 def qmf_encode_batch(images: torch.Tensor, rank=None, quality=None, bounds=(-16, 15), num_iters: int = 10,
-                     init_sign=None, pack_workers: Optional[int] = None, patch: bool = True, patch_size=(8, 8), deflate: str = "host") -> list:
+                     init_sign=None, pack_workers: Optional[int] = None, patch: bool = True, patch_size=(8, 8), deflate: str = "host",
+                     color_space: str = "YCbCr") -> list:
     """Batched qmf_encode (YCbCr branch) -> list of byte streams, one per image.  The factorisation of the whole batch
     runs on the GPU; for the default 8x8 patches the byte containers are packed by liblrf_pack.so on native host threads
     (`pack_workers` None / 0: as many as this process may use, default_pack_threads), or, with pack_workers="python", by the Python container code on a
@@ -917,8 +918,14 @@ def qmf_encode_batch(images: torch.Tensor, rank=None, quality=None, bounds=(-16,
     deflate="device": the columns are deflated on the GPU (Huffman-only zlib streams, lrf_deflate_columns_i8) while the factors
     are still there, and the host only folds them into the container: same factors, other bytes, read by every decoder.  8x8
     patches only (NotImplementedError otherwise).  A host tensor then takes the context path (upload, factorise, deflate), not
-    the pipelined encoder: wiring the pipe's slots to the coder is a follow-up."""
+    the pipelined encoder: wiring the pipe's slots to the coder is a follow-up.
+
+    color_space="RGB": gray images [B,1,H,W] with 8x8 patches, the streams of qmf_encode(images[i], color_space="RGB")
+    (_qmf_encode_batch_gray); other channel counts, patch settings and deflate="device" raise NotImplementedError."""
     assert (rank, quality) != (None, None), "Either 'rank' or 'quality' must be specified."
+    assert color_space in ("RGB", "YCbCr"), "`color_space` must be one of 'RGB' or 'YCbCr'."
+    if color_space == "RGB":  # gray images [B,1,H,W]: one lrf_qmf_encode_gray_u8 call
+        return _qmf_encode_batch_gray(images, rank, quality, bounds, num_iters, init_sign, pack_workers, patch, patch_size, deflate)
     H, W = images.shape[-2:]
     on_device = _deflate_on_device(deflate, patch, patch_size)
     if on_device:
@@ -1155,7 +1162,8 @@ def qmf_encode(image: torch.Tensor, rank=None, quality=None, color_space: str = 
                scale_factor=(0.5, 0.5), patch: bool = True, patch_size=(8, 8), bounds=(-16, 15),
                dtype: torch.dtype = torch.int8, **kwargs) -> bytes:
     """QMF compression of one image [3,H,W]: same signature and byte stream as the reference's
-    lrf.qmf_encode (lrf/compression/qmf.py:116-292)."""
+    lrf.qmf_encode (lrf/compression/qmf.py:116-292).  With color_space="RGB" the image may have any channel count [C,H,W],
+    1 <= C <= 16 (_qmf_encode_channels)."""
     assert (rank, quality) != (None, None), "Either 'rank' or 'quality' must be specified."
     assert color_space in ("RGB", "YCbCr"), "`color_space` must be one of 'RGB' or 'YCbCr'."
     num_iters, lo, hi, init_sign, qmf_opts = _check_hip_branch(color_space, scale_factor, patch, patch_size, bounds, dtype,
@@ -1163,8 +1171,18 @@ def qmf_encode(image: torch.Tensor, rank=None, quality=None, color_space: str = 
     if image.dtype != torch.uint8:
         raise NotImplementedError("HIP path takes uint8 images")
     H, W = image.shape[-2:]
+    C = image.shape[0] if image.dim() == 3 else 3
+    if C != 3:  # gray and n-channel images: the RGB colour-space branch, where the reference infers c (qmf.py:43-56)
+        if color_space != "RGB":
+            raise NotImplementedError(f"color_space='YCbCr' needs three channels, got {C}: use color_space='RGB' (the reference's "
+                                      "result there is an accident of einsum broadcasting)")
+        if qmf_opts:
+            raise NotImplementedError(f"{', '.join(sorted(qmf_opts))}: the general solver's options are not served for {C} channels")
     ctx = _lib.context(image.device.index if image.is_cuda else None)
     dev = (image if image.is_cuda else image.cuda(ctx.device)).unsqueeze(0)
+    if C != 3:
+        return _qmf_encode_channels(ctx, dev, rank, quality, bounds, (lo, hi), tuple(patch_size) if patch else None, num_iters, init_sign,
+                                    kwargs.get("init"))
     if qmf_opts:  # l2 / l1_ratio / eps / num_levels: the general solver behind the same driver (qmf.py:256 forwards them to QMF)
         return _qmf_encode_general(ctx, dev, color_space, rank, quality, bounds, tuple(patch_size) if patch else None, num_iters,
                                    init_sign, kwargs.get("init"), _lib.chroma_size(H, W, scale_factor) if color_space == "YCbCr" else None,
@@ -1461,6 +1479,92 @@ def _qmf_encode_rgbspace(ctx, dev, rank, quality, bounds, int_bounds, patch_size
     return combine_bytes([dict_to_bytes(metadata), combine_bytes([encode_tensor(np.ascontiguousarray(f)) for f in factors])])
 
 
+def _two_factor_stream(dtype_name, bounds, patch_size, hw, padded, R, factors) -> bytes:
+    """the container of the RGB colour-space branch (qmf.py:180-187, 204-212): its metadata, a scalar rank and two factors"""
+    metadata = {"dtype": dtype_name, "color space": "RGB", "patch": patch_size is not None, "bounds": bounds}
+    if patch_size is not None:
+        metadata.update({"patch size": patch_size, "original size": list(hw), "padded size": list(padded), "rank": R})
+    else:
+        metadata["rank"] = R
+    return combine_bytes([dict_to_bytes(metadata), combine_bytes([encode_tensor(np.ascontiguousarray(f)) for f in factors])])
+
+
+def _qmf_encode_channels(ctx, dev, rank, quality, bounds, int_bounds, patch_size, num_iters, init_sign, init):
+    """qmf_encode(color_space="RGB") of one image dev [1,C,H,W] with C != 3 (the reference infers c: lrf/compression/qmf.py:43-56,
+    164-212).  C = 1 with 8x8 patches and num_iters >= 1 is one [M,64] matrix, the shape of the tuned kernels: one
+    lrf_qmf_encode_gray_u8 call.  Every other form goes matrix (lrf_qmf_chan_matrix_u8) -> lrf_qmf_decompose_f32 / _bcd_f32 /
+    _svd_init_f32 (any shape), as _qmf_encode_rgbspace does for three channels."""
+    if isinstance(rank, (list, tuple)) or isinstance(quality, (list, tuple)):
+        raise ValueError("color_space='RGB' takes a scalar rank / quality")
+    C, H, W = dev.shape[-3:]
+    Hp, Wp, M, N = _lib.chan_dims(H, W, C, patch_size)
+    R = _lib.chan_rank(M, N, rank, quality)
+    nmat = 1 if patch_size is not None else C
+    sign = None if init_sign is None else torch.as_tensor(init_sign, dtype=torch.int8).reshape(-1, R).expand(nmat, R).contiguous()
+    u0 = v0 = None
+    if init is not None:
+        u0 = torch.as_tensor(init[0], dtype=torch.float32).reshape(nmat, M, R).contiguous().cuda(dev.device)
+        v0 = torch.as_tensor(init[1], dtype=torch.float32).reshape(nmat, N, R).contiguous().cuda(dev.device)
+    if C == 1 and patch_size == (8, 8) and num_iters >= 1:
+        U, V = ctx.encode_gray(dev[:, 0], R, num_iters, int_bounds, sign, None if init is None else (u0, v0))
+        Uh, Vh = ctx.to_host(U, V)
+        factors = [Uh[0].numpy(), Vh[0].numpy()]
+    else:
+        X = ctx.chan_matrix(dev, patch_size)
+        X = X[0] if patch_size is None else X  # [C, H, W]: C matrices; [1, M, N]: one
+        sg = None if sign is None else sign.cuda(dev.device)
+        if num_iters == 0:  # the float factors go straight through torch's truncating cast (qmf.py:188, 210)
+            if init is None:
+                u0, v0 = ctx.svd_init(X, R, sg)
+            u, v = u0.cpu().to(torch.int8), v0.cpu().to(torch.int8)
+        elif init is not None:
+            u, v = ctx.to_host(*ctx.bcd(X, u0, v0, num_iters, int_bounds[0], int_bounds[1]))
+        else:
+            u, v = ctx.to_host(*ctx.decompose(X, R, num_iters, int_bounds[0], int_bounds[1], sg))
+        u, v = u.numpy(), v.numpy()
+        factors = [u[0], v[0]] if patch_size is not None else [u, v]  # patch=False keeps the channel axis (qmf.py:208-210)
+    return _two_factor_stream(str(dev.dtype).split(".")[-1], bounds, patch_size, (H, W), (Hp, Wp), R, factors)
+
+
+def _qmf_encode_batch_gray(images, rank, quality, bounds, num_iters, init_sign, pack_workers, patch, patch_size, deflate) -> list:
+    """qmf_encode_batch(color_space="RGB") of gray images [B,1,H,W]: ONE lrf_qmf_encode_gray_u8 call, then the Python container
+    code on the pack pool (zlib releases the GIL) -> the streams qmf_encode(images[i], color_space="RGB") gives."""
+    if deflate not in ("host", "device"):
+        raise ValueError(f"deflate must be 'host' or 'device', got {deflate!r}")
+    if deflate == "device":
+        raise NotImplementedError("deflate='device' is not served with color_space='RGB' (two-factor containers are packed on the host)")
+    if images.dim() != 4 or images.shape[1] != 1:
+        raise NotImplementedError(f"qmf_encode_batch(color_space='RGB') serves gray images [B,1,H,W], got {tuple(images.shape)}: "
+                                  "other channel counts go one by one through qmf_encode")
+    if not patch or tuple(patch_size) != (8, 8):
+        raise NotImplementedError("qmf_encode_batch(color_space='RGB') serves 8x8 patches only: other patch settings go one by one "
+                                  "through qmf_encode")
+    if images.dtype != torch.uint8:
+        raise NotImplementedError("HIP path takes uint8 images")
+    if num_iters < 1:
+        raise NotImplementedError("qmf_encode_batch(color_space='RGB') needs num_iters >= 1")
+    if isinstance(rank, (list, tuple)) or isinstance(quality, (list, tuple)):
+        raise ValueError("color_space='RGB' takes a scalar rank / quality")
+    B, _, H, W = images.shape
+    Hp, Wp, M, N = _lib.chan_dims(H, W, 1, (8, 8))
+    R = _lib.chan_rank(M, N, rank, quality)
+    ctx = _lib.context(images.device.index if images.is_cuda else None)
+    dev = images if images.is_cuda else images.cuda(ctx.device)
+    sign = None if init_sign is None else torch.as_tensor(init_sign, dtype=torch.int8).reshape(-1, R).expand(B, R).contiguous()
+    U, V = ctx.encode_gray(dev[:, 0], R, num_iters, (math.ceil(bounds[0]), math.floor(bounds[1])), sign)
+    Uh, Vh = (t.numpy() for t in ctx.to_host(U, V))
+    dtype_name = str(images.dtype).split(".")[-1]
+
+    def pack(b):
+        return _two_factor_stream(dtype_name, bounds, (8, 8), (H, W), (Hp, Wp), R, [Uh[b], Vh[b]])
+
+    import os
+    workers = abs(pack_workers) if isinstance(pack_workers, int) and pack_workers else min(32, os.cpu_count() or 1)
+    if workers <= 1 or B == 1:
+        return [pack(b) for b in range(B)]
+    return list(_pack_pool(workers).map(pack, range(B)))
+
+
 def _svd_init_factors(ctx, dev, ranks, init_sign):
     """num_iters=0 (experiments/ablation_numiters/eval.py:51): the float SVD factors go straight through `.to(int8)`
     (lrf/compression/qmf.py:258-260), i.e. torch's truncating cast, done here with torch itself on the host."""
@@ -1681,15 +1785,19 @@ def _inflate_refusal(k, Rs, what) -> str:
 
 def qmf_decode_batch(streams: Sequence[bytes], device=None, inflate: str = "host") -> torch.Tensor:
     """Decodes streams of equal geometry and ranks -> uint8 CUDA tensor [B,3,H,W].  Streams of the other branches (another
-    patch size, patch=False, another chroma scale, the RGB colour space) are decoded one by one and stacked.
+    patch size, patch=False, another chroma scale, the RGB colour space) are decoded one by one and stacked, except gray
+    streams (RGB colour space, one channel, 8x8 patches) of one size and rank: one call -> [B,1,H,W].  A list that mixes gray
+    and colour streams raises ValueError; inflate="device" on gray streams NotImplementedError.
     inflate="device": the columns' zlib streams are inflated on the GPU (_factors_ragged_device) instead of on host threads."""
     on_device = _check_inflate(inflate)
     m_first = bytes_to_dict(separate_bytes(streams[0], 2)[0])
     H0, W0 = (m_first["original size"][0] if m_first["color space"] == "YCbCr" else (0, 0))
     if m_first["color space"] != "YCbCr" or not m_first["patch"] or list(m_first["patch size"]) != [8, 8] \
             or list(m_first["original size"][1]) != [H0 // 2, W0 // 2]:
-        one = _qmf_decode_rgbspace if m_first["color space"] == "RGB" else _qmf_decode_anyshape
-        return torch.stack([one(s) for s in streams])
+        if m_first["color space"] == "RGB":
+            _refuse_mixed_streams(streams)
+            return _qmf_decode_batch_rgbspace(streams, device, on_device)
+        return torch.stack([_qmf_decode_anyshape(s) for s in streams])
     if on_device:
         ctx, images, U, V = _factors_ragged_device(streams, device)
         H, W, ranks = images[0][:3]
@@ -1697,6 +1805,8 @@ def qmf_decode_batch(streams: Sequence[bytes], device=None, inflate: str = "host
             raise ValueError("streams differ in geometry or ranks")
         return ctx.decode_rgb(U.view(len(images), -1), V.view(len(images), -1), H, W, ranks)
     got = _factors_native(streams)
+    if got is None:
+        _refuse_mixed_streams(streams)
     metas, Uh, Vh = got if got is not None else _factors_python(streams)
     m0 = metas[0]
     for m in metas[1:]:
@@ -2048,38 +2158,76 @@ def qmf_decode_scaled(source, scale, device=None, inflate: str = "host") -> list
     return _resident(*_factors_ragged(source), device).decode(int(scale))
 
 
-def _qmf_decode_rgbspace(encoded_image: bytes, device=None) -> torch.Tensor:
-    """RGB colour-space branch of qmf_decode (lrf/compression/qmf.py:309-323) -> uint8 CUDA tensor [3,H,W]."""
+def _two_factor_parts(encoded_image: bytes):
+    """host only: -> (metadata, u, v, (C, H, W, patch_size, R)) of a stream of the RGB colour-space branch; the geometry from
+    _lib.chan_stream_geometry, which refuses factors that do not match the header"""
     encoded_metadata, encoded_factors = separate_bytes(encoded_image, 2)
     metadata = bytes_to_dict(encoded_metadata)
+    if metadata["color space"] != "RGB":
+        raise ValueError(f"not a stream of the RGB colour-space branch: {metadata['color space']!r}")
     if metadata["dtype"] != "uint8":
         raise NotImplementedError("HIP decode writes uint8 images")
     u, v = (decode_tensor(f) for f in separate_bytes(encoded_factors, 2))
     if u.dtype != np.int8 or v.dtype != np.int8:
         raise ValueError("stream factors are not int8")
-    R = int(metadata["rank"])
-    if metadata["patch"]:
-        patch_size = tuple(metadata["patch size"])
-        H, W = metadata["original size"]
-        Hp, Wp, M, N = _lib.rgbspace_dims_any(H, W, patch_size)
-        if list(metadata["padded size"]) != [Hp, Wp] or tuple(u.shape) != (M, R) or tuple(v.shape) != (N, R):
-            raise ValueError("stream factors do not match the reflect-padded patch geometry its metadata describes")
-    else:  # patch=False: u [3, H, R], v [3, W, R]; the image size is the factors' (qmf.py:320-323)
-        patch_size = None
-        if u.ndim != 3 or v.ndim != 3 or u.shape[0] != 3 or v.shape[0] != 3 or u.shape[2] != R or v.shape[2] != R:
-            raise ValueError("stream factors are not [3, H, R] / [3, W, R]")
-        H, W = int(u.shape[1]), int(v.shape[1])
+    return metadata, u, v, _lib.chan_stream_geometry(metadata, u.shape, v.shape)
+
+
+def _is_gray_stream(geom) -> bool:
+    C, _, _, patch_size, R = geom
+    return C == 1 and patch_size == (8, 8) and R <= 64
+
+
+def _qmf_decode_rgbspace(encoded_image: bytes, device=None) -> torch.Tensor:
+    """RGB colour-space branch of qmf_decode (lrf/compression/qmf.py:309-323) -> uint8 CUDA tensor [C,H,W]: C from the factor
+    shapes, as in the reference (v.shape[0] / (p q) with patches, u.shape[0] without)."""
+    _, u, v, geom = _two_factor_parts(encoded_image)
+    C, H, W, patch_size, R = geom
     ctx = _lib.context(device)
     U = torch.from_numpy(np.array(u, dtype=np.int8)).unsqueeze(0).cuda(ctx.device)  # copies: decode_tensor may return read-only views
     V = torch.from_numpy(np.array(v, dtype=np.int8)).unsqueeze(0).cuda(ctx.device)
-    if patch_size == (8, 8):
-        return ctx.qmf_rgbspace_decode(U, V, H, W)[0]
-    return ctx.qmf_rgbspace_decode_any(U, V, H, W, patch_size)[0]
+    if C == 3:
+        if patch_size == (8, 8):
+            return ctx.qmf_rgbspace_decode(U, V, H, W)[0]
+        return ctx.qmf_rgbspace_decode_any(U, V, H, W, patch_size)[0]
+    if _is_gray_stream(geom):
+        return ctx.decode_gray(U, V, H, W)
+    return ctx.chan_decode(U, V, C, H, W, patch_size)[0]
+
+
+def _qmf_decode_batch_rgbspace(streams: Sequence[bytes], device, on_device: bool) -> torch.Tensor:
+    """qmf_decode_batch of RGB colour-space streams: gray 8x8 streams of one size and rank in ONE lrf_qmf_decode_gray_u8 call
+    -> [B,1,H,W]; colour streams one by one and stacked, as before.  A list that mixes the two raises ValueError."""
+    parts = [_two_factor_parts(s) for s in streams]
+    gray = [_is_gray_stream(p[3]) for p in parts]
+    if not any(gray):
+        if any(p[3][0] != parts[0][3][0] for p in parts):
+            raise ValueError("streams differ in channel count")
+        return torch.stack([_qmf_decode_rgbspace(s, device) for s in streams])
+    if not all(gray):
+        raise ValueError("the list mixes gray and colour streams")
+    if on_device:
+        raise NotImplementedError("inflate='device' is not served for gray streams (two-factor containers inflate on the host)")
+    if any(p[3] != parts[0][3] for p in parts):
+        raise ValueError("streams differ in geometry or ranks")
+    _, H, W, _, _ = parts[0][3]
+    ctx = _lib.context(device)
+    U = torch.from_numpy(np.stack([np.asarray(p[1], dtype=np.int8) for p in parts])).cuda(ctx.device)
+    V = torch.from_numpy(np.stack([np.asarray(p[2], dtype=np.int8) for p in parts])).cuda(ctx.device)
+    return ctx.decode_gray(U, V, H, W).unsqueeze(1)
+
+
+def _refuse_mixed_streams(streams: Sequence[bytes]):
+    """ValueError when a list of default-branch streams also holds streams of the RGB colour space (gray among them)"""
+    spaces = {bytes_to_dict(separate_bytes(s, 2)[0])["color space"] for s in streams}
+    if len(spaces) > 1:
+        raise ValueError(f"the list mixes streams of different colour spaces ({', '.join(sorted(spaces))}): gray and colour streams "
+                         "decode in calls of their own")
 
 
 def qmf_decode(encoded_image: bytes) -> torch.Tensor:
     """Decode a QMF stream -> uint8 tensor [3,H,W] on the CPU, like the reference's lrf.qmf_decode
-    (lrf/compression/qmf.py:295-353)."""
+    (lrf/compression/qmf.py:295-353); [C,H,W] for an RGB colour-space stream of C channels."""
     meta = bytes_to_dict(separate_bytes(encoded_image, 2)[0])
     if meta["color space"] == "RGB":
         return _qmf_decode_rgbspace(encoded_image).cpu()

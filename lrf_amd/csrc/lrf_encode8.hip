@@ -314,13 +314,14 @@ static int init_to_fp32(lrf_ctx* c, const float* X, const Tables& t, const BcdPl
     return LRF_OK;
 }
 
-int lrf_qmf_decompose_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64_t N, int R, int K, int lo, int hi,
-                          const int8_t* sign, int8_t* U, int8_t* V)
+} // extern "C"
+
+// The 64-column route of lrf_qmf_decompose_f32 (own initialisation, R <= LRF_MAX_RANK) and of lrf_qmf_bcd_f32 (the caller's
+// factors, R <= LRF_BIG_TO_ANY_RANK): also what lrf_qmf_encode_gray_u8 (lrf_channels.hip) runs behind its planes kernel, so
+// that a gray batch takes the same plan and the same kernels as the same X handed in as floats.
+int decompose64(lrf_ctx* c, const float* X, int64_t B, int64_t M, int R, int K, int lo, int hi, const int8_t* sign, int8_t* U, int8_t* V)
 {
-    if (!c || !X || !U || !V) return set_err(LRF_EINVAL, "NULL argument");
-    static const bool force_any = dev_flag("LRF_FORCE_ANY");
-    if (N != LRF_PATCH_ELEMS || R > LRF_MAX_RANK || force_any) return any_decompose(c, X, B, M, N, R, K, lo, hi, sign, U, V);
-    int rc = check_params(M, N, R, K, lo, hi);
+    int rc = check_params(M, LRF_PATCH_ELEMS, R, K, lo, hi);
     if (rc) return rc;
     if (B < 1) return set_err(LRF_EINVAL, "B must be >= 1");
     LRF_ON_DEVICE(c);
@@ -336,12 +337,10 @@ int lrf_qmf_decompose_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int6
     return init_then_bcd(c, X, t, plan, sign, LRF_GRAM_EXP_FROM_DATA, U, V);
 }
 
-int lrf_qmf_bcd_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64_t N, int R, int K, int lo, int hi,
-                    const float* U0, const float* V0, int8_t* U, int8_t* V)
+int bcd64(lrf_ctx* c, const float* X, int64_t B, int64_t M, int R, int K, int lo, int hi, const float* U0, const float* V0, int8_t* U,
+          int8_t* V)
 {
-    if (!c || !X || !U || !V || !U0 || !V0) return set_err(LRF_EINVAL, "NULL argument");
-    if (N != LRF_PATCH_ELEMS || R > LRF_BIG_TO_ANY_RANK) return any_bcd(c, X, B, M, N, R, K, lo, hi, U0, V0, U, V);
-    int rc = check_params(M, N, R, K, lo, hi);
+    int rc = check_params(M, LRF_PATCH_ELEMS, R, K, lo, hi);
     if (rc) return rc;
     if (B < 1) return set_err(LRF_EINVAL, "B must be >= 1");
     LRF_ON_DEVICE(c);
@@ -353,6 +352,25 @@ int lrf_qmf_bcd_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64_t N,
                        (float*)c->vf.p, plan.rp);
     LAUNCH_CHECK();
     return run_bcd(c, X, plan, U0, U, V);
+}
+
+extern "C" {
+
+int lrf_qmf_decompose_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64_t N, int R, int K, int lo, int hi,
+                          const int8_t* sign, int8_t* U, int8_t* V)
+{
+    if (!c || !X || !U || !V) return set_err(LRF_EINVAL, "NULL argument");
+    static const bool force_any = dev_flag("LRF_FORCE_ANY");
+    if (N != LRF_PATCH_ELEMS || R > LRF_MAX_RANK || force_any) return any_decompose(c, X, B, M, N, R, K, lo, hi, sign, U, V);
+    return decompose64(c, X, B, M, R, K, lo, hi, sign, U, V);
+}
+
+int lrf_qmf_bcd_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64_t N, int R, int K, int lo, int hi,
+                    const float* U0, const float* V0, int8_t* U, int8_t* V)
+{
+    if (!c || !X || !U || !V || !U0 || !V0) return set_err(LRF_EINVAL, "NULL argument");
+    if (N != LRF_PATCH_ELEMS || R > LRF_BIG_TO_ANY_RANK) return any_bcd(c, X, B, M, N, R, K, lo, hi, U0, V0, U, V);
+    return bcd64(c, X, B, M, R, K, lo, hi, U0, V0, U, V);
 }
 
 int lrf_qmf_svd_init_f32(lrf_ctx* c, const float* X, int64_t B, int64_t M, int64_t N, int R, const int8_t* sign,

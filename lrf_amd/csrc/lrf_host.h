@@ -209,6 +209,11 @@ struct EncodePlan {
 // upload false: the caller uploads the tables itself (lrf_qmf_encode_rgb_u8, behind plan_x_residency, which marks blocks).
 int encode_rgb_prepare(lrf_ctx* c, int64_t B, int64_t H, int64_t W, const int R[3], int K, int lo, int hi, bool with_sign, bool fuse_gram,
                        EncodePlan& ep, bool upload = true);
+// B equal matrices [M,64]: the bodies of lrf_qmf_decompose_f32 (R <= LRF_MAX_RANK) and lrf_qmf_bcd_f32 (R <= LRF_BIG_TO_ANY_RANK)
+// for N = 64, shared with lrf_qmf_encode_gray_u8 (lrf_channels.hip)
+int decompose64(lrf_ctx* c, const float* X, int64_t B, int64_t M, int R, int K, int lo, int hi, const int8_t* sign, int8_t* U, int8_t* V);
+int bcd64(lrf_ctx* c, const float* X, int64_t B, int64_t M, int R, int K, int lo, int hi, const float* U0, const float* V0, int8_t* U,
+          int8_t* V);
 bool planes_gram_eligible(const uint8_t* rgb, int64_t B, int64_t H, int64_t W); // lrf_planes_gram.hip
 int planes_gram_from_rgb(lrf_ctx* c, const uint8_t* rgb, int64_t H, int64_t W, const ImageGeom& g, const Tables& t, float* X, bool luma_out = true);
 

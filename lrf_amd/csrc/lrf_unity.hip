@@ -11,3 +11,4 @@
 #include "lrf_metrics.hip"
 #include "lrf_deflate.hip"
 #include "lrf_inflate.hip"
+#include "lrf_channels.hip"
