@@ -623,6 +623,64 @@ int lrf_qmf_encode_gray_u8(lrf_ctx* ctx, const uint8_t* gray, int64_t B, int64_t
  * int32 sums of int8 products: exact for any int8 factors and any R <= LRF_MAX_RANK.  gray [B,H,W] uint8 (device). */
 int lrf_qmf_decode_gray_u8(lrf_ctx* ctx, const int8_t* U, const int8_t* V, int64_t B, int64_t H, int64_t W, int R, uint8_t* gray);
 
+/*
+ * The resident-factor loader for gray images: lists of gray 8x8 streams that differ in size and rank, decoded whole, at
+ * 1/2, 1/4, 1/8 scale, as windows and as resized crops, in one call each — the gray counterparts of
+ * lrf_qmf_decode_ragged_rgb_u8, lrf_qmf_decode_scaled_rgb_u8, lrf_qmf_decode_scaled_crops_rgb_u8 and
+ * lrf_qmf_decode_resized_crops_rgb_u8 with their _tensor forms.  One plane, no chroma, no colour conversion, no floating point
+ * before the tensor format: every byte below is defined in exact integers.
+ *   P        the int32 plane of an image: sum_r U[m,r] V[n,r], depatchified, centre-cropped to H x W (the padding of
+ *            lrf_chan_dims(H, W, 1, 8, 8): top = pad / 2, left = pad / 2)
+ *   level 1  L1 = clamp(P, 0, 255): the bytes of lrf_qmf_decode_gray_u8
+ *   level f  f = 2, 4, 8: Hs x Ws = ceil(H / f) x ceil(W / f) (lrf_scaled_dims).  Output pixel (i, j) covers image rows
+ *            f i .. min(f i + f, H) - 1 and the columns likewise (n pixels, 1..64: the partial blocks at the bottom and right
+ *            edge hold the pixels that exist); s = the sum of P over them (|s| <= 2^26: int32 is exact);
+ *            Lf = clamp(s, 0, 255 n) / n, the integer quotient.  The pooling comes before the clamp, as in the colour decoder.
+ *   images   [n] descriptors in host memory: U [M][R] at u_off, V [64][R] at v_off (int8 elements), 1 <= R <= 64
+ * lrf_qmf_decode_gray_ragged_u8: image i at level `scale` (1, 2, 4 or 8) is written as [Hs_i][Ws_i] bytes at out_off.
+ * lrf_qmf_decode_gray_crops_u8: window j = rows y0 .. y0 + h - 1, columns x0 .. x0 + w - 1 of level `scale` of image `image`
+ *   (lrf_scaled_crop; scale 1 is allowed here, so one call serves crops of mixed levels), written as [h][w] at h w j.
+ * lrf_qmf_decode_gray_resized_crops_u8: box j of lrf_resized_crop resampled to (oh, ow) by exactly the level rule, the taps and
+ *   the blend of lrf_qmf_decode_resized_crops_rgb_u8 with L the gray level above, written as [oh][ow] at oh ow j.  So a box of
+ *   the output's size is the plain crop, a box with y0, x0 multiples of f, h = f oh and w = f ow the crop of level f at
+ *   (y0 / f, x0 / f), and flip mirrors the columns.
+ * The _tensor forms write lrf_tensor_format's chain for one channel instead of the byte b: t = fl32(float(b) * scale[0]),
+ *   v = fl32(t + bias[0]), rounded to nearest even into dtype — not an fma.  Only element 0 of scale and bias is used (all
+ *   six must be finite); for one channel NCHW and NHWC are the same memory, so `layout` is validated and otherwise immaterial.
+ * An image's, a window's or a box's bytes depend on nothing else in the call.  Launches: one per level present for the ragged
+ * and the crops entries (at most 4), one per (path, level) for the resized crops (at most 8; the staged path decodes a tile's
+ * footprint into LDS once, boxes whose footprint does not fit take one output pixel per thread).
+ * Asynchronous on the context's stream (a caller's stream after lrf_ctx_set_stream) and timed under LRF_K_DECODE.  The image
+ * descriptors stay on the device between calls, keyed on their bytes, in a table of their own (the first call of a new image
+ * list uploads them and waits for the stream; lrf_ctx_trim releases them); the item lists travel stream-ordered through the
+ * pinned staging slots of lrf_qmf_decode_crops_rgb_u8, with no stream wait.  Everything is validated on the host before any
+ * launch, and a refused call writes nothing.  LRF_EINVAL: a NULL pointer, n / n_images outside [1,65535], n_crops outside
+ * [1,2^20], a rank outside [1,64], a size lrf_chan_dims(H, W, 1, 8, 8) refuses or of 2^31 pixels or more, a negative offset, a
+ * U, V or output range that leaves its buffer, a scale outside {1, 2, 4, 8}, h or w below 1, oh or ow outside [1,16384], a
+ * crop whose image index is out of range or whose rectangle leaves its (scaled) image, 2^31 or more workgroups in one launch,
+ * and for the _tensor forms what lrf_qmf_decode_crops_tensor lists for its format, `out` and out_bytes.
+ */
+typedef struct {
+    int64_t H, W;
+    int R;
+    int64_t u_off, v_off, out_off; /* out_off: lrf_qmf_decode_gray_ragged_u8 alone */
+} lrf_gray_image;
+int lrf_qmf_decode_gray_ragged_u8(lrf_ctx* ctx, int64_t n, const lrf_gray_image* images /* host */, int scale, const int8_t* U, int64_t u_len,
+                                  const int8_t* V, int64_t v_len, uint8_t* out, int64_t out_len);
+int lrf_qmf_decode_gray_crops_u8(lrf_ctx* ctx, int64_t n_images, const lrf_gray_image* images /* host; out_off ignored */, const int8_t* U,
+                                 int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops, const lrf_scaled_crop* crops /* host */, int64_t h,
+                                 int64_t w, uint8_t* out /* [n_crops][h][w] */, int64_t out_len);
+int lrf_qmf_decode_gray_crops_tensor(lrf_ctx* ctx, int64_t n_images, const lrf_gray_image* images /* host; out_off ignored */, const int8_t* U,
+                                     int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops, const lrf_scaled_crop* crops /* host */,
+                                     int64_t h, int64_t w, const lrf_tensor_format* fmt /* host */, void* out, int64_t out_bytes);
+int lrf_qmf_decode_gray_resized_crops_u8(lrf_ctx* ctx, int64_t n_images, const lrf_gray_image* images /* host; out_off ignored */, const int8_t* U,
+                                         int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops, const lrf_resized_crop* crops /* host */,
+                                         int64_t oh, int64_t ow, uint8_t* out /* [n_crops][oh][ow] */, int64_t out_len);
+int lrf_qmf_decode_gray_resized_crops_tensor(lrf_ctx* ctx, int64_t n_images, const lrf_gray_image* images /* host; out_off ignored */,
+                                             const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len, int64_t n_crops,
+                                             const lrf_resized_crop* crops /* host */, int64_t oh, int64_t ow,
+                                             const lrf_tensor_format* fmt /* host */, void* out, int64_t out_bytes);
+
 /* The general route, 1 <= C <= 16, any patch size or none (qmf.py:164-212, decode :309-323): the host forms the matrices with
  * lrf_qmf_chan_matrix_u8, factorises them with lrf_qmf_decompose_f32 / lrf_qmf_bcd_f32 / lrf_qmf_svd_init_f32 (any shape; their
  * limits and errors apply) and decodes with lrf_qmf_chan_decode_u8.

@@ -60,6 +60,11 @@ class TensorFormat(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_int32), ("layout", ctypes.c_int32), ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3)]
 
 
+class GrayImage(ctypes.Structure):
+    """lrf_gray_image (include/lrf_hip.h)"""
+    _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int), ("u_off", c_i64), ("v_off", c_i64), ("out_off", c_i64)]
+
+
 class RaggedEncodeImage(ctypes.Structure):
     """lrf_ragged_encode_image (include/lrf_hip.h)"""
     _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int * 3), ("rgb_off", c_i64), ("u_off", c_i64), ("v_off", c_i64), ("sign_off", c_i64)]
@@ -163,6 +168,13 @@ def load():
         lib.lrf_qmf_encode_gray_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p]
         lib.lrf_qmf_decode_gray_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p]
+        gray_list = [c_void_p, c_i64, ctypes.POINTER(GrayImage), c_void_p, c_i64, c_void_p, c_i64, c_i64]
+        lib.lrf_qmf_decode_gray_ragged_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(GrayImage), c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_decode_gray_crops_u8.argtypes = gray_list + [ctypes.POINTER(ScaledCrop), c_i64, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_decode_gray_crops_tensor.argtypes = gray_list + [ctypes.POINTER(ScaledCrop), c_i64, c_i64, ctypes.POINTER(TensorFormat), c_void_p, c_i64]
+        lib.lrf_qmf_decode_gray_resized_crops_u8.argtypes = gray_list + [ctypes.POINTER(ResizedCrop), c_i64, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_decode_gray_resized_crops_tensor.argtypes = gray_list + [ctypes.POINTER(ResizedCrop), c_i64, c_i64, ctypes.POINTER(TensorFormat), c_void_p,
+                                                                             c_i64]
         lib.lrf_qmf_chan_matrix_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_void_p]
         lib.lrf_qmf_chan_decode_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_void_p]
         lib.lrf_plane_dims_any.argtypes = [c_i64, c_i64, c_int, c_int, c_int] + [ctypes.POINTER(c_i64)] * 6
@@ -201,7 +213,8 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_decode_crops_tensor", "lrf_qmf_decode_scaled_crops_tensor", "lrf_qmf_decode_resized_crops_tensor", "lrf_qmf_encode_ragged_rgb_u8", "lrf_qmf_encode_ragged_sweep_rgb_u8", "lrf_qmf_sse_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
-           "lrf_chan_dims", "lrf_qmf_encode_gray_u8", "lrf_qmf_decode_gray_u8", "lrf_qmf_chan_matrix_u8", "lrf_qmf_chan_decode_u8",
+           "lrf_chan_dims", "lrf_qmf_encode_gray_u8", "lrf_qmf_decode_gray_u8", "lrf_qmf_decode_gray_ragged_u8", "lrf_qmf_decode_gray_crops_u8",
+           "lrf_qmf_decode_gray_crops_tensor", "lrf_qmf_decode_gray_resized_crops_u8", "lrf_qmf_decode_gray_resized_crops_tensor", "lrf_qmf_chan_matrix_u8", "lrf_qmf_chan_decode_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
            "lrf_qmf_decode_any_hw_u8",
            "lrf_pipe_create", "lrf_pipe_destroy", "lrf_pipe_slots", "lrf_pipe_slot_ctx", "lrf_pipe_workspace_bytes",
@@ -618,6 +631,145 @@ def _tensor_output(entry, out, n, h, w, dtype, channels_last, device):
     if any(st != wt for st, wt, size in zip(out.stride(), want, out.shape) if size > 1):
         raise ValueError(f"{entry}: out must be {'channels_last' if channels_last else 'contiguous'} memory (strides {want}), got strides {tuple(out.stride())}")
     return out
+
+
+GRAY_SCALES = (1, 2, 4, 8)  # the levels of the gray loader (lrf_qmf_decode_gray_ragged_u8, lrf_qmf_decode_gray_crops_u8)
+
+
+def check_gray_images(U, V, images):
+    """The image list of the gray loader (lrf_gray_image), before any device is touched.  U, V: flat int8 tensors on one device;
+    images: 1 to 65535 tuples (H, W, R, u_off, v_off), R one rank in 1..64, the image's U [M, R] and V [64, R] inside U and V, M
+    from lrf_chan_dims(H, W, 1, 8, 8) (which refuses sizes the decoder refuses).  TypeError for anything but int8 tensors,
+    ValueError for everything else.  -> [(H, W, R, u_off, v_off)] as integers."""
+    import torch
+    if not isinstance(U, torch.Tensor) or not isinstance(V, torch.Tensor) or U.dtype != torch.int8 or V.dtype != torch.int8:
+        raise TypeError("factors must be int8 tensors")
+    if U.dim() != 1 or V.dim() != 1 or U.device != V.device or not U.is_contiguous() or not V.is_contiguous():
+        raise ValueError(f"U and V must be flat contiguous tensors on one device, got {tuple(U.shape)} on {U.device} and {tuple(V.shape)} on {V.device}")
+    if images is None or len(images) < 1 or len(images) > 65535:
+        raise ValueError("the gray loader needs 1 to 65535 images")
+    out = []
+    for i, im in enumerate(images):
+        if len(im) != 5 or hasattr(im[2], "__len__"):
+            raise ValueError(f"image {i}: (H, W, R, u_off, v_off) expected")
+        if any(int(x) != x for x in im):
+            raise ValueError(f"image {i}: integers expected")
+        H, W, R, u_off, v_off = (int(x) for x in im)
+        if H < 1 or W < 1 or H * W >= 2 ** 31 or R < 1 or R > 64:
+            raise ValueError(f"image {i}: size {H}x{W} or rank {R} out of range (rank 1..64, fewer than 2^31 pixels)")
+        M = chan_dims(H, W, 1, (8, 8))[2]
+        if u_off < 0 or v_off < 0 or u_off + M * R > U.numel() or v_off + 64 * R > V.numel():
+            raise ValueError(f"image {i}: its factors (U {M * R} elements at {u_off}, V {64 * R} at {v_off}) leave the buffers of "
+                             f"{U.numel()} and {V.numel()} elements")
+        out.append((H, W, R, u_off, v_off))
+    return out
+
+
+def gray_scaled_dims(H, W, scale):
+    """(ceil(H / scale), ceil(W / scale)) for scale 1, 2, 4, 8"""
+    if isinstance(scale, bool) or int(scale) != scale or int(scale) not in GRAY_SCALES:
+        raise ValueError(f"scale {scale!r}: 1, 2, 4 or 8 expected")
+    return -(-int(H) // int(scale)), -(-int(W) // int(scale))
+
+
+def check_gray_scale(scale):
+    """the level of a whole-image decode of the gray loader: TypeError unless an integer, ValueError unless 1, 2, 4 or 8 -> int"""
+    import numpy as np
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)):
+        raise TypeError(f"scale must be an integer, got {scale!r}")
+    if int(scale) not in GRAY_SCALES:
+        raise ValueError(f"scale {scale}: 1, 2, 4 or 8 expected")
+    return int(scale)
+
+
+def check_gray_crop_args(U, V, images, crops, size):
+    """The argument checks of lrf_qmf_decode_gray_crops_u8, before any device is touched.  U, V, images: as check_gray_images takes
+    them; crops: an integer array-like [n, 4] of (image, scale, y0, x0) on the host, 1 <= n <= 2^20, the scale per crop out of 1,
+    2, 4, 8 and y0, x0 in the image at that scale; size: (h, w), both >= 1; every window inside its image's scaled size.
+    -> (images, crops as an int32 array [n, 4], (h, w))."""
+    import numpy as np
+    ims = check_gray_images(U, V, images)
+    h, w = _check_size(size)
+    boxes = _check_boxes(crops, ("image", "scale", "y0", "x0"), "decode_crops")
+    Hs, Ws = _check_box_images(boxes, ims)
+    bad = np.flatnonzero(~np.isin(boxes[:, 1], GRAY_SCALES))
+    if bad.size:
+        raise ValueError(f"crop {bad[0]}: scale {boxes[bad[0], 1]}: 1, 2, 4 or 8 expected")
+    f = boxes[:, 1]
+    Hs, Ws = -(-Hs // f), -(-Ws // f)
+    bad = np.flatnonzero((boxes[:, 2] < 0) | (boxes[:, 3] < 0) | (boxes[:, 2] + h > Hs) | (boxes[:, 3] + w > Ws))
+    if bad.size:
+        j = bad[0]
+        raise ValueError(f"crop {j}: {h}x{w} at ({boxes[j, 2]}, {boxes[j, 3]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]} at scale 1/{f[j]}")
+    return ims, np.ascontiguousarray(boxes, dtype=np.int32), (h, w)
+
+
+def check_gray_resized_args(U, V, images, crops, size):
+    """The argument checks of lrf_qmf_decode_gray_resized_crops_u8, before any device is touched: check_resized_args for a gray
+    image list (check_gray_images) -> (images, crops as an int32 array [n, 6] with flip 0 or 1, (oh, ow))."""
+    import numpy as np
+    ims = check_gray_images(U, V, images)
+    oh, ow = _check_size(size, RESIZED_MAX_SIDE)
+    boxes = _check_boxes(crops, ("image", "y0", "x0", "h", "w", "flip"), "decode_resized_crops")
+    Hs, Ws = _check_box_images(boxes, ims)
+    bad = np.flatnonzero((boxes[:, 3] < 1) | (boxes[:, 4] < 1))
+    if bad.size:
+        raise ValueError(f"crop {bad[0]}: box of {boxes[bad[0], 3]}x{boxes[bad[0], 4]}: both sides must be >= 1")
+    bad = np.flatnonzero((boxes[:, 1] < 0) | (boxes[:, 2] < 0) | (boxes[:, 1] + boxes[:, 3] > Hs) | (boxes[:, 2] + boxes[:, 4] > Ws))
+    if bad.size:
+        j = bad[0]
+        raise ValueError(f"crop {j}: {boxes[j, 3]}x{boxes[j, 4]} at ({boxes[j, 1]}, {boxes[j, 2]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]}")
+    boxes[:, 5] = boxes[:, 5] != 0
+    return ims, np.ascontiguousarray(boxes, dtype=np.int32), (oh, ow)
+
+
+def _one_number(v, name):
+    """None, one number or a sequence of one -> that number for check_tensor_format, or None; three numbers (a colour triple) and
+    any other count: ValueError"""
+    if v is None or not hasattr(v, "__len__") or isinstance(v, (str, bytes)):
+        return v  # (a scalar, or a type check_tensor_format refuses)
+    if hasattr(v, "tolist"):
+        v = v.tolist()
+    if not isinstance(v, (list, tuple)):
+        return v
+    if len(v) != 1:
+        raise ValueError(f"{name} of a gray image must hold one value (one channel), got {len(v)}")
+    return v[0]
+
+
+def check_gray_tensor_request(entry, dtype, mean, std, channels_last, out):
+    """_tensor_request for the gray loader: mean and std are None, one number or a sequence of one (three numbers: ValueError);
+    only element 0 of the format's scale and bias is read -> None for the uint8 entry, else the TensorFormat"""
+    import torch
+    if dtype == torch.uint8:
+        if mean is not None or std is not None or channels_last or out is not None:
+            raise ValueError(f"{entry}: mean, std, channels_last and out= go with a float dtype (dtype=torch.uint8 is the byte entry, [n,1,h,w])")
+        return None
+    return check_tensor_format(dtype, _one_number(mean, "mean"), _one_number(std, "std"), channels_last)
+
+
+def _gray_tensor_output(entry, out, n, h, w, dtype, device):
+    """the [n,1,h,w] result of a gray tensor entry: the caller's `out`, checked (a refusal launches nothing), or a new tensor.  With
+    one channel NCHW and channels_last are the same memory: n images of h w elements, rows of w"""
+    import torch
+    if out is None:
+        return torch.empty((n, 1, h, w), dtype=dtype, device=device)
+    if not isinstance(out, torch.Tensor):
+        raise TypeError(f"{entry}: out must be a tensor, got {type(out).__name__}")
+    if out.dtype != dtype or tuple(out.shape) != (n, 1, h, w) or out.device != device:
+        raise ValueError(f"{entry}: out must be {dtype} {(n, 1, h, w)} on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    want = (h * w, None, w, 1)  # (the stride of the channel axis of size 1 is immaterial)
+    if any(wt is not None and st != wt for st, wt, size in zip(out.stride(), want, out.shape) if size > 1):
+        raise ValueError(f"{entry}: out must be dense memory (strides {(h * w, h * w, w, 1)}), got strides {tuple(out.stride())}")
+    return out
+
+
+def _gray_images(ims, out_offs=None):
+    """the lrf_gray_image array of a checked image list (check_gray_images); out_offs: where each image's output starts, else 0"""
+    desc = (GrayImage * len(ims))()
+    for i, (d, (H, W, R, u_off, v_off)) in enumerate(zip(desc, ims)):
+        d.H, d.W, d.R, d.u_off, d.v_off, d.out_off = H, W, R, u_off, v_off, 0 if out_offs is None else out_offs[i]
+    return desc
 
 
 def check_encode_ragged_args(rgb, images, sign=None):
@@ -1212,6 +1364,75 @@ class Context:
         check(self._lib.lrf_qmf_decode_resized_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
                                                             boxes.ctypes.data_as(ctypes.POINTER(ResizedCrop)), oh, ow, _dptr(rgb), rgb.numel()))
         return rgb
+
+    def decode_gray_ragged(self, U, V, images, scale=1):
+        """Gray images that differ in size and rank in one call, whole or at 1/2, 1/4, 1/8 scale (lrf_qmf_decode_gray_ragged_u8).
+        U, V: flat int8 CUDA tensors; images: [(H, W, R, u_off, v_off)], image i's U [M, R] at U[u_off:], V [64, R] at V[v_off:];
+        scale: 1, 2, 4 or 8 -> a list of uint8 CUDA tensors [1, ceil(H_i / scale), ceil(W_i / scale)]: views of one buffer, each
+        starting at a multiple of 16 bytes.  Asynchronous on torch's current stream."""
+        import torch
+        ims, scale = check_gray_images(U, V, images), check_gray_scale(scale)
+        self._need_here("decode_gray_ragged", U)
+        sizes = [gray_scaled_dims(H, W, scale) for H, W, *_ in ims]
+        offs, off = [], 0
+        for hs, ws in sizes:
+            offs.append(off)
+            off = (off + hs * ws + 15) // 16 * 16
+        desc = _gray_images(ims, offs)
+        out = torch.empty((off,), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_decode_gray_ragged_u8(self._h, len(ims), desc, scale, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(out), out.numel()))
+        return [out[o:o + hs * ws].view(1, hs, ws) for o, (hs, ws) in zip(offs, sizes)]
+
+    def decode_gray_crops(self, U, V, images, crops, size, dtype=None, mean=None, std=None, channels_last=False, out=None):
+        """Windows of gray images straight from the factors, each at its own level (lrf_qmf_decode_gray_crops_u8).  U, V, images: as
+        decode_gray_ragged takes them; crops: an integer array-like [n, 4] of (image, scale, y0, x0) on the host, the scale per
+        crop out of 1, 2, 4, 8 and y0, x0 in the image at that scale; size: (h, w) -> a uint8 CUDA tensor [n, 1, h, w], crop j equal
+        to decode_gray_ragged of its image at its scale sliced [:, y0:y0+h, x0:x0+w].  Asynchronous on torch's current stream; a new
+        crop list costs no stream wait (a new image list does, once).
+        dtype=torch.float32 / float16 / bfloat16: the model's tensor instead (lrf_qmf_decode_gray_crops_tensor), every byte b as
+        (b * scale) + bias in fp32 (two roundings) rounded to dtype; mean, std: None, one number or a sequence of one;
+        channels_last: validated and otherwise immaterial (one channel: the same memory); out: a dense [n, 1, h, w] tensor of that
+        dtype on this device (a slice along n of a larger batch, say), written in place."""
+        import torch
+        fmt = check_gray_tensor_request("decode_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
+        ims, boxes, (h, w) = check_gray_crop_args(U, V, images, crops, size)
+        self._need_here("decode_gray_crops", U)
+        desc = _gray_images(ims)
+        n = boxes.shape[0]
+        lead = (self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n, boxes.ctypes.data_as(ctypes.POINTER(ScaledCrop)), h, w)
+        if fmt is not None:
+            res = _gray_tensor_output("decode_crops", out, n, h, w, dtype, U.device)
+            self.use_torch_stream()
+            check(self._lib.lrf_qmf_decode_gray_crops_tensor(*lead, ctypes.byref(fmt), c_void_p(res.data_ptr()), res.numel() * res.element_size()))
+            return res
+        res = torch.empty((n, 1, h, w), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_decode_gray_crops_u8(*lead, _dptr(res), res.numel()))
+        return res
+
+    def decode_gray_resized_crops(self, U, V, images, crops, size, dtype=None, mean=None, std=None, channels_last=False, out=None):
+        """Boxes of any size out of gray images resampled to one output size straight from the factors
+        (lrf_qmf_decode_gray_resized_crops_u8).  U, V, images: as decode_gray_ragged takes them; crops: an integer array-like
+        [n, 6] of (image, y0, x0, h, w, flip) on the host, the box in full-resolution pixels; size: (oh, ow) -> a uint8 CUDA
+        tensor [n, 1, oh, ow]: the level rule, taps and blend of decode_resized_crops on the gray levels.
+        dtype, mean, std, channels_last, out: as decode_gray_crops takes them (lrf_qmf_decode_gray_resized_crops_tensor)."""
+        import torch
+        fmt = check_gray_tensor_request("decode_resized_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
+        ims, boxes, (oh, ow) = check_gray_resized_args(U, V, images, crops, size)
+        self._need_here("decode_gray_resized_crops", U)
+        desc = _gray_images(ims)
+        n = boxes.shape[0]
+        lead = (self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n, boxes.ctypes.data_as(ctypes.POINTER(ResizedCrop)), oh, ow)
+        if fmt is not None:
+            res = _gray_tensor_output("decode_resized_crops", out, n, oh, ow, dtype, U.device)
+            self.use_torch_stream()
+            check(self._lib.lrf_qmf_decode_gray_resized_crops_tensor(*lead, ctypes.byref(fmt), c_void_p(res.data_ptr()), res.numel() * res.element_size()))
+            return res
+        res = torch.empty((n, 1, oh, ow), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_decode_gray_resized_crops_u8(*lead, _dptr(res), res.numel()))
+        return res
 
     def encode_ragged(self, rgb, images, K, lo, hi, sign=None):
         """Images that differ in size and ranks in one encode (lrf_qmf_encode_ragged_rgb_u8).  rgb: a flat uint8 CUDA tensor;

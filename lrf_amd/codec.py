@@ -1915,8 +1915,15 @@ def qmf_decode_ragged(streams: Sequence[bytes], device=None, inflate: str = "hos
     in one call: -> a list of uint8 CUDA tensors [3,H_i,W_i] in input order (views of one buffer), each equal to
     qmf_decode of its stream.  The default branch only (YCbCr, 8x8 patches, chroma (0.5, 0.5), uint8): a stream of another
     branch raises NotImplementedError naming it.  One host-to-device copy of all U factors, one of all V, one kernel call.
-    inflate="device": the streams' payloads go up in one copy and are inflated on the GPU (_factors_ragged_device)."""
-    if _check_inflate(inflate):
+    inflate="device": the streams' payloads go up in one copy and are inflated on the GPU (_factors_ragged_device).
+    A list whose every stream is a gray stream (RGB colour space, one channel, 8x8 patches, uint8; sizes and ranks may differ)
+    takes the gray loader instead: -> uint8 CUDA tensors [1,H_i,W_i], views of one buffer (inflate="device": NotImplementedError)."""
+    on_device = _check_inflate(inflate)
+    gray = _gray_factors_ragged(streams)
+    if gray is not None:
+        _refuse_gray_inflate(on_device)
+        return _resident_gray(*gray, device).decode()
+    if on_device:
         ctx, images, U, V = _factors_ragged_device(streams, device)
         return ctx.decode_ragged(U, V, images)
     images, Uh, Vh = _factors_ragged(streams)
@@ -1991,10 +1998,12 @@ def _decode_crops_at_scales(ctx, U, V, images, crops, size, scale, **tensor) -> 
 class ResidentFactors:
     """The factors of a list of streams resident on one device (qmf_load_factors): flat int8 U and V, the image table decode_ragged
     takes, and the images' sizes.  A dataset kept this way costs its int8 factors, not its pixels; .decode() gives whole images,
-    .decode_crops(crops, size) windows of them, both also at 1/2, 1/4 or 1/8 scale (scale=)."""
+    .decode_crops(crops, size) windows of them, both also at 1/2, 1/4 or 1/8 scale (scale=).
+    channels: 3 for colour streams (images: (H, W, ranks, u_off, v_off)), 1 for a list of gray streams (images: (H, W, R, u_off,
+    v_off), one factor pair each): the same methods, results [1, H, W] / [n, 1, h, w], served by the gray loader's kernels."""
 
-    def __init__(self, ctx, U, V, images):
-        self._ctx, self.U, self.V, self.images = ctx, U, V, images
+    def __init__(self, ctx, U, V, images, channels=3):
+        self._ctx, self.U, self.V, self.images, self.channels = ctx, U, V, images, channels
         self.sizes = [(im[0], im[1]) for im in images]
 
     def __len__(self):
@@ -2006,6 +2015,8 @@ class ResidentFactors:
 
     def decode(self, scale=1) -> list:
         """every image: what qmf_decode_ragged gives for the streams; scale 2, 4, 8: what qmf_decode_scaled gives"""
+        if self.channels == 1:
+            return self._ctx.decode_gray_ragged(self.U, self.V, self.images, scale)
         if type(scale) is int and scale == 1:
             return self._ctx.decode_ragged(self.U, self.V, self.images)
         return self._ctx.decode_scaled(self.U, self.V, self.images, scale)
@@ -2014,6 +2025,9 @@ class ResidentFactors:
         """crops: integers [n, 3] of (image, y0, x0) on the host; size: (h, w) -> uint8 CUDA [n, 3, h, w].  scale: 1, 2, 4, 8 or
         one of them per crop: crop j is the window (y0, x0) of its image decoded at 1/scale_j, y0 and x0 in that scaled image.
         dtype, mean, std, channels_last, out: the model's tensor instead of bytes, as qmf_decode_crops describes"""
+        if self.channels == 1:  # per-crop scales go to the device in one call: the gray entry takes scale 1 too
+            tensor = _gray_tensor_kwargs("decode_crops", dtype, mean, std, channels_last, out)
+            return self._ctx.decode_gray_crops(self.U, self.V, self.images, _gray_crop_rows(crops, scale), size, **tensor)
         tensor = _tensor_kwargs("decode_crops", dtype, mean, std, channels_last, out)
         if type(scale) is int and scale == 1:
             return self._ctx.decode_crops(self.U, self.V, self.images, crops, size, **tensor)
@@ -2023,6 +2037,9 @@ class ResidentFactors:
         """boxes: integers [n, 5] of (image, y0, x0, h, w) on the host, full-resolution pixels; size: (oh, ow); flip: None, one
         bool, or one bool per box (mirror the output's columns) -> uint8 CUDA [n, 3, oh, ow]: qmf_decode_resized_crops, which
         also describes dtype, mean, std, channels_last and out"""
+        if self.channels == 1:
+            return self._ctx.decode_gray_resized_crops(self.U, self.V, self.images, _resized_boxes(boxes, flip), size,
+                                                       **_gray_tensor_kwargs("decode_resized_crops", dtype, mean, std, channels_last, out))
         return self._ctx.decode_resized_crops(self.U, self.V, self.images, _resized_boxes(boxes, flip), size,
                                               **_tensor_kwargs("decode_resized_crops", dtype, mean, std, channels_last, out))
 
@@ -2033,6 +2050,61 @@ def _tensor_kwargs(entry, dtype, mean, std, channels_last, out) -> dict:
     if _lib._tensor_request(entry, dtype, mean, std, channels_last, out) is None:
         return {}
     return dict(dtype=dtype, mean=mean, std=std, channels_last=channels_last, out=out)
+
+
+def _gray_tensor_kwargs(entry, dtype, mean, std, channels_last, out) -> dict:
+    """_tensor_kwargs for a gray source: mean and std are None, one number or a sequence of one (three numbers: ValueError)"""
+    if _lib.check_gray_tensor_request(entry, dtype, mean, std, channels_last, out) is None:
+        return {}
+    return dict(dtype=dtype, mean=mean, std=std, channels_last=channels_last, out=out)
+
+
+def _gray_crop_rows(crops, scale):
+    """crops: integers [n, 3] of (image, y0, x0) on the host; scale: 1, 2, 4, 8 or one of them per crop -> an int64 array [n, 4]
+    of (image, scale, y0, x0), the rows Context.decode_gray_crops takes (which validates the windows themselves)"""
+    boxes = _lib._check_boxes(crops, ("image", "y0", "x0"), "decode_crops")
+    sc = _crop_scales(scale, boxes.shape[0])
+    return np.concatenate([boxes[:, :1], sc[:, None], boxes[:, 1:]], axis=1)
+
+
+def _gray_factors_ragged(streams):
+    """None unless every stream of the list is a gray stream (RGB colour space, one channel, 8x8 patches, uint8: _is_gray_stream
+    of _two_factor_parts, which validates the factors against the header) — every other list, a malformed one included, is left
+    to the code and the errors it always had.  Else ([(H, W, R, u_off, v_off)], U int8 flat, V int8 flat) on the host: image i's
+    U [M, R] and V [64, R] back to back.  No GPU is touched."""
+    if isinstance(streams, (bytes, bytearray, str)) or not hasattr(streams, "__len__") or len(streams) < 1:
+        return None
+    parts = []
+    for s in streams:
+        if not isinstance(s, (bytes, bytearray)):
+            return None
+        try:
+            if bytes_to_dict(separate_bytes(bytes(s), 2)[0])["color space"] != "RGB":
+                return None
+            part = _two_factor_parts(bytes(s))
+        except Exception:
+            return None
+        if not _is_gray_stream(part[3]):
+            return None
+        parts.append(part)
+    images, uo, vo = [], 0, 0
+    for _, u, v, (_, H, W, _, R) in parts:
+        images.append((H, W, R, uo, vo))
+        uo += u.shape[0] * R
+        vo += 64 * R
+    U = np.concatenate([np.asarray(p[1], dtype=np.int8).reshape(-1) for p in parts])
+    V = np.concatenate([np.asarray(p[2], dtype=np.int8).reshape(-1) for p in parts])
+    return images, U, V
+
+
+def _refuse_gray_inflate(on_device):
+    if on_device:
+        raise NotImplementedError("inflate='device' is not served for gray streams (two-factor containers inflate on the host)")
+
+
+def _resident_gray(images, Uh, Vh, device) -> ResidentFactors:
+    ctx = _lib.context(device)
+    return ResidentFactors(ctx, torch.from_numpy(Uh).cuda(ctx.device), torch.from_numpy(Vh).cuda(ctx.device), images, channels=1)
 
 
 def _resized_boxes(boxes, flip):
@@ -2072,8 +2144,14 @@ def _resident(images, Uh, Vh, device) -> ResidentFactors:
 def qmf_load_factors(streams: Sequence[bytes], device=None, inflate: str = "host") -> ResidentFactors:
     """Parses and validates the streams once (the default branch only, as qmf_decode_ragged: a stream of another branch raises
     NotImplementedError naming it) and uploads their factors once -> ResidentFactors.  inflate="device": the compressed payloads
-    are uploaded instead and inflated on the GPU."""
-    if _check_inflate(inflate):
+    are uploaded instead and inflated on the GPU.  A list whose every stream is a gray stream (RGB colour space, one channel, 8x8
+    patches, uint8) gives a ResidentFactors with channels == 1 (inflate="device": NotImplementedError)."""
+    on_device = _check_inflate(inflate)
+    gray = _gray_factors_ragged(streams)
+    if gray is not None:
+        _refuse_gray_inflate(on_device)
+        return _resident_gray(*gray, device)
+    if on_device:
         ctx, images, U, V = _factors_ragged_device(streams, device)
         return ResidentFactors(ctx, U, V, images)
     return _resident(*_factors_ragged(streams), device)
@@ -2091,8 +2169,20 @@ def qmf_decode_crops(source, crops, size, device=None, inflate: str = "host", sc
     scale_k = float32(1 / (255 std_k)) and bias_k = float32(-mean_k / std_k) — torchvision's ToDtype(scale=True) and
     Normalize(mean, std) to within an fp32 rounding; mean, std: None, one number or three, in [0, 1] units; channels_last=True:
     torch.channels_last memory; out: a tensor of that dtype, shape, device and memory format, written in place and returned.
-    With dtype=torch.uint8 (the default) the other four must be left alone: ValueError."""
-    tensor = _tensor_kwargs("qmf_decode_crops", dtype, mean, std, channels_last, out)  # refused before anything is parsed or uploaded
+    With dtype=torch.uint8 (the default) the other four must be left alone: ValueError.
+    A gray source (a list of gray streams, or their ResidentFactors): [n, 1, h, w]; mean, std: None, one number or a sequence of
+    one (three numbers: ValueError); the crops of every scale leave in one kernel call."""
+    gray = source.channels == 1 if isinstance(source, ResidentFactors) else _gray_factors_ragged(source)  # (host only; raises nothing)
+    if gray:
+        tensor = _gray_tensor_kwargs("qmf_decode_crops", dtype, mean, std, channels_last, out)
+        on_device = _check_inflate(inflate)
+        if not isinstance(source, ResidentFactors):
+            _refuse_gray_inflate(on_device)
+            images, Uh, Vh = gray
+            _lib.check_gray_crop_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, _gray_crop_rows(crops, scale), size)  # before a GPU is asked for
+            source = _resident_gray(images, Uh, Vh, device)
+        return source.decode_crops(crops, size, scale, **tensor)
+    tensor = _tensor_kwargs("qmf_decode_crops", dtype, mean, std, channels_last, out)  # refused before anything is uploaded
     on_device = _check_inflate(inflate)
     if on_device and not isinstance(source, ResidentFactors):
         ctx, images, U, V = _factors_ragged_device(source, device)
@@ -2123,6 +2213,17 @@ def qmf_decode_resized_crops(source, boxes, size, flip=None, device=None, inflat
     branch raises NotImplementedError naming it.  inflate="device" (a list of streams only): their columns are inflated on the GPU.
     dtype, mean, std, channels_last, out: as qmf_decode_crops takes them — the resized crop, the flip, to-tensor and normalise in
     one call; under flip the pixels are mirrored, whatever the element size or layout."""
+    gray = source.channels == 1 if isinstance(source, ResidentFactors) else _gray_factors_ragged(source)  # (host only; raises nothing)
+    if gray:  # [n, 1, oh, ow]; mean, std: None, one number or a sequence of one
+        tensor = _gray_tensor_kwargs("qmf_decode_resized_crops", dtype, mean, std, channels_last, out)
+        on_device = _check_inflate(inflate)
+        rows = _resized_boxes(boxes, flip)
+        if not isinstance(source, ResidentFactors):
+            _refuse_gray_inflate(on_device)
+            images, Uh, Vh = gray
+            _lib.check_gray_resized_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, rows, size)  # refused before a GPU is asked for
+            source = _resident_gray(images, Uh, Vh, device)
+        return source._ctx.decode_gray_resized_crops(source.U, source.V, source.images, rows, size, **tensor)
     tensor = _tensor_kwargs("qmf_decode_resized_crops", dtype, mean, std, channels_last, out)
     on_device = _check_inflate(inflate)
     rows = _resized_boxes(boxes, flip)
@@ -2152,6 +2253,10 @@ def qmf_decode_scaled(source, scale, device=None, inflate: str = "host") -> list
         raise ValueError(f"scale {scale}: 2, 4 or 8 expected")
     if isinstance(source, ResidentFactors):
         return source.decode(int(scale))
+    gray = _gray_factors_ragged(source)
+    if gray is not None:  # a list of gray streams: [1, ceil(H_i / scale), ceil(W_i / scale)], the gray loader's exact-integer levels
+        _refuse_gray_inflate(on_device)
+        return _resident_gray(*gray, device).decode(int(scale))
     if on_device:
         ctx, images, U, V = _factors_ragged_device(source, device)
         return ctx.decode_scaled(U, V, images, int(scale))

@@ -4,9 +4,12 @@
 //       context's X workspace and the 64-column solver of lrf_qmf_decompose_f32 / lrf_qmf_bcd_f32 takes it from there
 //       (decompose64 / bcd64, lrf_encode8.hip); k_gray_decode turns the factors back into pixels.
 //   general (1 <= C <= 16, any patch size or none): matrix and decoder kernels around the any-shape entries, which the host calls.
-// Kernels: lrf_channels_kernel.hip.
+// Kernels: lrf_channels_kernel.hip.  The resident-factor loader for gray images (lists of mixed sizes and ranks, levels 1/2/4/8,
+// windows, resized crops, tensors) lives in lrf_gray_loader_host.inc / lrf_gray_loader_kernel.hip, included at the end.
 #include "lrf_host.h"
 #include "lrf_channels_kernel.hip"
+#include "lrf_decode_tensor_kernel.hip"
+#include "lrf_gray_loader_kernel.hip"
 
 #define LRF_CHAN_MAX 16
 
@@ -150,3 +153,5 @@ int lrf_qmf_chan_decode_u8(lrf_ctx* c, const int8_t* U, const int8_t* V, int64_t
 }
 
 } // extern "C"
+
+#include "lrf_gray_loader_host.inc"

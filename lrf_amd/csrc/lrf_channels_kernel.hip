@@ -82,15 +82,12 @@ __device__ __forceinline__ unsigned chan_clamp_u8(int v)
     return (unsigned)min(max(v, 0), 255);
 }
 
-// grid (ceil(M * 4 / 256), B), R <= LRF_GRAY_DEC_MAX_RANK.  Item t = (patch m, row pair ap): rows 2 ap and 2 ap + 1 of patch m.
-// LDS: vs[r4][n] = ranks 4 r4 .. 4 r4 + 3 of V[n] as one dword (zero above R), so a lane's 16 columns of one r4 are 64
-// consecutive bytes (four ds_read_b128).  u_words: U's rows can be read as dwords (R % 4 == 0 and an aligned base).
-__global__ __launch_bounds__(256) void k_gray_decode(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W, int top, int left,
-                                                     int nw, int M, int R, int u_words, uint8_t* __restrict__ gray)
+// The pieces of k_gray_decode that the gray loader's kernels (lrf_gray_loader_kernel.hip) run too, so that the arithmetic exists once.
+// gray_stage_v: vs[r4][n] = ranks 4 r4 .. 4 r4 + 3 of V[n] as one dword (zero above R), by the whole workgroup of 256 threads; the
+// caller places the barrier.
+__device__ __forceinline__ void gray_stage_v(const int8_t* __restrict__ Vb, int R, unsigned* __restrict__ vs)
 {
-    __shared__ unsigned vs[(LRF_GRAY_DEC_MAX_RANK / 4) * 64];
     const int r4n = (R + 3) >> 2;
-    const int8_t* Vb = V + (long)blockIdx.y * 64 * R;
     for (int i = threadIdx.x; i < r4n * 64; i += 256) {
         const int r4 = i >> 6, n = i & 63;
         unsigned w = 0;
@@ -100,25 +97,28 @@ __global__ __launch_bounds__(256) void k_gray_decode(const int8_t* __restrict__ 
         }
         vs[i] = w;
     }
-    __syncthreads();
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= M * 4) return;
-    const int m = t >> 2, ap = t & 3;
-    const int8_t* u = U + (long)blockIdx.y * M * R + (long)m * R;
-    int acc[16];
+}
+// ranks 4 r4 .. 4 r4 + 3 of the row u of U as one dword (zero above R).  u_words: U's rows can be read as dwords (R % 4 == 0
+// and an aligned base)
+__device__ __forceinline__ unsigned gray_u_word(const int8_t* __restrict__ u, int r4, int R, int u_words)
+{
+    if (u_words) return *reinterpret_cast<const unsigned*>(u + r4 * 4);
+    unsigned uw = 0;
+    for (int k = 0; k < 4; k++) {
+        const int r = r4 * 4 + k;
+        if (r < R) uw |= (unsigned)(uint8_t)u[r] << (8 * k);
+    }
+    return uw;
+}
+// acc[8 row + b]: pixel (2 ap + row, b) of the patch whose row of U is u, as the int32 sum of int8 products (v_dot4c_i32_i8): a
+// lane's 16 columns of one r4 are 64 consecutive bytes of vs (four ds_read_b128)
+__device__ __forceinline__ void gray_patch_rows(const int8_t* __restrict__ u, int R, int u_words, const unsigned* __restrict__ vs, int ap, int (&acc)[16])
+{
+    const int r4n = (R + 3) >> 2;
 #pragma unroll
     for (int i = 0; i < 16; i++) acc[i] = 0;
     for (int r4 = 0; r4 < r4n; r4++) {
-        unsigned uw;
-        if (u_words) {
-            uw = *reinterpret_cast<const unsigned*>(u + r4 * 4);
-        } else {
-            uw = 0;
-            for (int k = 0; k < 4; k++) {
-                const int r = r4 * 4 + k;
-                if (r < R) uw |= (unsigned)(uint8_t)u[r] << (8 * k);
-            }
-        }
+        const unsigned uw = gray_u_word(u, r4, R, u_words);
         const uint4* vrow = reinterpret_cast<const uint4*>(vs + r4 * 64 + ap * 16);
 #pragma unroll
         for (int g = 0; g < 4; g++) {
@@ -129,6 +129,29 @@ __global__ __launch_bounds__(256) void k_gray_decode(const int8_t* __restrict__ 
             acc[4 * g + 3] = chan_dot4(uw, vv.w, acc[4 * g + 3]);
         }
     }
+}
+// the eight clamped bytes of one row of gray_patch_rows' sums as two dwords
+__device__ __forceinline__ uint2 gray_row_bytes(const int (&acc)[16], int row)
+{
+    return make_uint2(chan_clamp_u8(acc[8 * row + 0]) | chan_clamp_u8(acc[8 * row + 1]) << 8 | chan_clamp_u8(acc[8 * row + 2]) << 16 |
+                          chan_clamp_u8(acc[8 * row + 3]) << 24,
+                      chan_clamp_u8(acc[8 * row + 4]) | chan_clamp_u8(acc[8 * row + 5]) << 8 | chan_clamp_u8(acc[8 * row + 6]) << 16 |
+                          chan_clamp_u8(acc[8 * row + 7]) << 24);
+}
+
+// grid (ceil(M * 4 / 256), B), R <= LRF_GRAY_DEC_MAX_RANK.  Item t = (patch m, row pair ap): rows 2 ap and 2 ap + 1 of patch m
+// (gray_stage_v, gray_patch_rows).
+__global__ __launch_bounds__(256) void k_gray_decode(const int8_t* __restrict__ U, const int8_t* __restrict__ V, int H, int W, int top, int left,
+                                                     int nw, int M, int R, int u_words, uint8_t* __restrict__ gray)
+{
+    __shared__ __attribute__((aligned(16))) unsigned vs[(LRF_GRAY_DEC_MAX_RANK / 4) * 64];
+    gray_stage_v(V + (long)blockIdx.y * 64 * R, R, vs);
+    __syncthreads();
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= M * 4) return;
+    const int m = t >> 2, ap = t & 3;
+    int acc[16];
+    gray_patch_rows(U + (long)blockIdx.y * M * R + (long)m * R, R, u_words, vs, ap, acc);
     const int hh = m / nw, ww = m - hh * nw;
     const int x0 = ww * 8 - left;
     uint8_t* out = gray + (long)blockIdx.y * H * W;
@@ -136,10 +159,8 @@ __global__ __launch_bounds__(256) void k_gray_decode(const int8_t* __restrict__ 
     for (int row = 0; row < 2; row++) {
         const int y = hh * 8 + 2 * ap + row - top;
         if (y < 0 || y >= H) continue;
-        const unsigned lo = chan_clamp_u8(acc[8 * row + 0]) | chan_clamp_u8(acc[8 * row + 1]) << 8 | chan_clamp_u8(acc[8 * row + 2]) << 16 |
-                            chan_clamp_u8(acc[8 * row + 3]) << 24;
-        const unsigned hi = chan_clamp_u8(acc[8 * row + 4]) | chan_clamp_u8(acc[8 * row + 5]) << 8 | chan_clamp_u8(acc[8 * row + 6]) << 16 |
-                            chan_clamp_u8(acc[8 * row + 7]) << 24;
+        const uint2 px = gray_row_bytes(acc, row);
+        const unsigned lo = px.x, hi = px.y;
         uint8_t* o = out + (long)y * W + x0; // formed as an address only: bytes outside [0, W) of the row are not touched
         if (x0 >= 0 && x0 + 8 <= W && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
             if ((reinterpret_cast<uintptr_t>(o) & 7) == 0) {

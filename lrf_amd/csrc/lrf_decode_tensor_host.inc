@@ -5,7 +5,7 @@
 // resident descriptors and the staging slots are that entry's own code.
 
 // fmt, out, out_bytes -> the output in elements; everything is checked before the body sees it
-static int tensor_out(const lrf_tensor_format* fmt, void* out, int64_t out_bytes, DecodeOut* o)
+int tensor_out(const lrf_tensor_format* fmt, void* out, int64_t out_bytes, DecodeOut* o)
 {
     if (!fmt || !out) return set_err(LRF_EINVAL, "NULL argument");
     if (fmt->dtype != LRF_T_F32 && fmt->dtype != LRF_T_F16 && fmt->dtype != LRF_T_BF16)

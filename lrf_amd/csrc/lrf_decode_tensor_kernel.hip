@@ -14,10 +14,9 @@
 // nothing more (w, ow, x0 are arbitrary), so the runs leave as pieces of 16, 8 and 4 bytes typed with the element's alignment,
 // as the uint8 sinks type theirs with aligned(1).
 
-struct TensorFmt { // a kernel argument
-    float scale[3], bias[3];
-    int nhwc;
-};
+#ifndef LRF_DECODE_TENSOR_KERNEL_HIP // (lrf_encode8.hip and lrf_channels.hip both include it: once per unit)
+#define LRF_DECODE_TENSOR_KERNEL_HIP
+// TensorFmt, the kernels' argument: lrf_internal.h
 
 template <class T>
 __device__ __forceinline__ T tensor_value(unsigned b, int k, const TensorFmt& f)
@@ -174,3 +173,4 @@ struct DecodeTensorOut {
         for (int k = 0; k < 3; k++) dst[k * step] = tensor_value<T>(v[k], k, f);
     }
 };
+#endif

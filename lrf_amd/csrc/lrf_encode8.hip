@@ -555,7 +555,7 @@ int lrf_qmf_encode_sweep_rgb_u8(lrf_ctx* c, const uint8_t* rgb, int64_t B, int64
 // A table that stays resident in `buf` under the bytes of its key: `tab`, and behind it `tail` — a function of the key that is
 // not part of it.  Calls that repeat the key skip the synchronising upload.  The key is cleared before the upload and assigned
 // only after it succeeded: a failed upload leaves no key that vouches for the buffer.
-static int keep_resident(lrf_ctx* c, DevBuf& buf, std::vector<char>& key, const void* tab, size_t tb, const void* tail = nullptr, size_t tail_bytes = 0)
+int keep_resident(lrf_ctx* c, DevBuf& buf, std::vector<char>& key, const void* tab, size_t tb, const void* tail, size_t tail_bytes)
 {
     if (key.size() == tb && memcmp(key.data(), tab, tb) == 0 && buf.p) return LRF_OK;
     key.clear();
@@ -902,7 +902,7 @@ int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* 
 // turns; a slot is written again only after the event recorded behind its last copy says that copy has run (a wait for that
 // one copy at most, LRF_CROP_SLOTS calls back).  The device table is one buffer: the copy of a call is ordered behind the
 // kernels of the call before it on the same stream.
-static int stage_crop_bytes(lrf_ctx* c, const void* table, size_t bytes)
+int stage_crop_bytes(lrf_ctx* c, const void* table, size_t bytes)
 {
     int rc = ensure(c, c->crop_tab, bytes);
     if (rc) return rc;
@@ -934,29 +934,9 @@ static int resident_crop_descs(lrf_ctx* c, const std::vector<RaggedDesc>& descs)
 // n_crops windows of one size (h, w) out of a list of images that differ in size and ranks (kernels:
 // lrf_decode_crops_kernel.hip; the launches: plan_decode_crops).  Everything the kernels index with is checked here, before
 // any launch.  The image descriptors stay resident between calls (their bytes are the key); the crop list does not.
-// DecodeOut: where the three entries that decode windows write — the bytes of the _rgb_u8 entries or the tensor of the _tensor
+// DecodeOut (lrf_host.h): where the three entries that decode windows write — the bytes of the _rgb_u8 entries or the tensor of the _tensor
 // entries (lrf_decode_tensor_host.inc), `len` counted in its elements.  One body per entry serves both: the checks, the launch
 // plan and the staging do not depend on it, only which instantiation a launch names.
-struct DecodeOut {
-    void* p;
-    int64_t len;
-    int dtype; // LRF_T_*, or -1: uint8 [3][h][w]
-    TensorFmt f;
-};
-static DecodeOut bytes_out(uint8_t* rgb, int64_t rgb_len) { return DecodeOut{rgb, rgb_len, -1, TensorFmt{}}; }
-// fn(T* out) with T the element type of a tensor output
-extern "C++" {
-template <class F>
-static void with_tensor_type(const DecodeOut& o, F&& fn)
-{
-    switch (o.dtype) {
-    case LRF_T_F32: fn((float*)o.p); break;
-    case LRF_T_F16: fn((_Float16*)o.p); break;
-    default: fn((__bf16*)o.p); break;
-    }
-}
-}
-
 static int decode_crops_to(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len,
                            int64_t n_crops, const lrf_crop* crops, int64_t h, int64_t w, const DecodeOut& o)
 {

@@ -91,6 +91,8 @@ struct lrf_ctx {
     };
     CropSlot crop_slot[LRF_CROP_SLOTS];
     int crop_next = 0;
+    DevBuf gray_desc; // the gray loader (lrf_qmf_decode_gray_ragged_u8, _crops_, _resized_crops_): its image descriptors (GrayDesc) ...
+    std::vector<char> gray_desc_key; // ... and the bytes now resident there; its item lists travel through crop_tab and the slots above
     DevBuf scaled_pool; // lrf_qmf_decode_scaled_*: the pooled V tables (int16) of the call in flight, written by its k_pool_v
     DevBuf enc_ragged_tab; // lrf_qmf_encode_ragged_rgb_u8: the image descriptors (EncRaggedDesc), behind them the workgroup table ...
     std::vector<char> enc_ragged_key; // ... and the descriptor bytes now resident there
@@ -178,6 +180,36 @@ struct Prof {
 
 
 #define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
+
+// ---- what the entries that decode windows share across units (lrf_encode8.hip defines the functions; lrf_channels.hip's gray
+// loader calls them too)
+// A table that stays resident in `buf` under the bytes of its key: `tab`, and behind it `tail` — a function of the key that is
+// not part of it.  Calls that repeat the key skip the synchronising upload
+int keep_resident(lrf_ctx* c, DevBuf& buf, std::vector<char>& key, const void* tab, size_t tb, const void* tail = nullptr, size_t tail_bytes = 0);
+// the item list of one call into lrf_ctx::crop_tab through the pinned staging slots: stream-ordered, no wait for the stream
+extern "C" int stage_crop_bytes(lrf_ctx* c, const void* table, size_t bytes);
+// DecodeOut: where such an entry writes — the bytes of the _u8 entries or the tensor of the _tensor entries, `len` counted in
+// its elements
+struct DecodeOut {
+    void* p;
+    int64_t len;
+    int dtype; // LRF_T_*, or -1: uint8
+    TensorFmt f;
+};
+inline DecodeOut bytes_out(uint8_t* rgb, int64_t rgb_len) { return DecodeOut{rgb, rgb_len, -1, TensorFmt{}}; }
+// fmt, out, out_bytes of a _tensor entry -> the output in elements; everything is checked before the body sees it
+// (lrf_decode_tensor_host.inc)
+int tensor_out(const lrf_tensor_format* fmt, void* out, int64_t out_bytes, DecodeOut* o);
+// fn(T* out) with T the element type of a tensor output
+template <class F>
+static void with_tensor_type(const DecodeOut& o, F&& fn)
+{
+    switch (o.dtype) {
+    case LRF_T_F32: fn((float*)o.p); break;
+    case LRF_T_F16: fn((_Float16*)o.p); break;
+    default: fn((__bf16*)o.p); break;
+    }
+}
 
 // ---- geometry (lrf_ctx.hip)
 int make_geom(int64_t H, int64_t W, ImageGeom* g);

@@ -132,6 +132,32 @@ struct ResizedItem {
     int place;          // its place in the caller's list: its output is [3][oh][ow] at 3 oh ow place
 };
 
+// ---- the tensor format of the model-ready decode entries as the kernels take it (lrf_tensor_format; the epilogue:
+// lrf_decode_tensor_kernel.hip).  A kernel argument; the gray entries read element 0 of scale and bias alone
+struct TensorFmt {
+    float scale[3], bias[3];
+    int nhwc;
+};
+
+// ---- the gray loader (lrf_qmf_decode_gray_ragged_u8, _crops_, _resized_crops_; kernels: lrf_gray_loader_kernel.hip) ----
+// One gray image of the call, as the kernels read it (uniform loads): U [M][R] at u_off, V [64][R] at v_off, the padding of
+// lrf_chan_dims(H, W, 1, 8, 8).  No padding bytes: the table's bytes are its key
+struct GrayDesc {
+    long u_off, v_off; // int8 elements from U / V to the image's factors
+    int H, W, R;
+    int top, left;     // padded rows above / columns left of the image
+    int nw;            // patches per row of the padded image
+};
+// One window or one box of the call (a uniform load per workgroup).  image: an index into GrayDesc
+struct GrayItem {
+    int image, f;      // the level: 1, 2, 4 or 8
+    int y0, x0, h, w;  // windows: the window inside level f of the image; resized crops: the box in full-resolution pixels
+    int flip;          // resized crops: != 0: output column c holds the value of column ow - 1 - c
+    int place;         // its place in the caller's list
+    long out_off;      // elements from the output's start to the item's first pixel
+    long pitch;        // elements from one output row of the item to the next
+};
+
 // ---- the ragged encode (lrf_qmf_encode_ragged_rgb_u8; kernels: lrf_planes_ragged_kernel.hip) ----
 // One image of the call, as the planes kernels read it (uniform loads, like RaggedDesc; the workgroup table is RaggedBlock's:
 // image, unit = strip * per_strip + column group)

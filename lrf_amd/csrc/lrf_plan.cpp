@@ -534,6 +534,105 @@ ResizedPlan plan_decode_resized(const std::vector<int>& r8, const std::vector<Re
     return p;
 }
 
+// ---- the gray loader ----------------------------------------------------------------------------------------------------------
+GrayRefusal describe_gray_images(int64_t n, const lrf_gray_image* images, int64_t u_len, int64_t v_len, int scale, int64_t out_len,
+                                 std::vector<GrayDesc>& descs)
+{
+    static_assert(sizeof(GrayDesc) == 2 * sizeof(long) + 6 * sizeof(int), "GrayDesc has padding bytes: they would be part of the table's key");
+    descs.assign((size_t)n, GrayDesc{});
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_gray_image& im = images[i];
+        GrayDesc& d = descs[(size_t)i];
+        if (im.H < 1 || im.W < 1 || im.H > (1 << 20) || im.W > (1 << 20) || im.H * im.W >= (1LL << 31)) return GrayRefusal{GDESC_SIZE, i, im.H, im.W};
+        // reflect padding to multiples of 8, top = pad / 2 (lrf_chan_dims; lrf/compression/utils.py:108-132)
+        const int64_t ph = (8 - im.H % 8) % 8, pw = (8 - im.W % 8) % 8;
+        if (ph / 2 >= im.H || ph - ph / 2 >= im.H || pw / 2 >= im.W || pw - pw / 2 >= im.W) return GrayRefusal{GDESC_GEOM, i, im.H, im.W};
+        if (im.R < 1 || im.R > 64) return GrayRefusal{GDESC_RANK, i, im.R, 0};
+        if (im.u_off < 0 || im.v_off < 0 || (scale && im.out_off < 0)) return GrayRefusal{GDESC_NEGATIVE, i, 0, 0};
+        const int64_t M = ((im.H + ph) / 8) * ((im.W + pw) / 8); // < 2^25 + ...: M R and 64 R cannot wrap
+        const int64_t u_img = M * im.R, v_img = 64LL * im.R;
+        if (u_img > u_len || im.u_off > u_len - u_img) return GrayRefusal{GDESC_U, i, u_len, 0};
+        if (v_img > v_len || im.v_off > v_len - v_img) return GrayRefusal{GDESC_V, i, v_len, 0};
+        if (scale) {
+            const int64_t px = ((im.H + scale - 1) / scale) * ((im.W + scale - 1) / scale);
+            if (px > out_len || im.out_off > out_len - px) return GrayRefusal{GDESC_OUT, i, out_len, 0};
+        }
+        d.u_off = im.u_off; d.v_off = im.v_off;
+        d.H = (int)im.H; d.W = (int)im.W; d.R = im.R;
+        d.top = (int)(ph / 2); d.left = (int)(pw / 2);
+        d.nw = (int)((im.W + pw) / 8);
+    }
+    return GrayRefusal{};
+}
+
+// The table is a stable sort of the call's items by slot; one launch per slot that occurs.  wgs_of: the workgroups item j needs
+template <class SlotOf, class WgsOf, class Finish>
+static GrayPlan plan_gray(const std::vector<GrayItem>& items, int nslots, SlotOf slot_of, WgsOf wgs_of, Finish finish)
+{
+    GrayPlan p;
+    std::vector<int> slot(items.size());
+    std::vector<long> count((size_t)nslots, 0), wgs((size_t)nslots, 0);
+    for (size_t j = 0; j < items.size(); j++) {
+        slot[j] = slot_of(items[j]);
+        count[(size_t)slot[j]]++;
+        const long g = wgs_of(items[j], slot[j]);
+        if (g > wgs[(size_t)slot[j]]) wgs[(size_t)slot[j]] = g;
+    }
+    for (int s = 0; s < nslots; s++)
+        if (count[(size_t)s] && (wgs[(size_t)s] >= (1L << 31) || count[(size_t)s] * wgs[(size_t)s] >= (1L << 31))) {
+            p.too_many = wgs[(size_t)s] >= (1L << 31) ? wgs[(size_t)s] : count[(size_t)s] * wgs[(size_t)s];
+            return p;
+        }
+    p.table.reserve(items.size());
+    for (int s = 0; s < nslots; s++) {
+        if (!count[(size_t)s]) continue;
+        GrayLaunch l;
+        l.f = 1 << (s & 3);
+        l.direct = s >> 2;
+        l.item0 = (long)p.table.size();
+        l.nitems = count[(size_t)s];
+        l.wgs = wgs[(size_t)s];
+        for (size_t j = 0; j < items.size(); j++) {
+            if (slot[j] != s) continue;
+            GrayItem e = items[j];
+            e.f = l.f;
+            e.place = (int)j;
+            e.flip = e.flip != 0;
+            finish(e);
+            p.table.push_back(e);
+        }
+        p.launches.push_back(l);
+    }
+    return p;
+}
+static int gray_level_slot(int f) { return f == 1 ? 0 : (f == 2 ? 1 : (f == 4 ? 2 : 3)); }
+
+GrayPlan plan_gray_windows(const std::vector<GrayDesc>& descs, const std::vector<GrayItem>& items)
+{
+    return plan_gray(
+        items, 4, [](const GrayItem& e) { return gray_level_slot(e.f); },
+        [&](const GrayItem& e, int) {
+            const GrayDesc& d = descs[(size_t)e.image];
+            return e.f == 1 ? gray_tile_wgs(d.top, d.left, e.y0, e.x0, e.h, e.w) : crop_quad_wgs(e.h, e.w);
+        },
+        [](GrayItem&) {});
+}
+
+GrayPlan plan_gray_resized(const std::vector<GrayItem>& boxes, int oh, int ow)
+{
+    return plan_gray(
+        boxes, 8,
+        [&](const GrayItem& e) {
+            const int f = resized_level(e.h, e.w, oh, ow);
+            return (resized_staged(e.h, e.w, oh, ow, f) ? 0 : 4) + gray_level_slot(f);
+        },
+        [&](const GrayItem&, int s) { return s >> 2 ? resized_direct_wgs(oh, ow) : resized_staged_wgs(oh, ow); },
+        [&](GrayItem& e) {
+            e.out_off = (long)e.place * oh * ow;
+            e.pitch = ow;
+        });
+}
+
 // ---- geometry -----------------------------------------------------------------------------------------------------------------
 void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M)
 {

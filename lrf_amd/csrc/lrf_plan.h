@@ -450,6 +450,65 @@ struct ResizedPlan {
 // place are set here)
 ResizedPlan plan_decode_resized(const std::vector<int>& r8, const std::vector<ResizedItem>& crops, int oh, int ow);
 
+// ---- the gray loader: the image list, the thread maps and the launches of lrf_qmf_decode_gray_ragged_u8, _crops_ and ---------
+// _resized_crops_ (kernels: lrf_gray_loader_kernel.hip).  The kernels and tests/test_gray_loader_plan.py call the same functions.
+// Level 1, the patch body (k_gray_decode's: a thread two rows of one 8x8 patch): the patches a window touches, row by row, 64 to
+// a workgroup.  top, left: GrayDesc's; y0, x0, h, w: the window in image pixels.
+LRF_HD inline long gray_tile_wgs(int top, int left, int y0, int x0, int h, int w)
+{
+    const long npr = ((y0 + h - 1 + top) >> 3) - ((y0 + top) >> 3) + 1, npc = ((x0 + w - 1 + left) >> 3) - ((x0 + left) >> 3) + 1;
+    return (npr * npc + 63) / 64;
+}
+struct GrayTile {
+    int pr, pc, ap; // padded rows 8 pr + 2 ap, + 1 of the patch (pr, pc)
+    CropSpan px;    // what of them lies inside the window: ny == 0 or nx == 0: nothing
+};
+LRF_HD inline GrayTile gray_tile_of(int top, int left, int y0, int x0, int h, int w, long wg, int tid)
+{
+    const int pr0 = (y0 + top) >> 3, pc0 = (x0 + left) >> 3;
+    const int npr = ((y0 + h - 1 + top) >> 3) - pr0 + 1, npc = ((x0 + w - 1 + left) >> 3) - pc0 + 1;
+    // (an image has fewer than 2^31 / 64 patches, so 32-bit arithmetic: the kernels do this division once per thread)
+    const unsigned o = (unsigned)wg * 64u + (unsigned)(tid >> 2);
+    GrayTile t = {pr0, pc0, tid & 3, {y0, x0, 0, 0}};
+    if (wg < 0 || wg >= gray_tile_wgs(top, left, y0, x0, h, w) || o >= (unsigned)npr * (unsigned)npc) return t;
+    t.pr = pr0 + (int)(o / (unsigned)npc);
+    t.pc = pc0 + (int)(o - (o / (unsigned)npc) * (unsigned)npc);
+    const int ya = 8 * t.pr + 2 * t.ap - top, xa = 8 * t.pc - left;
+    const int ylo = ya > y0 ? ya : y0, yhi = ya + 2 < y0 + h ? ya + 2 : y0 + h;
+    const int xlo = xa > x0 ? xa : x0, xhi = xa + 8 < x0 + w ? xa + 8 : x0 + w;
+    if (yhi > ylo && xhi > xlo) t.px = CropSpan{ylo, xlo, yhi - ylo, xhi - xlo};
+    return t;
+}
+// Levels 2, 4, 8: the window's pixel quads, row by row, 256 to a workgroup (crop_quad_wgs, crop_quad_of above).
+// The image list, checked and described as the kernels read it.  Checks per image, in this order: the size (sides in [1,2^20],
+// fewer than 2^31 pixels), the reflect padding of lrf_chan_dims(H, W, 1, 8, 8), the rank 1..64, negative offsets, the U and the
+// V extent against u_len / v_len, and — scale != 0 — out_off and the image's [Hs][Ws] at that level against out_len.  Every
+// term is checked against the length before it is added to an offset: no sum can wrap.
+enum { GDESC_OK = 0, GDESC_SIZE, GDESC_GEOM, GDESC_RANK, GDESC_NEGATIVE, GDESC_U, GDESC_V, GDESC_OUT };
+struct GrayRefusal {
+    int check = GDESC_OK;
+    int64_t image = 0, a = 0, b = 0; // GDESC_SIZE, GDESC_GEOM: H, W; GDESC_RANK: the rank; GDESC_U, GDESC_V, GDESC_OUT: the buffer's length
+};
+// descs: n descriptors (no padding bytes: their bytes are the device table's key).  On a refusal they are left unspecified.
+GrayRefusal describe_gray_images(int64_t n, const lrf_gray_image* images, int64_t u_len, int64_t v_len, int scale, int64_t out_len,
+                                 std::vector<GrayDesc>& descs);
+// One launch: items item0 .. item0 + nitems - 1 of the sorted table, wgs workgroups each (grid.x = nitems * wgs; wgs: the most
+// an item of the launch needs, the workgroups an item does not need exit)
+struct GrayLaunch {
+    int f, direct; // the level; resized crops: the path (0: staged)
+    long item0, nitems, wgs;
+};
+struct GrayPlan {
+    std::vector<GrayLaunch> launches; // windows: by level, at most 4; resized crops: by (path, level), staged first, at most 8
+    std::vector<GrayItem> table;      // the items grouped by launch, call order inside a group; place = the place in the call
+    long too_many = 0;                // != 0: a launch would have this many (>= 2^31) workgroups; no table is built
+};
+// items: validated windows (image, f, y0, x0, h, w in level coordinates, out_off, pitch) in call order (place is set here)
+GrayPlan plan_gray_windows(const std::vector<GrayDesc>& descs, const std::vector<GrayItem>& items);
+// boxes: validated (image, y0, x0, h, w in full-resolution pixels, flip) in call order (f, place, out_off and pitch are set
+// here: box j is [oh][ow] at oh ow j).  resized_level, resized_staged and the staged / direct thread maps are the colour entry's
+GrayPlan plan_gray_resized(const std::vector<GrayItem>& boxes, int oh, int ow);
+
 // ---- inflate of factor columns: which lane decodes which column (lrf_inflate_columns_i8; tests/test_inflate_plan.py) ----------
 // One lane per stream, 64 consecutive slots to a wave.  The slots are the matrices' columns, matrix after matrix, a matrix's
 // columns ascending — so a wave's lanes hold adjacent columns of one matrix (adjacent bytes of every row) until the matrix
