@@ -384,18 +384,23 @@ def check_sweep_sse_args(rgb, factors, triples):
                              f"{dev}, got {tuple(U.shape)} on {U.device} and {tuple(V.shape)} on {V.device}")
 
 
-def check_ragged_args(U, V, images):
-    """The argument checks of lrf_qmf_decode_ragged_rgb_u8 on its tensors, before any device is touched.  U, V: flat int8 tensors
-    on one device; images: 1 to 65535 tuples (H, W, ranks, u_off, v_off), every rank in 1..64, every image's factors inside U and
-    V (the kernels index them from the tuple alone: anything else would be an out-of-bounds read).  TypeError for anything but
-    int8 tensors, ValueError for everything else.  -> [(H, W, [R_Y, R_Cb, R_Cr], u_off, v_off)] as integers."""
+def _check_factor_tensors(U, V, images, who):
+    """what the colour and the gray image lists share: flat contiguous int8 U and V on one device, 1 to 65535 images"""
     import torch
     if not isinstance(U, torch.Tensor) or not isinstance(V, torch.Tensor) or U.dtype != torch.int8 or V.dtype != torch.int8:
         raise TypeError("factors must be int8 tensors")
     if U.dim() != 1 or V.dim() != 1 or U.device != V.device or not U.is_contiguous() or not V.is_contiguous():
         raise ValueError(f"U and V must be flat contiguous tensors on one device, got {tuple(U.shape)} on {U.device} and {tuple(V.shape)} on {V.device}")
     if images is None or len(images) < 1 or len(images) > 65535:
-        raise ValueError("decode_ragged needs 1 to 65535 images")
+        raise ValueError(f"{who} needs 1 to 65535 images")
+
+
+def check_ragged_args(U, V, images):
+    """The argument checks of lrf_qmf_decode_ragged_rgb_u8 on its tensors, before any device is touched.  U, V: flat int8 tensors
+    on one device; images: 1 to 65535 tuples (H, W, ranks, u_off, v_off), every rank in 1..64, every image's factors inside U and
+    V (the kernels index them from the tuple alone: anything else would be an out-of-bounds read).  TypeError for anything but
+    int8 tensors, ValueError for everything else.  -> [(H, W, [R_Y, R_Cb, R_Cr], u_off, v_off)] as integers."""
+    _check_factor_tensors(U, V, images, "decode_ragged")
     out = []
     for i, im in enumerate(images):
         if len(im) != 5 or len(im[2]) != 3:
@@ -432,22 +437,23 @@ def _check_size(size, upper=None):
     return h, w
 
 
-def _check_boxes(crops, columns, entry):
-    """The box list of `entry`: an integer array-like [n, len(columns)] on the host, 1 <= n <= 2^20; columns: their names, for
-    the messages -> an int64 array"""
+def _check_boxes(crops, columns, entry, noun="crops", most=2 ** 20):
+    """The box list of `entry`: an integer array-like [n, len(columns)] on the host, 1 <= n <= most (None: the caller splits the
+    list and its parts are checked); columns: their names and noun: what the caller calls the list, for the messages -> an
+    int64 array"""
     import numpy as np
     if hasattr(crops, "detach"):  # a torch tensor
         if crops.is_cuda:
-            raise ValueError("crops live on the host: the call validates every box before it launches")
+            raise ValueError(f"{noun} live on the host: the call validates every box before it launches")
         crops = crops.detach().numpy()
     boxes = np.asarray(crops)
     if boxes.size == 0:
         raise ValueError(f"{entry} needs 1 to 2^20 crops")
     if boxes.dtype.kind not in "iu":
-        raise TypeError(f"crops must be integers ({', '.join(columns)}), got {boxes.dtype}")
+        raise TypeError(f"{noun} must be integers ({', '.join(columns)}), got {boxes.dtype}")
     if boxes.ndim != 2 or boxes.shape[1] != len(columns):
-        raise ValueError(f"crops must be [n, {len(columns)}] ({', '.join(columns)}), got shape {tuple(boxes.shape)}")
-    if boxes.shape[0] > 2 ** 20:
+        raise ValueError(f"{noun} must be [n, {len(columns)}] ({', '.join(columns)}), got shape {tuple(boxes.shape)}")
+    if most is not None and boxes.shape[0] > most:
         raise ValueError(f"{entry} needs 1 to 2^20 crops")
     return boxes.astype(np.int64)
 
@@ -481,6 +487,25 @@ def check_crop_args(U, V, images, crops, size):
 SCALES = (2, 4, 8)  # lrf_qmf_decode_scaled_rgb_u8
 
 
+def _check_scaled_crops(ims, crops, size, scales, entry):
+    """crops of (image, scale, y0, x0) against the admitted scales and the checked images `ims` (their first two fields: H, W):
+    every window of `size` inside its image at its scale -> (ims, crops as an int32 array [n, 4], (h, w))"""
+    import numpy as np
+    h, w = _check_size(size)
+    boxes = _check_boxes(crops, ("image", "scale", "y0", "x0"), entry)
+    Hs, Ws = _check_box_images(boxes, ims)
+    bad = np.flatnonzero(~np.isin(boxes[:, 1], scales))
+    if bad.size:
+        raise ValueError(f"crop {bad[0]}: scale {boxes[bad[0], 1]}: {', '.join(str(f) for f in scales[:-1])} or {scales[-1]} expected")
+    f = boxes[:, 1]
+    Hs, Ws = -(-Hs // f), -(-Ws // f)
+    bad = np.flatnonzero((boxes[:, 2] < 0) | (boxes[:, 3] < 0) | (boxes[:, 2] + h > Hs) | (boxes[:, 3] + w > Ws))
+    if bad.size:
+        j = bad[0]
+        raise ValueError(f"crop {j}: {h}x{w} at ({boxes[j, 2]}, {boxes[j, 3]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]} at scale 1/{f[j]}")
+    return ims, np.ascontiguousarray(boxes, dtype=np.int32), (h, w)
+
+
 def scaled_dims(H, W, scale):
     """(ceil(H / scale), ceil(W / scale)): the size of an H x W image decoded at 1/scale (lrf_scaled_dims)"""
     if isinstance(scale, bool) or int(scale) != scale or int(scale) not in SCALES:
@@ -508,32 +533,16 @@ def check_scaled_args(U, V, images, scale=None, crops=None, size=None):
         return ims, int(scale)
     if scale is not None or crops is None or size is None:
         raise ValueError("give either a scale (whole images) or crops of (image, scale, y0, x0) and a size")
-    h, w = _check_size(size)
-    boxes = _check_boxes(crops, ("image", "scale", "y0", "x0"), "decode_scaled_crops")
-    Hs, Ws = _check_box_images(boxes, ims)
-    bad = np.flatnonzero(~np.isin(boxes[:, 1], SCALES))
-    if bad.size:
-        raise ValueError(f"crop {bad[0]}: scale {boxes[bad[0], 1]}: 2, 4 or 8 expected")
-    f = boxes[:, 1]
-    Hs, Ws = -(-Hs // f), -(-Ws // f)
-    bad = np.flatnonzero((boxes[:, 2] < 0) | (boxes[:, 3] < 0) | (boxes[:, 2] + h > Hs) | (boxes[:, 3] + w > Ws))
-    if bad.size:
-        j = bad[0]
-        raise ValueError(f"crop {j}: {h}x{w} at ({boxes[j, 2]}, {boxes[j, 3]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]} at scale 1/{f[j]}")
-    return ims, np.ascontiguousarray(boxes, dtype=np.int32), (h, w)
+    return _check_scaled_crops(ims, crops, size, SCALES, "decode_scaled_crops")
 
 
 RESIZED_MAX_SIDE = 16384  # lrf_qmf_decode_resized_crops_rgb_u8: the largest output side
 
 
-def check_resized_args(U, V, images, crops, size):
-    """The argument checks of lrf_qmf_decode_resized_crops_rgb_u8, before any device is touched.  U, V, images: as
-    check_ragged_args takes them; crops: an integer array-like [n, 6] of (image, y0, x0, h, w, flip) on the host, 1 <= n <= 2^20,
-    h and w >= 1, every box inside its image; size: (oh, ow), both in [1, 16384].  TypeError for factors that are not int8
-    tensors and for boxes or sizes that are not integers, ValueError for everything else.
-    -> (images as check_ragged_args returns them, crops as an int32 array [n, 6] with flip 0 or 1, (oh, ow))."""
+def _check_resized_boxes(ims, crops, size):
+    """boxes of (image, y0, x0, h, w, flip) against the checked images `ims` (their first two fields: H, W) and the output size
+    -> (ims, crops as an int32 array [n, 6] with flip 0 or 1, (oh, ow))"""
     import numpy as np
-    ims = check_ragged_args(U, V, images)
     oh, ow = _check_size(size, RESIZED_MAX_SIDE)
     boxes = _check_boxes(crops, ("image", "y0", "x0", "h", "w", "flip"), "decode_resized_crops")
     Hs, Ws = _check_box_images(boxes, ims)
@@ -546,6 +555,15 @@ def check_resized_args(U, V, images, crops, size):
         raise ValueError(f"crop {j}: {boxes[j, 3]}x{boxes[j, 4]} at ({boxes[j, 1]}, {boxes[j, 2]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]}")
     boxes[:, 5] = boxes[:, 5] != 0
     return ims, np.ascontiguousarray(boxes, dtype=np.int32), (oh, ow)
+
+
+def check_resized_args(U, V, images, crops, size):
+    """The argument checks of lrf_qmf_decode_resized_crops_rgb_u8, before any device is touched.  U, V, images: as
+    check_ragged_args takes them; crops: an integer array-like [n, 6] of (image, y0, x0, h, w, flip) on the host, 1 <= n <= 2^20,
+    h and w >= 1, every box inside its image; size: (oh, ow), both in [1, 16384].  TypeError for factors that are not int8
+    tensors and for boxes or sizes that are not integers, ValueError for everything else.
+    -> (images as check_ragged_args returns them, crops as an int32 array [n, 6] with flip 0 or 1, (oh, ow))."""
+    return _check_resized_boxes(check_ragged_args(U, V, images), crops, size)
 
 
 T_F32, T_F16, T_BF16 = 0, 1, 2  # lrf_tensor_format.dtype
@@ -605,31 +623,37 @@ def check_tensor_format(dtype, mean=None, std=None, channels_last=False):
     return fmt
 
 
-def _tensor_request(entry, dtype, mean, std, channels_last, out):
+def _tensor_request(entry, dtype, mean, std, channels_last, out, channels=3):
     """The output arguments the decode entries share, checked before any device is touched -> None for the uint8 entry (the
-    defaults), else the TensorFormat"""
+    defaults), else the TensorFormat.  channels 1 (the gray loader): mean and std are None, one number or a sequence of one (three
+    numbers: ValueError), and only element 0 of the format's scale and bias is read"""
     import torch
     if dtype == torch.uint8:
         if mean is not None or std is not None or channels_last or out is not None:
-            raise ValueError(f"{entry}: mean, std, channels_last and out= go with a float dtype (dtype=torch.uint8 is the byte entry, [n,3,h,w])")
+            raise ValueError(f"{entry}: mean, std, channels_last and out= go with a float dtype (dtype=torch.uint8 is the byte entry, [n,{channels},h,w])")
         return None
+    if channels == 1:
+        mean, std = _one_number(mean, "mean"), _one_number(std, "std")
     return check_tensor_format(dtype, mean, std, channels_last)
 
 
-def _tensor_output(entry, out, n, h, w, dtype, channels_last, device):
-    """the [n,3,h,w] result of a tensor entry: the caller's `out`, checked (a refusal launches nothing), or a new tensor"""
+def _tensor_output(entry, out, n, h, w, dtype, channels_last, device, channels=3):
+    """the [n,channels,h,w] result of a tensor entry: the caller's `out`, checked (a refusal launches nothing), or a new tensor.
+    With one channel NCHW and channels_last are the same memory: n images of h w elements, rows of w ("dense")"""
     import torch
-    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    C, channels_last = channels, channels_last and channels > 1
     if out is None:
-        return torch.empty((n, 3, h, w), dtype=dtype, device=device, memory_format=fmt)
+        return torch.empty((n, C, h, w), dtype=dtype, device=device, memory_format=torch.channels_last if channels_last else torch.contiguous_format)
     if not isinstance(out, torch.Tensor):
         raise TypeError(f"{entry}: out must be a tensor, got {type(out).__name__}")
-    if out.dtype != dtype or tuple(out.shape) != (n, 3, h, w) or out.device != device:
-        raise ValueError(f"{entry}: out must be {dtype} {(n, 3, h, w)} on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    # (strides, not is_contiguous(memory_format=...): for h = w = 1 or n = 1 torch calls more than one layout contiguous)
-    want = (3 * h * w, 1, 3 * w, 3) if channels_last else (3 * h * w, h * w, w, 1)
+    if out.dtype != dtype or tuple(out.shape) != (n, C, h, w) or out.device != device:
+        raise ValueError(f"{entry}: out must be {dtype} {(n, C, h, w)} on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    # (strides, not is_contiguous(memory_format=...): for h = w = 1 or n = 1 torch calls more than one layout contiguous; the
+    # stride of an axis of size 1 — the channel axis of a gray tensor — is immaterial)
+    want = (C * h * w, 1, C * w, C) if channels_last else (C * h * w, h * w, w, 1)
     if any(st != wt for st, wt, size in zip(out.stride(), want, out.shape) if size > 1):
-        raise ValueError(f"{entry}: out must be {'channels_last' if channels_last else 'contiguous'} memory (strides {want}), got strides {tuple(out.stride())}")
+        memory = "channels_last" if channels_last else ("contiguous" if C > 1 else "dense")
+        raise ValueError(f"{entry}: out must be {memory} memory (strides {want}), got strides {tuple(out.stride())}")
     return out
 
 
@@ -641,13 +665,7 @@ def check_gray_images(U, V, images):
     images: 1 to 65535 tuples (H, W, R, u_off, v_off), R one rank in 1..64, the image's U [M, R] and V [64, R] inside U and V, M
     from lrf_chan_dims(H, W, 1, 8, 8) (which refuses sizes the decoder refuses).  TypeError for anything but int8 tensors,
     ValueError for everything else.  -> [(H, W, R, u_off, v_off)] as integers."""
-    import torch
-    if not isinstance(U, torch.Tensor) or not isinstance(V, torch.Tensor) or U.dtype != torch.int8 or V.dtype != torch.int8:
-        raise TypeError("factors must be int8 tensors")
-    if U.dim() != 1 or V.dim() != 1 or U.device != V.device or not U.is_contiguous() or not V.is_contiguous():
-        raise ValueError(f"U and V must be flat contiguous tensors on one device, got {tuple(U.shape)} on {U.device} and {tuple(V.shape)} on {V.device}")
-    if images is None or len(images) < 1 or len(images) > 65535:
-        raise ValueError("the gray loader needs 1 to 65535 images")
+    _check_factor_tensors(U, V, images, "the gray loader")
     out = []
     for i, im in enumerate(images):
         if len(im) != 5 or hasattr(im[2], "__len__"):
@@ -687,40 +705,13 @@ def check_gray_crop_args(U, V, images, crops, size):
     them; crops: an integer array-like [n, 4] of (image, scale, y0, x0) on the host, 1 <= n <= 2^20, the scale per crop out of 1,
     2, 4, 8 and y0, x0 in the image at that scale; size: (h, w), both >= 1; every window inside its image's scaled size.
     -> (images, crops as an int32 array [n, 4], (h, w))."""
-    import numpy as np
-    ims = check_gray_images(U, V, images)
-    h, w = _check_size(size)
-    boxes = _check_boxes(crops, ("image", "scale", "y0", "x0"), "decode_crops")
-    Hs, Ws = _check_box_images(boxes, ims)
-    bad = np.flatnonzero(~np.isin(boxes[:, 1], GRAY_SCALES))
-    if bad.size:
-        raise ValueError(f"crop {bad[0]}: scale {boxes[bad[0], 1]}: 1, 2, 4 or 8 expected")
-    f = boxes[:, 1]
-    Hs, Ws = -(-Hs // f), -(-Ws // f)
-    bad = np.flatnonzero((boxes[:, 2] < 0) | (boxes[:, 3] < 0) | (boxes[:, 2] + h > Hs) | (boxes[:, 3] + w > Ws))
-    if bad.size:
-        j = bad[0]
-        raise ValueError(f"crop {j}: {h}x{w} at ({boxes[j, 2]}, {boxes[j, 3]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]} at scale 1/{f[j]}")
-    return ims, np.ascontiguousarray(boxes, dtype=np.int32), (h, w)
+    return _check_scaled_crops(check_gray_images(U, V, images), crops, size, GRAY_SCALES, "decode_crops")
 
 
 def check_gray_resized_args(U, V, images, crops, size):
     """The argument checks of lrf_qmf_decode_gray_resized_crops_u8, before any device is touched: check_resized_args for a gray
     image list (check_gray_images) -> (images, crops as an int32 array [n, 6] with flip 0 or 1, (oh, ow))."""
-    import numpy as np
-    ims = check_gray_images(U, V, images)
-    oh, ow = _check_size(size, RESIZED_MAX_SIDE)
-    boxes = _check_boxes(crops, ("image", "y0", "x0", "h", "w", "flip"), "decode_resized_crops")
-    Hs, Ws = _check_box_images(boxes, ims)
-    bad = np.flatnonzero((boxes[:, 3] < 1) | (boxes[:, 4] < 1))
-    if bad.size:
-        raise ValueError(f"crop {bad[0]}: box of {boxes[bad[0], 3]}x{boxes[bad[0], 4]}: both sides must be >= 1")
-    bad = np.flatnonzero((boxes[:, 1] < 0) | (boxes[:, 2] < 0) | (boxes[:, 1] + boxes[:, 3] > Hs) | (boxes[:, 2] + boxes[:, 4] > Ws))
-    if bad.size:
-        j = bad[0]
-        raise ValueError(f"crop {j}: {boxes[j, 3]}x{boxes[j, 4]} at ({boxes[j, 1]}, {boxes[j, 2]}) leaves image {boxes[j, 0]} of {Hs[j]}x{Ws[j]}")
-    boxes[:, 5] = boxes[:, 5] != 0
-    return ims, np.ascontiguousarray(boxes, dtype=np.int32), (oh, ow)
+    return _check_resized_boxes(check_gray_images(U, V, images), crops, size)
 
 
 def _one_number(v, name):
@@ -738,30 +729,13 @@ def _one_number(v, name):
 
 
 def check_gray_tensor_request(entry, dtype, mean, std, channels_last, out):
-    """_tensor_request for the gray loader: mean and std are None, one number or a sequence of one (three numbers: ValueError);
-    only element 0 of the format's scale and bias is read -> None for the uint8 entry, else the TensorFormat"""
-    import torch
-    if dtype == torch.uint8:
-        if mean is not None or std is not None or channels_last or out is not None:
-            raise ValueError(f"{entry}: mean, std, channels_last and out= go with a float dtype (dtype=torch.uint8 is the byte entry, [n,1,h,w])")
-        return None
-    return check_tensor_format(dtype, _one_number(mean, "mean"), _one_number(std, "std"), channels_last)
+    """_tensor_request for the gray loader -> None for the uint8 entry, else the TensorFormat"""
+    return _tensor_request(entry, dtype, mean, std, channels_last, out, channels=1)
 
 
 def _gray_tensor_output(entry, out, n, h, w, dtype, device):
-    """the [n,1,h,w] result of a gray tensor entry: the caller's `out`, checked (a refusal launches nothing), or a new tensor.  With
-    one channel NCHW and channels_last are the same memory: n images of h w elements, rows of w"""
-    import torch
-    if out is None:
-        return torch.empty((n, 1, h, w), dtype=dtype, device=device)
-    if not isinstance(out, torch.Tensor):
-        raise TypeError(f"{entry}: out must be a tensor, got {type(out).__name__}")
-    if out.dtype != dtype or tuple(out.shape) != (n, 1, h, w) or out.device != device:
-        raise ValueError(f"{entry}: out must be {dtype} {(n, 1, h, w)} on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    want = (h * w, None, w, 1)  # (the stride of the channel axis of size 1 is immaterial)
-    if any(wt is not None and st != wt for st, wt, size in zip(out.stride(), want, out.shape) if size > 1):
-        raise ValueError(f"{entry}: out must be dense memory (strides {(h * w, h * w, w, 1)}), got strides {tuple(out.stride())}")
-    return out
+    """_tensor_output for the gray loader: the [n,1,h,w] result, the caller's dense `out` or a new tensor"""
+    return _tensor_output(entry, out, n, h, w, dtype, False, device, channels=1)
 
 
 def _gray_images(ims, out_offs=None):
@@ -1010,12 +984,12 @@ def _ragged_images(ims, rgb_offs=None):
     return desc
 
 
-def _packed_outputs(sizes):
-    """[3, h, w] outputs in one buffer, each starting at a multiple of 16 bytes -> (their offsets, the buffer's size)"""
+def _packed_outputs(sizes, channels=3):
+    """[channels, h, w] outputs in one buffer, each starting at a multiple of 16 bytes -> (their offsets, the buffer's size)"""
     offs, off = [], 0
     for h, w in sizes:
         offs.append(off)
-        off = (off + 3 * h * w + 15) // 16 * 16
+        off = (off + channels * h * w + 15) // 16 * 16
     return offs, off
 
 
@@ -1270,6 +1244,28 @@ class Context:
         check(self._lib.lrf_qmf_decode_ragged_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(rgb), rgb.numel()))
         return [rgb[d.rgb_off:d.rgb_off + 3 * d.H * d.W].view(3, d.H, d.W) for d in desc]
 
+    def _decode_windows(self, method, U, V, desc, boxes, crop_type, size, fmt, tensor):
+        """The ctypes call of one of the ten C entries that decode crops, every argument checked by the caller.  method: the public
+        method's name, which names the rest: the C entries are lrf_qmf_<method>_rgb_u8 (gray: _u8) for fmt None and
+        lrf_qmf_<method>_tensor for a TensorFormat, and output refusals carry the name without "gray_".  desc: the lrf_ragged_image
+        or lrf_gray_image array (which says how many channels); boxes: int32 rows of crop_type; size: (h, w) or (oh, ow); tensor:
+        the caller's (dtype, channels_last, out) -> [n, channels, h, w], `out` if given."""
+        import torch
+        channels = 1 if desc._type_ is GrayImage else 3
+        dtype, channels_last, out = tensor
+        self._need_here(method, U)
+        n, (h, w) = boxes.shape[0], size
+        lead = (self._h, len(desc), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n, boxes.ctypes.data_as(ctypes.POINTER(crop_type)), h, w)
+        if fmt is not None:
+            res = _tensor_output(method.replace("gray_", ""), out, n, h, w, dtype, channels_last, U.device, channels)
+            self.use_torch_stream()
+            check(getattr(self._lib, f"lrf_qmf_{method}_tensor")(*lead, ctypes.byref(fmt), c_void_p(res.data_ptr()), res.numel() * res.element_size()))
+            return res
+        res = torch.empty((n, channels, h, w), dtype=torch.uint8, device=U.device)
+        self.use_torch_stream()
+        check(getattr(self._lib, f"lrf_qmf_{method}_{'rgb_u8' if channels == 3 else 'u8'}")(*lead, _dptr(res), res.numel()))
+        return res
+
     def decode_crops(self, U, V, images, crops, size, dtype=None, mean=None, std=None, channels_last=False, out=None):
         """Windows straight from the factors (lrf_qmf_decode_crops_rgb_u8).  U, V, images: as decode_ragged takes them; crops: an
         integer array-like [n, 3] of (image, y0, x0) on the host; size: (h, w) -> a uint8 CUDA tensor [n, 3, h, w], crop j equal
@@ -1281,22 +1277,9 @@ class Context:
         out: a tensor of that dtype, shape, device and memory format (a slice along n of a larger batch, say), written in place."""
         import torch
         fmt = _tensor_request("decode_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
-        ims, boxes, (h, w) = check_crop_args(U, V, images, crops, size)
-        self._need_here("decode_crops", U)
-        desc = _ragged_images(ims)
-        n = boxes.shape[0]
-        if fmt is not None:
-            res = _tensor_output("decode_crops", out, n, h, w, dtype, channels_last, U.device)
-            self.use_torch_stream()
-            check(self._lib.lrf_qmf_decode_crops_tensor(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
-                                                        boxes.ctypes.data_as(ctypes.POINTER(Crop)), h, w, ctypes.byref(fmt), c_void_p(res.data_ptr()),
-                                                        res.numel() * res.element_size()))
-            return res
-        rgb = torch.empty((n, 3, h, w), dtype=torch.uint8, device=U.device)
-        self.use_torch_stream()
-        check(self._lib.lrf_qmf_decode_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
-                                                    boxes.ctypes.data_as(ctypes.POINTER(Crop)), h, w, _dptr(rgb), rgb.numel()))
-        return rgb
+        ims, boxes, size = check_crop_args(U, V, images, crops, size)
+        return self._decode_windows("decode_crops", U, V, desc=_ragged_images(ims), boxes=boxes, crop_type=Crop, size=size, fmt=fmt,
+                                    tensor=(dtype, channels_last, out))
 
     def decode_scaled(self, U, V, images, scale):
         """Images at 1/scale straight from the factors (lrf_qmf_decode_scaled_rgb_u8).  U, V, images: as decode_ragged takes them;
@@ -1321,22 +1304,9 @@ class Context:
         dtype, mean, std, channels_last, out: as decode_crops takes them (lrf_qmf_decode_scaled_crops_tensor)."""
         import torch
         fmt = _tensor_request("decode_scaled_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
-        ims, boxes, (h, w) = check_scaled_args(U, V, images, crops=crops, size=size)
-        self._need_here("decode_scaled_crops", U)
-        desc = _ragged_images(ims)
-        n = boxes.shape[0]
-        if fmt is not None:
-            res = _tensor_output("decode_scaled_crops", out, n, h, w, dtype, channels_last, U.device)
-            self.use_torch_stream()
-            check(self._lib.lrf_qmf_decode_scaled_crops_tensor(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
-                                                               boxes.ctypes.data_as(ctypes.POINTER(ScaledCrop)), h, w, ctypes.byref(fmt),
-                                                               c_void_p(res.data_ptr()), res.numel() * res.element_size()))
-            return res
-        rgb = torch.empty((n, 3, h, w), dtype=torch.uint8, device=U.device)
-        self.use_torch_stream()
-        check(self._lib.lrf_qmf_decode_scaled_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
-                                                           boxes.ctypes.data_as(ctypes.POINTER(ScaledCrop)), h, w, _dptr(rgb), rgb.numel()))
-        return rgb
+        ims, boxes, size = check_scaled_args(U, V, images, crops=crops, size=size)
+        return self._decode_windows("decode_scaled_crops", U, V, desc=_ragged_images(ims), boxes=boxes, crop_type=ScaledCrop, size=size, fmt=fmt,
+                                    tensor=(dtype, channels_last, out))
 
     def decode_resized_crops(self, U, V, images, crops, size, dtype=None, mean=None, std=None, channels_last=False, out=None):
         """Boxes of any size resampled to one output size straight from the factors (lrf_qmf_decode_resized_crops_rgb_u8).  U, V,
@@ -1348,22 +1318,9 @@ class Context:
         to-tensor and normalise in one call, no uint8 batch in between."""
         import torch
         fmt = _tensor_request("decode_resized_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
-        ims, boxes, (oh, ow) = check_resized_args(U, V, images, crops, size)
-        self._need_here("decode_resized_crops", U)
-        desc = _ragged_images(ims)
-        n = boxes.shape[0]
-        if fmt is not None:
-            res = _tensor_output("decode_resized_crops", out, n, oh, ow, dtype, channels_last, U.device)
-            self.use_torch_stream()
-            check(self._lib.lrf_qmf_decode_resized_crops_tensor(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
-                                                                boxes.ctypes.data_as(ctypes.POINTER(ResizedCrop)), oh, ow, ctypes.byref(fmt),
-                                                                c_void_p(res.data_ptr()), res.numel() * res.element_size()))
-            return res
-        rgb = torch.empty((n, 3, oh, ow), dtype=torch.uint8, device=U.device)
-        self.use_torch_stream()
-        check(self._lib.lrf_qmf_decode_resized_crops_rgb_u8(self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n,
-                                                            boxes.ctypes.data_as(ctypes.POINTER(ResizedCrop)), oh, ow, _dptr(rgb), rgb.numel()))
-        return rgb
+        ims, boxes, size = check_resized_args(U, V, images, crops, size)
+        return self._decode_windows("decode_resized_crops", U, V, desc=_ragged_images(ims), boxes=boxes, crop_type=ResizedCrop, size=size, fmt=fmt,
+                                    tensor=(dtype, channels_last, out))
 
     def decode_gray_ragged(self, U, V, images, scale=1):
         """Gray images that differ in size and rank in one call, whole or at 1/2, 1/4, 1/8 scale (lrf_qmf_decode_gray_ragged_u8).
@@ -1374,10 +1331,7 @@ class Context:
         ims, scale = check_gray_images(U, V, images), check_gray_scale(scale)
         self._need_here("decode_gray_ragged", U)
         sizes = [gray_scaled_dims(H, W, scale) for H, W, *_ in ims]
-        offs, off = [], 0
-        for hs, ws in sizes:
-            offs.append(off)
-            off = (off + hs * ws + 15) // 16 * 16
+        offs, off = _packed_outputs(sizes, channels=1)
         desc = _gray_images(ims, offs)
         out = torch.empty((off,), dtype=torch.uint8, device=U.device)
         self.use_torch_stream()
@@ -1396,20 +1350,9 @@ class Context:
         dtype on this device (a slice along n of a larger batch, say), written in place."""
         import torch
         fmt = check_gray_tensor_request("decode_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
-        ims, boxes, (h, w) = check_gray_crop_args(U, V, images, crops, size)
-        self._need_here("decode_gray_crops", U)
-        desc = _gray_images(ims)
-        n = boxes.shape[0]
-        lead = (self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n, boxes.ctypes.data_as(ctypes.POINTER(ScaledCrop)), h, w)
-        if fmt is not None:
-            res = _gray_tensor_output("decode_crops", out, n, h, w, dtype, U.device)
-            self.use_torch_stream()
-            check(self._lib.lrf_qmf_decode_gray_crops_tensor(*lead, ctypes.byref(fmt), c_void_p(res.data_ptr()), res.numel() * res.element_size()))
-            return res
-        res = torch.empty((n, 1, h, w), dtype=torch.uint8, device=U.device)
-        self.use_torch_stream()
-        check(self._lib.lrf_qmf_decode_gray_crops_u8(*lead, _dptr(res), res.numel()))
-        return res
+        ims, boxes, size = check_gray_crop_args(U, V, images, crops, size)
+        return self._decode_windows("decode_gray_crops", U, V, desc=_gray_images(ims), boxes=boxes, crop_type=ScaledCrop, size=size, fmt=fmt,
+                                    tensor=(dtype, channels_last, out))
 
     def decode_gray_resized_crops(self, U, V, images, crops, size, dtype=None, mean=None, std=None, channels_last=False, out=None):
         """Boxes of any size out of gray images resampled to one output size straight from the factors
@@ -1419,20 +1362,9 @@ class Context:
         dtype, mean, std, channels_last, out: as decode_gray_crops takes them (lrf_qmf_decode_gray_resized_crops_tensor)."""
         import torch
         fmt = check_gray_tensor_request("decode_resized_crops", torch.uint8 if dtype is None else dtype, mean, std, channels_last, out)
-        ims, boxes, (oh, ow) = check_gray_resized_args(U, V, images, crops, size)
-        self._need_here("decode_gray_resized_crops", U)
-        desc = _gray_images(ims)
-        n = boxes.shape[0]
-        lead = (self._h, len(ims), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), n, boxes.ctypes.data_as(ctypes.POINTER(ResizedCrop)), oh, ow)
-        if fmt is not None:
-            res = _gray_tensor_output("decode_resized_crops", out, n, oh, ow, dtype, U.device)
-            self.use_torch_stream()
-            check(self._lib.lrf_qmf_decode_gray_resized_crops_tensor(*lead, ctypes.byref(fmt), c_void_p(res.data_ptr()), res.numel() * res.element_size()))
-            return res
-        res = torch.empty((n, 1, oh, ow), dtype=torch.uint8, device=U.device)
-        self.use_torch_stream()
-        check(self._lib.lrf_qmf_decode_gray_resized_crops_u8(*lead, _dptr(res), res.numel()))
-        return res
+        ims, boxes, size = check_gray_resized_args(U, V, images, crops, size)
+        return self._decode_windows("decode_gray_resized_crops", U, V, desc=_gray_images(ims), boxes=boxes, crop_type=ResizedCrop, size=size, fmt=fmt,
+                                    tensor=(dtype, channels_last, out))
 
     def encode_ragged(self, rgb, images, K, lo, hi, sign=None):
         """Images that differ in size and ranks in one encode (lrf_qmf_encode_ragged_rgb_u8).  rgb: a flat uint8 CUDA tensor;

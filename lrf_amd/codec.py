@@ -1922,7 +1922,7 @@ def qmf_decode_ragged(streams: Sequence[bytes], device=None, inflate: str = "hos
     gray = _gray_factors_ragged(streams)
     if gray is not None:
         _refuse_gray_inflate(on_device)
-        return _resident_gray(*gray, device).decode()
+        return _resident(*gray, device, 1).decode()
     if on_device:
         ctx, images, U, V = _factors_ragged_device(streams, device)
         return ctx.decode_ragged(U, V, images)
@@ -1952,21 +1952,11 @@ def _split_crops_by_scale(U, V, images, crops, size, scale):
     """The crops of a call with per-crop scales, split for the two kernels calls and validated (no device is touched): ->
     (where the full-scale crops stand in the call, their boxes [n1, 3], where the scaled ones stand, their boxes [n2, 4] of
     (image, scale, y0, x0)); either part may be empty."""
-    if hasattr(crops, "detach"):
-        if crops.is_cuda:
-            raise ValueError("crops live on the host: the call validates every box before it launches")
-        crops = crops.detach().numpy()
-    boxes = np.asarray(crops)
-    if boxes.size == 0:
-        raise ValueError("decode_crops needs 1 to 2^20 crops")
-    if boxes.dtype.kind not in "iu":
-        raise TypeError(f"crops must be integers (image, y0, x0), got {boxes.dtype}")
-    if boxes.ndim != 2 or boxes.shape[1] != 3:
-        raise ValueError(f"crops must be [n, 3] (image, y0, x0), got shape {tuple(boxes.shape)}")
+    boxes = _lib._check_boxes(crops, ("image", "y0", "x0"), "decode_crops", most=None)  # (each part takes its own kernel call of 1 to 2^20)
     sc = _crop_scales(scale, boxes.shape[0])
     full, scaled = np.flatnonzero(sc == 1), np.flatnonzero(sc != 1)
     b1 = boxes[full]
-    b2 = np.concatenate([boxes[scaled, :1], sc[scaled, None].astype(boxes.dtype), boxes[scaled, 1:]], axis=1)
+    b2 = np.concatenate([boxes[scaled, :1], sc[scaled, None], boxes[scaled, 1:]], axis=1)
     if full.size:
         _lib.check_crop_args(U, V, images, b1, size)
     if scaled.size:
@@ -2025,10 +2015,9 @@ class ResidentFactors:
         """crops: integers [n, 3] of (image, y0, x0) on the host; size: (h, w) -> uint8 CUDA [n, 3, h, w].  scale: 1, 2, 4, 8 or
         one of them per crop: crop j is the window (y0, x0) of its image decoded at 1/scale_j, y0 and x0 in that scaled image.
         dtype, mean, std, channels_last, out: the model's tensor instead of bytes, as qmf_decode_crops describes"""
+        tensor = _tensor_kwargs("decode_crops", dtype, mean, std, channels_last, out, self.channels)
         if self.channels == 1:  # per-crop scales go to the device in one call: the gray entry takes scale 1 too
-            tensor = _gray_tensor_kwargs("decode_crops", dtype, mean, std, channels_last, out)
             return self._ctx.decode_gray_crops(self.U, self.V, self.images, _gray_crop_rows(crops, scale), size, **tensor)
-        tensor = _tensor_kwargs("decode_crops", dtype, mean, std, channels_last, out)
         if type(scale) is int and scale == 1:
             return self._ctx.decode_crops(self.U, self.V, self.images, crops, size, **tensor)
         return _decode_crops_at_scales(self._ctx, self.U, self.V, self.images, crops, size, scale, **tensor)
@@ -2037,24 +2026,20 @@ class ResidentFactors:
         """boxes: integers [n, 5] of (image, y0, x0, h, w) on the host, full-resolution pixels; size: (oh, ow); flip: None, one
         bool, or one bool per box (mirror the output's columns) -> uint8 CUDA [n, 3, oh, ow]: qmf_decode_resized_crops, which
         also describes dtype, mean, std, channels_last and out"""
-        if self.channels == 1:
-            return self._ctx.decode_gray_resized_crops(self.U, self.V, self.images, _resized_boxes(boxes, flip), size,
-                                                       **_gray_tensor_kwargs("decode_resized_crops", dtype, mean, std, channels_last, out))
-        return self._ctx.decode_resized_crops(self.U, self.V, self.images, _resized_boxes(boxes, flip), size,
-                                              **_tensor_kwargs("decode_resized_crops", dtype, mean, std, channels_last, out))
+        rows = _resized_boxes(boxes, flip)
+        return self._decode_resized_rows(rows, size, _tensor_kwargs("decode_resized_crops", dtype, mean, std, channels_last, out, self.channels))
+
+    def _decode_resized_rows(self, rows, size, tensor) -> torch.Tensor:
+        """rows: _resized_boxes' [n, 6]; tensor: _tensor_kwargs' keywords"""
+        decode = self._ctx.decode_gray_resized_crops if self.channels == 1 else self._ctx.decode_resized_crops
+        return decode(self.U, self.V, self.images, rows, size, **tensor)
 
 
-def _tensor_kwargs(entry, dtype, mean, std, channels_last, out) -> dict:
+def _tensor_kwargs(entry, dtype, mean, std, channels_last, out, channels=3) -> dict:
     """the output arguments of the crop entries, checked (no device is touched), as the keywords Context's methods take: none for
-    the defaults, which are the uint8 calls as they always were"""
-    if _lib._tensor_request(entry, dtype, mean, std, channels_last, out) is None:
-        return {}
-    return dict(dtype=dtype, mean=mean, std=std, channels_last=channels_last, out=out)
-
-
-def _gray_tensor_kwargs(entry, dtype, mean, std, channels_last, out) -> dict:
-    """_tensor_kwargs for a gray source: mean and std are None, one number or a sequence of one (three numbers: ValueError)"""
-    if _lib.check_gray_tensor_request(entry, dtype, mean, std, channels_last, out) is None:
+    the defaults, which are the uint8 calls as they always were.  channels 1 (a gray source): mean and std are None, one number or
+    a sequence of one (three numbers: ValueError)"""
+    if _lib._tensor_request(entry, dtype, mean, std, channels_last, out, channels) is None:
         return {}
     return dict(dtype=dtype, mean=mean, std=std, channels_last=channels_last, out=out)
 
@@ -2102,25 +2087,10 @@ def _refuse_gray_inflate(on_device):
         raise NotImplementedError("inflate='device' is not served for gray streams (two-factor containers inflate on the host)")
 
 
-def _resident_gray(images, Uh, Vh, device) -> ResidentFactors:
-    ctx = _lib.context(device)
-    return ResidentFactors(ctx, torch.from_numpy(Uh).cuda(ctx.device), torch.from_numpy(Vh).cuda(ctx.device), images, channels=1)
-
-
 def _resized_boxes(boxes, flip):
     """boxes: integers [n, 5] of (image, y0, x0, h, w) on the host; flip: None, one bool, or one bool per box -> an int64 array
     [n, 6] of (image, y0, x0, h, w, flip), the rows Context.decode_resized_crops takes (which validates the boxes themselves)"""
-    if hasattr(boxes, "detach"):
-        if boxes.is_cuda:
-            raise ValueError("boxes live on the host: the call validates every box before it launches")
-        boxes = boxes.detach().numpy()
-    b = np.asarray(boxes)
-    if b.size == 0:
-        raise ValueError("decode_resized_crops needs 1 to 2^20 crops")
-    if b.dtype.kind not in "iu":
-        raise TypeError(f"boxes must be integers (image, y0, x0, h, w), got {b.dtype}")
-    if b.ndim != 2 or b.shape[1] != 5:
-        raise ValueError(f"boxes must be [n, 5] (image, y0, x0, h, w), got shape {tuple(b.shape)}")
+    b = _lib._check_boxes(boxes, ("image", "y0", "x0", "h", "w"), "decode_resized_crops", noun="boxes", most=None)  # (check_resized_args counts them)
     n = b.shape[0]
     if flip is None:
         fl = np.zeros(n, dtype=np.int64)
@@ -2133,12 +2103,12 @@ def _resized_boxes(boxes, flip):
         if fl.ndim != 1 or fl.shape[0] != n:
             raise ValueError(f"flip must be one value or one per box ({n}), got shape {tuple(fl.shape)}")
         fl = fl.astype(np.int64)
-    return np.concatenate([b.astype(np.int64), fl[:, None]], axis=1)
+    return np.concatenate([b, fl[:, None]], axis=1)
 
 
-def _resident(images, Uh, Vh, device) -> ResidentFactors:
+def _resident(images, Uh, Vh, device, channels=3) -> ResidentFactors:
     ctx = _lib.context(device)
-    return ResidentFactors(ctx, torch.from_numpy(Uh).cuda(ctx.device), torch.from_numpy(Vh).cuda(ctx.device), images)
+    return ResidentFactors(ctx, torch.from_numpy(Uh).cuda(ctx.device), torch.from_numpy(Vh).cuda(ctx.device), images, channels)
 
 
 def qmf_load_factors(streams: Sequence[bytes], device=None, inflate: str = "host") -> ResidentFactors:
@@ -2150,7 +2120,7 @@ def qmf_load_factors(streams: Sequence[bytes], device=None, inflate: str = "host
     gray = _gray_factors_ragged(streams)
     if gray is not None:
         _refuse_gray_inflate(on_device)
-        return _resident_gray(*gray, device)
+        return _resident(*gray, device, 1)
     if on_device:
         ctx, images, U, V = _factors_ragged_device(streams, device)
         return ResidentFactors(ctx, U, V, images)
@@ -2173,21 +2143,19 @@ def qmf_decode_crops(source, crops, size, device=None, inflate: str = "host", sc
     A gray source (a list of gray streams, or their ResidentFactors): [n, 1, h, w]; mean, std: None, one number or a sequence of
     one (three numbers: ValueError); the crops of every scale leave in one kernel call."""
     gray = source.channels == 1 if isinstance(source, ResidentFactors) else _gray_factors_ragged(source)  # (host only; raises nothing)
-    if gray:
-        tensor = _gray_tensor_kwargs("qmf_decode_crops", dtype, mean, std, channels_last, out)
-        on_device = _check_inflate(inflate)
-        if not isinstance(source, ResidentFactors):
-            _refuse_gray_inflate(on_device)
-            images, Uh, Vh = gray
-            _lib.check_gray_crop_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, _gray_crop_rows(crops, scale), size)  # before a GPU is asked for
-            source = _resident_gray(images, Uh, Vh, device)
-        return source.decode_crops(crops, size, scale, **tensor)
-    tensor = _tensor_kwargs("qmf_decode_crops", dtype, mean, std, channels_last, out)  # refused before anything is uploaded
+    tensor = _tensor_kwargs("qmf_decode_crops", dtype, mean, std, channels_last, out, 1 if gray else 3)  # refused before anything is uploaded
     on_device = _check_inflate(inflate)
-    if on_device and not isinstance(source, ResidentFactors):
+    if isinstance(source, ResidentFactors):
+        pass
+    elif gray:
+        _refuse_gray_inflate(on_device)
+        images, Uh, Vh = gray
+        _lib.check_gray_crop_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, _gray_crop_rows(crops, scale), size)  # before a GPU is asked for
+        source = _resident(images, Uh, Vh, device, 1)
+    elif on_device:
         ctx, images, U, V = _factors_ragged_device(source, device)
         source = ResidentFactors(ctx, U, V, images)
-    if not isinstance(source, ResidentFactors):
+    else:
         images, Uh, Vh = _factors_ragged(source)
         if type(scale) is int and scale == 1:
             _lib.check_crop_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, crops, size)  # refused before a GPU is asked for
@@ -2214,27 +2182,25 @@ def qmf_decode_resized_crops(source, boxes, size, flip=None, device=None, inflat
     dtype, mean, std, channels_last, out: as qmf_decode_crops takes them — the resized crop, the flip, to-tensor and normalise in
     one call; under flip the pixels are mirrored, whatever the element size or layout."""
     gray = source.channels == 1 if isinstance(source, ResidentFactors) else _gray_factors_ragged(source)  # (host only; raises nothing)
-    if gray:  # [n, 1, oh, ow]; mean, std: None, one number or a sequence of one
-        tensor = _gray_tensor_kwargs("qmf_decode_resized_crops", dtype, mean, std, channels_last, out)
-        on_device = _check_inflate(inflate)
-        rows = _resized_boxes(boxes, flip)
-        if not isinstance(source, ResidentFactors):
-            _refuse_gray_inflate(on_device)
-            images, Uh, Vh = gray
-            _lib.check_gray_resized_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, rows, size)  # refused before a GPU is asked for
-            source = _resident_gray(images, Uh, Vh, device)
-        return source._ctx.decode_gray_resized_crops(source.U, source.V, source.images, rows, size, **tensor)
-    tensor = _tensor_kwargs("qmf_decode_resized_crops", dtype, mean, std, channels_last, out)
+    # (a gray source: [n, 1, oh, ow]; mean, std: None, one number or a sequence of one)
+    tensor = _tensor_kwargs("qmf_decode_resized_crops", dtype, mean, std, channels_last, out, 1 if gray else 3)
     on_device = _check_inflate(inflate)
     rows = _resized_boxes(boxes, flip)
-    if on_device and not isinstance(source, ResidentFactors):
+    if isinstance(source, ResidentFactors):
+        pass
+    elif gray:
+        _refuse_gray_inflate(on_device)
+        images, Uh, Vh = gray
+        _lib.check_gray_resized_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, rows, size)  # refused before a GPU is asked for
+        source = _resident(images, Uh, Vh, device, 1)
+    elif on_device:
         ctx, images, U, V = _factors_ragged_device(source, device)
         source = ResidentFactors(ctx, U, V, images)
-    if not isinstance(source, ResidentFactors):
+    else:
         images, Uh, Vh = _factors_ragged(source)
         _lib.check_resized_args(torch.from_numpy(Uh), torch.from_numpy(Vh), images, rows, size)  # refused before a GPU is asked for
         source = _resident(images, Uh, Vh, device)
-    return source._ctx.decode_resized_crops(source.U, source.V, source.images, rows, size, **tensor)
+    return source._decode_resized_rows(rows, size, tensor)
 
 
 def qmf_decode_scaled(source, scale, device=None, inflate: str = "host") -> list:
@@ -2256,7 +2222,7 @@ def qmf_decode_scaled(source, scale, device=None, inflate: str = "host") -> list
     gray = _gray_factors_ragged(source)
     if gray is not None:  # a list of gray streams: [1, ceil(H_i / scale), ceil(W_i / scale)], the gray loader's exact-integer levels
         _refuse_gray_inflate(on_device)
-        return _resident_gray(*gray, device).decode(int(scale))
+        return _resident(*gray, device, 1).decode(int(scale))
     if on_device:
         ctx, images, U, V = _factors_ragged_device(source, device)
         return ctx.decode_scaled(U, V, images, int(scale))

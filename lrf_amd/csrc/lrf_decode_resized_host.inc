@@ -7,30 +7,15 @@ static int decode_resized_to(lrf_ctx* c, int64_t n_images, const lrf_ragged_imag
                              int64_t n_crops, const lrf_resized_crop* crops, int64_t oh, int64_t ow, const DecodeOut& o)
 {
     void* const rgb = o.p;
-    const int64_t rgb_len = o.len;
-    if (!c || !images || !U || !V || !crops || !rgb) return set_err(LRF_EINVAL, "NULL argument");
-    if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
-    if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
-    if (oh < 1 || ow < 1 || oh > 16384 || ow > 16384) return set_err(LRF_EINVAL, "output size %ldx%ld out of range [1,16384]", (long)oh, (long)ow);
-    std::vector<RaggedDesc> descs;
-    int rc = describe(n_images, images, u_len, v_len, DescribeOptions{}, "image", "output", descs);
+    const WindowCall k = {n_images, n_crops, oh, ow, true, 0, 3, o.len};
+    int rc = check_crop_call(!c || !images || !U || !V || !crops || !rgb, k);
     if (rc) return rc;
-    // (oh ow <= 2^28 and n_crops <= 2^20: 3 oh ow n_crops cannot wrap)
-    if (rgb_len < 3 || n_crops > rgb_len / (3 * oh * ow))
-        return set_err(LRF_EINVAL, "%ld crops of 3x%ldx%ld leave the output buffer of %ld bytes", (long)n_crops, (long)oh, (long)ow, (long)rgb_len);
+    std::vector<RaggedDesc> descs;
+    if ((rc = describe(n_images, images, u_len, v_len, DescribeOptions{}, "image", "output", descs))) return rc;
+    std::vector<ResizedItem> list;
+    if ((rc = checked_windows(k, descs, crops, list))) return rc;
     std::vector<int> r8(descs.size());
     std::transform(descs.begin(), descs.end(), r8.begin(), [](const RaggedDesc& d) { return d.R0 <= 8 && d.R1 <= 8 && d.R2 <= 8; });
-    std::vector<ResizedItem> list((size_t)n_crops);
-    for (int64_t j = 0; j < n_crops; j++) {
-        const lrf_resized_crop& cr = crops[j];
-        if (cr.image < 0 || cr.image >= n_images) return set_err(LRF_EINVAL, "crop %ld: image %d out of range [0,%ld)", (long)j, cr.image, (long)n_images);
-        const lrf_ragged_image& im = images[cr.image];
-        if (cr.h < 1 || cr.w < 1) return set_err(LRF_EINVAL, "crop %ld: box of %dx%d: both sides must be >= 1", (long)j, cr.h, cr.w);
-        if (cr.y0 < 0 || cr.x0 < 0 || cr.h > im.H || cr.w > im.W || cr.y0 > im.H - cr.h || cr.x0 > im.W - cr.w)
-            return set_err(LRF_EINVAL, "crop %ld: %dx%d at (%d,%d) leaves image %d of %ldx%ld", (long)j, cr.h, cr.w, cr.y0, cr.x0, cr.image, (long)im.H,
-                           (long)im.W);
-        list[(size_t)j] = ResizedItem{cr.image, 1, cr.y0, cr.x0, cr.h, cr.w, cr.flip != 0, (int)j};
-    }
     const ResizedPlan plan = plan_decode_resized(r8, list, (int)oh, (int)ow);
     if (plan.too_many) return set_err(LRF_EINVAL, "%ld workgroups in one launch: split the list", plan.too_many);
     LRF_ON_DEVICE(c);

@@ -108,30 +108,13 @@ int lrf_qmf_decode_scaled_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* 
 static int decode_scaled_crops_to(lrf_ctx* c, int64_t n_images, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
                                   int64_t v_len, int64_t n_crops, const lrf_scaled_crop* crops, int64_t h, int64_t w, const DecodeOut& o)
 {
-    void* const rgb = o.p;
-    const int64_t rgb_len = o.len;
-    if (!c || !images || !U || !V || !crops || !rgb) return set_err(LRF_EINVAL, "NULL argument");
-    if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
-    if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
-    if (h < 1 || w < 1 || h > INT32_MAX || w > INT32_MAX) return set_err(LRF_EINVAL, "crop size %ldx%ld out of range", (long)h, (long)w);
-    std::vector<RaggedDesc> descs;
-    int rc = describe(n_images, images, u_len, v_len, DescribeOptions{}, "image", "output", descs);
+    const WindowCall k = {n_images, n_crops, h, w, false, LRF_WIN_SCALES_COLOUR, 3, o.len};
+    int rc = check_crop_call(!c || !images || !U || !V || !crops || !o.p, k);
     if (rc) return rc;
-    // (h * w <= rgb_len / 3 first: then 3 h w cannot wrap)
-    if (rgb_len < 3 || h > rgb_len / 3 / w || n_crops > rgb_len / (3 * h * w))
-        return set_err(LRF_EINVAL, "%ld crops of 3x%ldx%ld leave the output buffer of %ld bytes", (long)n_crops, (long)h, (long)w, (long)rgb_len);
-    std::vector<ScaledItem> items((size_t)n_crops);
-    for (int64_t j = 0; j < n_crops; j++) {
-        const lrf_scaled_crop& cr = crops[j];
-        if (cr.image < 0 || cr.image >= n_images) return set_err(LRF_EINVAL, "crop %ld: image %d out of range [0,%ld)", (long)j, cr.image, (long)n_images);
-        if (!scaled_f_ok(cr.scale)) return set_err(LRF_EINVAL, "crop %ld: scale %d: 2, 4 or 8 expected", (long)j, cr.scale);
-        const lrf_ragged_image& im = images[cr.image];
-        const int64_t hs = scaled_dim(im.H, cr.scale), ws = scaled_dim(im.W, cr.scale);
-        if (cr.y0 < 0 || cr.x0 < 0 || h > hs || w > ws || cr.y0 > hs - h || cr.x0 > ws - w)
-            return set_err(LRF_EINVAL, "crop %ld: %ldx%ld at (%d,%d) leaves image %d of %ldx%ld at scale 1/%d", (long)j, (long)h, (long)w, cr.y0, cr.x0, cr.image,
-                           (long)hs, (long)ws, cr.scale);
-        items[(size_t)j] = ScaledItem{cr.image, cr.scale, cr.y0, cr.x0, (int)h, (int)w, (int)j, 0, 3 * h * w * j, 0};
-    }
+    std::vector<RaggedDesc> descs;
+    if ((rc = describe(n_images, images, u_len, v_len, DescribeOptions{}, "image", "output", descs))) return rc;
+    std::vector<ScaledItem> items;
+    if ((rc = checked_windows(k, descs, crops, items))) return rc;
     return run_scaled(c, descs, items, U, V, o);
 }
 

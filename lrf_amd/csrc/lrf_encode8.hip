@@ -602,6 +602,39 @@ static int run_planes_ragged(lrf_ctx* c, const std::vector<EncRaggedDesc>& descs
     return LRF_OK;
 }
 
+// A refusal of check_window_call or check_windows (lrf_plan.h) in the words of the ten entries that decode crops
+int refuse_window(const WindowRefusal& r, const WindowCall& k)
+{
+    const long j = (long)r.crop;
+    switch (r.check) {
+    case WIN_N_IMAGES: return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)k.n_images);
+    case WIN_N_CROPS: return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)k.n_crops);
+    case WIN_SIZE:
+        if (k.resized) return set_err(LRF_EINVAL, "output size %ldx%ld out of range [1,16384]", (long)k.h, (long)k.w);
+        return set_err(LRF_EINVAL, "crop size %ldx%ld out of range", (long)k.h, (long)k.w);
+    case WIN_CAPACITY:
+        if (k.channels == 1)
+            return set_err(LRF_EINVAL, "%ld crops of %ldx%ld leave the output buffer of %ld elements", (long)k.n_crops, (long)k.h, (long)k.w, (long)k.out_len);
+        return set_err(LRF_EINVAL, "%ld crops of 3x%ldx%ld leave the output buffer of %ld bytes", (long)k.n_crops, (long)k.h, (long)k.w, (long)k.out_len);
+    case WIN_IMAGE: return set_err(LRF_EINVAL, "crop %ld: image %d out of range [0,%ld)", j, r.image, (long)k.n_images);
+    case WIN_SCALE:
+        if (k.scales == LRF_WIN_SCALES_GRAY) return set_err(LRF_EINVAL, "crop %ld: scale %d: 1, 2, 4 or 8 expected", j, r.scale);
+        return set_err(LRF_EINVAL, "crop %ld: scale %d: 2, 4 or 8 expected", j, r.scale);
+    case WIN_SIDES: return set_err(LRF_EINVAL, "crop %ld: box of %ldx%ld: both sides must be >= 1", j, (long)r.h, (long)r.w);
+    default:
+        if (k.scales)
+            return set_err(LRF_EINVAL, "crop %ld: %ldx%ld at (%d,%d) leaves image %d of %ldx%ld at scale 1/%d", j, (long)r.h, (long)r.w, r.y0, r.x0, r.image,
+                           (long)r.H, (long)r.W, r.scale);
+        return set_err(LRF_EINVAL, "crop %ld: %ldx%ld at (%d,%d) leaves image %d of %ldx%ld", j, (long)r.h, (long)r.w, r.y0, r.x0, r.image, (long)r.H, (long)r.W);
+    }
+}
+int check_crop_call(bool null_argument, const WindowCall& k)
+{
+    if (null_argument) return set_err(LRF_EINVAL, "NULL argument");
+    const WindowRefusal r = check_window_call(k);
+    return r.check == WIN_OK ? LRF_OK : refuse_window(r, k);
+}
+
 extern "C" {
 
 // A list of images that differ in size and ranks in one encode (planes kernels: lrf_planes_ragged_kernel.hip; the tables:
@@ -941,29 +974,15 @@ static int decode_crops_to(lrf_ctx* c, int64_t n_images, const lrf_ragged_image*
                            int64_t n_crops, const lrf_crop* crops, int64_t h, int64_t w, const DecodeOut& o)
 {
     void* const rgb = o.p;
-    const int64_t rgb_len = o.len;
-    if (!c || !images || !U || !V || !crops || !rgb) return set_err(LRF_EINVAL, "NULL argument");
-    if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
-    if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
-    if (h < 1 || w < 1 || h > INT32_MAX || w > INT32_MAX) return set_err(LRF_EINVAL, "crop size %ldx%ld out of range", (long)h, (long)w);
+    const WindowCall k = {n_images, n_crops, h, w, false, 0, 3, o.len};
+    int rc = check_crop_call(!c || !images || !U || !V || !crops || !rgb, k);
+    if (rc) return rc;
     std::vector<RaggedDesc> descs;
     std::vector<RaggedWork> work;
     // (the output is the crops', and the windowed tiled body stores at any alignment: the defaults)
-    int rc = describe(n_images, images, u_len, v_len, DescribeOptions{}, "image", "output", descs, &work);
-    if (rc) return rc;
-    // (h * w <= rgb_len / 3 first: then 3 h w cannot wrap)
-    if (rgb_len < 3 || h > rgb_len / 3 / w || n_crops > rgb_len / (3 * h * w))
-        return set_err(LRF_EINVAL, "%ld crops of 3x%ldx%ld leave the output buffer of %ld bytes", (long)n_crops, (long)h, (long)w, (long)rgb_len);
-    std::vector<CropEntry> list((size_t)n_crops);
-    for (int64_t j = 0; j < n_crops; j++) {
-        const lrf_crop& cr = crops[j];
-        if (cr.image < 0 || cr.image >= n_images) return set_err(LRF_EINVAL, "crop %ld: image %d out of range [0,%ld)", (long)j, cr.image, (long)n_images);
-        const lrf_ragged_image& im = images[cr.image];
-        if (cr.y0 < 0 || cr.x0 < 0 || h > im.H || w > im.W || cr.y0 > im.H - h || cr.x0 > im.W - w)
-            return set_err(LRF_EINVAL, "crop %ld: %ldx%ld at (%d,%d) leaves image %d of %ldx%ld", (long)j, (long)h, (long)w, cr.y0, cr.x0, cr.image, (long)im.H,
-                           (long)im.W);
-        list[(size_t)j] = CropEntry{cr.image, cr.y0, cr.x0, (int)j};
-    }
+    if ((rc = describe(n_images, images, u_len, v_len, DescribeOptions{}, "image", "output", descs, &work))) return rc;
+    std::vector<CropEntry> list;
+    if ((rc = checked_windows(k, descs, crops, list))) return rc;
     const CropPlan plan = plan_decode_crops(work, list, (int)h, (int)w);
     if (plan.too_many) return set_err(LRF_EINVAL, "%ld workgroups in one launch: split the list", plan.too_many);
     LRF_ON_DEVICE(c);

@@ -58,55 +58,26 @@ static int run_gray_windows(lrf_ctx* c, const std::vector<GrayDesc>& descs, cons
 static int gray_crops_to(lrf_ctx* c, int64_t n_images, const lrf_gray_image* images, const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len,
                          int64_t n_crops, const lrf_scaled_crop* crops, int64_t h, int64_t w, const DecodeOut& o)
 {
-    if (!c || !images || !U || !V || !crops || !o.p) return set_err(LRF_EINVAL, "NULL argument");
-    if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
-    if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
-    if (h < 1 || w < 1 || h > INT32_MAX || w > INT32_MAX) return set_err(LRF_EINVAL, "crop size %ldx%ld out of range", (long)h, (long)w);
-    std::vector<GrayDesc> descs;
-    int rc = gray_describe(n_images, images, u_len, v_len, 0, 0, descs);
+    const WindowCall k = {n_images, n_crops, h, w, false, LRF_WIN_SCALES_GRAY, 1, o.len};
+    int rc = check_crop_call(!c || !images || !U || !V || !crops || !o.p, k);
     if (rc) return rc;
-    // (h <= len / w first: then h w cannot wrap)
-    if (o.len < 1 || h > o.len / w || n_crops > o.len / (h * w))
-        return set_err(LRF_EINVAL, "%ld crops of %ldx%ld leave the output buffer of %ld elements", (long)n_crops, (long)h, (long)w, (long)o.len);
-    std::vector<GrayItem> items((size_t)n_crops);
-    for (int64_t j = 0; j < n_crops; j++) {
-        const lrf_scaled_crop& cr = crops[j];
-        if (cr.image < 0 || cr.image >= n_images) return set_err(LRF_EINVAL, "crop %ld: image %d out of range [0,%ld)", (long)j, cr.image, (long)n_images);
-        if (!gray_scale_ok(cr.scale)) return set_err(LRF_EINVAL, "crop %ld: scale %d: 1, 2, 4 or 8 expected", (long)j, cr.scale);
-        const lrf_gray_image& im = images[cr.image];
-        const int64_t Hs = scaled_dim(im.H, cr.scale), Ws = scaled_dim(im.W, cr.scale);
-        if (cr.y0 < 0 || cr.x0 < 0 || h > Hs || w > Ws || cr.y0 > Hs - h || cr.x0 > Ws - w)
-            return set_err(LRF_EINVAL, "crop %ld: %ldx%ld at (%d,%d) leaves image %d of %ldx%ld at scale 1/%d", (long)j, (long)h, (long)w, cr.y0, cr.x0,
-                           cr.image, (long)Hs, (long)Ws, cr.scale);
-        items[(size_t)j] = GrayItem{cr.image, cr.scale, cr.y0, cr.x0, (int)h, (int)w, 0, (int)j, (long)(j * h * w), (long)w};
-    }
+    std::vector<GrayDesc> descs;
+    if ((rc = gray_describe(n_images, images, u_len, v_len, 0, 0, descs))) return rc;
+    std::vector<GrayItem> items;
+    if ((rc = checked_windows(k, descs, crops, items))) return rc;
     return run_gray_windows(c, descs, items, U, V, o);
 }
 
 static int gray_resized_to(lrf_ctx* c, int64_t n_images, const lrf_gray_image* images, const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len,
                            int64_t n_crops, const lrf_resized_crop* crops, int64_t oh, int64_t ow, const DecodeOut& o)
 {
-    if (!c || !images || !U || !V || !crops || !o.p) return set_err(LRF_EINVAL, "NULL argument");
-    if (n_images < 1 || n_images > 65535) return set_err(LRF_EINVAL, "n_images=%ld out of range [1,65535]", (long)n_images);
-    if (n_crops < 1 || n_crops > (1 << 20)) return set_err(LRF_EINVAL, "n_crops=%ld out of range [1,2^20]", (long)n_crops);
-    if (oh < 1 || ow < 1 || oh > 16384 || ow > 16384) return set_err(LRF_EINVAL, "output size %ldx%ld out of range [1,16384]", (long)oh, (long)ow);
-    std::vector<GrayDesc> descs;
-    int rc = gray_describe(n_images, images, u_len, v_len, 0, 0, descs);
+    const WindowCall k = {n_images, n_crops, oh, ow, true, 0, 1, o.len};
+    int rc = check_crop_call(!c || !images || !U || !V || !crops || !o.p, k);
     if (rc) return rc;
-    // (oh ow <= 2^28 and n_crops <= 2^20: oh ow n_crops cannot wrap)
-    if (o.len < 1 || n_crops > o.len / (oh * ow))
-        return set_err(LRF_EINVAL, "%ld crops of %ldx%ld leave the output buffer of %ld elements", (long)n_crops, (long)oh, (long)ow, (long)o.len);
-    std::vector<GrayItem> boxes((size_t)n_crops);
-    for (int64_t j = 0; j < n_crops; j++) {
-        const lrf_resized_crop& cr = crops[j];
-        if (cr.image < 0 || cr.image >= n_images) return set_err(LRF_EINVAL, "crop %ld: image %d out of range [0,%ld)", (long)j, cr.image, (long)n_images);
-        const lrf_gray_image& im = images[cr.image];
-        if (cr.h < 1 || cr.w < 1) return set_err(LRF_EINVAL, "crop %ld: box of %dx%d: both sides must be >= 1", (long)j, cr.h, cr.w);
-        if (cr.y0 < 0 || cr.x0 < 0 || cr.h > im.H || cr.w > im.W || cr.y0 > im.H - cr.h || cr.x0 > im.W - cr.w)
-            return set_err(LRF_EINVAL, "crop %ld: %dx%d at (%d,%d) leaves image %d of %ldx%ld", (long)j, cr.h, cr.w, cr.y0, cr.x0, cr.image, (long)im.H,
-                           (long)im.W);
-        boxes[(size_t)j] = GrayItem{cr.image, 1, cr.y0, cr.x0, cr.h, cr.w, cr.flip != 0, (int)j, 0, 0};
-    }
+    std::vector<GrayDesc> descs;
+    if ((rc = gray_describe(n_images, images, u_len, v_len, 0, 0, descs))) return rc;
+    std::vector<GrayItem> boxes;
+    if ((rc = checked_windows(k, descs, crops, boxes))) return rc;
     const GrayPlan plan = plan_gray_resized(boxes, (int)oh, (int)ow);
     if (plan.too_many) return set_err(LRF_EINVAL, "%ld workgroups in one launch: split the list", plan.too_many);
     LRF_ON_DEVICE(c);

@@ -200,6 +200,18 @@ inline DecodeOut bytes_out(uint8_t* rgb, int64_t rgb_len) { return DecodeOut{rgb
 // fmt, out, out_bytes of a _tensor entry -> the output in elements; everything is checked before the body sees it
 // (lrf_decode_tensor_host.inc)
 int tensor_out(const lrf_tensor_format* fmt, void* out, int64_t out_bytes, DecodeOut* o);
+// The checks of the ten entries that decode crops (lrf_plan.h: check_window_call, check_windows), refused in the entries' words
+// (lrf_encode8.hip defines the two functions).
+// check_crop_call: the prologue — NULL, then the ranges of n_images, n_crops and the size; checked_windows: the output's
+// capacity and the crop list -> the items of the call's plan
+int refuse_window(const WindowRefusal& r, const WindowCall& k);
+int check_crop_call(bool null_argument, const WindowCall& k);
+template <class Desc, class Crop, class Item>
+static int checked_windows(const WindowCall& k, const std::vector<Desc>& descs, const Crop* crops, std::vector<Item>& items)
+{
+    const WindowRefusal r = check_windows(k, descs, crops, items);
+    return r.check == WIN_OK ? LRF_OK : refuse_window(r, k);
+}
 // fn(T* out) with T the element type of a tensor output
 template <class F>
 static void with_tensor_type(const DecodeOut& o, F&& fn)

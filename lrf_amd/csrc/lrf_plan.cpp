@@ -633,6 +633,91 @@ GrayPlan plan_gray_resized(const std::vector<GrayItem>& boxes, int oh, int ow)
         });
 }
 
+// ---- the window list of the entries that decode crops ----------------------------------------------------------------------------
+WindowRefusal check_window_call(const WindowCall& k)
+{
+    WindowRefusal r;
+    if (k.n_images < 1 || k.n_images > 65535) r.check = WIN_N_IMAGES;
+    else if (k.n_crops < 1 || k.n_crops > LRF_WIN_MAX_CROPS) r.check = WIN_N_CROPS;
+    else if (k.h < 1 || k.w < 1 || k.h > (k.resized ? LRF_WIN_MAX_RESIZED_SIDE : INT32_MAX) || k.w > (k.resized ? LRF_WIN_MAX_RESIZED_SIDE : INT32_MAX))
+        r.check = WIN_SIZE;
+    return r;
+}
+
+namespace {
+// what the three ABI shapes differ in: whether a crop carries a scale (else it is at scale 1) and sides of its own (else the call's)
+template <class Crop> struct CropShape { static constexpr bool scaled = false, boxed = false; };
+template <> struct CropShape<lrf_scaled_crop> { static constexpr bool scaled = true, boxed = false; };
+template <> struct CropShape<lrf_resized_crop> { static constexpr bool scaled = false, boxed = true; };
+struct Window { int image, scale, y0, x0; int64_t h, w; int flip; }; // an accepted crop of any shape
+// the validated window j as each plan takes it (sides and j fit an int: checked)
+template <class Item>
+Item item_of(const Window& v, int64_t j, const WindowCall& k);
+template <> inline CropEntry item_of(const Window& v, int64_t j, const WindowCall&) { return CropEntry{v.image, v.y0, v.x0, (int)j}; }
+template <> inline ScaledItem item_of(const Window& v, int64_t j, const WindowCall& k)
+{
+    return ScaledItem{v.image, v.scale, v.y0, v.x0, (int)v.h, (int)v.w, (int)j, 0, (long)(k.channels * v.h * v.w * j), 0};
+}
+template <> inline ResizedItem item_of(const Window& v, int64_t j, const WindowCall&)
+{
+    return ResizedItem{v.image, 1, v.y0, v.x0, (int)v.h, (int)v.w, v.flip, (int)j};
+}
+template <> inline GrayItem item_of(const Window& v, int64_t j, const WindowCall& k) // (boxes: plan_gray_resized sets out_off and pitch)
+{
+    return GrayItem{v.image, v.scale, v.y0, v.x0, (int)v.h, (int)v.w, v.flip, (int)j, k.resized ? 0 : (long)(j * v.h * v.w), k.resized ? 0 : (long)v.w};
+}
+}
+
+template <class Desc, class Crop, class Item>
+WindowRefusal check_windows(const WindowCall& call, const std::vector<Desc>& descs, const Crop* crops, std::vector<Item>& items)
+{
+    using Shape = CropShape<Crop>;
+    const WindowCall k = call; // (locals, like `size` and `out` below: the item stores cannot alias them, so the loop keeps them in registers)
+    // (h <= len / channels / w first: then channels h w cannot wrap)
+    if (k.out_len < k.channels || k.h > k.out_len / k.channels / k.w || k.n_crops > k.out_len / (k.channels * k.h * k.w))
+        return WindowRefusal{WIN_CAPACITY};
+    items.resize((size_t)k.n_crops);
+    Item* const out = items.data();
+    // (H, W) per image, compact and as wide as the comparisons: the loop reads nothing else of a descriptor
+    std::vector<int64_t> sizes(2 * (size_t)k.n_images);
+    for (int64_t i = 0; i < k.n_images; i++) { sizes[2 * (size_t)i] = descs[(size_t)i].H; sizes[2 * (size_t)i + 1] = descs[(size_t)i].W; }
+    const int64_t* const size = sizes.data();
+    // one crop: what the shape does not carry is the call's, constants of the loop (the call's sides are >= 1: check_window_call).
+    // r: null in the loop; the refusal's operands, filled on the way out
+    auto check_crop = [&](const Crop& c, int64_t j, WindowRefusal* r) -> int {
+        int scale = 1, flip = 0;
+        int64_t h = k.h, w = k.w;
+        if constexpr (Shape::scaled) scale = c.scale;
+        if constexpr (Shape::boxed) { h = c.h; w = c.w; flip = c.flip != 0; }
+        int check = WIN_OK;
+        int64_t H = 0, W = 0; // the image at the window's scale
+        if (c.image < 0 || c.image >= k.n_images) check = WIN_IMAGE;
+        else if (Shape::scaled && (scale < 0 || scale > 8 || !((k.scales >> scale) & 1u))) check = WIN_SCALE;
+        else if (Shape::boxed && (h < 1 || w < 1)) check = WIN_SIDES;
+        else {
+            H = size[2 * c.image]; W = size[2 * c.image + 1];
+            if constexpr (Shape::scaled) { H = scaled_dim(H, scale); W = scaled_dim(W, scale); }
+            const int64_t dy = H - h, dx = W - w; // (all four below 2^31: the room below and right of the window's origin)
+            if (c.y0 < 0 || c.x0 < 0 || dy < 0 || dx < 0 || c.y0 > dy || c.x0 > dx) check = WIN_BOX;
+        }
+        if (r) *r = WindowRefusal{check, j, c.image, scale, c.y0, c.x0, h, w, H, W};
+        else if (check == WIN_OK) out[j] = item_of<Item>(Window{c.image, scale, c.y0, c.x0, h, w, flip}, j, k);
+        return check;
+    };
+    for (int64_t j = 0; j < k.n_crops; j++)
+        if (check_crop(crops[j], j, nullptr) != WIN_OK) { // (the loop carries no operand of a refusal: the first offender is looked at again)
+            WindowRefusal r;
+            check_crop(crops[j], j, &r);
+            return r;
+        }
+    return WindowRefusal{};
+}
+template WindowRefusal check_windows(const WindowCall&, const std::vector<RaggedDesc>&, const lrf_crop*, std::vector<CropEntry>&);
+template WindowRefusal check_windows(const WindowCall&, const std::vector<RaggedDesc>&, const lrf_scaled_crop*, std::vector<ScaledItem>&);
+template WindowRefusal check_windows(const WindowCall&, const std::vector<RaggedDesc>&, const lrf_resized_crop*, std::vector<ResizedItem>&);
+template WindowRefusal check_windows(const WindowCall&, const std::vector<GrayDesc>&, const lrf_scaled_crop*, std::vector<GrayItem>&);
+template WindowRefusal check_windows(const WindowCall&, const std::vector<GrayDesc>&, const lrf_resized_crop*, std::vector<GrayItem>&);
+
 // ---- geometry -----------------------------------------------------------------------------------------------------------------
 void plane_dims(int64_t H, int64_t W, int c, int64_t* h, int64_t* w, int64_t* hp, int64_t* wp, int64_t* M)
 {

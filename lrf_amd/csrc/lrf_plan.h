@@ -509,6 +509,42 @@ GrayPlan plan_gray_windows(const std::vector<GrayDesc>& descs, const std::vector
 // here: box j is [oh][ow] at oh ow j).  resized_level, resized_staged and the staged / direct thread maps are the colour entry's
 GrayPlan plan_gray_resized(const std::vector<GrayItem>& boxes, int oh, int ow);
 
+// ---- the window list of the ten entries that decode crops: checked, and handed on as the items the kernels read ----------------
+// (lrf_qmf_decode_crops_, _scaled_crops_, _resized_crops_, _gray_crops_, _gray_resized_crops_, each _u8 and _tensor).  The kernels
+// index with the items alone, so next to describe_images this is the one place between a caller's crop list and an
+// out-of-bounds read.  tests/test_decode_windows_host.py calls it on the CPU.
+enum { WIN_OK = 0, WIN_N_IMAGES, WIN_N_CROPS, WIN_SIZE, WIN_CAPACITY, WIN_IMAGE, WIN_SCALE, WIN_SIDES, WIN_BOX };
+#define LRF_WIN_SCALES_COLOUR 0x114u // bit f: scale f is admitted — 2, 4, 8 ...
+#define LRF_WIN_SCALES_GRAY 0x116u   // ... and 1, 2, 4, 8
+#define LRF_WIN_MAX_CROPS (1 << 20)
+#define LRF_WIN_MAX_RESIZED_SIDE 16384
+struct WindowCall {
+    int64_t n_images, n_crops;
+    int64_t h, w;    // the size all windows share; resized: the output size (oh, ow) all boxes are resampled to
+    bool resized;    // the crops are boxes with sides of their own (lrf_resized_crop)
+    unsigned scales; // the admitted scales of lrf_scaled_crop (LRF_WIN_SCALES_*); 0: the crops carry none (lrf_crop, lrf_resized_crop)
+    int channels;    // 3 or 1: crop j is [channels][h][w] at channels h w j
+    int64_t out_len; // elements of the output
+};
+// the first offender: which check, and for the per-crop checks which crop, its fields and — WIN_BOX — its image's size at its scale
+struct WindowRefusal {
+    int check = WIN_OK;
+    int64_t crop = 0;
+    int image = 0, scale = 1, y0 = 0, x0 = 0;
+    int64_t h = 0, w = 0, H = 0, W = 0;
+};
+// the ranges of the call alone, in this order: n_images in [1,65535], n_crops in [1,2^20], both sides >= 1 and <= INT32_MAX
+// (resized: <= 16384)
+WindowRefusal check_window_call(const WindowCall& k);
+// k: accepted by check_window_call; descs: describe_images' or describe_gray_images' table of the k.n_images images.  First the
+// output's capacity (k.channels k.h k.w k.n_crops elements), then per crop, in this order: the image index, the scale, box
+// sides >= 1, the window inside its image at its scale (ceil(H / f) x ceil(W / f)).  Every comparison comes before the sum or
+// product it guards: nothing wraps.  items: the n_crops items in call order as plan_decode_crops, plan_decode_scaled,
+// plan_decode_resized, plan_gray_windows (lrf_scaled_crop) and plan_gray_resized (lrf_resized_crop) take them; on a refusal
+// they are left unspecified.  Instantiated in lrf_plan.cpp for those five (Desc, Crop, Item).
+template <class Desc, class Crop, class Item>
+WindowRefusal check_windows(const WindowCall& k, const std::vector<Desc>& descs, const Crop* crops, std::vector<Item>& items);
+
 // ---- inflate of factor columns: which lane decodes which column (lrf_inflate_columns_i8; tests/test_inflate_plan.py) ----------
 // One lane per stream, 64 consecutive slots to a wave.  The slots are the matrices' columns, matrix after matrix, a matrix's
 // columns ascending — so a wave's lanes hold adjacent columns of one matrix (adjacent bytes of every row) until the matrix
