@@ -562,8 +562,8 @@ __global__ __launch_bounds__(256) void k_rgb_decode_any(const int8_t* __restrict
 }
 
 // svd_decode of the RGB branch for any patch size / no patches and for quantised (uint8) or float factors
-// (lrf/compression/svd.py:310-326, 359): dequantize (utils.py:223-243: (q - q.min()) * scale + min) when QUANT, u @ v.mT as
-// a k-ordered fp32 fma chain, depatchify + unpad (p > 0), clamp + truncate.  Layouts as k_rgb_decode_any.  One thread per pixel.
+// (lrf/compression/svd.py:310-326, 359): dequantize (utils.py:223-243: (q - q.min()) * scale + min) when QUANT, u @ v.mT in
+// fp32 in the reference's order (below), depatchify + unpad (p > 0), clamp + truncate.  Layouts as k_rgb_decode_any.  One thread per pixel.
 template <bool QUANT>
 __global__ __launch_bounds__(256) void k_svd_decode_any(const void* __restrict__ Uv, const void* __restrict__ Vv, int H, int W, int p, int q,
                                                         int top, int left, int nw, long u_img, long v_img, int R,
@@ -584,20 +584,31 @@ __global__ __launch_bounds__(256) void k_svd_decode_any(const void* __restrict__
         uo = (long)blockIdx.y * u_img + ((long)(yy / p) * nw + (xx / q)) * R;
         vo = (long)blockIdx.y * v_img + (long)(c * p * q + (yy % p) * q + (xx % q)) * R;
     }
+    // The product as the reference's CPU computes it, as far as the oracle states it (oracle/lrf_oracle.c, lrf_oracle_mm_blas
+    // and mm_torch): a k-ordered fma chain per block of the ranks, the block sums added in order — blocks of LRF_KC ranks,
+    // two halves of ceil(R / 2) for LRF_KC < R < 2 LRF_KC; and for patch=False, where u @ v.mT is a batched product, torch's
+    // small-product kernel when R H W < 400: every product rounded, then added (block-uniform).  Held to torch's CPU product
+    // for matrices of 16 rows or more at ranks up to 3072 and for ranks up to 7 (tests/test_svd_cases.py); for fewer rows
+    // and longer contractions the reference's BLAS takes routines with orders of their own, which nothing here restates.
+    const bool small = p == 0 && (long)R * H * W < 400;
+    const uint8_t* u8 = static_cast<const uint8_t*>(Uv) + uo;
+    const uint8_t* v8 = static_cast<const uint8_t*>(Vv) + vo;
+    const float* uf32 = static_cast<const float*>(Uv) + uo;
+    const float* vf32 = static_cast<const float*>(Vv) + vo;
+    const float* g = QUANT ? qp + (long)blockIdx.y * 6 : nullptr; // scale_u, min_u, qmin_u, scale_v, min_v, qmin_v
+    auto uf = [&](int r) __attribute__((always_inline)) { return QUANT ? ((float)u8[r] - g[2]) * g[0] + g[1] : uf32[r]; };
+    auto vf = [&](int r) __attribute__((always_inline)) { return QUANT ? ((float)v8[r] - g[5]) * g[3] + g[4] : vf32[r]; };
     float acc = 0.f;
-    if (QUANT) {
-        const uint8_t* u = static_cast<const uint8_t*>(Uv) + uo;
-        const uint8_t* v = static_cast<const uint8_t*>(Vv) + vo;
-        const float* g = qp + (long)blockIdx.y * 6; // scale_u, min_u, qmin_u, scale_v, min_v, qmin_v
-        for (int r = 0; r < R; r++) {
-            const float uf = ((float)u[r] - g[2]) * g[0] + g[1];
-            const float vf = ((float)v[r] - g[5]) * g[3] + g[4];
-            acc = fmaf(uf, vf, acc);
-        }
+    if (small) {
+        for (int r = 0; r < R; r++) acc = __fadd_rn(acc, __fmul_rn(uf(r), vf(r)));
     } else {
-        const float* u = static_cast<const float*>(Uv) + uo;
-        const float* v = static_cast<const float*>(Vv) + vo;
-        for (int r = 0; r < R; r++) acc = fmaf(u[r], v[r], acc);
+        const int kc = (R > LRF_KC && R < 2 * LRF_KC) ? (R + 1) / 2 : LRF_KC;
+        for (int r0 = 0; r0 < R; r0 += kc) {
+            const int r1 = min(R, r0 + kc);
+            float s = 0.f;
+            for (int r = r0; r < r1; r++) s = fmaf(uf(r), vf(r), s);
+            acc = r0 == 0 ? s : acc + s;
+        }
     }
     acc = fminf(fmaxf(acc, 0.f), 255.f);
     rgb[(long)blockIdx.y * n + e] = (uint8_t)acc;

@@ -1088,6 +1088,10 @@ void lrf_oracle_quantize_u8(const float* t, long n, uint8_t* qv, float* scale, f
     }
     float sc = (mx - mn) / 255.f;
     for (long i = 0; i < n; i++) {
+        if (sc == 0.f) { /* a constant tensor: 0 / 0 there; code 0 is what dequantizes back to it (0 * scale + min) */
+            qv[i] = 0;
+            continue;
+        }
         float v = (t[i] - mn) / sc + 0.f;
         if (v < 0.f) v = 0.f;
         if (v > 255.f) v = 255.f;
@@ -1240,6 +1244,71 @@ int lrf_oracle_svd_decode_rgb(const uint8_t* qu, const uint8_t* qv, long M, int 
     lrf_oracle_depatchify_unpad(X, 3, Hp, Wp, H, W, 8, 8, img);
     lrf_oracle_to_u8(img, 3 * H * W, rgb);
     free(u); free(v); free(X); free(img);
+    return 0;
+}
+
+/* torch.mm of fp32 u [M,R] and v [N,R].mT on the CPU (MKL sgemm, one thread), as far as it is known: every output element
+ * is a k-ordered fma chain per block of the contraction, the block sums added in order.  The blocks are LRF_KC ranks, except
+ * that a contraction of LRF_KC < R < 2 LRF_KC is cut into two halves of ceil(R / 2).  tests/test_svd_cases.py holds this to
+ * torch's recorded products (tests/golden/svd_product.json) bit for bit for M >= 16 rows at ranks up to 3072, and for any M at ranks up to 7.  With fewer than 16 rows and a long
+ * contraction MKL takes routines whose order is not restated here (nor by mm_mkl, which lrf_oracle_svd_decode_rgb still
+ * goes through — with mm_torch's small-product kernel below R M N = 400, which torch.mm does not have: the two definitions
+ * differ for a single 8x8 patch at rank 2). */
+static long blas_kc(long R)
+{
+    return (R > LRF_KC && R < 2 * LRF_KC) ? (R + 1) / 2 : LRF_KC;
+}
+
+void lrf_oracle_mm_blas(const float* u, const float* v, long M, long N, int R, float* X)
+{
+    const long kc = blas_kc(R);
+    for (long m = 0; m < M; m++)
+        for (long n = 0; n < N; n++) {
+            float acc = 0.f;
+            for (long k0 = 0; k0 < R; k0 += kc) {
+                const long k1 = k0 + kc < R ? k0 + kc : R;
+                float sum = 0.f;
+                for (long k = k0; k < k1; k++) sum = fmaf(u[m * R + k], v[n * R + k], sum);
+                acc = (k0 == 0) ? sum : acc + sum;
+            }
+            X[m * N + n] = acc;
+        }
+}
+
+/* svd_decode of the RGB branch for any patch setting and either factor type (svd.py:310-326, 359).  Patches (p, q > 0):
+ * U [M,R], V [3 p q,R] are matrices, so `u @ v.mT` is torch.mm (lrf_oracle_mm_blas).  patch=False (p = q = 0): U [3,H,R],
+ * V [3,W,R] are batches of three, so it is torch.bmm: mm_torch per channel, the small-product kernel included.  Quantised
+ * factors (is_float = 0) are dequantized as whole tensors, all three channels together. */
+int lrf_oracle_svd_decode_any(const void* U, const void* V, int is_float, long H, long W, long p, long q, int R, float su, float mu,
+                              float sv, float mv, uint8_t* rgb)
+{
+    long Hp = H, Wp = W, M = 3 * H, N = 3 * W;
+    if (p > 0) {
+        Hp = H + (p - H % p) % p;
+        Wp = W + (q - W % q) % q;
+        M = (Hp / p) * (Wp / q);
+        N = 3 * p * q;
+    }
+    float* u = (float*)malloc(sizeof(float) * M * R);
+    float* v = (float*)malloc(sizeof(float) * N * R);
+    float* img = (float*)malloc(sizeof(float) * 3 * H * W);
+    if (is_float) {
+        memcpy(u, U, sizeof(float) * M * R);
+        memcpy(v, V, sizeof(float) * N * R);
+    } else {
+        lrf_oracle_dequantize_u8((const uint8_t*)U, M * R, su, mu, u);
+        lrf_oracle_dequantize_u8((const uint8_t*)V, N * R, sv, mv, v);
+    }
+    if (p > 0) {
+        float* X = (float*)malloc(sizeof(float) * M * N);
+        lrf_oracle_mm_blas(u, v, M, N, R, X);
+        lrf_oracle_depatchify_unpad(X, 3, Hp, Wp, H, W, p, q, img);
+        free(X);
+    } else {
+        for (long c = 0; c < 3; c++) mm_torch(u + c * H * R, R, 1, v + c * W * R, 1, R, img + c * H * W, W, H, R, W);
+    }
+    lrf_oracle_to_u8(img, 3 * H * W, rgb);
+    free(u); free(v); free(img);
     return 0;
 }
 

@@ -269,6 +269,48 @@ def svd_decode_rgb(qu, qv, quant_u, quant_v, H, W):
     return out
 
 
+def reconstruct(u, v):
+    """fp32 u [M,R] @ v [N,R].mT as torch's batched product of one matrix computes it (lrf_oracle_reconstruct)."""
+    u, v = _f32(u), _f32(v)
+    (M, R), N = u.shape, v.shape[0]
+    assert v.shape == (N, R)
+    X = np.empty((M, N), np.float32)
+    lib().lrf_oracle_reconstruct(_ptr(u, _fp), _ptr(v, _fp), c_long(M), c_long(N), c_int(R), _ptr(X, _fp))
+    return X
+
+
+def mm_blas(u, v):
+    """fp32 u [M,R] @ v [N,R].mT as torch.mm computes it on the CPU, as far as lrf_oracle_mm_blas states it"""
+    u, v = _f32(u), _f32(v)
+    (M, R), N = u.shape, v.shape[0]
+    assert v.shape == (N, R)
+    X = np.empty((M, N), np.float32)
+    lib().lrf_oracle_mm_blas(_ptr(u, _fp), _ptr(v, _fp), c_long(M), c_long(N), c_int(R), _ptr(X, _fp))
+    return X
+
+
+def svd_decode_any(u, v, H, W, patch_size, quant_u=None, quant_v=None):
+    """svd_decode of the RGB branch for patches (p, q) (u [M,R], v [3 p q,R]) or patch_size None (u [3,H,R], v [3,W,R]):
+    uint8 codes with quant_u / quant_v = (scale, min), or fp32 factors (both None) -> uint8 [3,H,W]."""
+    is_float = quant_u is None
+    assert (quant_v is None) == is_float
+    u = np.ascontiguousarray(u, dtype=np.float32 if is_float else np.uint8)
+    v = np.ascontiguousarray(v, dtype=u.dtype)
+    R = u.shape[-1]
+    p, q = (0, 0) if patch_size is None else patch_size
+    if patch_size is None:
+        assert u.shape == (3, H, R) and v.shape == (3, W, R)
+    else:
+        Hp, Wp = H + (p - H % p) % p, W + (q - W % q) % q
+        assert u.shape == ((Hp // p) * (Wp // q), R) and v.shape == (3 * p * q, R)
+    (su, mu), (sv, mv) = (0.0, 0.0) if is_float else quant_u, (0.0, 0.0) if is_float else quant_v
+    out = np.empty((3, H, W), np.uint8)
+    rc = lib().lrf_oracle_svd_decode_any(_ptr(u, ctypes.c_void_p), _ptr(v, ctypes.c_void_p), c_int(int(is_float)), c_long(H), c_long(W),
+                                         c_long(p), c_long(q), c_int(R), c_float(su), c_float(mu), c_float(sv), c_float(mv), _ptr(out, _u8p))
+    assert rc == 0
+    return out
+
+
 # ---- qmf_encode / qmf_decode, RGB colour-space branch (lrf/compression/qmf.py:164-187, 309-323) -----------------
 def qmf_rgbspace_decompose(img_u8, R, num_iters=10, bounds=(-16, 15), sign=None, init=None):
     """uint8 [3,H,W] -> int8 (u [M,R], v [192,R]): X = patchify(pad(img)), SVD initialisation (svd_topr) unless

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import hard_spectra as hs
+from svd_cases import image_of_patch_matrix as _image_of_patch_matrix
 from test_init_hard_spectra import END_TO_END
 
 pytestmark = pytest.mark.gpu
@@ -56,11 +57,6 @@ def test_hip_init_bits_and_properties(path, cls, name, R, ctx, oracle):
         assert np.array_equal(v0[b].view(np.int32), wv.view(np.int32)), f"v0 of matrix {b} differs from the oracle's"
         assert np.array_equal(u0[b].view(np.int32), wu.view(np.int32)), f"u0 of matrix {b} differs from the oracle's"
     hs.check_init(X, R, u0[1], v0[1], only_p12=name in hs.P12_ONLY)
-
-
-def _image_of_patch_matrix(X, hb, wb):
-    """uint8 [3, 8 hb, 8 wb] whose 8 x 8 RGB patch matrix (rows (h, w), columns (c, p, q)) is X [hb wb, 192]"""
-    return np.ascontiguousarray(X.reshape(hb, wb, 3, 8, 8).transpose(2, 0, 3, 1, 4).reshape(3, 8 * hb, 8 * wb)).astype(np.uint8)
 
 
 U8 = [(cls, name, R) for cls, name, R in hs.case_ids("u8")]
