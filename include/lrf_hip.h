@@ -681,6 +681,59 @@ int lrf_qmf_decode_gray_resized_crops_tensor(lrf_ctx* ctx, int64_t n_images, con
                                              const lrf_resized_crop* crops /* host */, int64_t oh, int64_t ow,
                                              const lrf_tensor_format* fmt /* host */, void* out, int64_t out_bytes);
 
+/*
+ * Lists of gray images on the encode side: images that differ in size and rank in one call, each image at a list of candidate
+ * ranks in one call, and the squared error of gray factors against their sources — the gray counterparts of
+ * lrf_qmf_encode_ragged_rgb_u8, lrf_qmf_encode_ragged_sweep_rgb_u8 and lrf_qmf_sse_ragged_rgb_u8.  A gray image is one matrix
+ * X [M,64] (lrf_qmf_encode_gray_u8): no colour conversion, no chroma.
+ *   gray     one uint8 buffer (device); image i is [H][W] bytes at gray_off
+ *   sign     optional int8 buffer (device); sign_off -1 (or sign NULL): the default signs
+ * lrf_qmf_encode_gray_ragged_u8: image i at rank R_i; U [M][R] at u_off, V [64][R] at v_off, its [R] signs at sign_off.  Its
+ *   bytes are exactly those lrf_qmf_encode_gray_u8(B = 1, U0 = V0 = NULL) writes for that image alone with the same R, K, lo,
+ *   hi and signs, whatever else the list holds and in whatever order.  It is the sweep below with one candidate per image.
+ * lrf_qmf_encode_gray_ragged_sweep_u8: m candidates (image, R) over n images; candidate j's bytes are exactly those the ragged
+ *   encode writes for (image, R) alone.  An image's signs are [Rmax], Rmax its largest candidate rank; a candidate uses the
+ *   leading R of them and the leading R columns of the Rmax initialisation (the colour sweep's convention).  The planes stage,
+ *   X, the Gram matrix and the initialisation run once per image; the X workspace is the sum over images, not candidates.
+ * lrf_qmf_sse_gray_ragged_u8: sse[i] = sum over the H W samples of (source - clamp(P, 0, 255))^2, an exact integer: what
+ *   lrf_qmf_decode_gray_ragged_u8 at scale 1 followed by lrf_image_metrics_u8(C = 1, ssim = NULL) gives.  items: lrf_gray_image
+ *   with out_off naming where the SOURCE [H][W] is read in `gray`; ranks 1..64; several items may read one source.  Integer
+ *   sums (uint32 per lane and wave, uint64 per workgroup, one 64-bit integer atomic per workgroup); sse [n] uint64 (device) is
+ *   zeroed by the call on its stream; the item table travels through the pinned staging slots, with no stream wait.
+ * The planes stage: at most two launches, timed under LRF_K_PLANES — images with W % 16 == 0 whose bytes start at a multiple
+ * of 16 take lrf_qmf_encode_gray_u8's 16-byte body, the others its general body: X is the same bits either way.  The scorer
+ * is timed under LRF_K_DECODE.  Asynchronous on the context's stream (a caller's stream after lrf_ctx_set_stream); a new list
+ * uploads its tables and waits once.  Everything is validated on the host before any launch or write, and a refused call writes
+ * nothing.  LRF_EINVAL: a NULL pointer, n outside [1,65535], m outside [n,2^20], a candidate naming no image, an image without
+ * a candidate, a size lrf_chan_dims(H, W, 1, 8, 8) refuses, a rank below 1, bounds outside int8, a negative offset, pixels,
+ * signs or factors that leave their buffer, overlapping factor ranges.  LRF_ENOTSUP: K < 1, an encode rank above 32 (those
+ * iterate on the any-shape kernels: lrf_qmf_encode_gray_u8 per image), an image of 2^31 pixels or more, 2^31 or more blocks or
+ * workgroups in a launch.
+ */
+typedef struct {
+    int64_t H, W;
+    int64_t gray_off, sign_off; /* sign_off -1: default signs */
+} lrf_gray_sweep_image;
+typedef struct {
+    int32_t image;
+    int R; /* 1..32 */
+    int64_t u_off, v_off;
+} lrf_gray_sweep_candidate;
+int lrf_qmf_encode_gray_ragged_sweep_u8(lrf_ctx* ctx, int64_t n, const lrf_gray_sweep_image* images /* host */, int64_t m,
+                                        const lrf_gray_sweep_candidate* cands /* host */, const uint8_t* gray, int64_t gray_len, int K, int lo,
+                                        int hi, const int8_t* sign /* optional */, int64_t sign_len, int8_t* U, int64_t u_len, int8_t* V,
+                                        int64_t v_len);
+typedef struct {
+    int64_t H, W;
+    int R;
+    int64_t gray_off, u_off, v_off, sign_off;
+} lrf_gray_encode_image;
+int lrf_qmf_encode_gray_ragged_u8(lrf_ctx* ctx, int64_t n, const lrf_gray_encode_image* images /* host */, const uint8_t* gray, int64_t gray_len,
+                                  int K, int lo, int hi, const int8_t* sign, int64_t sign_len, int8_t* U, int64_t u_len, int8_t* V, int64_t v_len);
+int lrf_qmf_sse_gray_ragged_u8(lrf_ctx* ctx, int64_t n, const lrf_gray_image* items /* host; out_off = where the SOURCE [H][W] is read */,
+                               const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len, const uint8_t* gray, int64_t gray_len,
+                               uint64_t* sse /* [n], device */);
+
 /* The general route, 1 <= C <= 16, any patch size or none (qmf.py:164-212, decode :309-323): the host forms the matrices with
  * lrf_qmf_chan_matrix_u8, factorises them with lrf_qmf_decompose_f32 / lrf_qmf_bcd_f32 / lrf_qmf_svd_init_f32 (any shape; their
  * limits and errors apply) and decodes with lrf_qmf_chan_decode_u8.

@@ -80,6 +80,21 @@ class RaggedSweepCandidate(ctypes.Structure):
     _fields_ = [("image", ctypes.c_int32), ("R", c_int * 3), ("u_off", c_i64), ("v_off", c_i64)]
 
 
+class GraySweepImage(ctypes.Structure):
+    """lrf_gray_sweep_image (include/lrf_hip.h)"""
+    _fields_ = [("H", c_i64), ("W", c_i64), ("gray_off", c_i64), ("sign_off", c_i64)]
+
+
+class GraySweepCandidate(ctypes.Structure):
+    """lrf_gray_sweep_candidate (include/lrf_hip.h)"""
+    _fields_ = [("image", ctypes.c_int32), ("R", c_int), ("u_off", c_i64), ("v_off", c_i64)]
+
+
+class GrayEncodeImage(ctypes.Structure):
+    """lrf_gray_encode_image (include/lrf_hip.h)"""
+    _fields_ = [("H", c_i64), ("W", c_i64), ("R", c_int), ("gray_off", c_i64), ("u_off", c_i64), ("v_off", c_i64), ("sign_off", c_i64)]
+
+
 def load():
     """Loads liblrf_hip.so; raises ImportError when it has not been built (see __graft_entry__.build)."""
     global _lib
@@ -175,6 +190,11 @@ def load():
         lib.lrf_qmf_decode_gray_resized_crops_u8.argtypes = gray_list + [ctypes.POINTER(ResizedCrop), c_i64, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_decode_gray_resized_crops_tensor.argtypes = gray_list + [ctypes.POINTER(ResizedCrop), c_i64, c_i64, ctypes.POINTER(TensorFormat), c_void_p,
                                                                              c_i64]
+        lib.lrf_qmf_encode_gray_ragged_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(GrayEncodeImage), c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64,
+                                                      c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_encode_gray_ragged_sweep_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(GraySweepImage), c_i64, ctypes.POINTER(GraySweepCandidate),
+                                                            c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
+        lib.lrf_qmf_sse_gray_ragged_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(GrayImage), c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]
         lib.lrf_qmf_chan_matrix_u8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_void_p]
         lib.lrf_qmf_chan_decode_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_void_p]
         lib.lrf_plane_dims_any.argtypes = [c_i64, c_i64, c_int, c_int, c_int] + [ctypes.POINTER(c_i64)] * 6
@@ -214,7 +234,8 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_chan_dims", "lrf_qmf_encode_gray_u8", "lrf_qmf_decode_gray_u8", "lrf_qmf_decode_gray_ragged_u8", "lrf_qmf_decode_gray_crops_u8",
-           "lrf_qmf_decode_gray_crops_tensor", "lrf_qmf_decode_gray_resized_crops_u8", "lrf_qmf_decode_gray_resized_crops_tensor", "lrf_qmf_chan_matrix_u8", "lrf_qmf_chan_decode_u8",
+           "lrf_qmf_decode_gray_crops_tensor", "lrf_qmf_decode_gray_resized_crops_u8", "lrf_qmf_decode_gray_resized_crops_tensor",
+           "lrf_qmf_encode_gray_ragged_u8", "lrf_qmf_encode_gray_ragged_sweep_u8", "lrf_qmf_sse_gray_ragged_u8", "lrf_qmf_chan_matrix_u8", "lrf_qmf_chan_decode_u8",
            "lrf_plane_dims_any", "lrf_qmf_planes_any_u8", "lrf_qmf_decode_any_u8", "lrf_plane_dims_any_hw", "lrf_qmf_planes_any_hw_u8",
            "lrf_qmf_decode_any_hw_u8",
            "lrf_pipe_create", "lrf_pipe_destroy", "lrf_pipe_slots", "lrf_pipe_slot_ctx", "lrf_pipe_workspace_bytes",
@@ -744,6 +765,122 @@ def _gray_images(ims, out_offs=None):
     for i, (d, (H, W, R, u_off, v_off)) in enumerate(zip(desc, ims)):
         d.H, d.W, d.R, d.u_off, d.v_off, d.out_off = H, W, R, u_off, v_off, 0 if out_offs is None else out_offs[i]
     return desc
+
+
+def _check_gray_pixels(entry, gray, sign):
+    import torch
+    if not isinstance(gray, torch.Tensor) or gray.dtype != torch.uint8:
+        raise TypeError(f"{entry} takes its pixels as a uint8 tensor")
+    if sign is not None and (not isinstance(sign, torch.Tensor) or sign.dtype != torch.int8):
+        raise TypeError(f"{entry} takes its signs as an int8 tensor")
+    if gray.dim() != 1 or not gray.is_contiguous() or (sign is not None and (sign.dim() != 1 or not sign.is_contiguous() or sign.device != gray.device)):
+        raise ValueError("gray (and sign) must be flat contiguous tensors on one device")
+
+
+def _check_gray_rank(who, R):
+    if isinstance(R, bool) or hasattr(R, "__len__") or int(R) != R:
+        raise ValueError(f"{who}: one integer rank expected (a gray stream has a scalar rank), got {R!r}")
+    if int(R) < 1 or int(R) > 32:
+        raise ValueError(f"{who}: rank {int(R)} out of range (1..32)")
+    return int(R)
+
+
+def _check_gray_source(i, im, gray, lead):
+    """(H, W, gray_off, sign_off) of the image tuple whose first `lead` + 1 fields are H, W[, R], gray_off, then an optional sign_off"""
+    H, W, gray_off = im[0], im[1], im[lead]
+    sign_off = im[lead + 1] if len(im) == lead + 2 and im[lead + 1] is not None else -1
+    if any(isinstance(x, bool) or int(x) != x for x in (H, W, gray_off, sign_off)):
+        raise ValueError(f"image {i}: integers expected")
+    H, W, gray_off, sign_off = int(H), int(W), int(gray_off), int(sign_off)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"image {i}: size {H}x{W} out of range (fewer than 2^31 pixels)")
+    chan_dims(H, W, 1, (8, 8))  # (refuses what the encoder refuses)
+    if gray_off < 0 or gray_off + H * W > gray.numel():
+        raise ValueError(f"image {i}: its {H * W} bytes at {gray_off} leave the buffer of {gray.numel()} bytes")
+    return H, W, gray_off, sign_off
+
+
+def _check_gray_signs(i, sign_off, R, sign):
+    if sign_off < -1 or (sign_off >= 0 and (sign is None or sign_off + R > sign.numel())):
+        raise ValueError(f"image {i}: its {R} signs at {sign_off} leave the sign buffer")
+
+
+def check_encode_gray_ragged_args(gray, images, sign=None):
+    """The argument checks of lrf_qmf_encode_gray_ragged_u8 on its tensors, before any device is touched.  gray: a flat uint8
+    tensor; images: 1 to 65535 tuples (H, W, R, gray_off[, sign_off]) with R one rank in 1..32 and every image's [H, W] bytes
+    inside gray; sign: None or a flat int8 tensor on gray's device, an image's sign_off (-1 or absent: the default signs) naming
+    where its R signs start.  TypeError for tensors of another type, ValueError for everything else.
+    -> [(H, W, R, gray_off, sign_off)] as integers."""
+    _check_gray_pixels("encode_gray_ragged", gray, sign)
+    if images is None or len(images) < 1 or len(images) > 65535:
+        raise ValueError("encode_gray_ragged needs 1 to 65535 images")
+    out = []
+    for i, im in enumerate(images):
+        if not hasattr(im, "__len__") or len(im) not in (4, 5):
+            raise ValueError(f"image {i}: (H, W, R, gray_off[, sign_off]) expected")
+        R = _check_gray_rank(f"image {i}", im[2])
+        H, W, gray_off, sign_off = _check_gray_source(i, im, gray, 3)
+        _check_gray_signs(i, sign_off, R, sign)
+        out.append((H, W, R, gray_off, sign_off))
+    return out
+
+
+def check_encode_gray_ragged_sweep_args(gray, images, cands, sign=None):
+    """The argument checks of lrf_qmf_encode_gray_ragged_sweep_u8 on its tensors, before any device is touched.  gray: a flat
+    uint8 tensor; images: 1 to 65535 tuples (H, W, gray_off[, sign_off]); cands: up to 2^20 tuples (image, R), R in 1..32, at
+    least one per image, in any order; sign: None or a flat int8 tensor on gray's device, an image's sign_off (-1 or absent: the
+    default signs) naming where its signs start — as many as its largest candidate rank.  TypeError for tensors of another
+    type, ValueError for everything else.  -> ([(H, W, gray_off, sign_off)], [(image, R)]) as integers."""
+    _check_gray_pixels("encode_gray_ragged_sweep", gray, sign)
+    if images is None or len(images) < 1 or len(images) > 65535:
+        raise ValueError("encode_gray_ragged_sweep needs 1 to 65535 images")
+    if cands is None or len(cands) < len(images) or len(cands) > 2 ** 20:
+        raise ValueError(f"encode_gray_ragged_sweep needs a candidate per image at least and 2^20 at most, got {0 if cands is None else len(cands)} for {len(images)} images")
+    ims = []
+    for i, im in enumerate(images):
+        if not hasattr(im, "__len__") or len(im) not in (3, 4):
+            raise ValueError(f"image {i}: (H, W, gray_off[, sign_off]) expected")
+        ims.append(_check_gray_source(i, im, gray, 2))
+    rmax, cds = [0] * len(ims), []
+    for j, cd in enumerate(cands):
+        if not hasattr(cd, "__len__") or len(cd) != 2:
+            raise ValueError(f"candidate {j}: (image, R) expected")
+        if isinstance(cd[0], bool) or int(cd[0]) != cd[0] or int(cd[0]) < 0 or int(cd[0]) >= len(ims):
+            raise ValueError(f"candidate {j}: image {cd[0]!r} out of range [0,{len(ims)})")
+        R = _check_gray_rank(f"candidate {j}", cd[1])
+        rmax[int(cd[0])] = max(rmax[int(cd[0])], R)
+        cds.append((int(cd[0]), R))
+    for i, (r, im) in enumerate(zip(rmax, ims)):
+        if r == 0:
+            raise ValueError(f"image {i} has no candidate")
+        _check_gray_signs(i, im[3], r, sign)
+    return ims, cds
+
+
+def check_sse_gray_ragged_args(gray, items, U, V):
+    """The argument checks of lrf_qmf_sse_gray_ragged_u8 on its tensors, before any device is touched.  gray: a flat uint8 tensor
+    holding the sources; U, V: flat int8 tensors on its device; items: 1 to 65535 tuples (H, W, R, u_off, v_off, gray_off), R in
+    1..64, the factors inside U and V (check_gray_images) and the [H, W] source inside gray (sources may be shared).  TypeError
+    for tensors of another type, ValueError for everything else.  -> [(H, W, R, u_off, v_off, gray_off)] as integers."""
+    import torch
+    if not isinstance(gray, torch.Tensor) or gray.dtype != torch.uint8:
+        raise TypeError("sse_gray_ragged takes its sources as a uint8 tensor")
+    if gray.dim() != 1 or not gray.is_contiguous():
+        raise ValueError("sse_gray_ragged takes its sources as a flat contiguous tensor")
+    if items is not None and any(not hasattr(it, "__len__") or len(it) != 6 for it in items):
+        raise ValueError("items: (H, W, R, u_off, v_off, gray_off) expected")
+    ims = check_gray_images(U, V, None if items is None else [it[:5] for it in items])
+    if U.device != gray.device:
+        raise ValueError(f"sse_gray_ragged needs its tensors on one device, got {gray.device} and {U.device}")
+    out = []
+    for i, (im, it) in enumerate(zip(ims, items)):
+        if isinstance(it[5], bool) or int(it[5]) != it[5]:
+            raise ValueError(f"item {i}: integers expected")
+        off = int(it[5])
+        if off < 0 or off + im[0] * im[1] > gray.numel():
+            raise ValueError(f"item {i}: its source of {im[0] * im[1]} bytes at {off} leaves the buffer of {gray.numel()} bytes")
+        out.append(im + (off,))
+    return out
 
 
 def check_encode_ragged_args(rgb, images, sign=None):
@@ -1436,6 +1573,72 @@ class Context:
             part = rec[k:k + 65535]
             check(self._lib.lrf_qmf_sse_ragged_rgb_u8(self._h, part.shape[0], part.ctypes.data_as(ctypes.POINTER(RaggedImage)), _dptr(U), U.numel(), _dptr(V),
                                                       V.numel(), _dptr(rgb), rgb.numel(), c_void_p(sse[k:].data_ptr())))
+        return sse
+
+    def encode_gray_ragged(self, gray, images, K, lo, hi, sign=None):
+        """Gray images that differ in size and rank in one encode (lrf_qmf_encode_gray_ragged_u8).  gray: a flat uint8 CUDA tensor;
+        images: [(H, W, R, gray_off[, sign_off])], image i's [H, W] bytes at gray[gray_off:]; sign: None or a flat int8 CUDA tensor
+        -> (U, V, u_off, v_off): two flat int8 CUDA tensors and, per image, where its U [M, R] and V [64, R] start in them, back
+        to back in call order: the bytes of encode_gray on that image alone.  Asynchronous on torch's current stream."""
+        import torch
+        ims = check_encode_gray_ragged_args(gray, images, sign)
+        self._need_here("encode_gray_ragged", gray)
+        desc = (GrayEncodeImage * len(ims))()
+        u_off, v_off, uo, vo = [], [], 0, 0
+        for d, (H, W, R, gray_off, sign_off) in zip(desc, ims):
+            d.H, d.W, d.R, d.gray_off, d.u_off, d.v_off, d.sign_off = H, W, R, gray_off, uo, vo, sign_off
+            u_off.append(uo)
+            v_off.append(vo)
+            uo += chan_dims(H, W, 1, (8, 8))[2] * R
+            vo += 64 * R
+        U = torch.empty((uo,), dtype=torch.int8, device=gray.device)
+        V = torch.empty((vo,), dtype=torch.int8, device=gray.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_encode_gray_ragged_u8(self._h, len(ims), desc, _dptr(gray), gray.numel(), int(K), int(lo), int(hi), _dptr(sign),
+                                                      0 if sign is None else sign.numel(), _dptr(U), uo, _dptr(V), vo))
+        return U, V, u_off, v_off
+
+    def encode_gray_ragged_sweep(self, gray, images, cands, K, lo, hi, sign=None):
+        """Gray images that differ in size, each at candidate ranks of its own, in one encode
+        (lrf_qmf_encode_gray_ragged_sweep_u8).  gray: a flat uint8 CUDA tensor; images: [(H, W, gray_off[, sign_off])]; cands:
+        [(image, R)] in any order, at least one per image; sign: None or a flat int8 CUDA tensor holding, per image with a
+        sign_off, the signs of its largest rank -> (U, V, u_off, v_off): two flat int8 CUDA tensors and, per candidate, where its
+        U [M, R] and V [64, R] start in them, back to back in list order: the bytes of encode_gray_ragged for (image, R) alone."""
+        import torch
+        ims, cds = check_encode_gray_ragged_sweep_args(gray, images, cands, sign)
+        self._need_here("encode_gray_ragged_sweep", gray)
+        idesc = (GraySweepImage * len(ims))()
+        for d, (H, W, gray_off, sign_off) in zip(idesc, ims):
+            d.H, d.W, d.gray_off, d.sign_off = H, W, gray_off, sign_off
+        Ms = [chan_dims(H, W, 1, (8, 8))[2] for H, W, *_ in ims]
+        cdesc = (GraySweepCandidate * len(cds))()
+        u_off, v_off, uo, vo = [], [], 0, 0
+        for d, (image, R) in zip(cdesc, cds):
+            d.image, d.R, d.u_off, d.v_off = image, R, uo, vo
+            u_off.append(uo)
+            v_off.append(vo)
+            uo += Ms[image] * R
+            vo += 64 * R
+        U = torch.empty((uo,), dtype=torch.int8, device=gray.device)
+        V = torch.empty((vo,), dtype=torch.int8, device=gray.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_encode_gray_ragged_sweep_u8(self._h, len(ims), idesc, len(cds), cdesc, _dptr(gray), gray.numel(), int(K), int(lo), int(hi),
+                                                            _dptr(sign), 0 if sign is None else sign.numel(), _dptr(U), uo, _dptr(V), vo))
+        return U, V, u_off, v_off
+
+    def sse_gray_ragged(self, gray, items, U, V):
+        """The squared error of gray items that differ in size and rank straight from their factors (lrf_qmf_sse_gray_ragged_u8).
+        gray: a flat uint8 CUDA tensor holding the sources; items: [(H, W, R, u_off, v_off, gray_off)], item i's factors at
+        U[u_off:], V[v_off:] and its source [H, W] at gray[gray_off:] (several items may share a source) -> int64 CUDA tensor
+        [len(items)], sse[i] = ((decode_gray_ragged's image of item i).long() - source.long()) ** 2 summed, without the decoded
+        images.  Asynchronous on torch's current stream."""
+        import torch
+        its = check_sse_gray_ragged_args(gray, items, U, V)
+        self._need_here("sse_gray_ragged", gray)
+        desc = _gray_images([it[:5] for it in its], [it[5] for it in its])
+        sse = torch.empty((len(its),), dtype=torch.int64, device=gray.device)
+        self.use_torch_stream()
+        check(self._lib.lrf_qmf_sse_gray_ragged_u8(self._h, len(its), desc, _dptr(U), U.numel(), _dptr(V), V.numel(), _dptr(gray), gray.numel(), _dptr(sse)))
         return sse
 
     def deflate_columns_into(self, src, table, slots, lens):

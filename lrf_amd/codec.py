@@ -195,7 +195,7 @@ def _sweep_candidates(images, qualities, bounds, num_iters):
 
 
 def qmf_encode_target(images, psnr, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
-                      pack_workers: Optional[int] = None, deflate: str = "host", x_workspace_bytes: int = 1 << 30) -> dict:
+                      pack_workers: Optional[int] = None, deflate: str = "host", x_workspace_bytes: int = 1 << 30, color_space: str = "YCbCr") -> dict:
     """Per image of a batch [B,3,H,W], the smallest-quality stream that reaches `psnr` dB (one number, or one per image).
 
     Default branch only (YCbCr, 8x8 patches, uint8, num_iters >= 1).  Every distinct rank triple of `qualities` is factorised on
@@ -218,8 +218,20 @@ def qmf_encode_target(images, psnr, qualities=range(1, 33), bounds=(-16, 15), nu
     computed over its own 3 H_i W_i samples.  A quality whose triple has a rank above 32 on some image is refused
     (NotImplementedError naming the image and the quality; the default grid never gives one).  x_workspace_bytes bounds the fp32
     patch matrices of one GPU call: a longer list is processed in chunks of consecutive images, which changes no byte.  A batch
-    of equal sizes is best given as a tensor."""
+    of equal sizes is best given as a tensor.
+
+    color_space="RGB": gray images, a list of [1,H_i,W_i] tensors or a tensor [B,1,H,W] (which goes the same way as the list of
+    its images: _rate_control_list_gray).  The candidates of image i are the distinct ranks chan_rank(M_i, 64, quality) of
+    `qualities`, the samples H_i W_i, a chunk counts 4 * 64 * M_i bytes per image; same keys, same meanings, stream i
+    byte-identical to qmf_encode_ragged([images[i]], quality=quality[i], color_space="RGB", deflate=deflate)[0] (with the default
+    deflate: to qmf_encode_batch(images[i][None], quality=quality[i], color_space="RGB")[0]).  A quality
+    whose rank passes 32 on some image raises NotImplementedError naming the image and the quality; three-channel images raise
+    NotImplementedError."""
+    assert color_space in ("RGB", "YCbCr"), "`color_space` must be one of 'RGB' or 'YCbCr'."
     on_device = _deflate_on_device(deflate)
+    if color_space == "RGB":
+        return _rate_control_list_gray(images, "qmf_encode_target", dict(psnr=psnr), qualities, bounds, num_iters, pack_workers, on_device,
+                                       x_workspace_bytes)
     if isinstance(images, (list, tuple)):
         return _rate_control_list(images, "qmf_encode_target", dict(psnr=psnr), qualities, bounds, num_iters, pack_workers, on_device, x_workspace_bytes)
     qualities, target = _check_target_args(images, psnr, qualities, num_iters)
@@ -363,7 +375,7 @@ def _check_budget_args(images, bpp, nbytes, qualities, num_iters):
 
 
 def qmf_encode_budget(images, bpp=None, nbytes=None, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
-                      pack_workers: Optional[int] = None, x_workspace_bytes: int = 1 << 30) -> dict:
+                      pack_workers: Optional[int] = None, x_workspace_bytes: int = 1 << 30, color_space: str = "YCbCr") -> dict:
     """Per image of a batch [B,3,H,W], the best stream that fits a byte budget: `nbytes` bytes, or `bpp` bits per pixel (=
     floor(bpp H W / 8) bytes); one number, or one per image.
 
@@ -382,8 +394,16 @@ def qmf_encode_budget(images, bpp=None, nbytes=None, qualities=range(1, 33), bou
 
     `images` may also be a list or tuple of uint8 [3,H_i,W_i] tensors of differing sizes, all on the host or all on one device
     (_rate_control_list): `bpp` / `nbytes` are then one number or one per image, `bpp` converted with each image's own H_i W_i;
-    same keys, same meanings.  Refusals and x_workspace_bytes: as in qmf_encode_target."""
+    same keys, same meanings.  Refusals and x_workspace_bytes: as in qmf_encode_target.
+
+    color_space="RGB": gray images, a list of [1,H_i,W_i] tensors or a tensor [B,1,H,W], as in qmf_encode_target; the sizes are
+    those of the two-factor containers the device coder's columns fold into (qmf_stream_sizes_gray_ragged), and stream i is
+    byte-identical to qmf_encode_ragged([images[i]], quality=quality[i], color_space="RGB", deflate="device")[0]."""
     from .metrics import bits_per_pixel, psnr_from_sse
+    assert color_space in ("RGB", "YCbCr"), "`color_space` must be one of 'RGB' or 'YCbCr'."
+    if color_space == "RGB":
+        return _rate_control_list_gray(images, "qmf_encode_budget", dict(bpp=bpp, nbytes=nbytes), qualities, bounds, num_iters, pack_workers, True,
+                                       x_workspace_bytes)
     if isinstance(images, (list, tuple)):
         return _rate_control_list(images, "qmf_encode_budget", dict(bpp=bpp, nbytes=nbytes), qualities, bounds, num_iters, pack_workers, True,
                                   x_workspace_bytes)
@@ -921,7 +941,8 @@ def qmf_encode_batch(images: torch.Tensor, rank=None, quality=None, bounds=(-16,
     the pipelined encoder: wiring the pipe's slots to the coder is a follow-up.
 
     color_space="RGB": gray images [B,1,H,W] with 8x8 patches, the streams of qmf_encode(images[i], color_space="RGB")
-    (_qmf_encode_batch_gray); other channel counts, patch settings and deflate="device" raise NotImplementedError."""
+    (_qmf_encode_batch_gray); other channel counts, patch settings and deflate="device" raise NotImplementedError (the device
+    coder serves gray images through qmf_encode_ragged(color_space="RGB", deflate="device"))."""
     assert (rank, quality) != (None, None), "Either 'rank' or 'quality' must be specified."
     assert color_space in ("RGB", "YCbCr"), "`color_space` must be one of 'RGB' or 'YCbCr'."
     if color_space == "RGB":  # gray images [B,1,H,W]: one lrf_qmf_encode_gray_u8 call
@@ -1077,7 +1098,7 @@ def _check_encode_ragged_args(images, rank, quality, ranks, num_iters, init_sign
 
 
 def qmf_encode_ragged(images, rank=None, quality=None, ranks=None, bounds=(-16, 15), num_iters: int = 10, init_sign=None,
-                      pack_workers: Optional[int] = None, deflate: str = "host") -> list:
+                      pack_workers: Optional[int] = None, deflate: str = "host", color_space: str = "YCbCr") -> list:
     """qmf_encode of a list of uint8 images [3,H_i,W_i] (host or device) that differ in size and in ranks, in one GPU call
     (lrf_qmf_encode_ragged_rgb_u8) -> one byte stream per image, stream i byte-identical to
     qmf_encode_batch(images[i][None], ...)[0] with that image's parameters.  Default branch only (YCbCr, 8x8 patches, uint8,
@@ -1092,7 +1113,18 @@ def qmf_encode_ragged(images, rank=None, quality=None, ranks=None, bounds=(-16, 
     through qmf_encode_batch and put back in place.  For a list of equal sizes and ranks qmf_encode_batch is the call to use.
 
     deflate="device": as in qmf_encode_batch — the columns are deflated on the GPU and only folded into the containers on the
-    host; the streams hold the same factors but are not the zlib-9 bytes."""
+    host; the streams hold the same factors but are not the zlib-9 bytes.
+
+    color_space="RGB": gray images, a list of [1,H_i,W_i] tensors or a tensor [B,1,H,W], in one lrf_qmf_encode_gray_ragged_u8 call
+    (_qmf_encode_ragged_gray): `rank` or `quality` is one scalar or one per image (through chan_rank(M_i, 64, ...)), `ranks` is
+    refused (a gray stream has a scalar rank), init_sign holds R signs; stream i is byte-identical to
+    qmf_encode_batch(images[i][None], ..., color_space="RGB")[0], images of rank above 32 go through that call one by one, and
+    three-channel images raise NotImplementedError, as qmf_encode_batch(color_space="RGB") does.  deflate="device" is served
+    here (gray_streams_from_device_factors: the device coder's column streams inside the two-factor container's layout; a stream
+    depends on its own image and parameters alone)."""
+    assert color_space in ("RGB", "YCbCr"), "`color_space` must be one of 'RGB' or 'YCbCr'."
+    if color_space == "RGB":
+        return _qmf_encode_ragged_gray(images, rank, quality, ranks, bounds, num_iters, init_sign, pack_workers, deflate)
     on_device = _deflate_on_device(deflate)
     sizes, triples, signs = _check_encode_ragged_args(images, rank, quality, ranks, num_iters, init_sign)
     n = len(sizes)
@@ -1479,14 +1511,20 @@ def _qmf_encode_rgbspace(ctx, dev, rank, quality, bounds, int_bounds, patch_size
     return combine_bytes([dict_to_bytes(metadata), combine_bytes([encode_tensor(np.ascontiguousarray(f)) for f in factors])])
 
 
-def _two_factor_stream(dtype_name, bounds, patch_size, hw, padded, R, factors) -> bytes:
-    """the container of the RGB colour-space branch (qmf.py:180-187, 204-212): its metadata, a scalar rank and two factors"""
+def _two_factor_metadata(dtype_name, bounds, patch_size, hw, padded, R) -> bytes:
+    """the metadata block of a two-factor container (qmf.py:180-187, 204-212)"""
     metadata = {"dtype": dtype_name, "color space": "RGB", "patch": patch_size is not None, "bounds": bounds}
     if patch_size is not None:
         metadata.update({"patch size": patch_size, "original size": list(hw), "padded size": list(padded), "rank": R})
     else:
         metadata["rank"] = R
-    return combine_bytes([dict_to_bytes(metadata), combine_bytes([encode_tensor(np.ascontiguousarray(f)) for f in factors])])
+    return dict_to_bytes(metadata)
+
+
+def _two_factor_stream(dtype_name, bounds, patch_size, hw, padded, R, factors) -> bytes:
+    """the container of the RGB colour-space branch (qmf.py:180-187, 204-212): its metadata, a scalar rank and two factors"""
+    return combine_bytes([_two_factor_metadata(dtype_name, bounds, patch_size, hw, padded, R),
+                          combine_bytes([encode_tensor(np.ascontiguousarray(f)) for f in factors])])
 
 
 def _qmf_encode_channels(ctx, dev, rank, quality, bounds, int_bounds, patch_size, num_iters, init_sign, init):
@@ -1532,7 +1570,8 @@ def _qmf_encode_batch_gray(images, rank, quality, bounds, num_iters, init_sign, 
     if deflate not in ("host", "device"):
         raise ValueError(f"deflate must be 'host' or 'device', got {deflate!r}")
     if deflate == "device":
-        raise NotImplementedError("deflate='device' is not served with color_space='RGB' (two-factor containers are packed on the host)")
+        raise NotImplementedError("deflate='device' is not served by qmf_encode_batch(color_space='RGB'): qmf_encode_ragged(color_space='RGB', "
+                                  "deflate='device') folds the device coder's columns into two-factor containers")
     if images.dim() != 4 or images.shape[1] != 1:
         raise NotImplementedError(f"qmf_encode_batch(color_space='RGB') serves gray images [B,1,H,W], got {tuple(images.shape)}: "
                                   "other channel counts go one by one through qmf_encode")
@@ -1563,6 +1602,392 @@ def _qmf_encode_batch_gray(images, rank, quality, bounds, num_iters, init_sign, 
     if workers <= 1 or B == 1:
         return [pack(b) for b in range(B)]
     return list(_pack_pool(workers).map(pack, range(B)))
+
+
+# ---- gray image lists: ragged encode, target PSNR and byte budget (lrf_qmf_encode_gray_ragged_u8, _sweep_, lrf_qmf_sse_gray_ragged_u8)
+def container_bytes_two_factor(meta_len, R, column_lengths):
+    """len() of a two-factor container (_two_factor_stream's layout) whose columns are given streams, by host arithmetic: the
+    metadata JSON of meta_len bytes, then two factors (u, v), each one JSON header {"num_fibers", "mode", "dtype"} in front of
+    its R columns; combine_bytes puts four length bytes in front of every part but the last (container.py).  column_lengths:
+    integers [..., 2 R] (an array or a tensor, on any device), the lengths of an image's column streams in any order -> their
+    sum over the last axis plus the constant of (meta_len, R)."""
+    R = int(R)
+    lens = column_lengths if isinstance(column_lengths, torch.Tensor) else np.asarray(column_lengths, dtype=np.int64)
+    if R < 1 or lens.shape[-1] != 2 * R:
+        raise ValueError(f"container_bytes_two_factor: a rank >= 1 and 2 R column lengths expected, got {R} and {tuple(lens.shape)}")
+    # the metadata's prefix, the prefix of u; per factor: the header and its prefix, a prefix for every column but the last
+    const = 4 + int(meta_len) + 4 + 2 * (4 + _factor_header_len(R) + 4 * (R - 1))
+    total = lens.sum(dim=-1, dtype=torch.int64) if isinstance(lens, torch.Tensor) else lens.sum(axis=-1, dtype=np.int64)
+    return total + const
+
+
+def _gray_factor_mats(sizes, ranks, u_off, v_off):
+    """(src_off, rows, cols) of the factors of m gray streams, int64 [m, 2, 3]: U [M, R] then V [64, R]"""
+    m = len(sizes)
+    if m < 1 or not (len(ranks) == len(u_off) == len(v_off) == m):
+        raise ValueError("one size, rank, u_off and v_off per stream expected")
+    m_of = {}
+    for hw in sizes:
+        if tuple(hw) not in m_of:
+            m_of[tuple(hw)] = _lib.chan_dims(int(hw[0]), int(hw[1]), 1, (8, 8))[2]
+    mats = np.empty((m, 2, 3), dtype=np.int64)
+    mats[:, 0, 0] = np.asarray(u_off, dtype=np.int64)
+    mats[:, 0, 1] = [m_of[tuple(hw)] for hw in sizes]
+    mats[:, 1, 0] = np.asarray(v_off, dtype=np.int64)
+    mats[:, 1, 1] = 64
+    mats[:, :, 2] = np.asarray(ranks, dtype=np.int64).reshape(m, 1)
+    if mats[:, :, 2].min() < 1:
+        raise ValueError("ranks must be >= 1")
+    return mats
+
+
+def _gray_metadata(hw, R, bounds) -> bytes:
+    Hp, Wp, _, _ = _lib.chan_dims(int(hw[0]), int(hw[1]), 1, (8, 8))
+    return _two_factor_metadata("uint8", bounds, (8, 8), (int(hw[0]), int(hw[1])), (Hp, Wp), int(R))
+
+
+def gray_streams_from_device_factors(ctx, U, V, sizes, ranks, u_off, v_off, bounds) -> list:
+    """The way gray factors become streams with deflate="device": U, V flat int8 CUDA tensors holding n gray images of sizes[i] =
+    (H, W) and rank ranks[i], U [M, R] at u_off[i] and V [64, R] at v_off[i].  Every column is deflated where it lies
+    (ctx.deflate_columns_into, one call for the U matrices and one for the V matrices into the same slots and lengths), the
+    slots and the lengths come to the host in one copy each, and the container code folds them: the column streams take the
+    place of zlib.compress's output inside encode_tensor's layout.  The streams are not byte-identical to the zlib-9 ones; they
+    hold the same factors and every inflate reads them."""
+    n = len(sizes)
+    mats = _gray_factor_mats(sizes, ranks, u_off, v_off)
+    table, nbytes, ncols = _lib.deflate_table(mats.reshape(-1, 3))
+    slots = torch.empty((nbytes,), dtype=torch.uint8, device=U.device)
+    lens = torch.empty((ncols,), dtype=torch.int32, device=U.device)
+    by_factor = table.reshape(n, 2, 5)
+    ctx.deflate_columns_into(U.reshape(-1), by_factor[:, 0], slots, lens)
+    ctx.deflate_columns_into(V.reshape(-1), by_factor[:, 1], slots, lens)
+    slots_h, lens_h = (t.numpy() for t in ctx.to_host(slots, lens))
+    col_off = _lib.deflate_column_offsets(table)
+    blob = slots_h.tobytes()
+    streams, at = [], 0
+    for i in range(n):
+        R = int(ranks[i])
+        header = dict_to_bytes({"num_fibers": R, "mode": "col", "dtype": "int8"})
+        factors = []
+        for _ in range(2):
+            cols = [blob[int(col_off[at + j]):int(col_off[at + j]) + int(lens_h[at + j])] for j in range(R)]
+            factors.append(combine_bytes([header, combine_bytes(cols)]))
+            at += R
+        streams.append(combine_bytes([_gray_metadata(sizes[i], R, bounds), combine_bytes(factors)]))
+    return streams
+
+
+def qmf_stream_sizes_gray_ragged(U, V, sizes, ranks, u_off, v_off, bounds=(-16, 15)) -> torch.Tensor:
+    """The exact length of the deflate="device" stream of every gray candidate, counted on the GPU without producing one.  U, V:
+    flat int8 CUDA tensors holding m candidates of sizes[j] = (H, W) and rank ranks[j] at u_off[j] / v_off[j]
+    (Context.encode_gray_ragged_sweep's layout, or encode_gray_ragged's) -> int64 CUDA tensor [m], out[j] = len() of the stream
+    gray_streams_from_device_factors produces for candidate j.  One ctx.deflate_sizes count over all U matrices and one over all V
+    matrices; the column lengths are summed per candidate on the device and container_bytes_two_factor adds the constant of the
+    candidate's own metadata length and rank."""
+    if not (isinstance(U, torch.Tensor) and isinstance(V, torch.Tensor) and U.dtype == torch.int8 and V.dtype == torch.int8):
+        raise TypeError("factors must be int8 tensors")
+    m = len(sizes)
+    mats = _gray_factor_mats(sizes, ranks, u_off, v_off)
+    Rs = mats[:, 0, 2]
+    const_of = {}
+    for hw, R in zip(sizes, Rs.tolist()):
+        key = (int(hw[0]), int(hw[1]), R)
+        if key not in const_of:
+            const_of[key] = int(container_bytes_two_factor(len(_gray_metadata(hw, R, bounds)), R, np.zeros(2 * R, dtype=np.int64)))
+    const = np.array([const_of[(int(hw[0]), int(hw[1]), R)] for hw, R in zip(sizes, Rs.tolist())], dtype=np.int64)
+    ctx = _lib.context(U.device.index)
+    out = torch.from_numpy(const).to(U.device)
+    step = 1 << 20  # (lrf_deflate_sizes_i8 takes 2^20 matrices a call)
+    for k in range(0, m, step):
+        owner = torch.from_numpy(np.repeat(np.arange(k, min(k + step, m), dtype=np.int64), Rs[k:k + step])).to(U.device)
+        for flat, which in ((U, 0), (V, 1)):
+            out.index_add_(0, owner, ctx.deflate_sizes(flat.reshape(-1), mats[k:k + step, which]).to(torch.int64))
+    return out
+
+
+def _gray_image_list(images, name):
+    """the images of a color_space="RGB" list call as a list of uint8 [1,H,W] tensors: a list or tuple of them, or a tensor
+    [B,1,H,W]; refusals raised before a GPU is asked for"""
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise ValueError(f"{name}(color_space='RGB') takes a list of [1,H,W] images or a tensor [B,1,H,W], got a tensor of shape {tuple(images.shape)}")
+        images = list(images)
+    if isinstance(images, (bytes, str)) or not isinstance(images, (list, tuple)) or len(images) < 1:
+        raise ValueError(f"{name} takes a non-empty sequence of images")
+    for i, im in enumerate(images):
+        if not isinstance(im, torch.Tensor):
+            raise TypeError(f"{name}: image {i} is {type(im).__name__}, not a tensor")
+        if im.dtype != torch.uint8:
+            raise NotImplementedError(f"{name}: image {i} is {im.dtype}; the HIP path takes uint8 images")
+        if im.dim() == 3 and im.shape[0] == 3:
+            raise NotImplementedError(f"{name}(color_space='RGB') serves gray images [1,H,W], image {i} is {tuple(im.shape)}: other channel "
+                                      "counts go one by one through qmf_encode")
+        if im.dim() != 3 or im.shape[0] != 1 or im.shape[1] < 1 or im.shape[2] < 1:
+            raise ValueError(f"{name}: image {i} must be [1,H,W], got {tuple(im.shape)}")
+    if len({im.device for im in images}) != 1:
+        raise ValueError(f"{name}: the images of a list must all be on the host or all on one device, got {sorted({str(im.device) for im in images})}")
+    return list(images)
+
+
+def _check_encode_gray_ragged_args(images, rank, quality, ranks, num_iters, init_sign):
+    """qmf_encode_ragged(color_space="RGB")'s refusals, raised before a GPU is asked for -> (images as a list, [(H, W)], [rank per
+    image], [sign per image: None or int8 array])"""
+    name = "qmf_encode_ragged"
+    if ranks is not None:
+        raise ValueError("qmf_encode_ragged(color_space='RGB'): 'ranks' is refused, a gray stream has a scalar rank (give 'rank' or 'quality')")
+    images = _gray_image_list(images, name)
+    n = len(images)
+    if num_iters < 1:
+        raise NotImplementedError("qmf_encode_ragged: num_iters = 0 (the truncated initialisation) is outside the fused encoder (qmf_encode takes it)")
+    if (rank is None) == (quality is None):
+        raise ValueError("qmf_encode_ragged(color_space='RGB'): give exactly one of 'rank' and 'quality'")
+    scalar = lambda v: not isinstance(v, Iterable)
+    rank_l = _per_image(rank, n, "rank", scalar)
+    quality_l = _per_image(quality, n, "quality", scalar)
+    sizes = [(int(im.shape[1]), int(im.shape[2])) for im in images]
+    Rs = []
+    for i, hw in enumerate(sizes):
+        if not scalar(rank_l[i]) or not scalar(quality_l[i]):
+            raise ValueError(f"qmf_encode_ragged(color_space='RGB'): image {i}: a scalar rank / quality expected")
+        if hw[0] * hw[1] >= 2 ** 31:
+            raise NotImplementedError(f"qmf_encode_ragged: image {i} of {hw[0]}x{hw[1]} has 2^31 pixels or more")
+        M = _lib.chan_dims(hw[0], hw[1], 1, (8, 8))[2]
+        R = int(_lib.chan_rank(M, 64, rank_l[i], quality_l[i]))
+        if R < 1:
+            raise ValueError(f"qmf_encode_ragged: image {i}: rank {R} must be >= 1")
+        Rs.append(R)
+    one_sign = lambda v: isinstance(v, (np.ndarray, torch.Tensor)) or (len(v) > 0 and all(x is not None and scalar(x) for x in v))
+    signs = []
+    for i, sg in enumerate(_per_image(init_sign, n, "init_sign", one_sign)):
+        if sg is not None:
+            sg = np.ascontiguousarray(torch.as_tensor(sg, dtype=torch.int8).reshape(-1).numpy())
+            if sg.size != Rs[i]:
+                raise ValueError(f"qmf_encode_ragged: image {i}: init_sign holds {sg.size} signs, its rank needs {Rs[i]}")
+        signs.append(sg)
+    return images, sizes, Rs, signs
+
+
+def _gray_flat(images, idxs, sizes, dev):
+    """the images idxs of the list in one flat device buffer, each at a multiple of 16 bytes (so that widths that are multiples
+    of 16 keep the planes body made for them); host images go through one page-locked buffer and one copy -> (flat, offsets)"""
+    offs, off = [], 0
+    for i in idxs:
+        offs.append(off)
+        off = (off + sizes[i][0] * sizes[i][1] + 15) // 16 * 16
+    if images[idxs[0]].is_cuda:
+        flat = torch.empty((off,), dtype=torch.uint8, device=dev)
+        for i, o in zip(idxs, offs):
+            flat[o:o + images[i].numel()].view(images[i].shape).copy_(images[i])
+    else:
+        stage = torch.empty((off,), dtype=torch.uint8).pin_memory()
+        for i, o in zip(idxs, offs):
+            stage[o:o + images[i].numel()].view(images[i].shape).copy_(images[i])
+        flat = stage.to(dev, non_blocking=True)
+    return flat, offs
+
+
+def _gray_host_streams(Uh, Vh, sizes, ranks, u_off, v_off, bounds, pack_workers) -> list:
+    """the zlib-9 containers of gray factors on the host: _two_factor_stream per image on the pack pool, as _qmf_encode_batch_gray"""
+    def pack(k):
+        H, W = sizes[k]
+        Hp, Wp, M, _ = _lib.chan_dims(H, W, 1, (8, 8))
+        R = ranks[k]
+        return _two_factor_stream("uint8", bounds, (8, 8), (H, W), (Hp, Wp), R,
+                                  [Uh[u_off[k]:u_off[k] + M * R].reshape(M, R), Vh[v_off[k]:v_off[k] + 64 * R].reshape(64, R)])
+
+    import os
+    workers = abs(pack_workers) if isinstance(pack_workers, int) and pack_workers else min(32, os.cpu_count() or 1)
+    if workers <= 1 or len(sizes) == 1:
+        return [pack(k) for k in range(len(sizes))]
+    return list(_pack_pool(workers).map(pack, range(len(sizes))))
+
+
+def _qmf_encode_ragged_gray(images, rank, quality, ranks, bounds, num_iters, init_sign, pack_workers, deflate) -> list:
+    """qmf_encode_ragged(color_space="RGB"): a list of gray images [1,H_i,W_i] (or a tensor [B,1,H,W]) of differing sizes and
+    ranks in ONE lrf_qmf_encode_gray_ragged_u8 call -> stream i byte-identical to qmf_encode_batch(images[i][None], ...,
+    color_space="RGB")[0].  Images of rank above 32 go one by one through that call and are put back in place."""
+    if deflate not in ("host", "device"):
+        raise ValueError(f"deflate must be 'host' or 'device', got {deflate!r}")
+    images, sizes, Rs, signs = _check_encode_gray_ragged_args(images, rank, quality, ranks, num_iters, init_sign)
+    n = len(images)
+    streams = [None] * n
+    fused = [i for i in range(n) if Rs[i] <= 32]
+    ctx = _lib.context(images[0].device.index if images[0].is_cuda else None)
+    dev = torch.device("cuda", ctx.device)
+    lo, hi = math.ceil(bounds[0]), math.floor(bounds[1])
+    for i in range(n):
+        if Rs[i] <= 32:
+            continue
+        if deflate == "device":  # (the batch call packs on the host only: its factors, the device coder's columns)
+            sg = None if signs[i] is None else torch.from_numpy(signs[i]).reshape(1, -1)
+            U1, V1 = ctx.encode_gray(images[i].to(dev), Rs[i], num_iters, (lo, hi), sg)
+            streams[i] = gray_streams_from_device_factors(ctx, U1.reshape(-1), V1.reshape(-1), [sizes[i]], [Rs[i]], [0], [0], bounds)[0]
+        else:
+            streams[i] = qmf_encode_batch(images[i][None], rank=Rs[i], bounds=bounds, num_iters=num_iters, init_sign=signs[i], pack_workers=pack_workers,
+                                          color_space="RGB")[0]
+    if not fused:
+        return streams
+    flat, offs = _gray_flat(images, fused, sizes, dev)
+    sign, sign_offs = None, [-1] * len(fused)
+    if any(signs[i] is not None for i in fused):
+        so = 0
+        for k, i in enumerate(fused):
+            if signs[i] is not None:
+                sign_offs[k] = so
+                so += signs[i].size
+        sign = torch.from_numpy(np.concatenate([signs[i] for i in fused if signs[i] is not None])).to(dev)
+    U, V, u_off, v_off = ctx.encode_gray_ragged(flat, [(sizes[i][0], sizes[i][1], Rs[i], o, s) for i, o, s in zip(fused, offs, sign_offs)],
+                                                num_iters, lo, hi, sign)
+    f_sizes, f_ranks = [sizes[i] for i in fused], [Rs[i] for i in fused]
+    if deflate == "device":
+        packed = gray_streams_from_device_factors(ctx, U, V, f_sizes, f_ranks, u_off, v_off, bounds)
+    else:
+        Uh, Vh = (t.numpy() for t in ctx.to_host(U, V))  # waits for the stream, then raises if a launch of this call gave up
+        packed = _gray_host_streams(Uh, Vh, f_sizes, f_ranks, u_off, v_off, bounds, pack_workers)
+    for i, s_ in zip(fused, packed):
+        streams[i] = s_
+    return streams
+
+
+def gray_target_candidates(image_hw, qualities):
+    """The ranks a quality grid gives on a gray H x W image, each once, in ascending quality, with the LOWEST quality that gives
+    it: ([rank], [quality])"""
+    M = _lib.chan_dims(int(image_hw[0]), int(image_hw[1]), 1, (8, 8))[2]
+    ranks, lowest = [], []
+    for q in sorted(qualities):
+        r = int(_lib.chan_rank(M, 64, None, q))
+        if r not in ranks:
+            ranks.append(r)
+            lowest.append(q)
+    return ranks, lowest
+
+
+def _check_gray_rate_list_args(images, qualities, num_iters, name):
+    """what qmf_encode_target / qmf_encode_budget (color_space="RGB") refuse about images, qualities and num_iters, before a GPU is
+    asked for -> (images as a list, qualities as a list, [(H, W)], per image (ranks, lowest, rows): what gray_target_candidates
+    gives for its size and, per quality in ascending order, which of the ranks it has)"""
+    images = _gray_image_list(images, name)
+    if num_iters < 1:
+        raise NotImplementedError(f"{name}: num_iters = 0 (the truncated initialisation) is outside the fused sweep")
+    qualities = list(qualities)
+    if not qualities or any(not (0 <= q <= 100) for q in qualities):
+        raise ValueError(f"{name}: 'qualities' must be a non-empty sequence of numbers between 0 and 100")
+    sizes = [(int(im.shape[1]), int(im.shape[2])) for im in images]
+    per_size = {}
+    for i, hw in enumerate(sizes):
+        if hw in per_size:
+            continue
+        if hw[0] * hw[1] >= 2 ** 31:
+            raise NotImplementedError(f"{name}: image {i} of {hw[0]}x{hw[1]} has 2^31 pixels or more")
+        M = _lib.chan_dims(hw[0], hw[1], 1, (8, 8))[2]
+        for q in sorted(qualities):
+            r = int(_lib.chan_rank(M, 64, None, q))
+            if r > 32:
+                raise NotImplementedError(f"{name}: image {i} ({hw[0]}x{hw[1]}) at quality {q} has rank {r}: a gray list takes ranks up to 32 "
+                                          f"(encode such images through qmf_encode_batch(color_space='RGB'))")
+        ranks, lowest = gray_target_candidates(hw, qualities)
+        per_size[hw] = (ranks, lowest, [ranks.index(int(_lib.chan_rank(M, 64, None, q))) for q in sorted(qualities)])
+    return images, qualities, sizes, [per_size[hw] for hw in sizes]
+
+
+def _exact_goal(value):
+    """a goal given as Python or numpy floats as a float64 tensor (torch.as_tensor alone makes a list of floats float32, and a
+    target that sits exactly on a table value must stay there); everything else as it came"""
+    if value is None or isinstance(value, torch.Tensor):
+        return value
+    a = np.asarray(value)
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)) if a.dtype.kind == "f" else value
+
+
+def _rate_control_list_gray(images, name, goal, qualities, bounds, num_iters, pack_workers, on_device, x_workspace_bytes) -> dict:
+    """qmf_encode_target / qmf_encode_budget with color_space="RGB": gray images of differing sizes (a list of [1,H,W], or a tensor
+    [B,1,H,W], which goes the same way as the list of its images).  _rate_control_list's structure on the gray entries: per chunk
+    of consecutive images (4 * 64 * M bytes of fp32 patch matrix each within x_workspace_bytes; one image at least) ONE ragged
+    sweep encode of every (image, candidate rank), ONE ragged squared error straight from the factors, for the budget ONE ragged
+    size count, the choice on the device (select_target / select_budget, unchanged), and only the winners packed."""
+    from .metrics import bits_per_pixel, psnr_from_sse
+    budget_mode = name == "qmf_encode_budget"
+    images, qualities, sizes, cand_of = _check_gray_rate_list_args(images, qualities, num_iters, name)
+    B = len(images)
+    if budget_mode:
+        goal_t = budget_bytes_per_image(sizes, _exact_goal(goal["bpp"]), _exact_goal(goal["nbytes"]))
+    else:
+        goal_t = _per_image_numbers(_exact_goal(goal["psnr"]), B, name, "psnr")
+    if int(x_workspace_bytes) < 1:
+        raise ValueError(f"{name}: x_workspace_bytes must be >= 1")
+    sorted_q = sorted(qualities)
+    x_bytes = [4 * 64 * _lib.chan_dims(hw[0], hw[1], 1, (8, 8))[2] for hw in sizes]
+    chunks, at = [], 0
+    while at < B:
+        end, tot, ncand = at, 0, 0
+        while end < B and (end == at or (tot + x_bytes[end] <= x_workspace_bytes and end - at < 65535 and ncand + len(cand_of[end][0]) <= 2 ** 20)):
+            tot += x_bytes[end]
+            ncand += len(cand_of[end][0])
+            end += 1
+        chunks.append(range(at, end))
+        at = end
+    ctx = _lib.context(images[0].device.index if images[0].is_cuda else None)
+    dev = torch.device("cuda", ctx.device)
+    lo, hi = math.ceil(bounds[0]), math.floor(bounds[1])
+    streams, quality = [None] * B, [None] * B
+    tables, size_tables, chosen, reached_all, counted_all = [], [], [], [], []
+    for chunk in chunks:
+        n = len(chunk)
+        flat, offs = _gray_flat(images, list(chunk), sizes, dev)
+        # the candidates, image after image in ascending quality, and row[q][k]: the candidate of (sorted quality q, image k)
+        counts = np.array([len(cand_of[i][0]) for i in chunk], dtype=np.int64)
+        first = np.cumsum(counts) - counts
+        owner = np.repeat(np.arange(n, dtype=np.int64), counts).tolist()  # the image (within the chunk) of every candidate
+        ranks = [r for i in chunk for r in cand_of[i][0]]
+        row = first.reshape(1, n) + np.array([cand_of[i][2] for i in chunk], dtype=np.int64).T
+        U, V, u_off, v_off = ctx.encode_gray_ragged_sweep(flat, [(sizes[i][0], sizes[i][1], o) for i, o in zip(chunk, offs)], list(zip(owner, ranks)),
+                                                          num_iters, lo, hi, None)
+        c_hw = [sizes[chunk[k]] for k in owner]
+        sse_vec = ctx.sse_gray_ragged(flat, [(hw[0], hw[1], r, uo, vo, offs[k]) for hw, r, uo, vo, k in zip(c_hw, ranks, u_off, v_off, owner)], U, V)
+        row_d = torch.from_numpy(row).to(dev)
+        sse = sse_vec[row_d]
+        samples = torch.tensor([sizes[i][0] * sizes[i][1] for i in chunk], dtype=torch.int64)  # (on the host: psnr_from_sse groups the columns by count)
+        goal_c = goal_t[chunk.start:chunk.stop]
+        if budget_mode:
+            size = qmf_stream_sizes_gray_ragged(U, V, c_hw, ranks, u_off, v_off, bounds)[row_d]
+            index, reached = select_budget(size, sse, goal_c)
+            table = psnr_from_sse(sse, samples)[1]
+            counted_all.append(size.gather(0, index.reshape(1, -1))[0].cpu())
+            size_tables.append(size.cpu())
+        else:
+            table, index, reached = select_target(sse, samples, goal_c)
+        chosen.append(table.gather(0, index.reshape(1, -1))[0].cpu())
+        tables.append(table.cpu())
+        reached_all.append(reached.cpu())
+        index = index.cpu().tolist()
+        win = [int(row[index[k], k]) for k in range(n)]
+        w_sizes, w_ranks = [sizes[i] for i in chunk], [ranks[j] for j in win]
+        if on_device:
+            packed = gray_streams_from_device_factors(ctx, U, V, w_sizes, w_ranks, [u_off[j] for j in win], [v_off[j] for j in win], bounds)
+        else:  # only the winners' factors come to the host: gathered back to back on the device first
+            nus = [_lib.chan_dims(hw[0], hw[1], 1, (8, 8))[2] * r for hw, r in zip(w_sizes, w_ranks)]
+            nvs = [64 * r for r in w_ranks]
+            Uw = torch.cat([U[u_off[j]:u_off[j] + nu] for j, nu in zip(win, nus)])
+            Vw = torch.cat([V[v_off[j]:v_off[j] + nv] for j, nv in zip(win, nvs)])
+            Uh, Vh = (x.numpy() for x in ctx.to_host(Uw, Vw))  # waits for the stream, then raises if a launch of this call gave up
+            packed = _gray_host_streams(Uh, Vh, w_sizes, w_ranks, np.cumsum([0] + nus[:-1]).tolist(), np.cumsum([0] + nvs[:-1]).tolist(), bounds,
+                                        pack_workers)
+        for k, i in enumerate(chunk):
+            streams[i] = packed[k]
+            quality[i] = sorted_q[index[k]]
+    if budget_mode:
+        counted = torch.cat(counted_all)
+        for b, s_ in enumerate(streams):
+            if len(s_) != int(counted[b]):
+                raise RuntimeError(f"qmf_encode_budget: image {b} at quality {quality[b]}: the stream has {len(s_)} bytes, {int(counted[b])} were counted")
+    row_of = [sorted_q.index(q) for q in qualities]
+    out = {"streams": streams, "quality": quality, "psnr": torch.cat(chosen), "reached": torch.cat(reached_all),
+           "table": torch.cat(tables, dim=1)[row_of]}
+    if budget_mode:
+        out["nbytes"] = counted
+        out["bpp"] = torch.tensor([bits_per_pixel(hw, s_) for hw, s_ in zip(sizes, streams)], dtype=torch.float64)
+        out["size_table"] = torch.cat(size_tables, dim=1)[row_of]
+    return out
 
 
 def _svd_init_factors(ctx, dev, ranks, init_sign):

@@ -5,11 +5,14 @@
 //       (decompose64 / bcd64, lrf_encode8.hip); k_gray_decode turns the factors back into pixels.
 //   general (1 <= C <= 16, any patch size or none): matrix and decoder kernels around the any-shape entries, which the host calls.
 // Kernels: lrf_channels_kernel.hip.  The resident-factor loader for gray images (lists of mixed sizes and ranks, levels 1/2/4/8,
-// windows, resized crops, tensors) lives in lrf_gray_loader_host.inc / lrf_gray_loader_kernel.hip, included at the end.
+// windows, resized crops, tensors) lives in lrf_gray_loader_host.inc / lrf_gray_loader_kernel.hip, the gray encode lists (images of
+// mixed sizes and ranks, candidate ranks per image, the squared error of factors against their sources) in
+// lrf_gray_encode_host.inc / lrf_gray_encode_kernel.hip; both are included at the end.
 #include "lrf_host.h"
 #include "lrf_channels_kernel.hip"
 #include "lrf_decode_tensor_kernel.hip"
 #include "lrf_gray_loader_kernel.hip"
+#include "lrf_gray_encode_kernel.hip"
 
 #define LRF_CHAN_MAX 16
 
@@ -155,3 +158,4 @@ int lrf_qmf_chan_decode_u8(lrf_ctx* c, const int8_t* U, const int8_t* V, int64_t
 } // extern "C"
 
 #include "lrf_gray_loader_host.inc"
+#include "lrf_gray_encode_host.inc"

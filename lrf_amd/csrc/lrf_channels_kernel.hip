@@ -28,6 +28,34 @@ __device__ __forceinline__ float4 chan_f4(unsigned w)
     return make_float4((float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), (float)(w >> 24));
 }
 
+// The per-item bodies of the two planes kernels: k_gray_planes16 / k_gray_planes run them on a batch of equal images, the ragged
+// kernels of lrf_gray_encode_kernel.hip on a list of images of mixed sizes, so that X is the same bits by construction.
+// gray_planes16_item: row a of the patch pair j of patch row hh — 16 pixels of one image row (one 16-byte load) as the two patch
+// rows they are (four 16-byte stores).  img: the image's [H][W] bytes, 16-byte aligned, W % 16 == 0; o: its X at the pair's row a
+__device__ __forceinline__ void gray_planes16_item(const uint8_t* __restrict__ img, int H, int W, int top, int hh, int j, int a, float4* __restrict__ o)
+{
+    const int y = chan_reflect(hh * 8 + a - top, H);
+    const uint4 px = *reinterpret_cast<const uint4*>(img + (long)y * W + j * 16);
+    o[0] = chan_f4(px.x);
+    o[1] = chan_f4(px.y);
+    o[16] = chan_f4(px.z);
+    o[17] = chan_f4(px.w);
+}
+// gray_planes_item: columns b0 .. b0 + 3 of row a of patch (hh, ww) from single bytes, reflect padding in both directions, as one
+// 16-byte piece of X
+__device__ __forceinline__ void gray_planes_item(const uint8_t* __restrict__ img, int H, int W, int top, int left, int hh, int ww, int a, int b0,
+                                                 float4* __restrict__ o)
+{
+    const uint8_t* row = img + (long)chan_reflect(hh * 8 + a - top, H) * W;
+    const int x0 = ww * 8 + b0 - left;
+    float4 v;
+    v.x = (float)row[chan_reflect(x0, W)];
+    v.y = (float)row[chan_reflect(x0 + 1, W)];
+    v.z = (float)row[chan_reflect(x0 + 2, W)];
+    v.w = (float)row[chan_reflect(x0 + 3, W)];
+    *o = v;
+}
+
 // grid (ceil(nh * (W / 16) * 8 / 256), B).  Item t = (patch pair, row a in the patch): pair = t / 8 counts the pairs of an
 // image in row-major order, which is the order of X (nw = W / 8 is even), so X + pair * 128 + a * 8 are the first patch's eight
 // floats and + 64 the second's.
@@ -39,13 +67,8 @@ __global__ __launch_bounds__(256) void k_gray_planes16(const uint8_t* __restrict
     const long pair = t >> 3;
     const int nch = W >> 4;
     const int hh = (int)(pair / nch), j = (int)(pair - (long)hh * nch);
-    const int y = chan_reflect(hh * 8 + a - top, H);
-    const uint4 px = *reinterpret_cast<const uint4*>(gray + (long)blockIdx.y * H * W + (long)y * W + j * 16);
-    float4* o = reinterpret_cast<float4*>(X + (long)blockIdx.y * (items >> 3) * 128 + pair * 128 + a * 8);
-    o[0] = chan_f4(px.x);
-    o[1] = chan_f4(px.y);
-    o[16] = chan_f4(px.z);
-    o[17] = chan_f4(px.w);
+    gray_planes16_item(gray + (long)blockIdx.y * H * W, H, W, top, hh, j, a,
+                       reinterpret_cast<float4*>(X + (long)blockIdx.y * (items >> 3) * 128 + pair * 128 + a * 8));
 }
 
 // grid (ceil(M * 16 / 256), B).  Item e = (patch m, row a, half): four floats of X at m * 64 + a * 8 + half * 4.
@@ -57,14 +80,8 @@ __global__ __launch_bounds__(256) void k_gray_planes(const uint8_t* __restrict__
     const long m = e >> 4;
     const int a = (int)(e & 15) >> 1, b0 = (int)(e & 1) * 4;
     const int hh = (int)(m / nw), ww = (int)(m - (long)hh * nw);
-    const uint8_t* row = gray + (long)blockIdx.y * H * W + (long)chan_reflect(hh * 8 + a - top, H) * W;
-    const int x0 = ww * 8 + b0 - left;
-    float4 v;
-    v.x = (float)row[chan_reflect(x0, W)];
-    v.y = (float)row[chan_reflect(x0 + 1, W)];
-    v.z = (float)row[chan_reflect(x0 + 2, W)];
-    v.w = (float)row[chan_reflect(x0 + 3, W)];
-    *reinterpret_cast<float4*>(X + (long)blockIdx.y * (items >> 4) * 64 + e * 4) = v;
+    gray_planes_item(gray + (long)blockIdx.y * H * W, H, W, top, left, hh, ww, a, b0,
+                     reinterpret_cast<float4*>(X + (long)blockIdx.y * (items >> 4) * 64 + e * 4));
 }
 
 __device__ __forceinline__ int chan_dot4(unsigned a, unsigned b, int acc)

@@ -232,6 +232,11 @@ static int init_then_bcd(lrf_ctx* c, const float* X, const Tables& t, const BcdP
     }
     return run_bcd(c, X, plan, nullptr, U, V);
 }
+// the same for the entries of other units (lrf_channels.hip: the ragged gray encode)
+int init_then_bcd64(lrf_ctx* c, const float* X, const Tables& t, const BcdPlan& plan, const int8_t* sign, int gram_exp, int8_t* U, int8_t* V)
+{
+    return init_then_bcd(c, X, t, plan, sign, gram_exp, U, V);
+}
 
 // ---- C ABI ------------------------------------------------------------------------------------
 extern "C" {

@@ -96,6 +96,8 @@ struct lrf_ctx {
     DevBuf scaled_pool; // lrf_qmf_decode_scaled_*: the pooled V tables (int16) of the call in flight, written by its k_pool_v
     DevBuf enc_ragged_tab; // lrf_qmf_encode_ragged_rgb_u8: the image descriptors (EncRaggedDesc), behind them the workgroup table ...
     std::vector<char> enc_ragged_key; // ... and the descriptor bytes now resident there
+    DevBuf enc_gray_tab; // lrf_qmf_encode_gray_ragged_sweep_u8: the image descriptors (EncGrayDesc), behind them the workgroup table ...
+    std::vector<char> enc_gray_key; // ... and the descriptor bytes now resident there
     DevBuf deflate_tab; // lrf_deflate_columns_i8: the matrix table (DeflateMat) of the call in flight, filled stream-ordered from ...
     CropSlot deflate_slot[LRF_CROP_SLOTS]; // ... pinned slots of its own, which take turns as the crop table's do
     int deflate_next = 0;
@@ -258,6 +260,8 @@ int encode_rgb_prepare(lrf_ctx* c, int64_t B, int64_t H, int64_t W, const int R[
 int decompose64(lrf_ctx* c, const float* X, int64_t B, int64_t M, int R, int K, int lo, int hi, const int8_t* sign, int8_t* U, int8_t* V);
 int bcd64(lrf_ctx* c, const float* X, int64_t B, int64_t M, int R, int K, int lo, int hi, const float* U0, const float* V0, int8_t* U,
           int8_t* V);
+// run_init then run_bcd on uploaded tables (upload_tables): what every entry that initialises and iterates at once ends in
+int init_then_bcd64(lrf_ctx* c, const float* X, const Tables& t, const BcdPlan& plan, const int8_t* sign, int gram_exp, int8_t* U, int8_t* V);
 bool planes_gram_eligible(const uint8_t* rgb, int64_t B, int64_t H, int64_t W); // lrf_planes_gram.hip
 int planes_gram_from_rgb(lrf_ctx* c, const uint8_t* rgb, int64_t H, int64_t W, const ImageGeom& g, const Tables& t, float* X, bool luma_out = true);
 

@@ -170,6 +170,18 @@ struct EncRaggedDesc {
     int per_strip;     // workgroups per 16-row strip
 };
 
+// ---- the ragged gray encode (lrf_qmf_encode_gray_ragged_sweep_u8; kernels: lrf_gray_encode_kernel.hip) ----
+// One gray image of the call, as the planes kernels read it (uniform loads; the workgroup table is RaggedBlock's: image, tile =
+// the group of 256 items inside it).  No padding bytes: the table's bytes are its key
+struct EncGrayDesc {
+    long gray_off;     // bytes from gray to the image's [H][W]
+    long x_off;        // floats from the X workspace to the image's matrix [M][64]
+    int H, W;
+    int top, left;     // padded rows above / columns left of the image (lrf_chan_dims(H, W, 1, 8, 8))
+    int nw;            // patches per row of the padded image
+    int items;         // the body's work items: (hp / 8) (W / 16) 8 (ENC_GRAY16) or 16 M (ENC_GRAY_ANY)
+};
+
 struct GsParams {
     float lo, hi;      // clamp
     float flimit;      // |q~| >= flimit: certainly outside [lo,hi] after rounding

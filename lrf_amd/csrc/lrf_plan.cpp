@@ -918,6 +918,145 @@ EncRaggedSweepPlan plan_encode_ragged_sweep(const std::vector<EncSweepImage>& im
     return p;
 }
 
+// ---- the tables of a ragged gray sweep ----------------------------------------------------------------------------------------------
+GrayEncRefusal describe_gray_encode(int64_t n, const lrf_gray_sweep_image* images, int64_t m, const lrf_gray_sweep_candidate* cands,
+                                    const GrayEncCall& k, std::vector<EncGrayImage>& ims, std::vector<EncGrayCand>& cs)
+{
+    ims.clear();
+    cs.clear();
+    if (n < 1 || n > 65535) return GrayEncRefusal{GENC_N, 0, n, 0, 0};
+    if (m < n || m > (1 << 20)) return GrayEncRefusal{GENC_M, 0, m, 0, 0};
+    std::vector<EncGrayImage> im_out((size_t)n);
+    std::vector<int64_t> Ms((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_gray_sweep_image& im = images[i];
+        if (im.H < 1 || im.W < 1 || im.H > (1 << 20) || im.W > (1 << 20)) return GrayEncRefusal{GENC_SIZE, 0, i, im.H, im.W};
+        const int64_t ph = (8 - im.H % 8) % 8, pw = (8 - im.W % 8) % 8;
+        if (ph / 2 >= im.H || ph - ph / 2 >= im.H || pw / 2 >= im.W || pw - pw / 2 >= im.W) return GrayEncRefusal{GENC_GEOM, 0, i, im.H, im.W};
+        if (im.H * im.W >= (1LL << 31)) return GrayEncRefusal{GENC_PIXELS, 0, i, im.H, im.W};
+        if (im.gray_off < 0 || im.sign_off < -1) return GrayEncRefusal{GENC_NEGATIVE, 0, i, 0, 0};
+        const int64_t bytes = im.H * im.W;
+        if (bytes > k.gray_len || im.gray_off > k.gray_len - bytes) return GrayEncRefusal{GENC_GRAY, 0, i, k.gray_len, 0};
+        Ms[(size_t)i] = ((im.H + ph) / 8) * ((im.W + pw) / 8);
+        EncGrayImage& e = im_out[(size_t)i];
+        e.H = (long)im.H; e.W = (long)im.W;
+        e.gray_off = (long)im.gray_off;
+        e.sign_off = k.sign_len > 0 && im.sign_off >= 0 ? (long)im.sign_off : -1;
+        e.aligned16 = ((k.gray_base + (uintptr_t)im.gray_off) & 15) == 0;
+    }
+    if (k.K < 1) return GrayEncRefusal{GENC_K, 0, 0, k.K, 0};
+    if (k.lo > k.hi || k.lo < -128 || k.hi > 127) return GrayEncRefusal{GENC_BOUNDS, 0, 0, k.lo, k.hi};
+    std::vector<EncGrayCand> c_out((size_t)m);
+    std::vector<int> rmax((size_t)n, 0);
+    struct Range { int64_t off, len; };
+    std::vector<Range> ur((size_t)m), vr((size_t)m);
+    for (int64_t j = 0; j < m; j++) {
+        const lrf_gray_sweep_candidate& cd = cands[j];
+        if (cd.image < 0 || cd.image >= n) return GrayEncRefusal{GENC_IMAGE, 1, j, cd.image, 0};
+        if (cd.R < 1) return GrayEncRefusal{GENC_RANK_LOW, 1, j, cd.R, 0};
+        if (cd.R > LRF_BIG_TO_ANY_RANK) return GrayEncRefusal{GENC_RANK_BIG, 1, j, cd.R, 0};
+        if (cd.u_off < 0 || cd.v_off < 0) return GrayEncRefusal{GENC_NEGATIVE, 1, j, 0, 0};
+        const int64_t u_img = Ms[(size_t)cd.image] * cd.R, v_img = 64LL * cd.R; // (M < 2^25 + ...: no wrap)
+        if (u_img > k.u_len || cd.u_off > k.u_len - u_img) return GrayEncRefusal{GENC_U, 1, j, k.u_len, 0};
+        if (v_img > k.v_len || cd.v_off > k.v_len - v_img) return GrayEncRefusal{GENC_V, 1, j, k.v_len, 0};
+        c_out[(size_t)j] = EncGrayCand{cd.image, cd.R, (long)cd.u_off, (long)cd.v_off};
+        if (cd.R > rmax[(size_t)cd.image]) rmax[(size_t)cd.image] = cd.R;
+        ur[(size_t)j] = Range{cd.u_off, u_img};
+        vr[(size_t)j] = Range{cd.v_off, v_img};
+    }
+    for (int64_t i = 0; i < n; i++) {
+        if (rmax[(size_t)i] == 0) return GrayEncRefusal{GENC_NO_CAND, 0, i, 0, 0};
+        const int64_t s = rmax[(size_t)i];
+        if (im_out[(size_t)i].sign_off >= 0 && (s > k.sign_len || im_out[(size_t)i].sign_off > k.sign_len - s || k.sign_len > INT32_MAX))
+            return GrayEncRefusal{GENC_SIGN, 0, i, k.sign_len, 0};
+    }
+    for (std::vector<Range>* r : {&ur, &vr}) { // no two candidates may share output bytes
+        std::sort(r->begin(), r->end(), [](const Range& a, const Range& b) { return a.off < b.off; });
+        for (size_t i = 1; i < r->size(); i++)
+            if ((*r)[i].off - (*r)[i - 1].off < (*r)[i - 1].len) return GrayEncRefusal{r == &ur ? GENC_OVERLAP_U : GENC_OVERLAP_V, 1, 0, (*r)[i].off, 0};
+    }
+    ims.swap(im_out);
+    cs.swap(c_out);
+    return GrayEncRefusal{};
+}
+
+// The planes stage: the ENC_GRAY16 images share one launch, the others another; a workgroup finds its image and its 256 items
+// through blocks[i].  Behind it the call is a table of m planes on n matrices: per image the first candidate of the largest
+// rank computes the initialisation (and alone owns Gram chunks: finish_gram_chunks), the others name it in init_src and take
+// its leading columns (k_init_share).
+EncGraySweepPlan plan_encode_gray_ragged_sweep(const std::vector<EncGrayImage>& images, const std::vector<EncGrayCand>& cands, const PlanSettings& s)
+{
+    static_assert(sizeof(EncGrayDesc) == 2 * sizeof(long) + 6 * sizeof(int), "EncGrayDesc has padding bytes: they would be part of the table's key");
+    EncGraySweepPlan p;
+    const size_t n = images.size(), m = cands.size();
+    std::vector<EncGrayDesc> descs(n, EncGrayDesc{});
+    std::vector<int> body(n), Ms(n);
+    std::vector<long> units(n);
+    long count[2] = {0, 0}, x_floats = 0;
+    for (size_t i = 0; i < n; i++) {
+        const EncGrayImage& im = images[i];
+        EncGrayDesc& d = descs[i];
+        const long ph = (8 - im.H % 8) % 8, pw = (8 - im.W % 8) % 8;
+        const long nh = (im.H + ph) / 8, nw = (im.W + pw) / 8;
+        Ms[i] = (int)(nh * nw);
+        d.gray_off = im.gray_off;
+        d.x_off = x_floats;
+        x_floats += 64L * Ms[i];
+        d.H = (int)im.H; d.W = (int)im.W;
+        d.top = (int)(ph / 2); d.left = (int)(pw / 2);
+        d.nw = (int)nw;
+        body[i] = im.W % 16 == 0 && im.aligned16 ? ENC_GRAY16 : ENC_GRAY_ANY;
+        d.items = body[i] == ENC_GRAY16 ? (int)(nh * (im.W / 16) * 8) : 16 * Ms[i];
+        units[i] = ((long)d.items + 255) / 256;
+        count[body[i]] += units[i];
+    }
+    p.rmax.assign(n, 0);
+    std::vector<int> base(n, -1); // the candidate that initialises the image
+    int rmax_t = 1;
+    long bcd_blocks = 0; // of the candidates' table: the only plane table this call has
+    for (size_t j = 0; j < m; j++) {
+        const size_t i = (size_t)cands[j].image;
+        if (cands[j].R > p.rmax[i]) { p.rmax[i] = cands[j].R; base[i] = (int)j; }
+        rmax_t = cands[j].R > rmax_t ? cands[j].R : rmax_t;
+        bcd_blocks += (Ms[i] + LRF_KC - 1) / LRF_KC;
+    }
+    if (bcd_blocks >= (1L << 31) || count[0] >= (1L << 31) || count[1] >= (1L << 31)) {
+        p.too_many = bcd_blocks;
+        for (long cnt : count) p.too_many = cnt > p.too_many ? cnt : p.too_many;
+        p.rmax.clear();
+        return p;
+    }
+    p.blocks.reserve((size_t)(count[0] + count[1]));
+    for (int b = 0; b < 2; b++) {
+        if (!count[b]) continue;
+        p.launches.push_back(EncGrayLaunch{b, (long)p.blocks.size(), count[b]});
+        for (size_t i = 0; i < n; i++) {
+            if (body[i] != b) continue;
+            for (long u = 0; u < units[i]; u++) p.blocks.push_back(RaggedBlock{(int)i, (int)u});
+        }
+    }
+    p.descs.swap(descs);
+    p.x_floats = x_floats;
+    p.split = plan_splits(bcd_blocks, rmax_t, s);
+    p.order.reserve(m);
+    for (int fam = 0; fam < (p.split ? 3 : 1); fam++)
+        for (int self = 1; self >= 0; self--)
+            for (size_t j = 0; j < m; j++) {
+                if (p.split && fam_of_rank(cands[j].R) != fam) continue;
+                if ((base[(size_t)cands[j].image] == (int)j) != (self == 1)) continue;
+                p.order.push_back((int)j);
+            }
+    std::vector<int> base_plane(n, -1);
+    for (int j : p.order) {
+        const EncGrayCand& cd = cands[(size_t)j];
+        const size_t i = (size_t)cd.image;
+        if (base[i] == j) base_plane[i] = (int)p.t.planes.size();
+        add_plane(p.t, p.descs[i].x_off, cd.u_off, cd.v_off, 0, 0, Ms[i], cd.R, images[i].sign_off < 0 ? -1 : (int)images[i].sign_off);
+    }
+    for (size_t pi = 0; pi < p.t.planes.size(); pi++) p.t.planes[pi].init_src = base_plane[(size_t)cands[(size_t)p.order[pi]].image];
+    return p;
+}
+
 // ---- inflate of factor columns -------------------------------------------------------------------------------------------------
 std::vector<InflateSlot> plan_inflate(const std::vector<InflateMatDim>& mats)
 {

@@ -623,6 +623,61 @@ struct EncRaggedSweepPlan {
 // plan_encode_ragged's.  Every image must have a candidate (the entry point checks).
 EncRaggedSweepPlan plan_encode_ragged_sweep(const std::vector<EncSweepImage>& images, const std::vector<EncSweepCand>& cands, const PlanSettings& s);
 
+// ---- encode: the tables of a ragged gray sweep (lrf_qmf_encode_gray_ragged_sweep_u8; the plain ragged gray encode is the sweep
+// with one candidate per image).  A gray image is one matrix [M][64]: one plane per candidate.
+// the planes body that serves an image: k_gray_planes16's when W % 16 == 0 and its bytes start at a multiple of 16, else
+// k_gray_planes' (lrf_channels_kernel.hip)
+enum { ENC_GRAY16 = 0, ENC_GRAY_ANY = 1 };
+// The list as the caller hands it over, checked and described (describe_gray_encode).  Checks, in this order: n in [1,65535],
+// m in [n,2^20]; per image: the size (sides in [1,2^20]), the reflect padding of lrf_chan_dims(H, W, 1, 8, 8), fewer than 2^31
+// pixels, negative offsets, the pixels against gray_len; K, the bounds; per candidate: the image index, the rank (>= 1, then
+// <= LRF_BIG_TO_ANY_RANK), negative offsets, the U and the V extent against u_len / v_len; per image: a candidate, its [Rmax]
+// signs against sign_len; then overlapping U and V ranges.  Every term is checked against the length before it is added to an
+// offset: no sum can wrap.
+enum { GENC_OK = 0, GENC_N, GENC_M, GENC_SIZE, GENC_GEOM, GENC_PIXELS, GENC_NEGATIVE, GENC_GRAY, GENC_K, GENC_BOUNDS, GENC_IMAGE, GENC_RANK_LOW,
+       GENC_RANK_BIG, GENC_U, GENC_V, GENC_NO_CAND, GENC_SIGN, GENC_OVERLAP_U, GENC_OVERLAP_V };
+struct GrayEncRefusal {
+    int check = GENC_OK;
+    int candidate = 0;               // 1: `index` counts candidates, 0: images
+    int64_t index = 0, a = 0, b = 0; // GENC_SIZE, GENC_GEOM: H, W; GENC_IMAGE, GENC_RANK_*: the value; GENC_GRAY, GENC_U, GENC_V, GENC_SIGN: the
+                                     // buffer's length; GENC_OVERLAP_*: the element where two ranges meet
+};
+struct EncGrayImage {
+    long H, W;
+    long gray_off, sign_off; // sign_off: -1 = the default signs, else where its [Rmax] signs start
+    bool aligned16;          // gray + gray_off is a multiple of 16
+};
+struct EncGrayCand {
+    int image, R;
+    long u_off, v_off;
+};
+struct GrayEncCall {
+    int64_t gray_len, sign_len, u_len, v_len; // sign_len: 0 = no sign buffer (every sign_off counts as -1)
+    uintptr_t gray_base;                      // the address of `gray`: decides aligned16
+    int K, lo, hi;
+};
+// ims, cs: filled only when the whole list is accepted — a refused list builds nothing (both stay empty)
+GrayEncRefusal describe_gray_encode(int64_t n, const lrf_gray_sweep_image* images, int64_t m, const lrf_gray_sweep_candidate* cands,
+                                    const GrayEncCall& k, std::vector<EncGrayImage>& ims, std::vector<EncGrayCand>& cs);
+struct EncGrayLaunch {
+    int body;
+    long block0, nblocks; // its workgroups: entries block0 .. block0 + nblocks - 1 of the workgroup table
+};
+struct EncGraySweepPlan {
+    std::vector<EncGrayDesc> descs;      // per image; x_off = the running sum of 64 M
+    std::vector<EncGrayLaunch> launches; // by body, ENC_GRAY16 first: at most two
+    std::vector<RaggedBlock> blocks;     // per launch the images in call order, an image's groups of 256 items ascending
+    Tables t;                            // one plane per candidate; init_src: the plane of the image's first candidate of largest rank
+    std::vector<int> order;              // which candidate plane i of the table is
+    std::vector<int> rmax;               // [n]: the largest rank over the image's candidates
+    bool split = false;                  // plan_splits of the whole call: the table is ordered by kernel family
+    long x_floats = 0;                   // the X workspace: the sum over IMAGES
+    long too_many = 0;                   // != 0: this many (>= 2^31) BCD blocks or planes workgroups; nothing is built
+};
+// Plane order, plan_encode_ragged_sweep's: by kernel family when the call splits, inside a family — or in the whole table of a
+// call that does not split — the self-initialising planes first, candidates in call order.  images, cands: describe_gray_encode's
+EncGraySweepPlan plan_encode_gray_ragged_sweep(const std::vector<EncGrayImage>& images, const std::vector<EncGrayCand>& cands, const PlanSettings& s);
+
 // ---- the any-shape path (lrf_anyshape_host.inc executes these; tests/test_any_plan.py reads them on the CPU) ----------------
 #define LRF_ANY_GS_MAX_LDS (160 * 1024) // dynamic LDS of k_any_gs<float, .>
 #define LRF_ANY_NATIVE_BELOW 400        // products of fewer multiply-adds take ATen's small-product order
