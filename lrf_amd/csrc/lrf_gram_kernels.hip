@@ -148,9 +148,10 @@ __device__ __forceinline__ void gram_digits4_planes(const float (&x)[4], unsigne
         const float top = truncf(x[b] * 0x1p-5f);
         const float rem = fmaf(-32.f, top, x[b]);
         const unsigned lo = (unsigned)(rem * 0x1p27f), hi = (unsigned)top;
-        const unsigned lob = lo + 0x80808080u;
+        unsigned lob;
+        const bool carry = __builtin_add_overflow(lo, 0x80808080u, &lob); // (the add's own carry-out, no compare)
         xb[b] = lob ^ 0x80808080u;
-        d4[b] = hi + (lob < lo ? 1u : 0u);
+        d4[b] = hi + (carry ? 1u : 0u);
     }
     // v_perm_b32(s0, s1, sel): byte selectors 0-3 pick from s1, 4-7 from s0
     const unsigned t0 = __builtin_amdgcn_perm(xb[1], xb[0], 0x05010400u); // x0.b0 x1.b0 x0.b1 x1.b1

@@ -15,6 +15,11 @@
 #include "lrf_device.h"
 #include "lrf_internal.h"
 
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+// byte J (0..7) of an 8-byte word held as two dwords -> float: one v_cvt_f32_ubyteN
+template <int J>
+__device__ __forceinline__ float pg_byte_f(u32x2 w) { return (float)((w[J >> 2] >> (8 * (J & 3))) & 255u); }
+
 // LUMA_OUT false: a call whose k_bcd_p reads luma from the image bytes (plan_luma_bytes, lrf_plan.h): nobody reads luma X, the
 // "luma rows out" phase is left out (the staging, the Gram digits and the chroma rows are the same).
 template <bool LUMA_OUT>
@@ -47,43 +52,61 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int w = 0; w < 9; w++) acc[p][w] = (i32x4){0, 0, 0, 0};
 
-    uint64_t chn[3][2];
-    auto issue_rgb = [&](int unit) {
-        const int strip = unit / per_strip, ww = (unit - strip * per_strip) * 32 + wwl;
-        const int wc = ww < nwl ? ww : nwl - 1; // (threads past the last patch column load a valid address and produce zeros)
-        const int y = 16 * strip + 2 * rp, x = 8 * wc;
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-#pragma unroll
-            for (int rr = 0; rr < 2; rr++) chn[k][rr] = *reinterpret_cast<const uint64_t*>(img + k * hw + (y + rr) * W + x);
+    // (strip, segment) of a unit are carried as wave-uniform counters, one division per chunk: `cp` is the unit compute() forms
+    // next, `rq` the unit whose bytes issue_rgb() requests next
+    struct UnitPos { int strip, seg; };
+    auto advance = [&](UnitPos& p) {
+        if (++p.seg == per_strip) {
+            p.seg = 0;
+            p.strip++;
+        }
     };
-    // k_planes16's arithmetic for this thread's 2 x 8 pixel block of `unit` (ycc_of; chroma window sums row-major): luma into the
-    // staging buffer, chroma straight out (lanes of an even / odd column-block pair fill whole 32-byte rows)
-    auto compute = [&](int unit, float* Ls) {
-        const int strip = unit / per_strip;
-        const int ww = (unit - strip * per_strip) * 32 + wwl;
-        const bool live = ww < nwl;
+    const int strip0 = u0 / per_strip;
+    UnitPos cp = {strip0, u0 - strip0 * per_strip}, rq = cp;
+    // The source bytes through one buffer resource per image that ends with the image (3 hw records; k_bcd_p's luma-from-bytes
+    // body reads the same bytes the same way): the thread's 2 x 8 pixel block inside a unit is the lane's offset, fixed for the
+    // chunk, the unit and the channel are the scalar offset — no address arithmetic per load.  A thread past the last patch
+    // column takes an offset past the records: the range check answers zero bytes without touching memory, and zero bytes
+    // give luma_of(0, 0, 0) = +0.f, the zero rows of the Gram block, through the same chain as every other pixel.
+    const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(img), (short)0, 3 * hw, 0x00020000);
+    const int off0 = 2 * rp * W + 8 * wwl, off1 = off0 + W;
+    const int off_dead = (int)0x80000000u; // (3 hw < 2^31: planes_gram_eligible)
+    const unsigned coff = (wwl >> 1) * 64 + rp * 8 + 4 * (wwl & 1); // the block's chroma floats inside the unit's 16 x 64
+    u32x2 chn[3][2];
+    auto issue_rgb = [&](const UnitPos& p) {
+        const bool live = wwl < nwl - 32 * p.seg;
+        const int o0 = live ? off0 : off_dead, o1 = live ? off1 : off_dead;
+        const int so = p.strip * 16 * W + p.seg * 256;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            chn[k][0] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(irs, o0, so + k * hw, 0));
+            chn[k][1] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(irs, o1, so + k * hw, 0));
+        }
+    };
+    // k_planes16's arithmetic for this thread's 2 x 8 pixel block of unit `p` (luma_of / ycc_of; chroma window sums row-major):
+    // luma into the staging buffer, chroma straight out (lanes of an even / odd column-block pair fill whole 32-byte rows).
+    // Every byte is converted once (v_cvt_f32_ubyteN on the dword that holds it) and serves luma and both chroma planes.
+    auto compute = [&](const UnitPos& p, float* Ls) {
+        const bool live = wwl < nwl - 32 * p.seg;
         float* Lp = Ls + ((rp >> 2) * 32 + wwl) * 64;
         const int swz = (rp >> 1) & 3;
+        float rf[2][8], gf[2][8], bf[2][8];
 #pragma unroll
         for (int rr = 0; rr < 2; rr++) {
+#define LRF_PG_CVT(J) rf[rr][J] = pg_byte_f<J>(chn[0][rr]); gf[rr][J] = pg_byte_f<J>(chn[1][rr]); bf[rr][J] = pg_byte_f<J>(chn[2][rr]);
+            LRF_PG_CVT(0) LRF_PG_CVT(1) LRF_PG_CVT(2) LRF_PG_CVT(3) LRF_PG_CVT(4) LRF_PG_CVT(5) LRF_PG_CVT(6) LRF_PG_CVT(7)
+#undef LRF_PG_CVT
             f32x4 o0, o1;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                o0[i] = ycc_of((float)((chn[0][rr] >> (8 * i)) & 255u), (float)((chn[1][rr] >> (8 * i)) & 255u),
-                               (float)((chn[2][rr] >> (8 * i)) & 255u), 0);
-                o1[i] = ycc_of((float)((chn[0][rr] >> (8 * (i + 4))) & 255u), (float)((chn[1][rr] >> (8 * (i + 4))) & 255u),
-                               (float)((chn[2][rr] >> (8 * (i + 4))) & 255u), 0);
-            }
-            if (!live) { // a patch column past the plane: zero rows of the Gram block
-                o0 = (f32x4){0.f, 0.f, 0.f, 0.f};
-                o1 = o0;
+                o0[i] = luma_of(rf[rr][i], gf[rr][i], bf[rr][i]);
+                o1[i] = luma_of(rf[rr][i + 4], gf[rr][i + 4], bf[rr][i + 4]);
             }
             const int q = 4 * (rp & 3) + 2 * rr;
             *reinterpret_cast<f32x4*>(Lp + 4 * (q ^ swz)) = o0;
             *reinterpret_cast<f32x4*>(Lp + 4 * ((q + 1) ^ swz)) = o1;
         }
-        if (live) {
+        if (live) { // (a dead thread's chroma is not stored)
 #pragma unroll
             for (int c = 1; c < 3; c++) {
                 f32x4 o;
@@ -93,15 +116,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                     for (int rr = 0; rr < 2; rr++)
 #pragma unroll
-                        for (int cc = 0; cc < 2; cc++) {
-                            const int sh = 8 * (2 * i + cc);
-                            sum = sum + ycc_of((float)((chn[0][rr] >> sh) & 255u), (float)((chn[1][rr] >> sh) & 255u),
-                                               (float)((chn[2][rr] >> sh) & 255u), c);
-                        }
-                    o[i] = sum / 2.f / 2.f;
+                        for (int cc = 0; cc < 2; cc++) sum = sum + ycc_of(rf[rr][2 * i + cc], gf[rr][2 * i + cc], bf[rr][2 * i + cc], c);
+                    o[i] = sum * 0.25f; // = sum / 2.f / 2.f: both halvings are exact (four samples of [0.5, 255.5])
                 }
-                float* Cp = Xi + g.p[c].xoff + ((long)strip * nwc + (ww >> 1)) * 64 + rp * 8 + 4 * (ww & 1);
-                *reinterpret_cast<f32x4*>(Cp) = o;
+                float* Cs = Xi + g.p[c].xoff + ((long)p.strip * nwc + p.seg * 16) * 64; // (wave-uniform)
+                *reinterpret_cast<f32x4*>(Cs + coff) = o;
             }
         }
     };
@@ -109,16 +128,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // X), forms unit u + 1 into Ls[(u + 1) & 1], meets the others at barrier u and runs unit u's MFMAs from lds[u & 1].  Ls[b] is
     // rewritten two barriers after its last reader left it, lds[b] likewise.
     if (u0 < u1) {
-        issue_rgb(u0);
-        compute(u0, Lsb[0]);
-        if (u0 + 1 < u1) issue_rgb(u0 + 1);
+        issue_rgb(rq);
+        advance(rq);
+        compute(cp, Lsb[0]);
+        advance(cp);
+        if (u0 + 1 < u1) {
+            issue_rgb(rq);
+            advance(rq);
+        }
         __syncthreads();
     }
+    UnitPos up = {strip0, u0 - strip0 * per_strip}; // the unit of the loop
     for (int unit = u0; unit < u1; unit++) {
         const int bsel = (unit - u0) & 1;
         const float* Ls = Lsb[bsel];
-        const int strip = unit / per_strip;
-        const int ww0 = (unit - strip * per_strip) * 32;
         // ---- the Gram digits of these 64 rows (k_gram64's loop body): lane (li, kq) of wave t takes column 16 t + li of the rows
         // 16 kq .. 16 kq + 15 of the tile — row r = 32 h + pw sits at Ls[r * 64 + 4 * (slot ^ swz) + (column & 3)], slot = column >> 2,
         // swz = (2 h + (slot >> 3)) & 3 as written by compute()
@@ -142,6 +165,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int a = 0; a < 5; a++) lb[(wave * 5 + a) * 64 + lane] = make_uint4(pk[a][0], pk[a][1], pk[a][2], pk[a][3]);
         // ---- luma rows out, lane-contiguous (k_planes16's second phase)
         if constexpr (LUMA_OUT) {
+            const int strip = up.strip, ww0 = up.seg * 32;
             const int npw = nwl - ww0 < 32 ? nwl - ww0 : 32;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -156,9 +180,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __builtin_amdgcn_sched_barrier(0);
         // ---- the next unit into the other staging buffer (its bytes were requested a unit ago), the one after that requested
         if (unit + 1 < u1) { // (wave-uniform)
-            compute(unit + 1, Lsb[bsel ^ 1]);
-            if (unit + 2 < u1) issue_rgb(unit + 2);
+            compute(cp, Lsb[bsel ^ 1]);
+            advance(cp);
+            if (unit + 2 < u1) {
+                issue_rgb(rq);
+                advance(rq);
+            }
         }
+        advance(up);
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
         gram_accumulate(lb, lane, wave, acc);
