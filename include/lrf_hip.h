@@ -538,6 +538,55 @@ int lrf_qmf_sweep_sse_rgb_u8(lrf_ctx* ctx, const uint8_t* rgb /* [B,3,H,W] */, c
 int lrf_qmf_sse_ragged_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_image* items /* host */, const int8_t* U, int64_t u_len, const int8_t* V,
                               int64_t v_len, const uint8_t* rgb, int64_t rgb_len, uint64_t* sse /* [n] */);
 
+/*
+ * Squared error and SSIM of n pairs of uint8 images that differ in size, in one call: pair i is the [C][H_i][W_i] at
+ * a + pairs[i].a_off against the [C][H_i][W_i] at b + pairs[i].b_off (device memory) — lrf/utils/metrics.py:57-71 and :74-91
+ * per pair, as lrf_image_metrics_u8 states them.
+ *   pairs  n descriptors in host memory; several pairs may read one a image (the candidates of an image do) and ranges may
+ *          overlap: both buffers are read-only
+ *   sse    [n] uint64 (device memory); zeroed by the call on its stream
+ *   ssim   [n] float64, or NULL to skip the SSIM work
+ * sse[i] and ssim[i] are bit for bit what lrf_image_metrics_u8 gives for pair i alone (B = 1), NaN included: the kernels run that
+ * entry's device functions on its tiling of (H_i, W_i).  Deterministic; the result depends on neither the order of the list
+ * nor the other pairs nor where the images start (exact integer window sums, one float64 partial sum per tile of 24 x 64
+ * window positions added in a fixed order, 64-bit integer atomics for the squared error, no floating-point atomics).
+ * Launches, with ssim: one flat read for (max, 255 - min) of every DISTINCT a image (pairs that share (a_off, H, W) share it),
+ * a workgroup per (pair, channel, tile) — one launch per load width that occurs in the list, at most three —, one launch of a
+ * workgroup per pair; without: one flat read.  Images are read 16, 4 or 1 bytes at a time, decided per pair from where its
+ * images start and W_i; the width changes no value.  Asynchronous on the context's stream
+ * and timed under LRF_K_METRICS; the table travels stream-ordered through pinned slots and is not kept.  Everything is
+ * validated on the host before any launch, and a refused call writes nothing.  LRF_EINVAL: a NULL pointer, n outside
+ * [1,65535], C outside [1,65535], a side below 1 (with ssim: below 7, the reference's ValueError) or above 2^20, an image of
+ * 2^40 samples or more, a negative offset, an image that leaves its buffer, 2^31 or more workgroups.
+ */
+typedef struct {
+    int64_t H, W;         /* the size both images of the pair share */
+    int64_t a_off, b_off; /* bytes from a / b to the pair's [C][H][W] */
+} lrf_image_pair;
+int lrf_image_metrics_ragged_u8(lrf_ctx* ctx, int64_t n, const lrf_image_pair* pairs /* host */, int C, const uint8_t* a, int64_t a_len,
+                                const uint8_t* b, int64_t b_len, uint64_t* sse /* [n] */, double* ssim /* [n] or NULL */);
+
+/*
+ * Squared error and SSIM of n (factors, source) items that differ in size and ranks, scored from the factors: what
+ * lrf_qmf_decode_ragged_rgb_u8 followed by lrf_image_metrics_u8(source_i, decoded_i) gives per item, bit for bit, and sse[i]
+ * is lrf_qmf_sse_ragged_rgb_u8's.  What qmf_encode_target(ssim=...) scores the candidates of a sweep with (the SSIM curve of
+ * the reference's experiments: lrf/utils/metrics.py:74-91).
+ *   items          lrf_qmf_sse_ragged_rgb_u8's: rgb_off names where the SOURCE [3][H][W] is read; sources may be shared
+ *   scratch_bytes  the cap on the decoded bytes alive at once; 0: 256 MiB (a cap, not a tuned value)
+ *   sse, ssim      [n] (device memory)
+ * Consecutive items form a chunk while their decoded bytes (3 H W each, rounded up to 16) fit the cap; an item larger than the
+ * cap is a chunk of its own.  Per chunk: the ragged decode into the context's scratch buffer (at most eight launches), then the
+ * launches of lrf_image_metrics_ragged_u8 with the sources as a and the scratch as b.  Memory is bounded by the cap (or
+ * the largest item), not by n, and the results are identical for every scratch_bytes.  Deterministic as both parts are.
+ * Asynchronous on the context's stream (a stream the caller set included) and timed under LRF_K_METRICS; every table travels
+ * stream-ordered through pinned slots; the call waits for the stream only when the scratch buffer has to grow.
+ * lrf_ctx_trim frees the scratch.  Everything — every chunk's tables too — is validated on the host before any launch, and a
+ * refused call writes nothing.  LRF_EINVAL: what lrf_qmf_sse_ragged_rgb_u8 refuses, H or W below 7, a negative scratch_bytes.
+ */
+int lrf_qmf_ssim_ragged_rgb_u8(lrf_ctx* ctx, int64_t n, const lrf_ragged_image* items /* host; rgb_off = the SOURCE */, const int8_t* U,
+                               int64_t u_len, const int8_t* V, int64_t v_len, const uint8_t* rgb, int64_t rgb_len,
+                               int64_t scratch_bytes /* 0: default */, uint64_t* sse /* [n] */, double* ssim /* [n] */);
+
 /* ---- the SVD baseline ------------------------------------------------- */
 
 /*

@@ -162,6 +162,9 @@ def load():
         lib.lrf_qmf_encode_ragged_sweep_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedSweepImage), c_i64, ctypes.POINTER(RaggedSweepCandidate),
                                                            c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
         lib.lrf_qmf_sse_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]
+        lib.lrf_image_metrics_ragged_u8.argtypes = [c_void_p, c_i64, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p]
+        lib.lrf_qmf_ssim_ragged_rgb_u8.argtypes = [c_void_p, c_i64, ctypes.POINTER(RaggedImage), c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64,
+                                                   c_void_p, c_void_p]
         lib.lrf_deflate_bound.restype = c_i64
         lib.lrf_deflate_bound.argtypes = [c_i64]
         lib.lrf_deflate_columns_i8.argtypes = [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64]
@@ -230,7 +233,7 @@ EXPORTS = ["lrf_last_error", "lrf_device_count", "lrf_version", "lrf_ctx_create"
            "lrf_ctx_synchronize", "lrf_ctx_check", "lrf_ctx_last_luma_source", "lrf_ctx_last_x_residency", "lrf_ctx_workspace_bytes", "lrf_ctx_trim", "lrf_ctx_profile", "lrf_ctx_profile_kernels", "lrf_ctx_kernel_time",
            "lrf_ctx_profile_reset", "lrf_malloc", "lrf_free", "lrf_memcpy_h2d", "lrf_memcpy_d2h", "lrf_plane_dims",
            "lrf_qmf_planes_from_rgb_u8", "lrf_qmf_decompose_f32", "lrf_qmf_decompose_ex_f32", "lrf_qmf_bcd_f32", "lrf_qmf_svd_init_f32", "lrf_qmf_loss_f32",
-           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_decode_crops_tensor", "lrf_qmf_decode_scaled_crops_tensor", "lrf_qmf_decode_resized_crops_tensor", "lrf_qmf_encode_ragged_rgb_u8", "lrf_qmf_encode_ragged_sweep_rgb_u8", "lrf_qmf_sse_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
+           "lrf_qmf_encode_rgb_u8", "lrf_qmf_encode_sweep_rgb_u8", "lrf_qmf_decode_rgb_u8", "lrf_qmf_decode_ragged_rgb_u8", "lrf_qmf_decode_crops_rgb_u8", "lrf_scaled_dims", "lrf_qmf_decode_scaled_rgb_u8", "lrf_qmf_decode_scaled_crops_rgb_u8", "lrf_qmf_decode_resized_crops_rgb_u8", "lrf_qmf_decode_crops_tensor", "lrf_qmf_decode_scaled_crops_tensor", "lrf_qmf_decode_resized_crops_tensor", "lrf_qmf_encode_ragged_rgb_u8", "lrf_qmf_encode_ragged_sweep_rgb_u8", "lrf_qmf_sse_ragged_rgb_u8", "lrf_image_metrics_ragged_u8", "lrf_qmf_ssim_ragged_rgb_u8", "lrf_deflate_bound", "lrf_deflate_columns_i8", "lrf_deflate_sizes_i8", "lrf_inflate_columns_i8", "lrf_image_metrics_u8", "lrf_qmf_sweep_sse_rgb_u8", "lrf_svd_encode_rgb_u8", "lrf_svd_decode_rgb_u8",
            "lrf_qmf_rgbspace_encode_u8", "lrf_qmf_rgbspace_decode_u8", "lrf_rgbspace_dims_any", "lrf_qmf_rgbspace_matrix_u8",
            "lrf_qmf_rgbspace_decode_any_u8", "lrf_quantize_u8", "lrf_svd_decode_any_u8",
            "lrf_chan_dims", "lrf_qmf_encode_gray_u8", "lrf_qmf_decode_gray_u8", "lrf_qmf_decode_gray_ragged_u8", "lrf_qmf_decode_gray_crops_u8",
@@ -373,6 +376,51 @@ def check_metrics_args(a, b, want_ssim=True):
         raise ValueError(f"shape {tuple(a.shape)} out of range")
     if want_ssim and min(H, W) < 7:
         raise ValueError("win_size exceeds image extent.")
+
+
+def check_metrics_ragged_args(list_a, list_b, want_ssim=True):
+    """The argument checks of lrf_image_metrics_ragged_u8 on two lists of images, before any device is touched: TypeError for
+    anything but two lists of uint8 tensors, ValueError for lists that are empty, longer than 65535 or of differing lengths, for
+    a pair whose shapes are not one [C,H,W] (the same C >= 1 for every pair), whose sides are below the 7x7 window (with the SSIM)
+    or above 2^20, and for images that are not all on one device -> (C, [(H, W)])"""
+    import torch
+    for name, lst in (("list_a", list_a), ("list_b", list_b)):
+        if not isinstance(lst, (list, tuple)):
+            raise TypeError(f"image_metrics_ragged takes two lists of images, got {type(lst).__name__} for {name}")
+        for i, t in enumerate(lst):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+                raise TypeError(f"image_metrics_ragged: {name}[{i}] is {t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}, not a uint8 tensor")
+    if len(list_a) < 1 or len(list_a) > 65535 or len(list_a) != len(list_b):
+        raise ValueError(f"image_metrics_ragged takes two lists of one length in [1,65535], got {len(list_a)} and {len(list_b)} images")
+    sizes = []
+    C = int(list_a[0].shape[0]) if list_a[0].dim() == 3 else 0
+    for i, (x, y) in enumerate(zip(list_a, list_b)):
+        if x.dim() != 3 or tuple(x.shape) != tuple(y.shape):
+            raise ValueError(f"image_metrics_ragged: pair {i}: both images must have one [C,H,W] shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+        if x.shape[0] != C or C < 1 or C > 65535:
+            raise ValueError(f"image_metrics_ragged: pair {i} has {x.shape[0]} channels, pair 0 has {C} (every pair takes the same C in [1,65535])")
+        H, W = int(x.shape[1]), int(x.shape[2])
+        if min(H, W) < 1 or max(H, W) > 2 ** 20 or C * H * W >= 2 ** 40:
+            raise ValueError(f"image_metrics_ragged: pair {i}: size {H}x{W} out of range")
+        if want_ssim and min(H, W) < 7:
+            raise ValueError(f"image_metrics_ragged: pair {i} ({H}x{W}): win_size exceeds image extent.")
+        sizes.append((H, W))
+    if len({t.device for t in list(list_a) + list(list_b)}) != 1:
+        raise ValueError("image_metrics_ragged: the images must all be on one device")
+    return C, sizes
+
+
+def check_ssim_ragged_args(rgb, items, U, V, scratch_bytes=0):
+    """The argument checks of lrf_qmf_ssim_ragged_rgb_u8, before any device is touched: check_sse_ragged_args', plus ValueError for
+    an item with a side below the 7x7 window and for a negative scratch_bytes -> int64 array [n, 8] (the layout of _sse_items_array)"""
+    a = _sse_items_array(rgb, items, U, V)
+    small = (a[:, 0] < 7) | (a[:, 1] < 7)
+    if small.any():
+        i = int(np.nonzero(small)[0][0])
+        raise ValueError(f"item {i} ({a[i, 0]}x{a[i, 1]}): win_size exceeds image extent.")
+    if int(scratch_bytes) < 0:
+        raise ValueError(f"scratch_bytes must be >= 0 (0: the default cap), got {scratch_bytes}")
+    return a
 
 
 def check_sweep_sse_args(rgb, factors, triples):
@@ -1574,6 +1622,67 @@ class Context:
             check(self._lib.lrf_qmf_sse_ragged_rgb_u8(self._h, part.shape[0], part.ctypes.data_as(ctypes.POINTER(RaggedImage)), _dptr(U), U.numel(), _dptr(V),
                                                       V.numel(), _dptr(rgb), rgb.numel(), c_void_p(sse[k:].data_ptr())))
         return sse
+
+    def ssim_ragged(self, rgb, items, U, V, scratch_bytes=0):
+        """The squared error and the SSIM of items that differ in size and ranks, scored from their factors
+        (lrf_qmf_ssim_ragged_rgb_u8): sse_ragged's arguments -> (sse int64 [n], ssim float64 [n]) on the device, what decode_ragged
+        followed by image_metrics(source[None], decoded[None]) gives per item, bit for bit.  The decoded images live chunk by
+        chunk in the context's scratch buffer of at most scratch_bytes (0: 256 MiB; an item larger than the cap is a chunk of
+        its own); the results do not depend on it.  Lists above 65535 items take one call per 65535.  Asynchronous on torch's
+        current stream."""
+        import torch
+        its = check_ssim_ragged_args(rgb, items, U, V, scratch_bytes)
+        self._need_here("ssim_ragged", rgb)
+        assert _RAGGED_IMAGE_DT.itemsize == ctypes.sizeof(RaggedImage)
+        rec = np.zeros((its.shape[0],), dtype=_RAGGED_IMAGE_DT)
+        rec["H"], rec["W"], rec["R"], rec["u_off"], rec["v_off"], rec["rgb_off"] = its[:, 0], its[:, 1], its[:, 2:5], its[:, 5], its[:, 6], its[:, 7]
+        sse = torch.empty((its.shape[0],), dtype=torch.int64, device=rgb.device)
+        ssim = torch.empty((its.shape[0],), dtype=torch.float64, device=rgb.device)
+        self.use_torch_stream()
+        for k in range(0, its.shape[0], 65535):
+            part = rec[k:k + 65535]
+            check(self._lib.lrf_qmf_ssim_ragged_rgb_u8(self._h, part.shape[0], part.ctypes.data_as(ctypes.POINTER(RaggedImage)), _dptr(U), U.numel(), _dptr(V),
+                                                       V.numel(), _dptr(rgb), rgb.numel(), int(scratch_bytes), c_void_p(sse[k:].data_ptr()),
+                                                       c_void_p(ssim[k:].data_ptr())))
+        return sse, ssim
+
+    def metrics_ragged(self, a, b, pairs, C, want_ssim=True):
+        """The squared error and the SSIM of pairs that differ in size (lrf_image_metrics_ragged_u8).  a, b: flat uint8 CUDA
+        tensors; pairs: [(H, W, a_off, b_off)] (or an integer array [n, 4]), pair i's images [C,H,W] at a[a_off:] and b[b_off:]
+        (several pairs may share an a image) -> (sse int64 [n], ssim float64 [n] or None) on the device, per pair what
+        image_metrics gives for that pair alone, bit for bit.  Asynchronous on torch's current stream."""
+        import torch
+        for t in (a, b):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+                raise TypeError("metrics_ragged takes its images as uint8 tensors")
+            if t.dim() != 1 or not t.is_contiguous():
+                raise ValueError("metrics_ragged takes its images as flat contiguous tensors")
+        if a.device != b.device:
+            raise ValueError(f"metrics_ragged needs its tensors on one device, got {a.device} and {b.device}")
+        raw = np.asarray(pairs)
+        if raw.ndim != 2 or raw.shape[1] != 4 or raw.shape[0] < 1 or raw.shape[0] > 65535 or raw.dtype.kind not in "iu":
+            raise ValueError("metrics_ragged takes 1 to 65535 pairs of integers (H, W, a_off, b_off)")
+        p = np.ascontiguousarray(raw.astype(np.int64))
+        C = int(C)
+        if C < 1 or C > 65535:
+            raise ValueError(f"C={C} out of range [1,65535]")
+        lo = 7 if want_ssim else 1
+        bad = (p[:, :2].min(axis=1) < lo) | (p[:, :2].max(axis=1) > 2 ** 20)
+        if bad.any():
+            i = int(np.nonzero(bad)[0][0])
+            raise ValueError(f"pair {i}: size {p[i, 0]}x{p[i, 1]} out of range" + (" (win_size exceeds image extent.)" if p[i, :2].min() < 7 else ""))
+        px = C * p[:, 0] * p[:, 1]
+        bad = (p[:, 2] < 0) | (p[:, 3] < 0) | (p[:, 2] > a.numel() - px) | (p[:, 3] > b.numel() - px)
+        if bad.any():
+            i = int(np.nonzero(bad)[0][0])
+            raise ValueError(f"pair {i}: its images of {px[i]} bytes at {p[i, 2]} and {p[i, 3]} leave the buffers of {a.numel()} and {b.numel()} bytes")
+        self._need_here("metrics_ragged", a)
+        sse = torch.empty((p.shape[0],), dtype=torch.int64, device=a.device)
+        ssim = torch.empty((p.shape[0],), dtype=torch.float64, device=a.device) if want_ssim else None
+        self.use_torch_stream()
+        check(self._lib.lrf_image_metrics_ragged_u8(self._h, p.shape[0], c_void_p(p.ctypes.data), C, _dptr(a), a.numel(), _dptr(b), b.numel(), _dptr(sse),
+                                                    _dptr(ssim)))
+        return sse, ssim
 
     def encode_gray_ragged(self, gray, images, K, lo, hi, sign=None):
         """Gray images that differ in size and rank in one encode (lrf_qmf_encode_gray_ragged_u8).  gray: a flat uint8 CUDA tensor;

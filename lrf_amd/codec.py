@@ -146,6 +146,21 @@ def select_target(sse: torch.Tensor, n, target: torch.Tensor):
     return table, torch.where(reached, first_ok, best), reached
 
 
+def select_target_ssim(ssim_table: torch.Tensor, psnr_table: torch.Tensor, target: torch.Tensor):
+    """The choice qmf_encode_target(ssim=...) makes: ssim_table and psnr_table float64 [Q,B] (candidate q in ascending quality,
+    image b), target float64 [B] -> (index int64 [B], reached bool [B]).  index[b] is the FIRST candidate with ssim >= target[b]
+    — every candidate is looked at, nothing assumes that SSIM grows with quality, and a NaN never reaches —; where none reaches
+    it, the first candidate of the highest non-NaN SSIM (reached False); where every SSIM of the image is NaN (a constant source:
+    data_range 0), the first candidate of the highest PSNR.  Pure torch, evaluated on the device `ssim_table` lives on."""
+    ok = ssim_table >= target.to(ssim_table.device).reshape(1, -1)
+    reached = ok.any(dim=0)
+    first_ok = torch.argmax(ok.to(torch.uint8), dim=0)  # (argmax: the first of equal maxima)
+    nan = torch.isnan(ssim_table)
+    best = torch.argmax(torch.where(nan, torch.full_like(ssim_table, -math.inf), ssim_table), dim=0)
+    best = torch.where(nan.all(dim=0), torch.argmax(psnr_table.to(ssim_table.device), dim=0), best)
+    return torch.where(reached, first_ok, best), reached
+
+
 def _check_sweep_args(images, qualities, num_iters, name):
     """what qmf_encode_target and qmf_encode_budget refuse about images, qualities and num_iters -> qualities as a list"""
     if not isinstance(images, torch.Tensor):
@@ -194,8 +209,9 @@ def _sweep_candidates(images, qualities, bounds, num_iters):
     return ctx, dev, triples, lowest, factors, sse
 
 
-def qmf_encode_target(images, psnr, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
-                      pack_workers: Optional[int] = None, deflate: str = "host", x_workspace_bytes: int = 1 << 30, color_space: str = "YCbCr") -> dict:
+def qmf_encode_target(images, psnr=None, qualities=range(1, 33), bounds=(-16, 15), num_iters: int = 10,
+                      pack_workers: Optional[int] = None, deflate: str = "host", x_workspace_bytes: int = 1 << 30, color_space: str = "YCbCr",
+                      ssim=None) -> dict:
     """Per image of a batch [B,3,H,W], the smallest-quality stream that reaches `psnr` dB (one number, or one per image).
 
     Default branch only (YCbCr, 8x8 patches, uint8, num_iters >= 1).  Every distinct rank triple of `qualities` is factorised on
@@ -226,9 +242,27 @@ def qmf_encode_target(images, psnr, qualities=range(1, 33), bounds=(-16, 15), nu
     byte-identical to qmf_encode_ragged([images[i]], quality=quality[i], color_space="RGB", deflate=deflate)[0] (with the default
     deflate: to qmf_encode_batch(images[i][None], quality=quality[i], color_space="RGB")[0]).  A quality
     whose rank passes 32 on some image raises NotImplementedError naming the image and the quality; three-channel images raise
-    NotImplementedError."""
+    NotImplementedError.
+
+    ssim=: the target is an SSIM (one number, or one per image) instead of a PSNR — exactly one of `psnr` and `ssim` is given.
+    A list goes through _rate_control_list with every candidate scored from its factors by lrf_qmf_ssim_ragged_rgb_u8 (decoded
+    chunk by chunk into a scratch buffer of bounded size, never Q x B images); a tensor [B,3,H,W] goes the same way as the list
+    of its images.  Per image the choice is select_target_ssim's: the lowest quality whose SSIM >= ssim, else the candidate of
+    the highest SSIM (reached False), for a constant image (every SSIM NaN) the candidate of the highest PSNR.  Same keys —
+    "table" is still the PSNR table, from the same call's exact squared errors — plus "ssim" float64 [B], the chosen stream's
+    SSIM (what ssim_batch gives for its decode), and "ssim_table" float64 [len(qualities), B].  An image with a side below the
+    7x7 window raises ValueError naming it; color_space="RGB" raises NotImplementedError."""
     assert color_space in ("RGB", "YCbCr"), "`color_space` must be one of 'RGB' or 'YCbCr'."
+    if (psnr is None) == (ssim is None):
+        raise ValueError("qmf_encode_target: give exactly one of 'psnr' and 'ssim'")
     on_device = _deflate_on_device(deflate)
+    if ssim is not None:
+        if color_space == "RGB":
+            raise NotImplementedError("qmf_encode_target: ssim= takes three-channel images (color_space='YCbCr'); gray images take psnr=")
+        if not isinstance(images, (list, tuple)):
+            _check_sweep_args(images, qualities, num_iters, "qmf_encode_target")
+            images = list(images.unbind(0))
+        return _rate_control_list(images, "qmf_encode_target", dict(ssim=ssim), qualities, bounds, num_iters, pack_workers, on_device, x_workspace_bytes)
     if color_space == "RGB":
         return _rate_control_list_gray(images, "qmf_encode_target", dict(psnr=psnr), qualities, bounds, num_iters, pack_workers, on_device,
                                        x_workspace_bytes)
@@ -552,10 +586,16 @@ def _rate_control_list(images, name, goal, qualities, bounds, num_iters, pack_wo
     packed.  Nothing depends on the other images of a call, so a chunk boundary changes no byte."""
     from .metrics import bits_per_pixel, psnr_from_sse
     budget_mode = name == "qmf_encode_budget"
+    ssim_mode = not budget_mode and goal.get("ssim") is not None  # the target is an SSIM: the candidates are scored by ssim_ragged
     qualities, sizes, cand_of = _check_rate_list_args(images, qualities, num_iters, name)
     B = len(images)
     if budget_mode:
         goal_t = budget_bytes_per_image(sizes, goal["bpp"], goal["nbytes"])
+    elif ssim_mode:
+        goal_t = _per_image_numbers(goal["ssim"], B, name, "ssim")
+        for i, (h, w) in enumerate(sizes):
+            if min(h, w) < 7:
+                raise ValueError(f"{name}: image {i} ({h}x{w}) is smaller than the 7x7 window of the SSIM")
     else:
         goal_t = _per_image_numbers(goal["psnr"], B, name, "psnr")
     if int(x_workspace_bytes) < 1:
@@ -575,7 +615,7 @@ def _rate_control_list(images, name, goal, qualities, bounds, num_iters, pack_wo
     dev = torch.device("cuda", ctx.device)
     lo, hi = math.ceil(bounds[0]), math.floor(bounds[1])
     streams, quality = [None] * B, [None] * B
-    tables, size_tables, chosen, reached_all, counted_all = [], [], [], [], []
+    tables, size_tables, chosen, reached_all, counted_all, ssim_tables, chosen_ssim = [], [], [], [], [], [], []
     for chunk in chunks:
         n = len(chunk)
         offs, off = [], 0
@@ -603,8 +643,12 @@ def _rate_control_list(images, name, goal, qualities, bounds, num_iters, pack_wo
         u_off, v_off = np.asarray(u_off, dtype=np.int64), np.asarray(v_off, dtype=np.int64)
         c_hw = hw[owner]
         items = np.concatenate([c_hw, ranks, u_off.reshape(-1, 1), v_off.reshape(-1, 1), np.asarray(offs, dtype=np.int64)[owner].reshape(-1, 1)], axis=1)
-        sse_vec = ctx.sse_ragged(flat, items, U, V)
         row_d = torch.from_numpy(row).to(dev)
+        if ssim_mode:
+            sse_vec, ssim_vec = ctx.ssim_ragged(flat, items, U, V)
+            ssim_t = ssim_vec[row_d]
+        else:
+            sse_vec = ctx.sse_ragged(flat, items, U, V)
         sse = sse_vec[row_d]
         samples = torch.tensor([3 * sizes[i][0] * sizes[i][1] for i in chunk], dtype=torch.int64)  # (on the host: psnr_from_sse groups the columns by count)
         goal_c = goal_t[chunk.start:chunk.stop]
@@ -614,6 +658,11 @@ def _rate_control_list(images, name, goal, qualities, bounds, num_iters, pack_wo
             table = psnr_from_sse(sse, samples)[1]
             counted_all.append(size.gather(0, index.reshape(1, -1))[0].cpu())
             size_tables.append(size.cpu())
+        elif ssim_mode:
+            table = psnr_from_sse(sse, samples)[1]
+            index, reached = select_target_ssim(ssim_t, table, goal_c)
+            ssim_tables.append(ssim_t.cpu())
+            chosen_ssim.append(ssim_t.gather(0, index.reshape(1, -1))[0].cpu())
         else:
             table, index, reached = select_target(sse, samples, goal_c)
         chosen.append(table.gather(0, index.reshape(1, -1))[0].cpu())
@@ -655,6 +704,9 @@ def _rate_control_list(images, name, goal, qualities, bounds, num_iters, pack_wo
     row_of = [sorted_q.index(q) for q in qualities]
     out = {"streams": streams, "quality": quality, "psnr": torch.cat(chosen), "reached": torch.cat(reached_all),
            "table": torch.cat(tables, dim=1)[row_of]}
+    if ssim_mode:
+        out["ssim"] = torch.cat(chosen_ssim)
+        out["ssim_table"] = torch.cat(ssim_tables, dim=1)[row_of]
     if budget_mode:
         out["nbytes"] = counted
         out["bpp"] = torch.tensor([bits_per_pixel(hw, s) for hw, s in zip(sizes, streams)], dtype=torch.float64)

@@ -292,7 +292,7 @@ void lrf_ctx_destroy(lrf_ctx* c)
     DevBuf* bufs[] = {&c->gchunks, &c->gpart, &c->gexp, &c->planes, &c->blocks, &c->vf, &c->wf, &c->bf, &c->ppart, &c->qpart, &c->x, &c->sign,
                       &c->sx, &c->sg, &c->svn, &c->swn, &c->suf, &c->smm,
                       &c->any_uf, &c->any_vf, &c->any_a, &c->any_b, &c->any_p, &c->any_e2, &c->any_g, &c->any_td,
-                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->enc_gray_tab, &c->crop_desc, &c->crop_tab, &c->gray_desc, &c->scaled_pool, &c->deflate_tab, &c->inflate_tab};
+                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->ssim_scratch, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->enc_gray_tab, &c->crop_desc, &c->crop_tab, &c->gray_desc, &c->scaled_pool, &c->deflate_tab, &c->inflate_tab};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& a : c->talt) {
@@ -374,7 +374,7 @@ size_t lrf_ctx_workspace_bytes(const lrf_ctx* c)
     const DevBuf* bufs[] = {&c->gchunks, &c->gpart, &c->gexp, &c->planes, &c->blocks, &c->vf, &c->wf, &c->bf, &c->ppart, &c->qpart, &c->x, &c->sign,
                             &c->sx, &c->sg, &c->svn, &c->swn, &c->suf, &c->smm,
                             &c->any_uf, &c->any_vf, &c->any_a, &c->any_b, &c->any_p, &c->any_e2, &c->any_g, &c->any_td,
-                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->enc_gray_tab, &c->crop_desc, &c->crop_tab, &c->gray_desc, &c->scaled_pool, &c->deflate_tab, &c->inflate_tab};
+                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->ssim_scratch, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->enc_gray_tab, &c->crop_desc, &c->crop_tab, &c->gray_desc, &c->scaled_pool, &c->deflate_tab, &c->inflate_tab};
     size_t total = 0;
     for (const DevBuf* b : bufs) total += b->cap;
     for (const auto& a : c->talt) total += a.planes.cap + a.blocks.cap + a.gchunks.cap;
@@ -389,7 +389,7 @@ int lrf_ctx_trim(lrf_ctx* c)
     DevBuf* bufs[] = {&c->gchunks, &c->gpart, &c->gexp, &c->planes, &c->blocks, &c->vf,
                       &c->wf, &c->bf, &c->ppart, &c->qpart, &c->x, &c->sign, &c->sx, &c->sg, &c->svn, &c->swn, &c->suf, &c->smm,
                       &c->any_uf, &c->any_vf, &c->any_a, &c->any_b, &c->any_p, &c->any_e2, &c->any_g, &c->any_td,
-                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->enc_gray_tab, &c->crop_desc, &c->crop_tab, &c->gray_desc, &c->scaled_pool, &c->deflate_tab, &c->inflate_tab};
+                      &c->vf16, &c->wf16, &c->bf16, &c->pp16, &c->qp16, &c->metrics, &c->ssim_scratch, &c->sse_tab, &c->ragged_tab, &c->enc_ragged_tab, &c->enc_gray_tab, &c->crop_desc, &c->crop_tab, &c->gray_desc, &c->scaled_pool, &c->deflate_tab, &c->inflate_tab};
     for (DevBuf* b : bufs) {
         if (b->p) HIP_TRY(hipFree(b->p));
         b->p = nullptr;

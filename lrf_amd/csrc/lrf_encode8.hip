@@ -895,6 +895,28 @@ int lrf_qmf_decode_rgb_u8(lrf_ctx* c, const int8_t* U, const int8_t* V, int64_t 
     return LRF_OK;
 }
 
+// the launches of a ragged decode (plan_decode_ragged) over tables already on their way to the device
+static int launch_decode_ragged(lrf_ctx* c, const RaggedPlan& plan, const int8_t* U, const int8_t* V, uint8_t* rgb, const RaggedDesc* d_desc,
+                                const RaggedBlock* d_blk)
+{
+    for (const RaggedLaunch& l : plan.launches) {
+        const dim3 grid((unsigned)l.nblocks);
+        const RaggedBlock* bl = d_blk + l.block0;
+        if (l.kind == DEC_TILE16)
+            hipLaunchKernelGGL((k_decode_ragged_tiled<false, -1>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl);
+        else if (l.kind == DEC_STRIP) {
+#define LRF_RAGGED_STRIP(CLS) hipLaunchKernelGGL((k_decode_ragged_tiled<true, CLS>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl)
+            LRF_FOR_DEC_CLASS(l.cls, LRF_RAGGED_STRIP)
+#undef LRF_RAGGED_STRIP
+        } else if (l.kind == DEC_R8)
+            hipLaunchKernelGGL(k_decode8_ragged, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, l.reps);
+        else
+            hipLaunchKernelGGL(k_decode_ragged_any, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl);
+        LAUNCH_CHECK();
+    }
+    return LRF_OK;
+}
+
 // A list of images that differ in size and ranks in one call (kernels: lrf_decode_ragged_kernel.hip; the launches:
 // plan_decode_ragged).  Everything the kernels index with is checked here, before any launch.
 int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* images, const int8_t* U, int64_t u_len, const int8_t* V,
@@ -918,22 +940,7 @@ int lrf_qmf_decode_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* 
     const RaggedDesc* d_desc = (const RaggedDesc*)c->ragged_tab.p;
     const RaggedBlock* d_blk = (const RaggedBlock*)((const char*)c->ragged_tab.p + db);
     Prof p(c, LRF_K_DECODE);
-    for (const RaggedLaunch& l : plan.launches) {
-        const dim3 grid((unsigned)l.nblocks);
-        const RaggedBlock* bl = d_blk + l.block0;
-        if (l.kind == DEC_TILE16)
-            hipLaunchKernelGGL((k_decode_ragged_tiled<false, -1>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl);
-        else if (l.kind == DEC_STRIP) {
-#define LRF_RAGGED_STRIP(CLS) hipLaunchKernelGGL((k_decode_ragged_tiled<true, CLS>), grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl)
-            LRF_FOR_DEC_CLASS(l.cls, LRF_RAGGED_STRIP)
-#undef LRF_RAGGED_STRIP
-        } else if (l.kind == DEC_R8)
-            hipLaunchKernelGGL(k_decode8_ragged, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl, l.reps);
-        else
-            hipLaunchKernelGGL(k_decode_ragged_any, grid, dim3(256), 0, c->stream, U, V, rgb, d_desc, bl);
-        LAUNCH_CHECK();
-    }
-    return LRF_OK;
+    return launch_decode_ragged(c, plan, U, V, rgb, d_desc, d_blk);
 }
 
 // The crop table of one call on its way to the device: stream-ordered, no wait for the stream.  The pinned staging slots take
@@ -1162,6 +1169,83 @@ int lrf_qmf_sse_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* ite
     return LRF_OK;
 }
 
+
+// The squared error and the SSIM of n (factors, source) items from the factors, in bounded memory (plan_metrics_chunks): per
+// chunk of consecutive items the ragged decode into lrf_ctx::ssim_scratch, then the ragged metrics (lrf_metrics.hip) with the
+// sources as a and the scratch as b.  Validation is lrf_qmf_sse_ragged_rgb_u8's plus the 7x7 window; every chunk's tables are
+// built and checked once before the first launch (and dropped: a sweep's block tables run to tens of megabytes), then built
+// again chunk by chunk on their way to the device.  The tables travel through the pinned slots of the crop table.
+int lrf_qmf_ssim_ragged_rgb_u8(lrf_ctx* c, int64_t n, const lrf_ragged_image* items, const int8_t* U, int64_t u_len, const int8_t* V, int64_t v_len,
+                               const uint8_t* rgb, int64_t rgb_len, int64_t scratch_bytes, uint64_t* sse, double* ssim)
+{
+    if (!c || !items || !U || !V || !rgb || !sse || !ssim) return set_err(LRF_EINVAL, "NULL argument");
+    if (n < 1 || n > 65535) return set_err(LRF_EINVAL, "n=%ld out of range [1,65535]", (long)n);
+    if (scratch_bytes < 0) return set_err(LRF_EINVAL, "scratch_bytes=%ld is negative", (long)scratch_bytes);
+    std::vector<RaggedDesc> descs;
+    int rc = describe(n, items, u_len, v_len, full_size_rgb(rgb_len), "item", "source", descs);
+    if (rc) return rc;
+    for (int64_t i = 0; i < n; i++)
+        if (items[i].H < 7 || items[i].W < 7)
+            return set_err(LRF_EINVAL, "item %ld: win_size exceeds image extent (%ldx%ld, window 7x7)", (long)i, (long)items[i].H, (long)items[i].W);
+    const MetricsChunks ch = plan_metrics_chunks(n, items, scratch_bytes ? scratch_bytes : LRF_SSIM_SCRATCH_DEFAULT);
+    LRF_ON_DEVICE(c);
+    if ((size_t)ch.max_bytes > c->ssim_scratch.cap) { // exactly what the largest chunk holds: the cap bounds the buffer
+        DevBuf& b = c->ssim_scratch;
+        if (b.p) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            HIP_TRY(hipFree(b.p));
+            b.p = nullptr;
+            b.cap = 0;
+        }
+        const hipError_t e = hipMalloc(&b.p, (size_t)ch.max_bytes);
+        if (e != hipSuccess) return set_err(LRF_ENOMEM, "hipMalloc(%ld) failed: %s", (long)ch.max_bytes, hipGetErrorString(e));
+        b.cap = (size_t)ch.max_bytes;
+    }
+    uint8_t* scratch = (uint8_t*)c->ssim_scratch.p;
+    std::vector<RaggedWork> work;
+    std::vector<lrf_ragged_image> its;
+    std::vector<lrf_image_pair> pairs;
+    RaggedPlan dplan;
+    MetricsRaggedPlan mplan;
+    // the tables of one chunk: its items decoded back to back (16-byte steps) into the scratch, scored against their sources
+    auto build = [&](const MetricsChunk& k) -> int {
+        its.assign(items + k.item0, items + k.item0 + k.nitems);
+        pairs.resize((size_t)k.nitems);
+        for (int64_t j = 0; j < k.nitems; j++) {
+            pairs[(size_t)j] = lrf_image_pair{its[(size_t)j].H, its[(size_t)j].W, its[(size_t)j].rgb_off, ch.off[(size_t)(k.item0 + j)]};
+            its[(size_t)j].rgb_off = ch.off[(size_t)(k.item0 + j)];
+        }
+        DescribeOptions o = full_size_rgb(k.bytes);
+        o.aligned8 = false;
+        o.rgb_base = reinterpret_cast<uintptr_t>(scratch);
+        int rc_ = describe(k.nitems, its.data(), u_len, v_len, o, "item", "decoded image", descs, &work);
+        if (rc_) return rc_;
+        dplan = plan_decode_ragged(work);
+        if (dplan.too_many) return set_err(LRF_EINVAL, "%ld work items in one launch: split the list", dplan.too_many);
+        const MetricsCall mk = {3, rgb_len, k.bytes, reinterpret_cast<uintptr_t>(rgb), reinterpret_cast<uintptr_t>(scratch), true};
+        mplan = plan_metrics_ragged(k.nitems, pairs.data(), mk);
+        return mplan.refusal.check == MTR_OK ? LRF_OK : refuse_metrics(mplan.refusal);
+    };
+    size_t ws = 0;
+    for (const MetricsChunk& k : ch.chunks) {
+        if ((rc = build(k))) return rc;
+        ws = std::max(ws, metrics_ragged_workspace(mplan));
+    }
+    if ((rc = ensure(c, c->metrics, ws))) return rc;
+    Prof p(c, LRF_K_METRICS);
+    std::vector<char> tab;
+    for (const MetricsChunk& k : ch.chunks) {
+        if (ch.chunks.size() > 1 && (rc = build(k))) return rc; // (one chunk: the tables of the checking pass stand)
+        const size_t db = descs.size() * sizeof(RaggedDesc), bb = dplan.blocks.size() * sizeof(RaggedBlock);
+        tab.resize(db + bb);
+        memcpy(tab.data(), descs.data(), db);
+        memcpy(tab.data() + db, dplan.blocks.data(), bb);
+        if ((rc = stage_crop_bytes(c, tab.data(), tab.size()))) return rc;
+        if ((rc = launch_decode_ragged(c, dplan, U, V, scratch, (const RaggedDesc*)c->crop_tab.p, (const RaggedBlock*)((const char*)c->crop_tab.p + db)))) return rc;
+        if ((rc = metrics_ragged_launch(c, mplan, 3, rgb, scratch, sse + k.item0, ssim + k.item0))) return rc;
+    }
+    return LRF_OK;
+}
 
 #if defined(LRF_STAMPS) || defined(LRF_INIT_STAMPS) || defined(LRF_BLK_STAMPS) || defined(LRF_REG_STAMPS)
 int lrf_debug_read_stamps(lrf_ctx* c, unsigned long long* out_host, int n)

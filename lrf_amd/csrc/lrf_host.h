@@ -76,6 +76,7 @@ struct lrf_ctx {
     DevBuf sx, sg, svn, swn, suf, smm; // SVD baseline workspace
     DevBuf any_uf, any_vf, any_a, any_b, any_p, any_e2, any_g, any_td; // any-shape path (lrf_anyshape_host.inc)
     DevBuf metrics; // lrf_image_metrics_u8: a float64 slot per (image, channel, tile), then (max, 255 - min) per image
+    DevBuf ssim_scratch; // lrf_qmf_ssim_ragged_rgb_u8: the decoded images of the chunk in flight (at most its cap, or the largest item)
     DevBuf sse_tab; // lrf_qmf_sweep_sse_rgb_u8: its table of rank triples (SseItem) ...
     std::vector<char> sse_key; // ... and the bytes now resident there (calls that repeat a sweep skip the synchronising upload)
     DevBuf ragged_tab; // lrf_qmf_decode_ragged_rgb_u8: the image descriptors (RaggedDesc), behind them the block table ...
@@ -224,6 +225,12 @@ static void with_tensor_type(const DecodeOut& o, F&& fn)
     default: fn((__bf16*)o.p); break;
     }
 }
+
+// ---- the ragged metrics (lrf_metrics.hip), shared with lrf_qmf_ssim_ragged_rgb_u8 (lrf_encode8.hip)
+int refuse_metrics(const MetricsRefusal& r); // a refusal of plan_metrics_ragged in the entries' words
+size_t metrics_ragged_workspace(const MetricsRaggedPlan& p); // bytes of lrf_ctx::metrics the launches of p need
+// the launches of an accepted plan on the context's stream: the caller holds the device and the timer
+int metrics_ragged_launch(lrf_ctx* c, const MetricsRaggedPlan& p, int C, const uint8_t* a, const uint8_t* b, uint64_t* sse, double* ssim);
 
 // ---- geometry (lrf_ctx.hip)
 int make_geom(int64_t H, int64_t W, ImageGeom* g);

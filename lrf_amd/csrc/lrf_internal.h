@@ -182,6 +182,27 @@ struct EncGrayDesc {
     int items;         // the body's work items: (hp / 8) (W / 16) 8 (ENC_GRAY16) or 16 M (ENC_GRAY_ANY)
 };
 
+// ---- the ragged metrics (lrf_image_metrics_ragged_u8, lrf_qmf_ssim_ragged_rgb_u8; kernels: lrf_metrics_ragged_kernel.hip) ----
+// One pair of the call, as the kernels read it (uniform loads behind a prefix search over wg0).  Its workgroups — and its
+// float64 slots, one per workgroup — are wg0 .. wg0 + C nt - 1 in the order (channel, tile row, tile column).  No padding bytes
+struct MetricsPairDesc {
+    long a_off, b_off; // bytes from a / b to the pair's [C][H][W]
+    int H, W;
+    int ntx, nt;       // tiles of 24 x 64 window positions: per tile row, per channel (k_ssim_tiles' tiling of (H, W))
+    int wg0;           // the pair's first workgroup and slot
+    int src;           // which entry of the source table holds (max, 255 - min) of its a image
+    int vec;           // 16, 4 or 1: the widest piece every row of both images can be read in
+    int pad_;
+};
+// One flat range of bytes of k_ragged_metrics_pre: a distinct a image (min / max) or a pair (squared error only).  Its
+// workgroups are wg0 .. wg0 + ceil(n / LRF_MT_PRE_BYTES) - 1.  No padding bytes
+struct MetricsSpanDesc {
+    long a_off, b_off; // bytes from a / b to the range (b_off: the squared error only)
+    long n;            // its bytes
+    int wg0;
+    int vec;           // 16, 4 or 1: the widest piece the range can be read in
+};
+
 struct GsParams {
     float lo, hi;      // clamp
     float flimit;      // |q~| >= flimit: certainly outside [lo,hi] after rounding

@@ -4,6 +4,7 @@
 
 #include <math.h>
 #include <algorithm>
+#include <array>
 #include <string.h>
 
 #include "lrf_env.h"
@@ -390,6 +391,119 @@ RaggedPlan plan_decode_ragged(const std::vector<RaggedWork>& images)
         p.launches.push_back(l);
     }
     return p;
+}
+
+// ---- the tables of the ragged metrics ------------------------------------------------------------------------------------------
+static int metrics_vec_of(uintptr_t bits) { return (bits & 15) == 0 ? 16 : ((bits & 3) == 0 ? 4 : 1); }
+
+MetricsRaggedPlan plan_metrics_ragged(int64_t n, const lrf_image_pair* pairs, const MetricsCall& k)
+{
+    MetricsRaggedPlan p;
+    auto refuse = [&](int check, int64_t pair, int64_t a, int64_t b) {
+        p = MetricsRaggedPlan();
+        p.refusal.check = check;
+        p.refusal.pair = pair;
+        p.refusal.a = a;
+        p.refusal.b = b;
+        return p;
+    };
+    if (n < 1 || n > 65535) return refuse(MTR_N, 0, n, 0);
+    if (k.C < 1 || k.C > 65535) return refuse(MTR_C, 0, k.C, 0);
+    const int64_t side_min = k.want_ssim ? 7 : 1;
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_image_pair& q = pairs[i];
+        if (q.H < side_min || q.W < side_min || q.H > (1 << 20) || q.W > (1 << 20) || q.H * q.W >= ((int64_t)1 << 40) / k.C)
+            return refuse(MTR_SIZE, i, q.H, q.W);
+        if (q.a_off < 0 || q.b_off < 0) return refuse(MTR_NEGATIVE, i, 0, 0);
+        const int64_t bytes = (int64_t)k.C * q.H * q.W;
+        if (bytes > k.a_len || q.a_off > k.a_len - bytes) return refuse(MTR_A, i, k.a_len, 0);
+        if (bytes > k.b_len || q.b_off > k.b_len - bytes) return refuse(MTR_B, i, k.b_len, 0);
+    }
+    // the counts first: a refused list builds nothing
+    long tile_wgs = 0, span_wgs = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_image_pair& q = pairs[i];
+        if (k.want_ssim) tile_wgs += (long)k.C * metrics_tiles_x(q.W) * metrics_tiles_y(q.H);
+        span_wgs += ((long)k.C * q.H * q.W + LRF_MTR_PRE_BYTES - 1) / LRF_MTR_PRE_BYTES; // (an upper bound with the SSIM: shared sources count once)
+        if (tile_wgs >= (1L << 31)) return refuse(MTR_TOO_MANY, i, tile_wgs, 0);
+        if (span_wgs >= (1L << 31)) return refuse(MTR_TOO_MANY, i, span_wgs, 0);
+    }
+    p.pairs.resize((size_t)n);
+    memset(p.pairs.data(), 0, (size_t)n * sizeof(MetricsPairDesc));
+    std::vector<int> src((size_t)n, 0);
+    if (k.want_ssim) {
+        std::vector<int64_t> order((size_t)n);
+        for (int64_t i = 0; i < n; i++) order[(size_t)i] = i;
+        auto key = [&](int64_t i) { return std::array<int64_t, 3>{pairs[i].a_off, pairs[i].H, pairs[i].W}; };
+        std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return key(x) < key(y); });
+        // the first pair (in call order) of every group of equal keys stands for it; spans in order of first appearance
+        std::vector<int64_t> rep((size_t)n);
+        for (size_t j = 0; j < order.size(); j++) rep[(size_t)order[j]] = j && key(order[j]) == key(order[j - 1]) ? rep[(size_t)order[j - 1]] : order[j];
+        std::vector<int> span_of((size_t)n, -1);
+        for (int64_t i = 0; i < n; i++) {
+            if (rep[(size_t)i] == i) {
+                span_of[(size_t)i] = (int)p.spans.size();
+                MetricsSpanDesc s;
+                memset(&s, 0, sizeof s);
+                s.a_off = pairs[i].a_off;
+                s.n = (long)k.C * pairs[i].H * pairs[i].W;
+                p.spans.push_back(s);
+            }
+            src[(size_t)i] = span_of[(size_t)rep[(size_t)i]]; // (a group's first pair comes first in call order: already set)
+        }
+    } else {
+        for (int64_t i = 0; i < n; i++) {
+            MetricsSpanDesc s;
+            memset(&s, 0, sizeof s);
+            s.a_off = pairs[i].a_off;
+            s.b_off = pairs[i].b_off;
+            s.n = (long)k.C * pairs[i].H * pairs[i].W;
+            p.spans.push_back(s);
+            src[(size_t)i] = (int)i;
+        }
+    }
+    for (MetricsSpanDesc& s : p.spans) {
+        s.wg0 = (int)p.span_wgs;
+        s.vec = metrics_vec_of((k.a_base + (uintptr_t)s.a_off) | (k.want_ssim ? 0 : k.b_base + (uintptr_t)s.b_off) | (uintptr_t)s.n);
+        p.span_wgs += (s.n + LRF_MTR_PRE_BYTES - 1) / LRF_MTR_PRE_BYTES;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        const lrf_image_pair& q = pairs[i];
+        MetricsPairDesc& d = p.pairs[(size_t)i];
+        d.a_off = q.a_off;
+        d.b_off = q.b_off;
+        d.H = (int)q.H;
+        d.W = (int)q.W;
+        d.src = src[(size_t)i];
+        d.vec = metrics_vec_of((k.a_base + (uintptr_t)q.a_off) | (k.b_base + (uintptr_t)q.b_off) | (uintptr_t)q.W);
+        d.wg0 = (int)p.tile_wgs;
+        if (k.want_ssim) {
+            d.ntx = (int)metrics_tiles_x(q.W);
+            d.nt = (int)(metrics_tiles_x(q.W) * metrics_tiles_y(q.H));
+            p.tile_wgs += (long)k.C * d.nt;
+        }
+    }
+    return p;
+}
+
+MetricsChunks plan_metrics_chunks(int64_t n, const lrf_ragged_image* items, int64_t cap)
+{
+    MetricsChunks c;
+    c.off.resize((size_t)n);
+    MetricsChunk cur = {0, 0, 0};
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t bytes = (3 * items[i].H * items[i].W + 15) / 16 * 16;
+        if (cur.nitems && cur.bytes + bytes > cap) {
+            c.chunks.push_back(cur);
+            cur = MetricsChunk{i, 0, 0};
+        }
+        c.off[(size_t)i] = cur.bytes;
+        cur.bytes += bytes;
+        cur.nitems++;
+    }
+    if (cur.nitems) c.chunks.push_back(cur);
+    for (const MetricsChunk& k : c.chunks) c.max_bytes = std::max(c.max_bytes, k.bytes);
+    return c;
 }
 
 // ---- the launches of a decode of windows -----------------------------------------------------------------------------------------

@@ -184,6 +184,49 @@ struct DescribeRefusal {
 DescribeRefusal describe_images(int64_t n, const lrf_ragged_image* images, int64_t u_len, int64_t v_len, const DescribeOptions& o,
                                 std::vector<RaggedDesc>& descs, std::vector<RaggedWork>* work = nullptr);
 
+// ---- metrics of pairs that differ in size: the tables and launches of lrf_image_metrics_ragged_u8, and the chunks of -----------
+// lrf_qmf_ssim_ragged_rgb_u8 (kernels: lrf_metrics_ragged_kernel.hip).  tests/test_metrics_ragged_plan.py reads them on the CPU.
+#define LRF_MTR_TH 24 // window positions per tile: rows and columns (k_ssim_tiles' tiling, lrf_metrics_kernel.hip: LRF_MT_TH, LRF_MT_TW)
+#define LRF_MTR_TW 64
+#define LRF_MTR_PRE_BYTES (256 * 16 * 8) // bytes per workgroup of the flat read (LRF_MT_PRE_BYTES)
+#define LRF_SSIM_SCRATCH_DEFAULT ((int64_t)256 << 20) // lrf_qmf_ssim_ragged_rgb_u8's cap on decoded bytes (scratch_bytes = 0)
+inline long metrics_tiles_x(long W) { return (W - 6 + LRF_MTR_TW - 1) / LRF_MTR_TW; }
+inline long metrics_tiles_y(long H) { return (H - 6 + LRF_MTR_TH - 1) / LRF_MTR_TH; }
+// Checks, in this order: n in [1,65535], C in [1,65535]; per pair: the sides (>= 7 with the SSIM, else >= 1; <= 2^20; fewer than
+// 2^40 samples), negative offsets, the a and the b image against a_len / b_len (the extent is compared with the length before
+// it is added to an offset: no sum can wrap); then 2^31 or more workgroups in a launch.
+enum { MTR_OK = 0, MTR_N, MTR_C, MTR_SIZE, MTR_NEGATIVE, MTR_A, MTR_B, MTR_TOO_MANY };
+struct MetricsRefusal {
+    int check = MTR_OK;
+    int64_t pair = 0, a = 0, b = 0; // MTR_N, MTR_C: the value in a; MTR_SIZE: H, W; MTR_A, MTR_B: the buffer's length; MTR_TOO_MANY: the count
+};
+struct MetricsCall {
+    int C;
+    int64_t a_len, b_len;
+    uintptr_t a_base, b_base; // the addresses of a and b: with the offsets and W they decide a pair's load width
+    bool want_ssim;
+};
+struct MetricsRaggedPlan {
+    MetricsRefusal refusal;             // != MTR_OK: nothing below is built (every vector empty, every count 0)
+    std::vector<MetricsPairDesc> pairs; // in call order; wg0: the running sum of C nt — a pair's workgroups are its slots
+    // the flat read's ranges: with the SSIM the DISTINCT a images in order of first appearance (pairs of one (a_off, H, W) share
+    // an entry: MetricsPairDesc::src), without it the pairs themselves (the squared error of a against b)
+    std::vector<MetricsSpanDesc> spans;
+    long tile_wgs = 0;                  // workgroups of k_ragged_ssim_tiles = float64 slots (0 without the SSIM)
+    long span_wgs = 0;                  // workgroups of k_ragged_metrics_pre
+};
+MetricsRaggedPlan plan_metrics_ragged(int64_t n, const lrf_image_pair* pairs, const MetricsCall& k);
+// The chunks of the factor entry: consecutive items go into one chunk while their decoded bytes — 3 H W each, rounded up to 16 —
+// fit `cap`; an item larger than the cap gets a chunk of its own.  sizes: n validated (H, W).  off[i]: bytes from the chunk's
+// start to item i's decoded image
+struct MetricsChunk { int64_t item0, nitems, bytes; };
+struct MetricsChunks {
+    std::vector<MetricsChunk> chunks;
+    std::vector<int64_t> off;
+    int64_t max_bytes = 0; // the largest chunk: what the scratch buffer holds
+};
+MetricsChunks plan_metrics_chunks(int64_t n, const lrf_ragged_image* items, int64_t cap);
+
 // ---- decode of windows: the launches of lrf_qmf_decode_crops_rgb_u8 and which pixels a thread answers for --------------------
 // The windows of a call share one size (h, w), so a launch's grid is uniform: (workgroups per window) x (its windows), the
 // workgroups per window being the worst case over the alignments a window can have inside its image; workgroups a window's

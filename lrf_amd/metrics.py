@@ -144,3 +144,42 @@ def psnr_batch(img1: torch.Tensor, img2: torch.Tensor, max_value: int = 255) -> 
 def ssim_batch(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
     """float64 device tensor [B]: `image_metrics_batch(...)["ssim"]`"""
     return image_metrics_batch(img1, img2)["ssim"]
+
+
+def image_metrics_ragged(list_a, list_b, want_ssim: bool = True, max_value: int = 255, device=None) -> dict:
+    """image_metrics_batch for pairs that differ in size, in one GPU call (lrf_image_metrics_ragged_u8, include/lrf_hip.h).
+
+    list_a, list_b: two lists of uint8 [C,H_i,W_i] tensors, pair i of one shape, every pair of the same C, all on the host or
+    all on one device (host tensors are uploaded).  Returns device tensors of shape [n] under image_metrics_batch's keys: "sse"
+    int64, "mse" and "psnr" float64 over each pair's own C H_i W_i samples (psnr_from_sse with per-item counts), "ssim" float64
+    (absent with want_ssim=False).  Entry i has the bits image_metrics_batch(list_a[i][None], list_b[i][None]) gives, NaN
+    included, whatever the order of the lists.  Entries of list_a that are one tensor object are uploaded and scanned for their
+    data range once."""
+    from . import _lib
+    C, sizes = _lib.check_metrics_ragged_args(list_a, list_b, want_ssim)  # (before a context exists: these refusals need no GPU)
+    if device is None and list_a[0].is_cuda:
+        device = list_a[0].device.index
+    ctx = _lib.context(device)
+    dev = torch.device("cuda", ctx.device)
+    a_at, offs_a, offs_b, na, nb = {}, [], [], 0, 0
+    for (H, W), x in zip(sizes, list_a):
+        if id(x) not in a_at:
+            a_at[id(x)] = na
+            na = (na + C * H * W + 15) // 16 * 16
+        offs_a.append(a_at[id(x)])
+        offs_b.append(nb)
+        nb = (nb + C * H * W + 15) // 16 * 16
+    a, b = torch.empty((na,), dtype=torch.uint8, device=dev), torch.empty((nb,), dtype=torch.uint8, device=dev)
+    done = set()
+    for x, y, oa, ob in zip(list_a, list_b, offs_a, offs_b):
+        if oa not in done:
+            a[oa:oa + x.numel()].view(x.shape).copy_(x)
+            done.add(oa)
+        b[ob:ob + y.numel()].view(y.shape).copy_(y)
+    pairs = np.array([(H, W, oa, ob) for (H, W), oa, ob in zip(sizes, offs_a, offs_b)], dtype=np.int64)
+    sse, s = ctx.metrics_ragged(a, b, pairs, C, want_ssim=want_ssim)
+    m, p = psnr_from_sse(sse, torch.tensor([C * H * W for H, W in sizes], dtype=torch.int64), max_value)
+    out = {"sse": sse, "mse": m, "psnr": p}
+    if want_ssim:
+        out["ssim"] = s
+    return out
